@@ -25,6 +25,8 @@ algorithm, timed on this box's host at N = 1) and the other CPU legs SURVEY 8d l
 numpy restatement, numba restatement).  A step whose fused levels refuse is repeated level by level when
 its summary is read: the headline checks for that behind its timed region and times again level by level if it happened; the
 batch legs and the N > 1 path read the summary inside every step.
+`--dump-outputs DIR` writes what the headline's last timed step computed (a fixed sample of the rows, the per-signal summary) to
+DIR/<name>.npy; the input is the same from run to run, so two builds can be compared output for output.
 The headline has an untimed warm-up of its own (--warm-ms of its own steps, then the W warm-up steps), so it does not depend on any
 other leg.  At N = 1 the line also carries, all timed AFTER the headline and skipped by --no-extra: "config3_batch" (BASELINE
 configs[2], 1024 x 2^20 signals), "short_signal_batches" (4096 x 4096 and 60 000 x 256 samples through the resident form and level by
@@ -96,6 +98,39 @@ def own_bytes_per_sample(rows, first_fused_level):
         return 20.0 + 24.0 * (rows - 2) + 16.0 if rows >= 2 else 20.0
     L0 = int(first_fused_level)
     return 20.0 + 24.0 * (L0 - 1) + 8.0 + 8.0 * (rows - L0)
+
+
+DUMP_BYTES = 64 * 10 ** 6   # --dump-outputs: all files together at most this many bytes (64 MB)
+DUMP_SEED = 0               # --dump-outputs: the sample positions of a larger output are drawn from this seed
+DUMP_EDGE = 4096            # ... after the first and the last DUMP_EDGE samples of every row, which always go in
+
+
+def dump_outputs(path, rows, summ, n):
+    """--dump-outputs DIR: what the timed path handed its caller in its last step, as DIR/<name>.npy (float64), so that two builds can
+    be compared output for output.  `rows` [signals, rows, >= n] on the device (None: --stub), `summ` the step's summary.
+      rows_sample            [signals, rows, k] the rows at k fixed sample positions (all n if they fit); NaN past a signal's n_rows
+      rows_sample_positions  [k] those positions: both ends of the signal and a seeded draw from the rest
+      n_rows, n_baselines, stop, nan_levels, knot_counts: the summary (itd_get_summary), per signal"""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(summ[k], dtype=np.float64) for k in ("n_rows", "n_baselines", "stop", "nan_levels", "knot_counts")}
+    if rows is not None:
+        import torch
+        B, R = int(rows.shape[0]), int(rows.shape[1])
+        budget = DUMP_BYTES - (1 << 20) - sum(a.nbytes for a in arrays.values())      # (1 MB for the positions and the .npy headers)
+        k = max(1, min(n, budget // (8 * (B * R + 1))))
+        if k == n:
+            pos = np.arange(n, dtype=np.int64)
+        else:
+            e = min(DUMP_EDGE, k // 4)
+            mid = np.random.default_rng(DUMP_SEED).choice(n - 2 * e, size=k - 2 * e, replace=False) + e
+            pos = np.sort(np.concatenate([np.arange(e), mid, np.arange(n - e, n)])).astype(np.int64)
+        sample = rows.index_select(2, torch.from_numpy(pos).to(rows.device)).cpu().numpy().astype(np.float64)
+        for b in range(B):
+            sample[b, int(summ["n_rows"][b]):] = np.nan          # (rows past n_rows are workspace, not output)
+        arrays["rows_sample"] = sample
+        arrays["rows_sample_positions"] = pos.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def library_build_id():
@@ -383,7 +418,7 @@ def run_rank(args):
         # A decomposition whose fused sparse levels failed their verification is REPEATED level by level when its summary is read
         # (itd_get_summary) — i.e. behind the timed region.  Such a timing would leave work out: read the summary now, and if a
         # repeat happened (on any rank's shard) time the steps again — the engine then runs them level by level by itself.
-        sb.local_summary()
+        last_summ = sb.local_summary()
         fused_refused = eng.fuse_repeats > rep0
         if dist.is_initialized():
             fr = torch.tensor([1 if fused_refused else 0], dtype=torch.int32)
@@ -395,6 +430,11 @@ def run_rank(args):
             if not sharded:
                 eng.set_timing(args.steps, stride=TIMING_STRIDE)
             elapsed_local = timed_region()
+            if args.dump_outputs:
+                last_summ = sb.local_summary()
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results as its caller holds them once the summary is read (a refused call has been repeated by then)
+        dump_outputs(args.dump_outputs, rows, sb.local_summary() if stub else last_summ, n)
     elapsed = elapsed_local
     per_rank_ms = [elapsed_local / args.steps * 1e3]
     if dist.is_initialized():
@@ -1315,7 +1355,7 @@ def measure_traffic_live(timeout_s=110):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps of the headline (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--log2n", type=int, default=LOG2N, help="N = 1: samples of the single signal (24); N > 1: samples per signal (20)")
     ap.add_argument("--batch", type=int, default=1024, help="N > 1: signals per GPU (weak scaling: the batch grows with N)")
@@ -1338,7 +1378,12 @@ def main():
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)   # CPU test of the launcher only
     ap.add_argument("--no-live-traffic", action="store_true", help="N = 1: do not measure roofline.traffic in this run (two PMC passes of "
                                                                       "a 3-step child run, ~40 s, before the timed region); --no-extra implies it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64, at most 64 MB in all: "
+                         "a fixed sample of the rows' positions and the per-signal summary; N > 1: rank 0's shard)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and not args.stub and not args.rehearse_one_gpu:
         rc = preflight(args)
         if rc:

@@ -239,7 +239,9 @@ int itd_set_fuse_group(itd_engine *e, int32_t chunks);
  *   kind 6 / 7      the value (delta ulps) / position (delta) of halo knot `slot` (0, 1: the two in front, 2 .. 4: the three behind) as
  *                   knot-side workgroup `where` receives it from its neighbours at `level`;
  *   kind 8          delta added to the knot side's count of `level`'s knots (what its stop rules read): the sample pass's check
- *                   wavefronts count the verified flag words themselves, the verdict compares.
+ *                   wavefronts count the verified flag words themselves, the verdict compares;
+ *   kind 9          the gates of a pipelined batch (itd_set_batch_pipeline) wait for a knot side that never starts: each gives up after
+ *                   its time-out and the call is void — whether or not the runtime runs the batch's two streams on one hardware queue.
  * `level` is the absolute level (first fused level .. max_iteration + 1). */
 int itd_debug_kf_fault(itd_engine *e, int32_t kind, int32_t level, int32_t where, int32_t slot, int32_t delta);
 /* Tests only (ABI revision 11): the armed fault lands in signal `signal` of the batch instead of signal 0 (kinds 6 / 7: in that signal's

@@ -811,7 +811,8 @@ int enqueue_decompose(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int
             int rc = run_chunk(b0, nb, st, 3);
             if (rc) return rc;
             if (k >= 1) {
-                k_kf_gate<<<1, kWave, 0, q>>>(e->d_kf_started, e->kf_started_target, e->pipe_gate_timeout);      // (a gate that gives up says so: itd_get_summary)
+                // (a gate that gives up says so: itd_get_summary; fault kind 9, tests only: a target no knot side reaches — the gate gives up)
+                k_kf_gate<<<1, kWave, 0, q>>>(e->d_kf_started, e->fault_kind == 9 ? ~0ull : e->kf_started_target, e->pipe_gate_timeout);
                 rc = run_chunk(b0 - chunk, chunk, q, 4);
                 if (rc) return rc;
             }
@@ -1705,7 +1706,7 @@ int itd_debug_int_ratio_check(int device, int32_t max_den, int64_t *mismatches)
 
 int itd_debug_kf_fault(itd_engine *e, int32_t kind, int32_t level, int32_t where, int32_t slot, int32_t delta)
 {
-    if (!e || kind > 8 || (kind >= 0 && (level < 2 || level > ITD_MAX_ITERATION + 1 || where < 0 || slot < 0))) return ITD_ERR_INVALID_ARG;
+    if (!e || kind > 9 || (kind >= 0 && (level < 2 || level > ITD_MAX_ITERATION + 1 || where < 0 || slot < 0))) return ITD_ERR_INVALID_ARG;
     if ((kind == 6 || kind == 7) && slot > 4) return ITD_ERR_INVALID_ARG;
     e->fault_kind = kind < 0 ? -1 : kind;
     e->fault_level = level; e->fault_where = where; e->fault_slot = slot; e->fault_delta = delta;

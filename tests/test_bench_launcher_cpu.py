@@ -82,3 +82,20 @@ def test_eight_ranks_weak_scaling_form():
     d = _run(["--gpus", "8", "--batch", "5", "--log2n", "10"])
     assert d["n_gpus"] == 8 and d["scaling"] == "weak"
     assert d["config"]["signals_in_gathered_table"] == 40 and d["config"]["table_signal_ids"] == list(range(40))
+
+
+def test_dump_outputs_writes_the_summary_as_float64(tmp_path):
+    """`--dump-outputs DIR`: the last timed step's per-signal summary lands in DIR as float64 .npy files, rank 0's shard at N > 1
+    (the stub computes no rows, so only the summary is there)."""
+    _run(["--gpus", "2", "--batch", "3", "--log2n", "10", "--dump-outputs", str(tmp_path)])
+    names = sorted(p.name for p in tmp_path.iterdir())
+    assert names == ["knot_counts.npy", "n_baselines.npy", "n_rows.npy", "nan_levels.npy", "stop.npy"]
+    import numpy as np
+    kc = np.load(tmp_path / "knot_counts.npy")
+    assert kc.dtype == np.float64 and kc[:, 0].tolist() == [0, 1, 2]     # (the stub's signal ids: rank 0 owns signals 0 .. 2)
+    assert all(np.load(tmp_path / n).dtype == np.float64 for n in names)
+
+
+def test_steps_below_one_are_refused():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub", "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 2 and "--steps" in p.stderr
