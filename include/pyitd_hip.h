@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define ITD_ABI_VERSION 11
+#define ITD_ABI_VERSION 12
 
 /* rotations/baselines hold at most 22 rows in the reference (ITD.py:384-385): max_iteration <= 20 */
 #define ITD_MAX_ROWS 22
@@ -226,9 +226,6 @@ int itd_set_fuse_min_samples(itd_engine *e, int64_t samples);
 int itd_set_fuse_cap(itd_engine *e, int32_t first_level_not_fused);
 /* the cap of the last decomposition as it was enqueued (0: none — every level from the first fused one on ran fused, or no fused levels) */
 int itd_get_last_fuse_cap(const itd_engine *e);
-/* batches: how many consecutive chunks (itd_set_batch_chunk) share ONE knot-side launch of the fused levels (default 1; sharing it
- * paid while the knot side was a dozen launches) */
-int itd_set_fuse_group(itd_engine *e, int32_t chunks);
 /* Tests only (ABI revision 9): arm ONE fault in what the fused levels' knot side hands to their sample pass, applied to signal 0 of
  * every following fused call of this engine until disarmed (kind < 0).  The sample pass verifies everything it takes from the knot
  * side (itd_knotfirst.hpp: V0 .. V3); a fault in a field it uses must end in a refusal (ITD_FUSE_ONLY: itd_get_summary fails;
@@ -239,9 +236,7 @@ int itd_set_fuse_group(itd_engine *e, int32_t chunks);
  *   kind 6 / 7      the value (delta ulps) / position (delta) of halo knot `slot` (0, 1: the two in front, 2 .. 4: the three behind) as
  *                   knot-side workgroup `where` receives it from its neighbours at `level`;
  *   kind 8          delta added to the knot side's count of `level`'s knots (what its stop rules read): the sample pass's check
- *                   wavefronts count the verified flag words themselves, the verdict compares;
- *   kind 9          the gates of a pipelined batch (itd_set_batch_pipeline) wait for a knot side that never starts: each gives up after
- *                   its time-out and the call is void — whether or not the runtime runs the batch's two streams on one hardware queue.
+ *                   wavefronts count the verified flag words themselves, the verdict compares.
  * `level` is the absolute level (first fused level .. max_iteration + 1). */
 int itd_debug_kf_fault(itd_engine *e, int32_t kind, int32_t level, int32_t where, int32_t slot, int32_t delta);
 /* Tests only (ABI revision 11): the armed fault lands in signal `signal` of the batch instead of signal 0 (kinds 6 / 7: in that signal's
@@ -285,21 +280,10 @@ int itd_set_resident_window(itd_engine *e, int32_t segments);
  * level's baseline is still in the 256 MiB Infinity Cache when the next level reads it).  Results do not depend on the chunk size. */
 int itd_set_batch_chunk(itd_engine *e, int32_t signals_per_chunk);
 /* The chunks of a batch are independent: they rotate over `streams` streams (the caller's and streams - 1 of the engine's, forked
- * from / joined to the caller's stream by events), so that one chunk's launch boundaries and tails overlap another's work.
+ * from / joined to the caller's stream by events), each chunk's launches in order on its stream — its own knot side of the fused levels
+ * included —, so that one chunk's launch boundaries and tails overlap another's work.
  * 1 .. 4; default 2 (with automatic chunks of about 1.2e7 samples: 32.5 ms against 35.9 ms over one stream for 1024 x 2^20). */
 int itd_set_batch_streams(itd_engine *e, int32_t streams);
-/* ABI revision 11.  on = 1: a batch whose chunks run the fused sparse levels (itd_set_fuse_mode) is PIPELINED (needs
- * itd_set_batch_streams >= 2): the caller's stream runs every chunk's level launches and its knot side in order, ONE stream of the
- * engine the chunks' passes over the samples, chunk k's beside chunk k + 1's knot side (latency-bound: ~50 us per chunk with HBM idle).
- * A 65 KB workgroup finds no room on a device that one-wavefront workgroups have filled, so each sample pass waits behind a gate (one
- * wavefront that returns when every workgroup of the next knot side has started) instead of behind an event.  on = 0 (default): the
- * chunks rotate over the streams, each chunk's launches in order on its stream.  Measured on 512 x 2^20 samples, 8 levels: 12.8-13.0 ms
- * pipelined against 11.9-12.3 ms rotating — a resident knot side costs the memory-bound launches a quarter of the wave slots, more than
- * hiding it returns (profiles/r06/experiments/README.md); kept for devices / shapes where that balance differs.  Results do not depend
- * on it; a call that is being captured into a hipGraph always takes the rotating form.  The gate also orders a sample pass behind its OWN
- * knot side; one that gives up (50 ms: the device busy with somebody else's work) records it, the call is refused as a whole and repeated
- * level by level — by itd_get_summary, or by the device-side repair (itd_set_device_repair) — and the engine's later batches rotate. */
-int itd_set_batch_pipeline(itd_engine *e, int32_t on);
 
 /* Per-level knot lists are not retained by a decomposition (each level's list is consumed by the next
  * launch); to inspect them run itd_detect_* on the input or on a stored baseline row.  The single-level operators

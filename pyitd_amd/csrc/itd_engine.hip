@@ -67,36 +67,12 @@ __global__ void k_init_state(SigState *st, int batch, int32_t *gsum, int64_t gsu
 // non-finite value) and a level-by-level run would repair it.  A NaN in the caller's signal is neither (the host repeats such a
 // call the way the reference runs it): valid = 0, need = 0.
 __global__ void k_verdict(SigState *__restrict__ state, int batch, const KfSig *__restrict__ kf, int L0, int nan_follow,
-                          int32_t *__restrict__ valid, int32_t *__restrict__ need, const unsigned long long *__restrict__ pipe_gave_up = nullptr)
+                          int32_t *__restrict__ valid, int32_t *__restrict__ need)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= batch) return;
     SigState &st = state[b];
-    // (a pipelined batch whose gate gave up — k_kf_gate — may have run a sample pass in front of its knot side: every signal is refused)
-    if (kf && pipe_gave_up && *pipe_gave_up) st.kf_fail = kKfFailWait;
-    else if (kf) {
-        const KfSig &ks = kf[b];
-        if (!ks.active) { if (ks.fail) st.kf_fail = ks.fail; }
-        else {
-            int fail = ks.fail;
-            const int lend = ks.lend;
-            if (lend < 0) fail |= kKfFailCapacity;
-            // the last pending baseline feeds only the stop test (ITD.py:400-404): its exact count must take the same side of 2
-            if (!fail && (ks.natural ? ks.m_exact >= 2 : ks.m_exact < 2)) fail |= kKfFailVerify;
-            // (the levels' knot counts — what the stop rules were drawn from — the sample pass has compared with its verified flag words'.)
-            // A level that was decomposed had at least 2 knots (ITD.py:404)
-            for (int j = L0; !fail && j <= lend; ++j) if (j > L0 && ks.mlev[j] < 2) fail |= kKfFailVerify;
-            if (fail) st.kf_fail = fail;
-            else if (ks.cont) {         // capped fused levels that did not stop: the level launches behind them wrote the rest of the state
-                for (int j = L0 + 1; j <= lend; ++j) st.m[j] = ks.mlev[j];
-            } else {
-                for (int j = L0 + 1; j <= lend; ++j) st.m[j] = ks.mlev[j];
-                st.m[lend + 1] = ks.m_exact;
-                st.fin_stopped = ks.natural;
-                st.fin_stop_level = ks.natural ? lend + 1 : -1;
-            }
-        }
-    }
+    if (kf) kf_sig_verdict(kf[b], L0, st);
     const int nan_in = st.in_nan != 0;
     const int short_fall = !nan_in && (st.kf_fail != 0 || st.l0_fail != 0 || st.res_fail != 0);
     if (need) need[b] = short_fall;
@@ -172,11 +148,6 @@ __global__ void k_widen_idx(const int32_t *__restrict__ src, int64_t *__restrict
 }
 }  // namespace
 
-#ifdef ITD_DEBUG_GAP
-// experiment build only: an idle gap of ITD_DEBUG_GAP microseconds in front of the sample pass (does the memory system use it?)
-namespace { __global__ void k_debug_gap(long long ticks) { const long long t0 = wall_clock64(); while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8); } }
-#endif
-
 struct itd_engine {
     int device = 0;
     int64_t max_n = 0;
@@ -215,14 +186,6 @@ struct itd_engine {
     int32_t batch_streams = 2;     // chunks of a batch rotate over this many streams (itd_set_batch_streams): 1 .. kMaxBatchStreams
     hipStream_t aux_stream[3] = {nullptr, nullptr, nullptr};   // the others besides the caller's, created on demand
     hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
-    // the batch pipeline (itd_set_batch_pipeline; enqueue_decompose): the fused levels' knot side of chunk k + 1 on aux_stream[0] beside the
-    // memory-bound launches of the caller's stream
-    int32_t batch_pipeline = 0;                    // off by default: measured 12.8-13.0 ms against the rotating chunks' 11.9-12.3 on 512 x 2^20 (profiles/r06/experiments)
-    std::vector<hipEvent_t> ev_pipe;               // two per chunk: the chunk's level launches are done (caller's stream) / its knot side is (aux_stream[0])
-    unsigned long long *d_kf_started = nullptr;    // KfWs::started: knot-side workgroups that have started, over the engine's life
-    unsigned long long kf_started_target = 0;      // ... as many as have been launched
-    long long pipe_gate_timeout = 5000000;         // ticks of the 100 MHz clock the pipeline's waits last at most (50 ms: longer than a knot side
-                                                   // whose own halo waits are given up, ITD_KC_TIMEOUT)
 
     int32_t resident_mode = ITD_RESIDENT_AUTO;   // short signals as one workgroup each, one launch (itd_set_resident_mode)
     int32_t resident_off_left = 0;  // automatic mode: decompositions still to run level by level after a resident call met a non-finite value
@@ -251,9 +214,6 @@ struct itd_engine {
     int32_t fuse_cap_calls = 0;                      // delivered calls under the learned cap since the last probe
     int32_t fuse_cap_span = 16;                      // ... after this many the next call tries all levels again (a probe); doubles, up to 1024,
                                                      // every time a probe is refused at the learned level again
-    bool last_pipelined = false;                     // the last call was a pipelined batch (its gates' give-up word is read with its summary)
-    bool pipe_word_unread = false;                   // a pipelined batch has been enqueued since the give-up word was last read
-    unsigned long long *h_pipe = nullptr;            // pinned: that word on the host
     int last_kf_cap = 0, last_kf_cap_form = 0;       // the cap of the last call (as enqueued: itd_get_last_fuse_cap; 0 = all levels fused)
     bool kf_force_tickets = false;                   // a halo wait was given up on this engine (kKfFailWait): workgroup ids are tickets from then on
     bool fuse_level2_off = false;                    // automatic first fused level: a level-2 list has outgrown its workgroup, level 3 from then on
@@ -268,8 +228,6 @@ struct itd_engine {
     int32_t fuse_range = 0;                          // tiles per knot-side workgroup: 0 = automatic, or 16 / 32 / 64 (itd_set_fuse_range)
     int32_t kf_shrink = 0;                           // automatic: how often a list has outgrown a workgroup (each time halves the range, down to 16 tiles)
     int64_t kf_resident_wgs = 0;                     // knot-side workgroups the device holds at once (occupancy query at creation of the workspace)
-    int32_t fuse_group = 1;                          // chunks of a batch that share one knot side of the fused levels (1 since the knot side is one launch:
-                                                     // sharing it over 2 / 4 chunks measured 25.1 / 26.1 ms against 23.9 on 1024 x 2^20)
     int64_t fuse_min_samples = (int64_t)2 << 20;   // automatic mode: samples per launch sequence from which the fused form pays
     int64_t fuse_signal_repairs = 0;   // signals itd_get_summary has re-run on their own (a few of a batch refused the fused form)
     bool last_kf = false;
@@ -495,6 +453,206 @@ int ensure_kf_ws(itd_engine *e, int tpw, bool may_allocate)
     return ITD_OK;
 }
 
+// a launch through hipExtLaunchKernel that carries the timed pair `pair` (time_slot; -1: none): its two events take the dispatch's own
+// begin / end timestamps (no marker packets in the stream: nothing is added to the timed region)
+hipError_t launch_timed(itd_engine *e, const void *fn, dim3 grid, dim3 block, void **args, hipStream_t st, int pair)
+{
+    return hipExtLaunchKernel(fn, grid, block, args, 0, st, pair >= 0 ? e->ev[2 * (size_t)pair] : nullptr,
+                              pair >= 0 ? e->ev[2 * (size_t)pair + 1] : nullptr, 0);
+}
+
+// What every chunk of one decomposition shares, computed once per call by enqueue_decompose
+template <typename Tin>
+struct DecomposePlan {
+    const Tin *x; int64_t x_stride, n, rows_stride; int32_t M;
+    double *rows, *bases;             // bases: the caller's baselines buffer, or NULL (the baselines live in the engine's rotating slots)
+    bool fuse0, nan_input, kf;        // fused level 0; the NaN-input repeat (k_nan_level0); fused sparse levels
+    int L0, cap, Mk;                  // fused levels L0 .. Mk + 1; cap != 0: levels cap .. M + 1 one launch each behind them
+    int n_tiles, n_groups;
+    int kf_tpw, kf_wgs;               // the knot side's tiles per workgroup, its workgroups per signal
+    SigState *state, *other_state;    // the call's set of states / group sums, and the other set (left initialised for the next call)
+    int32_t *gsum, *other_gsum;
+    int chunk, S;                     // signals per chunk; streams the chunks rotate over
+};
+
+// One chunk's buffers: signals b0 .. b0 + nb - 1 of the call (grid.y of its launches), every per-signal pointer offset by b0
+struct ChunkBufs {
+    const itd_engine *e;
+    int nb, n_tiles; int64_t n, rows_stride;
+    hipStream_t st;
+    SigState *state; double *rows, *bases, *pp; int32_t *gsum, *counts; TileRec *recs; unsigned long long *near;
+    int32_t *gs(int level) const { return gsum + (int64_t)(level % 3) * e->gsum_third; }      // group sums rotate by level % 3,
+    int32_t *cnt(int level) const { return counts + (int64_t)(level & 1) * e->tiles_half; }   // counts and records by level parity
+    TileRec *rec(int level) const { return recs + (int64_t)(level & 1) * e->tiles_half; }
+    // level j's baseline: row j of the caller's buffer, or slot j % 3 of the engine's rotating slots
+    double *base(int j) const { return bases ? bases + (int64_t)j * n : pp + (int64_t)(j % 3) * e->pp_pitch; }
+    int64_t base_stride() const { return bases ? rows_stride : 3 * e->pp_pitch; }
+};
+
+// one level launch of a chunk (k_extract): level j's input xin -> rotation rows[j] and baseline j; level j's counts, records and group
+// sums -> level j + 1's (TIES: the launch in front of the fused sparse levels also flags the tiles of its baseline that hold a near tie)
+template <typename TIN, bool FIN, int CAPK, int KTW = kTilesPerWave, bool FUSE = false, bool TIES = false>
+hipError_t launch_extract(itd_engine *e, const ChunkBufs &c, const TIN *xin, int64_t xs, int j, int pair)
+{
+    const TIN *a_x = xin; int64_t a_xs = xs, a_n = c.n, a_rs = c.rows_stride, a_bs = c.base_stride();
+    int a_nt = c.n_tiles, a_b = c.nb, a_lvl = j, a_keep = 0;
+    const int32_t *a_ci = c.cnt(j), *a_gi = c.gs(j); int32_t *a_co = c.cnt(j + 1), *a_go = c.gs(j + 1), *a_gc = c.gs(j + 2);
+    const TileRec *a_ri = c.rec(j); TileRec *a_ro = c.rec(j + 1);
+    double *a_rot = c.rows + (int64_t)j * (c.n + ITD_ROW_PAD), *a_bas = c.base(j);
+    SigState *a_st = c.state; unsigned long long *a_tie = TIES ? c.near : nullptr;
+    void *args[] = {&a_x, &a_xs, &a_n, &a_nt, &a_b, &a_ci, &a_co, &a_ri, &a_ro, &a_gi, &a_go, &a_gc, &a_rot, &a_rs,
+                    &a_bas, &a_bs, &a_st, &a_lvl, &a_keep, &a_tie};
+    return launch_timed(e, reinterpret_cast<const void *>(&k_extract<TIN, T, FIN, CAPK, KTW, FUSE, TIES>),
+                        dim3((c.n_tiles + KTW - 1) / KTW, c.nb), dim3(kWave), args, c.st, pair);
+}
+
+// the fused levels' workspace as one chunk's launches see it: this call's geometry, every pointer offset to the chunk's first signal
+template <typename Tin>
+KfWs kf_chunk_ws(const itd_engine *e, const DecomposePlan<Tin> &p, const int b0, const int nb)
+{
+    KfWs w = e->kf;
+    w.n_tiles = p.n_tiles; w.L0 = p.L0; w.nlev = p.Mk + 3 - p.L0;
+    w.cap = p.cap;
+    w.xnext = p.cap ? e->d_pp + (int64_t)b0 * 3 * e->pp_pitch + (int64_t)((p.cap - 1) % 3) * e->pp_pitch : nullptr; w.xnext_stride = 3 * e->pp_pitch;
+    w.tpw = p.kf_tpw; w.wgs = p.kf_wgs; w.nb = nb;
+    // (ids from blockIdx only where the whole grid is resident at once — with S streams in flight each launch may count on its share
+    //  of the device only)
+    w.ticketed = ((int64_t)w.wgs * nb * p.S > e->kf_resident_wgs || e->kf_force_tickets) ? 1 : 0;
+    w.dbg_kind = e->fault_kind; w.dbg_lev = e->fault_level; w.dbg_wg = e->fault_where; w.dbg_slot = e->fault_slot; w.dbg_delta = e->fault_delta;
+    w.dbg_sig = e->fault_sig - b0;               // (relative to this launch's first signal; outside it: no workgroup matches)
+    const size_t B0 = (size_t)b0;
+    w.sig += B0; w.pool += B0 * (size_t)w.wgs_max * kKcSlab; w.rec += B0 * (size_t)w.rec_levels * w.wgs_max * kKcRecGran;
+    // (the per-signal strides of `first` / `tflags` follow this call's geometry: nlev levels x n_tiles tiles per signal)
+    w.first += B0 * (size_t)w.nlev * p.n_tiles; w.tflags += B0 * (size_t)w.nlev * p.n_tiles * 8; w.nearw += B0 * (size_t)p.n_tiles * 8;
+    return w;
+}
+
+// One chunk's launches, all on stream cst, in this order:
+//   1. level 0's knots: k_scan0 from the signal (record-driven level 0), or k_nan_level0 (the NaN-input repeat); none for the fused
+//      level-0 launch, which finds its own;
+//   2. the level launches up to j_last (M + 1, or the one in front of the first fused level);
+//   3. without fused levels: k_finalize.  With them: the knot side (k_kf_knots, which does k_finalize's work for the first fused level),
+//      the test-only k_kf_fault and the sample pass (k_kf_apply); behind capped fused levels a scan of the baseline the sample pass
+//      stored (k_clear_gsum, k_scan0), the remaining level launches and k_finalize.
+template <typename Tin>
+int run_chunk(itd_engine *e, const DecomposePlan<Tin> &p, const int b0, const int nb, const hipStream_t cst)
+{
+    const int64_t n = p.n, pp3 = 3 * e->pp_pitch;
+    const ChunkBufs c{e, nb, p.n_tiles, n, p.rows_stride, cst, p.state + b0, p.rows + (int64_t)b0 * p.rows_stride,
+                      p.bases ? p.bases + (int64_t)b0 * p.rows_stride : nullptr, e->d_pp + (int64_t)b0 * pp3,
+                      p.gsum + (int64_t)b0 * p.n_groups * kGsumPitch, e->d_counts + (int64_t)b0 * p.n_tiles,
+                      e->d_recs + (int64_t)b0 * p.n_tiles, p.kf ? e->kf.nearw + (size_t)b0 * p.n_tiles * 8 : nullptr};
+    const Tin *xc = p.x + (int64_t)b0 * p.x_stride;
+    double *xm_c = c.pp + 2 * e->pp_pitch;   // NaN-input repeat: the mutated signal, one per signal at the slots' stride
+    const dim3 blk(kWave);
+    // what k_finalize needs (the knot side as well, for the first fused level: its gsum is set there): the rows, the baselines, the other set
+    KfFin fin{c.rows, p.rows_stride, c.bases ? c.bases : c.pp, c.base_stride(), c.bases ? n : e->pp_pitch, c.bases ? 0 : 3, nullptr,
+              p.other_state + b0, p.other_gsum + (int64_t)b0 * p.n_groups * kGsumPitch, e->gsum_third};
+    // the level launches ja .. jb: extraction j + 1, input = the level-j signal, rotation -> rows[j], baseline -> baseline j
+    auto levels = [&](const int ja, const int jb) -> int {
+        for (int j = ja; j <= jb; ++j) {
+            const bool final_level = j == p.M + 1;        // (with fused levels: only behind capped ones)
+            const int pair = time_slot(e, final_level ? ITD_TIME_EXTRACT_FINAL : (j == 0 ? ITD_TIME_EXTRACT_L0 : ITD_TIME_EXTRACT));
+            const double *in = j ? c.base(j - 1) : nullptr;
+            const int64_t is = c.base_stride();
+            hipError_t rc;
+            if (j == 0) {   // never the last level: M >= 0
+                if (p.nan_input) rc = launch_extract<double, false, kRankCap0>(e, c, xm_c, pp3, 0, pair);
+                else if (p.fuse0) rc = launch_extract<Tin, false, kRankCap0, kFuse0TilesPerWave, true>(e, c, xc, p.x_stride, 0, pair);
+                else rc = launch_extract<Tin, false, kRankCap0>(e, c, xc, p.x_stride, 0, pair);
+            } else if (final_level) rc = launch_extract<double, true, kRankCap>(e, c, in, is, j, pair);
+            else if (p.kf && j == p.L0 - 1) rc = launch_extract<double, false, kRankCap, kTilesPerWave, false, true>(e, c, in, is, j, pair);
+            else rc = launch_extract<double, false, kRankCap>(e, c, in, is, j, pair);
+            if (rc != hipSuccess) return fail_hip(e, rc, "hipExtLaunchKernel(k_extract)");
+        }
+        return ITD_OK;
+    };
+    // stop test on the last pending baseline (ITD.py:400-404 takes priority over the timeout branch) and the residual row
+    auto finalize = [&]() {
+        // blocks per signal: a thread of the row fix-up moves 8 samples (four 16-byte accesses) before the grid is widened
+        const int fb = (int)std::min<int64_t>(std::max<int64_t>((n + 8 * kFinalizeThreads - 1) / (8 * kFinalizeThreads), 1), 1024);
+        const int jf = p.M + 2;      // the level whose input is pending
+        k_finalize<<<dim3(fb, nb), kFinalizeThreads, 0, cst>>>(fin.rows, fin.rows_stride, n, fin.bases, fin.bases_stride, fin.bases_row_pitch,
+                                                               fin.bases_rotate, c.gs(jf), p.n_tiles, jf, c.state, fin.other_state,
+                                                               fin.other_gsum, fin.other_third);
+    };
+
+    if (p.nan_input) {
+        k_nan_level0<Tin, T><<<dim3(p.n_tiles, nb), blk, 0, cst>>>(xc, p.x_stride, n, p.n_tiles, xm_c, pp3, c.cnt(0), c.rec(0), c.gs(0), c.state);
+    } else if (!p.fuse0) {
+        const Tin *a_x = xc; int64_t a_xs = p.x_stride, a_n = n; int a_nt = p.n_tiles;
+        int32_t *a_c = c.cnt(0), *a_g = c.gs(0); TileRec *a_r = c.rec(0); SigState *a_st = c.state; int a_lv = 0;
+        void *args[] = {&a_x, &a_xs, &a_n, &a_nt, &a_c, &a_r, &a_g, &a_st, &a_lv};
+        HIP_TRY(e, launch_timed(e, reinterpret_cast<const void *>(&k_scan0<Tin, T, kScanTilesPerWave>),
+                                dim3((p.n_tiles + kScanTilesPerWave - 1) / kScanTilesPerWave, nb), blk, args, cst, time_slot(e, ITD_TIME_SCAN0)));
+    }
+    if (const int rc = levels(0, p.kf ? p.L0 - 1 : p.M + 1)) return rc;
+    if (!p.kf) {
+        finalize();
+        return ITD_OK;
+    }
+
+    // ---- levels L0 .. Mk + 1 fused: ONE knot-side launch (hand-over and every fused level), ONE pass over the samples ----
+    const KfWs w = kf_chunk_ws(e, p, b0, nb);
+    const double *xl = c.base(p.L0 - 1);
+    const int64_t xl_stride = c.base_stride();
+    {   // the knot side: k_finalize's work for the first fused level (the stop test of its input, the other state set) included
+        KfWs a_w = w; int64_t a_ls = xl_stride, a_n = n; const double *a_xl = xl; int a_m = p.Mk;
+        const int32_t *a_c = c.cnt(p.L0); const TileRec *a_r = c.rec(p.L0); SigState *a_st = c.state;
+        KfFin a_f = fin;
+        a_f.gsum = c.gs(p.L0);
+        void *args[] = {&a_w, &a_f, &a_xl, &a_ls, &a_n, &a_m, &a_c, &a_r, &a_st};
+        HIP_TRY(e, launch_timed(e, reinterpret_cast<const void *>(&k_kf_knots<T>), dim3((unsigned)w.wgs * (unsigned)nb), dim3(kKcThreads),
+                                args, cst, time_slot(e, ITD_TIME_KF_KNOTS)));
+    }
+    if (e->fault_kind >= 0 && (e->fault_kind <= 5 || e->fault_kind == 8) && e->fault_level >= p.L0 && e->fault_level - p.L0 < w.nlev &&
+        e->fault_where >= 0 && e->fault_where < p.n_tiles && e->fault_sig >= b0 && e->fault_sig < b0 + nb)   // (tests only) one field of what the sample pass is about to read, perturbed
+        k_kf_fault<<<1, 64, 0, cst>>>(w, e->fault_sig - b0, e->fault_kind, e->fault_level - p.L0, e->fault_where, e->fault_slot & 0xffff, e->fault_delta);
+    {   // the sample pass: verifies the knot side's tables and writes the rows
+        KfWs a_w = w; const double *a_xl = xl; int64_t a_xs = xl_stride, a_n = n, a_rs = p.rows_stride, a_bs = p.rows_stride;
+        const TileRec *a_rec = c.rec(p.L0); double *a_rows = c.rows, *a_bases = c.bases;
+        void *args[] = {&a_w, &a_xl, &a_xs, &a_n, &a_rec, &a_rows, &a_rs, &a_bases, &a_bs};
+        const void *apply_fn = p.cap ? (c.bases ? reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, true, true>) : reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, true>))
+                                     : (c.bases ? reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, true, false>) : reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, false>));
+        HIP_TRY(e, launch_timed(e, apply_fn, dim3(p.n_tiles + kf_check_blocks(w.wgs), nb), blk, args, cst, time_slot(e, ITD_TIME_KF_APPLY)));
+    }
+    if (!p.cap) return ITD_OK;
+
+    // ---- capped: levels cap .. M + 1 one launch each, from a scan of the baseline the sample pass has stored (the input of level cap:
+    //      its knots' records, counts and group sums, the level's end samples).  A signal that stopped inside the fused levels carries
+    //      SigState::skip: these launches return at once for it.  Should the fused levels refuse, the whole call is repeated anyway:
+    //      what runs here then is discarded.
+    const int64_t ge = (int64_t)nb * p.n_groups * kGsumPitch;
+    k_clear_gsum<<<(int)std::min<int64_t>((ge + 255) / 256, 1024), 256, 0, cst>>>(c.gs(p.cap), c.gs(p.cap + 1), ge);
+    k_scan0<double, T, kScanTilesPerWave><<<dim3((p.n_tiles + kScanTilesPerWave - 1) / kScanTilesPerWave, nb), blk, 0, cst>>>(
+        c.base(p.cap - 1), c.base_stride(), n, p.n_tiles, c.cnt(p.cap), c.rec(p.cap), c.gs(p.cap), c.state, p.cap);
+    if (const int rc = levels(p.cap, p.M + 1)) return rc;
+    finalize();
+    return ITD_OK;
+}
+
+// The set of states / group sums a decomposition works on: the one the previous call did not use (the NaN-input repeat: the same
+// again, its states carry the in_nan flags), initialised by that call's k_finalize unless the bookkeeping says otherwise — a launch of
+// its own initialises it then (the device-side repair's k_repair_init: from the other set's final states).  Returns the set.
+int claim_state_set(itd_engine *e, int32_t batch, int64_t gs_extent, bool nan_input, bool capturing, const int32_t *repair_need, hipStream_t st)
+{
+    const int set = nan_input ? e->cur_set : (e->cur_set ^ 1);
+    SigState *const state = e->d_state + (size_t)set * e->max_batch;
+    int32_t *const gsum = e->d_gsum + (size_t)set * 3 * e->gsum_third;
+    if (repair_need || nan_input || capturing || e->dirty_sig[set] > 0 || e->dirty_gs[set] > 0) {
+        const int64_t ge = 3 * e->gsum_third;   // the buffers are small: clear all of them
+        const int gb = (int)std::min<int64_t>(std::max<int64_t>((ge + 255) / 256, (batch + 255) / 256), 2048);
+        if (repair_need) k_repair_init<<<gb, 256, 0, st>>>(e->d_state + (size_t)(set ^ 1) * e->max_batch, state, repair_need, batch, gsum, ge);
+        else k_init_state<<<gb, 256, 0, st>>>(state, batch, gsum, ge, nan_input ? 1 : 0);
+        e->dirty_sig[set] = std::max(e->dirty_sig[set], batch);
+    } else {
+        e->dirty_sig[set] = batch;
+    }
+    e->dirty_gs[set] = gs_extent;
+    e->cur_set = set;
+    return set;
+}
+
 template <typename Tin>
 int enqueue_decompose(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int64_t x_stride, int32_t M,
                       double *rows, double *bases_user, hipStream_t st, bool fuse0, bool nan_input = false, bool kf = false,
@@ -506,19 +664,21 @@ int enqueue_decompose(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int
     // reference runs it — k_nan_level0 writes the mutated signal (NaN -> +inf, ITD.py:50) into the third baseline slot, which
     // nothing touches before level 2, and the level-0 records; the record-driven level-0 extraction then reads that copy
     if (nan_input) fuse0 = false;
+    DecomposePlan<Tin> p;
+    p.x = x; p.x_stride = x_stride; p.n = n; p.M = M; p.rows = rows; p.bases = bases_user; p.fuse0 = fuse0; p.nan_input = nan_input;
     // kf: levels L0 .. max_iteration + 1 run fused (itd_knotfirst.hpp): one launch per level only for levels 0 .. L0 - 1
-    int L0 = kf_first_level(e, n, batch);
-    if (!e->fuse_level && L0 > M) L0 = 2;               // (automatic: few levels asked for)
-    kf = kf && fuse0 && L0 >= 2 && L0 <= M && n < ((int64_t)1 << 31) - 65536;
+    p.L0 = kf_first_level(e, n, batch);
+    if (!e->fuse_level && p.L0 > M) p.L0 = 2;               // (automatic: few levels asked for)
+    kf = kf && fuse0 && p.L0 >= 2 && p.L0 <= M && n < ((int64_t)1 << 31) - 65536;
     // a call that is being captured into a graph must be complete in itself (the graph may be replayed any number of times) and
     // cannot allocate: a captured call on an engine whose fused workspace does not exist yet runs level by level
     hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(st, &cap_status);
     const bool capturing = cap_status != hipStreamCaptureStatusNone;
-    const int kf_tpw = kf_tiles_per_wg(e, L0);
-    if (kf && capturing && ensure_kf_ws(e, kf_tpw, false) != ITD_OK) kf = false;
+    p.kf_tpw = kf_tiles_per_wg(e, p.L0);
+    if (kf && capturing && ensure_kf_ws(e, p.kf_tpw, false) != ITD_OK) kf = false;
     if (kf) {
-        const int rc = ensure_kf_ws(e, kf_tpw, true);
+        const int rc = ensure_kf_ws(e, p.kf_tpw, true);
         if (rc == ITD_ERR_NOMEM && e->fuse_mode != ITD_FUSE_ONLY) {
             // no room for the fused levels' workspace (136 B x max_n / 8 + 136 B per tile and level, per signal): this engine stays
             // level by level — the result is the same
@@ -527,19 +687,19 @@ int enqueue_decompose(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int
             kf = false;
         } else if (rc) return rc;
     }
+    p.kf = kf;
     // capped fused levels: levels L0 .. cap - 1 fused, cap .. M + 1 one launch each behind a scan of the baseline the sample pass leaves
-    int cap = 0;
+    p.cap = 0;
     if (kf) {
-        cap = e->fuse_cap ? e->fuse_cap : e->fuse_cap_auto;                          // (fuse_cap -1 = never: falls out below)
-        if (cap > 0 && !e->fuse_cap && e->fuse_cap_calls >= e->fuse_cap_span) cap = 0;   // (a learned cap is probed now and then: workloads change)
-        if (cap < L0 + 2 || cap > M + 1) cap = 0;                                    // (fewer than two fused levels are not worth a knot side; beyond the call's levels: no cap)
+        p.cap = e->fuse_cap ? e->fuse_cap : e->fuse_cap_auto;                            // (fuse_cap -1 = never: falls out below)
+        if (p.cap > 0 && !e->fuse_cap && e->fuse_cap_calls >= e->fuse_cap_span) p.cap = 0;   // (a learned cap is probed now and then: workloads change)
+        if (p.cap < p.L0 + 2 || p.cap > M + 1) p.cap = 0;                                // (fewer than two fused levels are not worth a knot side; beyond the call's levels: no cap)
     }
-    const int Mk = cap ? cap - 2 : M;               // the knot side's "max_iteration": its levels are L0 .. Mk + 1
-    const int n_tiles = (int)tiles_of(n);
-    const int n_groups = groups_of(n_tiles);
-    const int64_t R = (int64_t)M + 2;
-    const int64_t rows_stride = R * (n + ITD_ROW_PAD);
-    const dim3 blk(kWave);
+    p.Mk = p.cap ? p.cap - 2 : M;               // the knot side's "max_iteration": its levels are L0 .. Mk + 1
+    p.n_tiles = (int)tiles_of(n);
+    p.n_groups = groups_of(p.n_tiles);
+    p.kf_wgs = (p.n_tiles + p.kf_tpw - 1) / p.kf_tpw;
+    p.rows_stride = ((int64_t)M + 2) * (n + ITD_ROW_PAD);
 
     // instrument every timing_stride-th decomposition only: a launch that carries events needs a completion signal of its own
     // (~2 us per launch, measured), the whole-decomposition span two marker records (~5 us each)
@@ -549,67 +709,25 @@ int enqueue_decompose(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int
     // lies outside the span of a level-by-level call)
     const int span_pair = time_slot(e, ITD_TIME_DECOMPOSE);
     e->span_first = e->span_last = -1;
-    // the set of states / group sums this call works on: the one the previous call did not use (the NaN-input repeat: the same
-    // again, its states carry the in_nan flags), initialised by that call's k_finalize unless the bookkeeping says otherwise
-    const int set = nan_input ? e->cur_set : (e->cur_set ^ 1);
-    SigState *const set_state = e->d_state + (size_t)set * e->max_batch;
-    int32_t *const set_gsum = e->d_gsum + (size_t)set * 3 * e->gsum_third;
-    SigState *const other_state = e->d_state + (size_t)(set ^ 1) * e->max_batch;
-    int32_t *const other_gsum = e->d_gsum + (size_t)(set ^ 1) * 3 * e->gsum_third;
-    const int64_t gs_extent = (int64_t)batch * n_groups * kGsumPitch;
-    if (repair_need) {
-        const int64_t ge = 3 * e->gsum_third;
-        const int gb = (int)std::min<int64_t>(std::max<int64_t>((ge + 255) / 256, (batch + 255) / 256), 2048);
-        k_repair_init<<<gb, 256, 0, st>>>(other_state, set_state, repair_need, batch, set_gsum, ge);
-        e->dirty_sig[set] = std::max(e->dirty_sig[set], batch);
-    } else if (nan_input || capturing || e->dirty_sig[set] > 0 || e->dirty_gs[set] > 0) {
-        const int64_t ge = 3 * e->gsum_third;   // the buffers are small: clear all of them
-        const int gb = (int)std::min<int64_t>(std::max<int64_t>((ge + 255) / 256, (batch + 255) / 256), 2048);
-        k_init_state<<<gb, 256, 0, st>>>(set_state, batch, set_gsum, ge, nan_input ? 1 : 0);
-        e->dirty_sig[set] = std::max(e->dirty_sig[set], batch);
-    } else {
-        e->dirty_sig[set] = batch;
-    }
-    e->dirty_gs[set] = gs_extent;
-    e->cur_set = set;
+    const int64_t gs_extent = (int64_t)batch * p.n_groups * kGsumPitch;
+    const int set = claim_state_set(e, batch, gs_extent, nan_input, capturing, repair_need, st);
+    p.state = e->d_state + (size_t)set * e->max_batch; p.other_state = e->d_state + (size_t)(set ^ 1) * e->max_batch;
+    p.gsum = e->d_gsum + (size_t)set * 3 * e->gsum_third; p.other_gsum = e->d_gsum + (size_t)(set ^ 1) * 3 * e->gsum_third;
     if (bases_user)  // the reference's timeout result keeps an all-zero last baselines row (ITD.py:385,424)
-        HIP_TRY(e, hipMemset2DAsync(bases_user + (R - 1) * n, (size_t)rows_stride * sizeof(double), 0,
+        HIP_TRY(e, hipMemset2DAsync(bases_user + ((int64_t)M + 1) * n, (size_t)p.rows_stride * sizeof(double), 0,
                                     (size_t)n * sizeof(double), (size_t)batch, st));
-    const int chunk = chunk_of(e, n, batch);
+
     // chunks are independent (per-signal state, counts, records, group sums, slots): with two streams they alternate, so that one
-    // chunk's launch boundaries and tails overlap the other's work (fork after the init, join before the caller's stream goes on)
-    const int n_chunks = (batch + chunk - 1) / chunk;
-    // streams in use: the caller's and S - 1 of the engine's; signals too long for two of them to share the Infinity Cache
-    // (more than 3 * 2^22 samples each) keep to one stream
-    // chunks that share one knot side of the fused levels (grid.y of its launches: at most 65535 signals)
-    const int group = (kf && n_chunks > 1) ? std::max(1, std::min<int>(e->fuse_group, kMaxGridY / chunk)) : 1;
-    const int n_seqs = (n_chunks + group - 1) / group;
-    // The batch pipeline (itd_set_batch_pipeline): with fused levels the chunks do not rotate over the streams — the caller's stream runs
-    // every chunk's level launches and knot side in order, aux_stream[0] the sample passes, each beside the NEXT chunk's knot side
-    // (below).  Not while capturing: a graph replays by its dependencies, a gate would poll in vain.
-    const bool pipelined = kf && !capturing && e->batch_pipeline && e->batch_streams > 1 && n_chunks > 1 && group == 1;
-    const int S = pipelined ? 1 : ((e->chunk == 0 && (int64_t)chunk * n > ((int64_t)3 << 22)) ? 1 : std::min<int>(e->batch_streams, n_seqs));
-    if (pipelined) {
-        if (!e->aux_stream[0]) {
-            HIP_TRY(e, hipStreamCreateWithFlags(&e->aux_stream[0], hipStreamNonBlocking));
-            HIP_TRY(e, hipEventCreateWithFlags(&e->ev_join[0], hipEventDisableTiming));
-        }
-        if (!e->d_kf_started) {
-            HIP_TRY(e, hipMalloc(&e->d_kf_started, 16));
-            HIP_TRY(e, hipMemset(e->d_kf_started, 0, 16));
-            HIP_TRY(e, hipDeviceSynchronize());          // (a fill on the null stream is not ordered with the engine's non-blocking streams)
-            e->kf_started_target = 0;
-        }
-        while (e->ev_pipe.size() < 1) {
-            hipEvent_t ev = nullptr;
-            HIP_TRY(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            e->ev_pipe.push_back(ev);
-        }
-    }
-    if (S > 1) {
+    // chunk's launch boundaries and tails overlap the other's work (fork after the init, join before the caller's stream goes on).
+    // Streams in use: the caller's and S - 1 of the engine's; signals too long for two of them to share the Infinity Cache (more than
+    // 3 * 2^22 samples per chunk) keep to one stream
+    p.chunk = chunk_of(e, n, batch);
+    const int n_chunks = (batch + p.chunk - 1) / p.chunk;
+    p.S = (e->chunk == 0 && (int64_t)p.chunk * n > ((int64_t)3 << 22)) ? 1 : std::min<int>(e->batch_streams, n_chunks);
+    if (p.S > 1) {
         if (!e->ev_fork) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
         HIP_TRY(e, hipEventRecord(e->ev_fork, st));
-        for (int k = 0; k < S - 1; ++k) {
+        for (int k = 0; k < p.S - 1; ++k) {
             if (!e->aux_stream[k]) {
                 HIP_TRY(e, hipStreamCreateWithFlags(&e->aux_stream[k], hipStreamNonBlocking));
                 HIP_TRY(e, hipEventCreateWithFlags(&e->ev_join[k], hipEventDisableTiming));
@@ -617,229 +735,12 @@ int enqueue_decompose(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int
             HIP_TRY(e, hipStreamWaitEvent(e->aux_stream[k], e->ev_fork, 0));
         }
     }
-    // One chunk's launches, in three phases: 1 = the level launches + k_finalize, 2 = the fused levels' knot side, 4 = their sample
-    // pass.  Without fused levels a chunk is phase 1 alone.  With them, `group` consecutive chunks share ONE knot side: its dozen
-    // launches are bound by their boundaries (6-9 us each whatever the list lengths) and cannot hide behind another stream's
-    // memory-bound launches (measured: a short launch that meets a long one from the other stream ends when the long one ends, on a
-    // stream of the highest priority as well), so they are amortised over more signals instead — while the level launches keep the
-    // chunk size at which a level's baseline is still in the Infinity Cache for the next level.
-    auto run_chunk = [&](const int b0, const int nb, const hipStream_t cst, const int phase) -> int {
-        // signals b0 .. b0+nb-1: grid.y, every per-signal pointer offset by b0
-        auto gs = [&](int level) { return set_gsum + (int64_t)(level % 3) * e->gsum_third + (int64_t)b0 * n_groups * kGsumPitch; };
-        auto cnt = [&](int level) { return e->d_counts + (int64_t)(level & 1) * e->tiles_half + (int64_t)b0 * n_tiles; };
-        auto rec = [&](int level) { return e->d_recs + (int64_t)(level & 1) * e->tiles_half + (int64_t)b0 * n_tiles; };
-        SigState *state = set_state + b0;
-        const Tin *xc = x + (int64_t)b0 * x_stride;
-        double *rows_c = rows + (int64_t)b0 * rows_stride;
-        double *bases_c = bases_user ? bases_user + (int64_t)b0 * rows_stride : nullptr;
-        double *pp_c = e->d_pp + (int64_t)b0 * 3 * e->pp_pitch;
-        double *xm_c = pp_c + 2 * e->pp_pitch;   // NaN-input repeat: the mutated signal, one per signal at the slots' stride
-        const int j_last = kf ? L0 - 1 : M + 1;
-        unsigned long long *near_c = kf ? e->kf.nearw + (size_t)b0 * n_tiles * 8 : nullptr;
-        // the level launches ja .. jb of this chunk (one k_extract each)
-        auto run_levels = [&](const int ja, const int jb) -> int {
-        for (int j = ja; j <= jb; ++j) {
-            // extraction j+1: input = level-j signal, rotation -> rows[j], baseline -> bases[j]
-            double *base_out;
-            int64_t base_stride;
-            const double *base_in = nullptr;
-            int64_t base_in_stride = 0;
-            if (bases_c) {
-                base_out = bases_c + (int64_t)j * n;
-                base_stride = rows_stride;
-                if (j >= 1) { base_in = bases_c + (int64_t)(j - 1) * n; base_in_stride = rows_stride; }
-            } else {
-                base_out = pp_c + (int64_t)(j % 3) * e->pp_pitch;
-                base_stride = 3 * e->pp_pitch;
-                if (j >= 1) { base_in = pp_c + (int64_t)((j - 1) % 3) * e->pp_pitch; base_in_stride = 3 * e->pp_pitch; }
-            }
-            double *rot_out = rows_c + (int64_t)j * (n + ITD_ROW_PAD);
-            const bool final_level = j == M + 1;        // (with fused levels: only behind capped ones)
-            const int pair = time_slot(e, final_level ? ITD_TIME_EXTRACT_FINAL : (j == 0 ? ITD_TIME_EXTRACT_L0 : ITD_TIME_EXTRACT));
-            // launched through hipExtLaunchKernel: when this step is instrumented the two events take the dispatch's own
-            // begin / end timestamps (no marker packets in the stream: nothing is added to the timed region)
-#define ITD_LAUNCH_EXTRACT(TIN, FIN, XIN, XSTRIDE, CAPK, FUSE) ITD_LAUNCH_EXTRACT_KT(TIN, FIN, XIN, XSTRIDE, CAPK, FUSE, kTilesPerWave, false)
-#define ITD_LAUNCH_EXTRACT_KT(TIN, FIN, XIN, XSTRIDE, CAPK, FUSE, KTW, TIES)                                                \
-    do {                                                                                                                   \
-        const TIN *a_x = XIN; int64_t a_xs = XSTRIDE, a_n = n, a_rs = rows_stride, a_bs = base_stride;                     \
-        int a_nt = n_tiles, a_b = nb, a_lvl = j, a_keep = 0;                                                               \
-        const int32_t *a_ci = cnt(j), *a_gi = gs(j); int32_t *a_co = cnt(j + 1), *a_go = gs(j + 1), *a_gc = gs(j + 2);      \
-        const TileRec *a_ri = rec(j); TileRec *a_ro = rec(j + 1); double *a_rot = rot_out, *a_bas = base_out;              \
-        SigState *a_st = state; unsigned long long *a_tie = (TIES) ? near_c : nullptr;                                                 \
-        void *args[] = {&a_x, &a_xs, &a_n, &a_nt, &a_b, &a_ci, &a_co, &a_ri, &a_ro, &a_gi, &a_go, &a_gc, &a_rot, &a_rs,    \
-                        &a_bas, &a_bs, &a_st, &a_lvl, &a_keep, &a_tie};                                                    \
-        HIP_TRY(e, hipExtLaunchKernel(reinterpret_cast<const void *>(&k_extract<TIN, T, FIN, CAPK, KTW, FUSE, TIES>),              \
-                                      dim3((n_tiles + (KTW) - 1) / (KTW), nb),                                               \
-                                      blk, args, 0, cst, pair >= 0 ? e->ev[2 * (size_t)pair] : nullptr,                    \
-                                      pair >= 0 ? e->ev[2 * (size_t)pair + 1] : nullptr, 0));                              \
-    } while (0)
-            if (j == 0) {   // never the last level: M >= 0
-                if (nan_input) ITD_LAUNCH_EXTRACT(double, false, xm_c, 3 * e->pp_pitch, kRankCap0, false);
-                else if (fuse0) ITD_LAUNCH_EXTRACT_KT(Tin, false, xc, x_stride, kRankCap0, true, kFuse0TilesPerWave, false);
-                else ITD_LAUNCH_EXTRACT(Tin, false, xc, x_stride, kRankCap0, false);
-            } else {
-                if (final_level) ITD_LAUNCH_EXTRACT(double, true, base_in, base_in_stride, kRankCap, false);
-                // (the launch in front of the fused sparse levels also flags the tiles of its baseline that hold a near tie)
-                else if (kf && j == j_last) ITD_LAUNCH_EXTRACT_KT(double, false, base_in, base_in_stride, kRankCap, false, kTilesPerWave, true);
-                else ITD_LAUNCH_EXTRACT(double, false, base_in, base_in_stride, kRankCap, false);
-            }
-#undef ITD_LAUNCH_EXTRACT
-#undef ITD_LAUNCH_EXTRACT_KT
-        }
-        return ITD_OK;
-        };
-        // stop test on the last pending baseline (ITD.py:400-404 takes priority over the timeout branch) and the residual row
-        auto run_finalize = [&]() {
-            // blocks per signal: a thread of the row fix-up moves 8 samples (four 16-byte accesses) before the grid is widened
-            const int fb = (int)std::min<int64_t>(std::max<int64_t>((n + 8 * kFinalizeThreads - 1) / (8 * kFinalizeThreads), 1), 1024);
-            int32_t *og = other_gsum + (int64_t)b0 * n_groups * kGsumPitch;
-            const int jf = M + 2;      // the level whose input is pending
-            if (bases_c)
-                k_finalize<<<dim3(fb, nb), kFinalizeThreads, 0, cst>>>(rows_c, rows_stride, n, bases_c, rows_stride, n, 0,
-                                                                       gs(jf), n_tiles, jf, state, other_state + b0, og, e->gsum_third);
-            else
-                k_finalize<<<dim3(fb, nb), kFinalizeThreads, 0, cst>>>(rows_c, rows_stride, n, pp_c, 3 * e->pp_pitch,
-                                                                       e->pp_pitch, 3, gs(jf), n_tiles, jf, state, other_state + b0, og, e->gsum_third);
-        };
-        if (phase & 1) {
-        if (nan_input) {
-            k_nan_level0<Tin, T><<<dim3(n_tiles, nb), blk, 0, cst>>>(xc, x_stride, n, n_tiles, xm_c, 3 * e->pp_pitch, cnt(0), rec(0),
-                                                                    gs(0), state);
-        } else if (!fuse0) {
-            const int pair = time_slot(e, ITD_TIME_SCAN0);
-            const Tin *a_x = xc; int64_t a_xs = x_stride, a_n = n; int a_nt = n_tiles;
-            int32_t *a_c = cnt(0), *a_g = gs(0); TileRec *a_r = rec(0); SigState *a_st = state; int a_lv = 0;
-            void *args[] = {&a_x, &a_xs, &a_n, &a_nt, &a_c, &a_r, &a_g, &a_st, &a_lv};
-            HIP_TRY(e, hipExtLaunchKernel(reinterpret_cast<const void *>(&k_scan0<Tin, T, kScanTilesPerWave>),
-                                          dim3((n_tiles + kScanTilesPerWave - 1) / kScanTilesPerWave, nb), blk, args, 0, cst,
-                                          pair >= 0 ? e->ev[2 * (size_t)pair] : nullptr,
-                                          pair >= 0 ? e->ev[2 * (size_t)pair + 1] : nullptr, 0));
-        }
-
-        {
-            const int rc = run_levels(0, j_last);
-            if (rc) return rc;
-        }
-        // With fused sparse levels the knot side's launch does k_finalize's work for its first level (k_kf_knots: KfFin) — one launch less
-        if (!kf) run_finalize();
-        }
-        if (kf && (phase & 6)) {
-            // ---- levels L0 .. M + 1 fused: hand-over, the knot-side steps, ONE pass over the samples, the verdict ----
-            KfWs w = e->kf;
-            w.n_tiles = n_tiles; w.L0 = L0; w.nlev = Mk + 3 - L0;
-            w.cap = cap;
-            w.xnext = cap ? pp_c + (int64_t)((cap - 1) % 3) * e->pp_pitch : nullptr; w.xnext_stride = 3 * e->pp_pitch;
-            w.tpw = kf_tpw; w.wgs = (n_tiles + kf_tpw - 1) / kf_tpw; w.nb = nb;
-            // (ids from blockIdx only where the whole grid is resident at once — with S streams in flight each launch may count on
-            //  its share of the device only)
-            w.ticketed = ((int64_t)w.wgs * nb * S > e->kf_resident_wgs || e->kf_force_tickets) ? 1 : 0;
-            w.dbg_kind = e->fault_kind; w.dbg_lev = e->fault_level; w.dbg_wg = e->fault_where; w.dbg_slot = e->fault_slot; w.dbg_delta = e->fault_delta;
-            w.dbg_sig = e->fault_sig - b0;               // (relative to this launch's first signal; outside it: no workgroup matches)
-            w.started = pipelined ? e->d_kf_started : nullptr;
-            const size_t B0 = (size_t)b0;
-            w.sig += B0; w.pool += B0 * (size_t)w.wgs_max * kKcSlab; w.rec += B0 * (size_t)w.rec_levels * w.wgs_max * kKcRecGran;
-            w.first += B0 * (size_t)w.nlev * n_tiles; w.tflags += B0 * (size_t)w.nlev * n_tiles * 8; w.nearw += B0 * (size_t)n_tiles * 8;
-            // (the per-signal strides of `first` / `tflags` follow this call's geometry: nlev levels x n_tiles tiles per signal)
-            const double *xl = bases_c ? bases_c + (int64_t)(L0 - 1) * n : pp_c + (int64_t)((L0 - 1) % 3) * e->pp_pitch;
-            const int64_t xl_stride = bases_c ? rows_stride : 3 * e->pp_pitch;
-            const hipStream_t kst = cst;
-            if (phase & 2) {
-                // ONE launch: hand-over and every fused level (timed from its dispatch's own begin / end timestamps)
-                const int p_kn = time_slot(e, ITD_TIME_KF_KNOTS);
-                KfWs a_w = w; int64_t a_ls = xl_stride, a_n = n; const double *a_xl = xl; int a_m = Mk;
-                const int32_t *a_c = cnt(L0); const TileRec *a_r = rec(L0); SigState *a_st = state;
-                KfFin a_f;      // k_finalize's work for the first fused level (the stop test of its input, the other state set)
-                a_f.rows = rows_c; a_f.rows_stride = rows_stride;
-                a_f.bases = bases_c ? bases_c : pp_c; a_f.bases_stride = bases_c ? rows_stride : 3 * e->pp_pitch;
-                a_f.bases_row_pitch = bases_c ? n : e->pp_pitch; a_f.bases_rotate = bases_c ? 0 : 3;
-                a_f.gsum = gs(L0); a_f.other_state = other_state + b0; a_f.other_gsum = other_gsum + (int64_t)b0 * n_groups * kGsumPitch;
-                a_f.other_third = e->gsum_third;
-                void *args[] = {&a_w, &a_f, &a_xl, &a_ls, &a_n, &a_m, &a_c, &a_r, &a_st};
-                HIP_TRY(e, hipExtLaunchKernel(reinterpret_cast<const void *>(&k_kf_knots<T>), dim3((unsigned)w.wgs * (unsigned)nb), dim3(kKcThreads), args, 0, kst,
-                                              p_kn >= 0 ? e->ev[2 * (size_t)p_kn] : nullptr, p_kn >= 0 ? e->ev[2 * (size_t)p_kn + 1] : nullptr, 0));
-                if (w.started) e->kf_started_target += (unsigned long long)w.wgs * (unsigned long long)nb;
-            }
-            if (phase & 4) {
-#ifdef ITD_DEBUG_GAP
-                k_debug_gap<<<1, 64, 0, cst>>>((long long)(ITD_DEBUG_GAP) * 100);
-#endif
-                if (e->fault_kind >= 0 && (e->fault_kind <= 5 || e->fault_kind == 8) && e->fault_level >= L0 && e->fault_level - L0 < w.nlev && e->fault_where >= 0 &&
-                    e->fault_where < n_tiles && e->fault_sig >= b0 && e->fault_sig < b0 + nb)      // (tests only) one field of what the sample pass is about to read, perturbed
-                    k_kf_fault<<<1, 64, 0, cst>>>(w, e->fault_sig - b0, e->fault_kind, e->fault_level - L0, e->fault_where, e->fault_slot & 0xffff, e->fault_delta);
-                const int pair = time_slot(e, ITD_TIME_KF_APPLY);
-                KfWs a_w = w; const double *a_xl = xl; int64_t a_xs = xl_stride, a_n = n, a_rs = rows_stride, a_bs = rows_stride;
-                const TileRec *a_rec = rec(L0); double *a_rows = rows_c, *a_bases = bases_c;
-                void *args[] = {&a_w, &a_xl, &a_xs, &a_n, &a_rec, &a_rows, &a_rs, &a_bases, &a_bs};
-                const void *apply_fn = cap ? (bases_c ? reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, true, true>) : reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, true>))
-                                           : (bases_c ? reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, true, false>) : reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, false>));
-                HIP_TRY(e, hipExtLaunchKernel(apply_fn, dim3(n_tiles + kf_check_blocks(w.wgs), nb), dim3(kWave), args, 0, cst,
-                                              pair >= 0 ? e->ev[2 * (size_t)pair] : nullptr, pair >= 0 ? e->ev[2 * (size_t)pair + 1] : nullptr, 0));
-                if (cap) {
-                    // ---- capped: levels cap .. M + 1 one launch each, from a scan of the baseline the sample pass has stored (the
-                    //      input of level cap: its knots' records, counts and group sums, the level's end samples).  A signal that
-                    //      stopped inside the fused levels carries SigState::skip: these launches return at once for it.  Should the
-                    //      fused levels refuse, the whole call is repeated anyway: what runs here then is discarded.
-                    const int64_t ge = (int64_t)nb * n_groups * kGsumPitch;
-                    k_clear_gsum<<<(int)std::min<int64_t>((ge + 255) / 256, 1024), 256, 0, cst>>>(gs(cap), gs(cap + 1), ge);
-                    const double *a_x = bases_c ? bases_c + (int64_t)(cap - 1) * n : pp_c + (int64_t)((cap - 1) % 3) * e->pp_pitch;
-                    k_scan0<double, T, kScanTilesPerWave><<<dim3((n_tiles + kScanTilesPerWave - 1) / kScanTilesPerWave, nb), blk, 0, cst>>>(
-                        a_x, bases_c ? rows_stride : 3 * e->pp_pitch, n, n_tiles, cnt(cap), rec(cap), gs(cap), state, cap);
-                    const int rc = run_levels(cap, M + 1);
-                    if (rc) return rc;
-                    run_finalize();
-                }
-            }
-        }
-        return ITD_OK;
-    };
-    if (pipelined) {
-        // caller's stream X:   A_0 K_0 | A_1 K_1 | A_2 K_2 | ...                      A_k: chunk k's level launches, K_k: its knot side
-        // aux_stream[0]   Y:        g_1 P_0 | g_2 P_1 | ...  | P_last                P_k: its sample pass, g_k: a gate (k_kf_gate)
-        // A knot side needs room when it STARTS: 65 KB of LDS and eight wave slots per workgroup, which a device full of one-wavefront
-        // workgroups never has (profiles/r04/experiments/README.md) — but once its workgroups are resident it needs no bandwidth and
-        // runs hidden beside a memory-bound launch.  So K_k follows A_k in stream order (started ~2 us after A_k's last wavefront has
-        // gone), and the OTHER stream's next sample pass waits behind a gate — one wavefront that returns when every workgroup of
-        // K_k has started (KfWs::started) — instead of filling the device the moment A_k drains.  P_{k-1} then runs beside K_k, its
-        // tail beside A_{k+1}.  The gate also orders P_{k-1} behind K_{k-1}, which ended before A_k began.  No event crosses the
-        // queues on the way (an event costs ~13 us of idle device, measured), except at the call's two ends.
-        const hipStream_t q = e->aux_stream[0];
-        if (!e->ev_fork) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-        HIP_TRY(e, hipEventRecord(e->ev_fork, st));
-        HIP_TRY(e, hipStreamWaitEvent(q, e->ev_fork, 0));
-        for (int k = 0; k < n_chunks; ++k) {
-            const int b0 = k * chunk, nb = std::min(chunk, batch - b0);
-            int rc = run_chunk(b0, nb, st, 3);
-            if (rc) return rc;
-            if (k >= 1) {
-                // (a gate that gives up says so: itd_get_summary; fault kind 9, tests only: a target no knot side reaches — the gate gives up)
-                k_kf_gate<<<1, kWave, 0, q>>>(e->d_kf_started, e->fault_kind == 9 ? ~0ull : e->kf_started_target, e->pipe_gate_timeout);
-                rc = run_chunk(b0 - chunk, chunk, q, 4);
-                if (rc) return rc;
-            }
-        }
-        HIP_TRY(e, hipEventRecord(e->ev_pipe[0], st));
-        HIP_TRY(e, hipStreamWaitEvent(q, e->ev_pipe[0], 0));
-        const int bl = (n_chunks - 1) * chunk;
-        const int rc = run_chunk(bl, batch - bl, q, 4);
-        if (rc) return rc;
-        HIP_TRY(e, hipEventRecord(e->ev_join[0], q));
-        HIP_TRY(e, hipStreamWaitEvent(st, e->ev_join[0], 0));
-    }
-    int seq_no = 0;
-    for (int s0 = pipelined ? batch : 0; s0 < batch; s0 += chunk * group, ++seq_no) {
-        const int lane_s = seq_no % S;
-        const hipStream_t cst = lane_s == 0 ? st : e->aux_stream[lane_s - 1];   // this launch sequence's stream
-        const int s1 = std::min(batch, s0 + chunk * group);
-        int rc = ITD_OK;
-        if (group == 1) rc = run_chunk(s0, s1 - s0, cst, 7);
-        else {
-            for (int b0 = s0; b0 < s1 && !rc; b0 += chunk) rc = run_chunk(b0, std::min(chunk, s1 - b0), cst, 1);
-            if (!rc) rc = run_chunk(s0, s1 - s0, cst, 2);
-            for (int b0 = s0; b0 < s1 && !rc; b0 += chunk) rc = run_chunk(b0, std::min(chunk, s1 - b0), cst, 4);
-        }
+    for (int k = 0; k < n_chunks; ++k) {
+        const int b0 = k * p.chunk, lane = k % p.S;
+        const int rc = run_chunk(e, p, b0, std::min(p.chunk, batch - b0), lane == 0 ? st : e->aux_stream[lane - 1]);
         if (rc) return rc;
     }
-    for (int k = 0; k < S - 1; ++k) {
+    for (int k = 0; k < p.S - 1; ++k) {
         HIP_TRY(e, hipEventRecord(e->ev_join[k], e->aux_stream[k]));
         HIP_TRY(e, hipStreamWaitEvent(st, e->ev_join[k], 0));
     }
@@ -854,24 +755,11 @@ int enqueue_decompose(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int
     }
     HIP_TRY(e, hipGetLastError());
     e->ran = true;
-    e->last_batch = batch;
-    e->last_m = M;
-    e->last_n = n;
-    e->last_stream = st;
-    e->last_x = x;
-    e->last_x_f32 = sizeof(Tin) == 4;
-    e->last_x_stride = x_stride;
-    e->last_rows = rows;
-    e->last_bases = bases_user;
-    e->last_fused = fuse0;
-    e->last_resident = false;
-    e->last_nan_input = nan_input;
-    e->last_kf = kf;
-    e->last_kf_level = L0;
-    e->last_kf_cap = kf ? cap : 0;
-    e->last_pipelined = pipelined;
-    if (pipelined) e->pipe_word_unread = true;
-    if (!repair_need) { e->last_kf_form = kf ? L0 : 0; e->last_kf_cap_form = kf ? cap : 0; }
+    e->last_batch = batch; e->last_m = M; e->last_n = n; e->last_stream = st;
+    e->last_x = x; e->last_x_f32 = sizeof(Tin) == 4; e->last_x_stride = x_stride; e->last_rows = rows; e->last_bases = bases_user;
+    e->last_fused = fuse0; e->last_resident = false; e->last_nan_input = nan_input;
+    e->last_kf = kf; e->last_kf_level = p.L0; e->last_kf_cap = kf ? p.cap : 0;
+    if (!repair_need) { e->last_kf_form = kf ? p.L0 : 0; e->last_kf_cap_form = kf ? p.cap : 0; }
     return ITD_OK;
 }
 
@@ -992,8 +880,7 @@ int enqueue_any(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int64_t x
     SigState *state_a = e->d_state + (size_t)e->cur_set * e->max_batch;
     int32_t *valid = e->valid_dev ? e->valid_dev : e->d_valid_own;
     const int follow = e->nan_input_mode == ITD_NAN_INPUT_FOLLOW ? 1 : 0;
-    k_verdict<<<vb, 64, 0, st>>>(state_a, batch, e->last_kf ? e->kf.sig : nullptr, e->last_kf_level, follow, valid, e->device_repair ? e->d_need : nullptr,
-                                 (e->last_kf && e->last_pipelined) ? e->d_kf_started + 1 : nullptr);
+    k_verdict<<<vb, 64, 0, st>>>(state_a, batch, e->last_kf ? e->kf.sig : nullptr, e->last_kf_level, follow, valid, e->device_repair ? e->d_need : nullptr);
     if (e->device_repair) {
         // the same call level by level (record-driven level 0: any knot spacing), guarded per signal by d_need: rows_dev is final
         // when the stream has drained, with no host synchronisation in between
@@ -1146,8 +1033,6 @@ int itd_engine_create(itd_engine **out, int device_id, int64_t max_n, int32_t ma
     e->max_n = max_n;
     e->max_batch = max_batch;
     e->max_tiles = tiles_of(max_n);
-    // (sweeps only, tools/pipeline_sweep.py: the batch pipeline's two constants)
-    if (const char *v = getenv("PYITD_PIPE_GATE_US")) e->pipe_gate_timeout = 100ll * atoll(v);
     DevGuard g(device_id);
     const size_t B = (size_t)max_batch;
     const int max_groups = groups_of((int)e->max_tiles);
@@ -1199,7 +1084,6 @@ void itd_engine_destroy(itd_engine *e)
     (void)hipFree(e->d_sp); (void)hipFree(e->d_sp2); (void)hipFree(e->d_wpe);
     if (e->h_state) (void)hipHostFree(e->h_state);
     if (e->h_kf) (void)hipHostFree(e->h_kf);
-    if (e->h_pipe) (void)hipHostFree(e->h_pipe);
     for (int k = 0; k < 2; ++k) if (e->h_pin[k]) (void)hipHostFree(e->h_pin[k]);
     if (e->h_small) (void)hipHostFree(e->h_small);
     for (auto ev : e->ev) if (ev) (void)hipEventDestroy(ev);
@@ -1209,8 +1093,6 @@ void itd_engine_destroy(itd_engine *e)
         if (e->ev_join[k]) (void)hipEventDestroy(e->ev_join[k]);
     }
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-    for (auto ev : e->ev_pipe) if (ev) (void)hipEventDestroy(ev);
-    (void)hipFree(e->d_kf_started);
     delete e;
 }
 
@@ -1386,33 +1268,13 @@ int repair_signals(itd_engine *e, int B)
 }
 
 // The verdict of the fused sparse levels, drawn from the heads of their KfSig into the signals' states as the host sees them
-// (no launch of its own behind the sample pass): the knot counts of the fused levels, the stop; or kf_fail — the sample pass found a
-// knot the knot side had missed, a list outgrew its workspace, non-finite knot data, too many exact ties.
+// (no launch of its own behind the sample pass): kf_sig_verdict for every signal.
 void kf_verdict(itd_engine *e, int B)
 {
-    const int L0 = e->last_kf_level;
     for (int b = 0; b < B; ++b) {
         KfSig ks;
         memcpy(&ks, e->h_kf + (size_t)b * kKfSigHead, kKfSigHead);
-        SigState &st = e->h_state[b];
-        if (!ks.active) {
-            if (ks.fail) st.kf_fail = ks.fail;
-            continue;
-        }
-        int fail = ks.fail;
-        const int lend = ks.lend;
-        if (lend < 0) fail |= kKfFailCapacity;      // the steps never reached a stop rule (cannot happen: they run to max_iteration + 1)
-        // the last pending baseline feeds only the stop test (ITD.py:400-404): its exact count must take the same side of 2
-        if (!fail && (ks.natural ? ks.m_exact >= 2 : ks.m_exact < 2)) fail |= kKfFailVerify;
-        // (the levels' knot counts — what the stop rules were drawn from — the sample pass has compared with its verified flag words'.)
-        // A level that was decomposed had at least 2 knots (ITD.py:404)
-        for (int j = L0; !fail && j <= lend; ++j) if (j > L0 && ks.mlev[j] < 2) fail |= kKfFailVerify;
-        if (fail) { st.kf_fail = fail; continue; }
-        for (int j = L0 + 1; j <= lend; ++j) st.m[j] = ks.mlev[j];
-        if (ks.cont) continue;          // capped fused levels that did not stop: the level launches behind them wrote the rest of the state
-        st.m[lend + 1] = ks.m_exact;
-        st.fin_stopped = ks.natural;
-        st.fin_stop_level = ks.natural ? lend + 1 : -1;
+        kf_sig_verdict(ks, e->last_kf_level, e->h_state[b]);
     }
 }
 
@@ -1428,23 +1290,8 @@ int itd_get_summary(itd_engine *e, int32_t *n_rows, int32_t *n_baselines, int32_
         if (!e->h_kf) HIP_TRY(e, hipHostMalloc((void **)&e->h_kf, kKfSigHead * (size_t)e->max_batch));
         HIP_TRY(e, hipMemcpy2DAsync(e->h_kf, kKfSigHead, e->kf.sig, sizeof(KfSig), kKfSigHead, (size_t)B, hipMemcpyDeviceToHost, e->last_stream));
     }
-    const bool piped = e->pipe_word_unread;
-    if (piped) {
-        if (!e->h_pipe) HIP_TRY(e, hipHostMalloc((void **)&e->h_pipe, 8));
-        HIP_TRY(e, hipMemcpyAsync(e->h_pipe, e->d_kf_started + 1, 8, hipMemcpyDeviceToHost, e->last_stream));
-    }
     HIP_TRY(e, hipStreamSynchronize(e->last_stream));
     if (e->last_kf) kf_verdict(e, B);
-    e->pipe_word_unread = false;
-    if (piped && *e->h_pipe) {
-        // a gate of the pipelined batch gave up (k_kf_gate: the knot side it waited for did not start within its time-out — another
-        // process's work on the device): a sample pass may have run in front of its own knot side.  Every signal is refused (the whole
-        // call is repeated below) and this engine's batches rotate over the streams from now on.
-        // (behind a device-side repair the call has been re-run level by level already: k_verdict read the same word)
-        if (e->last_kf && e->last_pipelined) for (int b = 0; b < B; ++b) e->h_state[b].kf_fail |= kKfFailWait;
-        HIP_TRY(e, hipMemsetAsync(e->d_kf_started + 1, 0, 8, e->last_stream));
-        e->batch_pipeline = 0;
-    }
     if (e->last_device_repair) {
         // the call carried its own repair (itd_set_device_repair): nothing to repeat here; count what it re-ran and let the engine's
         // next calls start the way that would have delivered (workloads tend to be homogeneous) — as the host-side repeats do
@@ -1560,12 +1407,8 @@ int itd_get_summary(itd_engine *e, int32_t *n_rows, int32_t *n_baselines, int32_
                 return ITD_ERR_HIP;
             }
             e->l0_records_left = 16;
-            const int rc = e->last_x_f32
-                ? enqueue_decompose<float>(e, (const float *)e->last_x, e->last_n, B, e->last_x_stride, e->last_m, e->last_rows, e->last_bases, e->last_stream, false)
-                : enqueue_decompose<double>(e, (const double *)e->last_x, e->last_n, B, e->last_x_stride, e->last_m, e->last_rows, e->last_bases, e->last_stream, false);
+            const int rc = repeat(false, false);
             if (rc) return rc;
-            HIP_TRY(e, hipMemcpyAsync(e->h_state, e->d_state + (size_t)e->cur_set * e->max_batch, sizeof(SigState) * (size_t)B, hipMemcpyDeviceToHost, e->last_stream));
-            HIP_TRY(e, hipStreamSynchronize(e->last_stream));
         }
     }
     for (int b = 0; b < B; ++b) {
@@ -1677,13 +1520,6 @@ int itd_set_fuse_level(itd_engine *e, int32_t first_fused_level)
     return ITD_OK;
 }
 
-int itd_set_fuse_group(itd_engine *e, int32_t chunks)
-{
-    if (!e || chunks < 1 || chunks > 1024) return ITD_ERR_INVALID_ARG;
-    e->fuse_group = chunks;
-    return ITD_OK;
-}
-
 int itd_set_fuse_min_samples(itd_engine *e, int64_t samples)
 {
     if (!e || samples < 0) return ITD_ERR_INVALID_ARG;
@@ -1706,7 +1542,7 @@ int itd_debug_int_ratio_check(int device, int32_t max_den, int64_t *mismatches)
 
 int itd_debug_kf_fault(itd_engine *e, int32_t kind, int32_t level, int32_t where, int32_t slot, int32_t delta)
 {
-    if (!e || kind > 9 || (kind >= 0 && (level < 2 || level > ITD_MAX_ITERATION + 1 || where < 0 || slot < 0))) return ITD_ERR_INVALID_ARG;
+    if (!e || kind > 8 || (kind >= 0 && (level < 2 || level > ITD_MAX_ITERATION + 1 || where < 0 || slot < 0))) return ITD_ERR_INVALID_ARG;
     if ((kind == 6 || kind == 7) && slot > 4) return ITD_ERR_INVALID_ARG;
     e->fault_kind = kind < 0 ? -1 : kind;
     e->fault_level = level; e->fault_where = where; e->fault_slot = slot; e->fault_delta = delta;
@@ -1761,13 +1597,6 @@ int itd_set_batch_streams(itd_engine *e, int32_t streams)
 {
     if (!e || streams < 1 || streams > 4) return ITD_ERR_INVALID_ARG;
     e->batch_streams = streams;
-    return ITD_OK;
-}
-
-int itd_set_batch_pipeline(itd_engine *e, int32_t on)
-{
-    if (!e || on < 0 || on > 1) return ITD_ERR_INVALID_ARG;
-    e->batch_pipeline = on;
     return ITD_OK;
 }
 

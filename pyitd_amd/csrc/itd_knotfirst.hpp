@@ -96,9 +96,6 @@ constexpr uint32_t kKcPoison = 0xffffffffu;      // a record of a workgroup that
 #ifndef ITD_KF_CHECK_STEP
 #define ITD_KF_CHECK_STEP 2       // A/B builds: 1 = one table entry per lane and round in the check wavefronts
 #endif
-#ifndef ITD_KC_PRIO
-#define ITD_KC_PRIO 0
-#endif
 #ifndef ITD_KC_TIMEOUT
 #define ITD_KC_TIMEOUT 4000000ll                 // ticks of the 100 MHz wall clock a halo search waits at most (40 ms)
 #endif
@@ -140,6 +137,32 @@ struct KfSig {
 constexpr size_t kKfSigHead = (8 + (kMaxLevels + 2)) * sizeof(int32_t);
 static_assert(offsetof(KfSig, acc_mlev) == kKfSigHead, "KfSig layout");
 
+// The verdict of the fused levels for one signal, drawn from the head of its KfSig into the signal's state (the host's kf_verdict when
+// the summary is read, the device's k_verdict behind the call): the knot counts of the fused levels and the stop, or kf_fail — the
+// sample pass found a knot the knot side had missed, a list outgrew its workspace, non-finite knot data, too many exact ties.
+// Reads only fields inside the head (the host holds nothing else).
+__host__ __device__ inline void kf_sig_verdict(const KfSig &ks, int L0, SigState &st)
+{
+    if (!ks.active) {
+        if (ks.fail) st.kf_fail = ks.fail;
+        return;
+    }
+    int fail = ks.fail;
+    const int lend = ks.lend;
+    if (lend < 0) fail |= kKfFailCapacity;      // the steps never reached a stop rule (cannot happen: they run to max_iteration + 1)
+    // the last pending baseline feeds only the stop test (ITD.py:400-404): its exact count must take the same side of 2
+    if (!fail && (ks.natural ? ks.m_exact >= 2 : ks.m_exact < 2)) fail |= kKfFailVerify;
+    // (the levels' knot counts — what the stop rules were drawn from — the sample pass has compared with its verified flag words'.)
+    // A level that was decomposed had at least 2 knots (ITD.py:404)
+    for (int j = L0; !fail && j <= lend; ++j) if (j > L0 && ks.mlev[j] < 2) fail |= kKfFailVerify;
+    if (fail) { st.kf_fail = fail; return; }
+    for (int j = L0 + 1; j <= lend; ++j) st.m[j] = ks.mlev[j];
+    if (ks.cont) return;          // capped fused levels that did not stop: the level launches behind them wrote the rest of the state
+    st.m[lend + 1] = ks.m_exact;
+    st.fin_stopped = ks.natural;
+    st.fin_stop_level = ks.natural ? lend + 1 : -1;
+}
+
 // what the knot side's launch needs to do k_finalize's work (itd_kernels.hpp) for the hand-over level: the stop test of that level's
 // input with its row fix-up, and the other set of states / group sums left initialised for the call after this one
 struct KfFin {
@@ -166,9 +189,6 @@ struct KfWs {
     // receives it at level `lev` is perturbed (kinds 0 .. 5 are applied to the workspace by k_kf_fault between the two launches)
     int32_t dbg_kind, dbg_lev, dbg_wg, dbg_slot, dbg_delta;
     int32_t dbg_sig;              // ... of signal dbg_sig of the launch
-    // the batch pipeline (itd_engine.hip, enqueue_decompose): every knot-side workgroup counts itself here when it starts — a counter that
-    // only ever grows; k_kf_gate on the memory-bound launches' stream returns when all of a launch's workgroups are resident.  NULL: not counted
-    unsigned long long *started;
     // Capped fused levels (partial fusion): cap != 0 = the fused levels end at level cap - 1 although the call asks for more — a workload
     // whose fused form fails at level cap every time (periodic input whose baseline collapses there) keeps the fused form for the levels
     // in front of it.  The sample pass then stores the baseline behind level cap - 1 (the input of level cap) at xnext and the engine
@@ -284,10 +304,6 @@ __global__ __launch_bounds__(kKcThreads) void k_kf_knots(KfWs ws, KfFin fin, con
     for (int i = 0; i < 64; ++i) kc_marks[i] = 0;
 #endif
     KC_MARK(0);
-#if ITD_KC_PRIO
-    __builtin_amdgcn_s_setprio(ITD_KC_PRIO);       // A/B builds: the knot side's wavefronts issue in front of a co-resident launch's (batches)
-#endif
-    if (ws.started && tid == 0) atomicAdd(ws.started, 1ull);      // (in front of every return: the gate counts workgroups, whatever they go on to do)
     int id = blockIdx.x;
     if (ws.ticketed) {
         if (tid == 0) s_i[0] = atomicAdd(&ws.sig[0].ticket, 1);
@@ -1223,23 +1239,6 @@ void k_kf_apply(KfWs ws, const double *__restrict__ xl, int64_t xl_stride, int64
     if ((bad || __any(vbad != 0)) && lane == 0) { atomicOr(&ks->fail, kKfFailVerify); atomicMin(&ks->fail_lev, fl == 99 ? lend : fl); }
 }
 
-// The gate of the batch pipeline: ONE wavefront on the stream of the memory-bound launches.  The knot side of the next chunk has just become
-// ready on the engine's second stream (an event behind the launch that wrote its input); this launch returns when every workgroup of
-// it has started (KfWs::started has reached `target`), so that the launch behind the gate — tens of thousands of one-wavefront
-// workgroups — cannot take the LDS and the wave slots the knot side's 65 KB workgroups need: side by side from then on, the
-// latency-bound launch hides behind the memory-bound ones (tools/anyorder_probe.hip: no gate 229 us, gate 192, the parts 62 + 2 x 87).
-// Gives up after `timeout` ticks of the 100 MHz clock — and says so in started[1]: the gate is also what orders a sample pass behind ITS
-// knot side (which ended before the awaited one could start), so a gate that gave up voids the call: the engine reads the word with
-// the call's summary (or k_verdict does, on the device) and repeats the call level by level.
-__global__ __launch_bounds__(kWave) void k_kf_gate(unsigned long long *started, unsigned long long target, long long timeout)
-{
-    const long long t0 = wall_clock64();
-    while (__hip_atomic_load(started, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-        if (wall_clock64() - t0 > timeout) { if (threadIdx.x == 0) __hip_atomic_store(started + 1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-        __builtin_amdgcn_s_sleep(4);
-    }
-}
-
 // fault injection for the tests (itd_debug_kf_fault): ONE field of the workspace the sample pass is about to read is perturbed,
 // between the knot side's launch and the sample pass.  kind 0 / 1 / 2: X / B / S of entry `slot` (mod the run's length) of tile
 // `tile`'s run at fused level index `li` (delta added to the bit pattern: ulps); 3: its position; 4: first[li][tile]; 5: bit
@@ -1262,7 +1261,7 @@ __global__ void k_kf_fault(KfWs ws, int sig, int kind, int li, int tile, int slo
     if (kind == 3) en->pos += delta;
 }
 
-// The verdict of the fused levels — what k_kf_finish did as a launch of its own — is drawn on the host by itd_get_summary from
-// the head of KfSig (itd_engine.hip: kf_verdict).
+// The verdict of the fused levels — what k_kf_finish did as a launch of its own — is drawn from the head of KfSig by kf_sig_verdict
+// (above): on the host when itd_get_summary reads it, on the device by k_verdict (itd_engine.hip).
 
 }  // namespace itd

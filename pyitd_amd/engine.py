@@ -50,18 +50,12 @@ class Engine:
         mode = os.environ.get("PYITD_FUSE_CAP")         # capped fused levels (a whole suite with the fused levels cut at this level)
         if mode:
             self.set_fuse_cap(int(mode))
-        mode = os.environ.get("PYITD_FUSE_GROUP")       # chunks of a batch per knot side of the fused levels (sweeps)
-        if mode:
-            self.set_fuse_group(int(mode))
         mode = os.environ.get("PYITD_FUSE_RANGE")       # tiles per knot-side workgroup of the fused levels (sweeps; 16 / 32 / 64)
         if mode:
             self.set_fuse_range(int(mode))
         mode = os.environ.get("PYITD_FUSE_MIN")         # samples per launch sequence from which FUSE_AUTO fuses (tests: 65536)
         if mode:
             self.set_fuse_min_samples(int(mode))
-        mode = os.environ.get("PYITD_BATCH_PIPELINE")   # fused batches: 1 = pipelined instead of rotating chunks (A/B runs)
-        if mode:
-            self.set_batch_pipeline(int(mode))
         mode = os.environ.get("PYITD_RESIDENT_MODE")    # and for the one-workgroup form of short signals (RESIDENT_*)
         if mode:
             self.set_resident_mode(int(mode))
@@ -186,10 +180,6 @@ class Engine:
         launch is bound by its boundary and the fused form has more of them)."""
         self._check(self._L.itd_set_fuse_min_samples(self._h, int(samples)))
 
-    def set_fuse_group(self, chunks):
-        """Batches: consecutive chunks that share one knot side of the fused levels (default 4)."""
-        self._check(self._L.itd_set_fuse_group(self._h, int(chunks)))
-
     @property
     def fuse_repeats(self):
         """Calls of this engine that itd_get_summary had to repeat level by level because the fused levels reported a failure."""
@@ -227,11 +217,6 @@ class Engine:
     def set_batch_streams(self, streams):
         """1 or 2: the chunks of a batched decomposition alternate over that many streams."""
         self._check(self._L.itd_set_batch_streams(self._h, int(streams)))
-
-    def set_batch_pipeline(self, on):
-        """Fused batches: 1 = chunk k's pass over the samples runs on the engine's second stream beside chunk k + 1's knot side (behind a
-        gate: include/pyitd_hip.h); 0 (default, measured faster on MI355X) = the chunks rotate over the streams."""
-        self._check(self._L.itd_set_batch_pipeline(self._h, int(on)))
 
     def kernel_timing(self, which=TIME_EXTRACT):
         """(total ms, launches) of the recorded launches of class `which` (TIME_*)."""

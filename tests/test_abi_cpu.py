@@ -32,8 +32,8 @@ def test_library_exports_every_declared_symbol(lib):
     assert sorted(ABI) == names, "pyitd_amd/_lib.py prototypes and include/pyitd_hip.h disagree"
 
 
-def test_abi_version_and_status_strings(lib):
-    assert lib.itd_abi_version() == 11
+def test_abi_revision_12_and_status_strings(lib):
+    assert lib.itd_abi_version() == 12
     assert lib.itd_status_string(0) == b"ok"
     assert b"argument" in lib.itd_status_string(1)
 

@@ -818,35 +818,30 @@ def test_the_inputs_of_round_four_s_wrong_rows(P, torch, oracle, tiles):
     assert delivered >= 8
 
 
-def test_batch_pipeline_equals_the_rotating_chunks(P, torch, oracle):
-    """itd_set_batch_pipeline(1): the chunks' knot sides in stream order behind their level launches, the sample passes on the engine's
-    second stream behind a gate (itd_engine.hip) — the same rows, bit for bit, as the rotating chunks and the oracle; a refusing member
-    is run again on its own in either form."""
+def test_a_fused_batch_in_rotating_chunks_equals_the_oracle(P, torch, oracle):
+    """A fused batch in chunks of five signals, the last one short, rotating over the engine's streams, twice on one engine: every row
+    bit for bit the oracle's; a refusing member is run again on its own."""
     from pyitd_amd.engine import FUSE_AUTO
     n, m, B = 1 << 17, 7, 24
     x = np.stack([sines_noise(n, seed=300 + b, fscale=1 + b / 64.0) for b in range(B)])
     x[13] = coarse(x[13])
     refs = [oracle.itd_lean(x[b], m) for b in range(B)]
     xd = torch.from_numpy(x).cuda()
-    got = []
-    for pipe in (0, 1):
-        eng = P.Engine(n, B, 0)
-        eng.set_fuse_mode(FUSE_AUTO)
-        eng.set_fuse_min_samples(65536)
-        eng.set_batch_chunk(5)                       # five chunks, the last one short
-        eng.set_batch_pipeline(pipe)
-        rows = torch.full((B, m + 2, n), float("nan"), dtype=torch.float64, device="cuda")
-        torch.cuda.synchronize()
-        for _ in range(2):                           # (twice: the engine's state sets and the gate's counter go on from call to call)
-            eng.decompose_dev(xd.data_ptr(), np.float32, n, B, n, m, rows.data_ptr(), None, None)
-            s = eng.summary(B)
-        assert eng.last_fuse_level >= 2 and eng.fuse_repeats == 0 and eng.fuse_signal_repairs == 2
-        for b in range(B):
-            nr = refs[b]["rows"].shape[0]
-            assert int(s["n_rows"][b]) == nr
-            assert_bits_equal(rows[b, :nr].cpu().numpy(), refs[b]["rows"], "pipeline %d, signal %d" % (pipe, b))
-        got.append(rows)
-        eng.close()
+    eng = P.Engine(n, B, 0)
+    eng.set_fuse_mode(FUSE_AUTO)
+    eng.set_fuse_min_samples(65536)
+    eng.set_batch_chunk(5)                       # five chunks, the last one short
+    rows = torch.full((B, m + 2, n), float("nan"), dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    for _ in range(2):                           # (twice: the engine's state sets go on from call to call)
+        eng.decompose_dev(xd.data_ptr(), np.float32, n, B, n, m, rows.data_ptr(), None, None)
+        s = eng.summary(B)
+    assert eng.last_fuse_level >= 2 and eng.fuse_repeats == 0 and eng.fuse_signal_repairs == 2
+    for b in range(B):
+        nr = refs[b]["rows"].shape[0]
+        assert int(s["n_rows"][b]) == nr
+        assert_bits_equal(rows[b, :nr].cpu().numpy(), refs[b]["rows"], "signal %d" % b)
+    eng.close()
 
 
 def _run_capped(P, torch, x, m, L0, cap, bases):
@@ -957,47 +952,6 @@ def test_a_workload_that_fails_at_one_level_keeps_the_levels_in_front_of_it_fuse
     assert seen[0] == cap and seen[-1] == 0 and eng.fuse_repeats == 2, seen
     assert_bits_equal(rows[: int(s["n_rows"][0])].cpu().numpy(), ref_y["rows"], "the other workload")
     eng.close()
-
-
-def test_a_gate_that_gives_up_voids_the_pipelined_call(P, torch, oracle, monkeypatch):
-    """The pipelined batch's gate is also what orders a sample pass behind its own knot side; one that gives up (here: a time-out of zero,
-    PYITD_PIPE_GATE_US=0, and a knot side that never starts, fault kind 9) says so, and the call is void: refused as a whole, repeated level
-    by level — the oracle's rows —, and the engine's later batches rotate over the streams again.  With the repair on the device
-    (itd_set_device_repair) the same holds without the host.  (The fault, not the time-out alone: where the runtime puts the batch's two
-    streams on one hardware queue, GPU_MAX_HW_QUEUES=2, each gate runs after its knot side and never has to wait.)"""
-    from pyitd_amd.engine import FUSE_AUTO
-    monkeypatch.setenv("PYITD_PIPE_GATE_US", "0")
-    n, m, B = 1 << 17, 6, 12
-    x = np.stack([sines_noise(n, seed=500 + b, fscale=1 + b / 64.0) for b in range(B)])
-    refs = [oracle.itd_lean(x[b], m) for b in range(B)]
-    xd = torch.from_numpy(x).cuda()
-    for device_repair in (False, True):
-        eng = P.Engine(n, B, 0)
-        eng.set_fuse_mode(FUSE_AUTO)
-        eng.set_fuse_min_samples(65536)
-        eng.set_batch_chunk(4)
-        eng.set_batch_pipeline(1)
-        eng.debug_kf_fault(9)
-        valid = torch.zeros(B, dtype=torch.int32, device="cuda")
-        if device_repair:
-            eng.set_valid_flags(valid.data_ptr())
-            eng.set_device_repair(True)
-        rows = torch.full((B, m + 2, n), float("nan"), dtype=torch.float64, device="cuda")
-        torch.cuda.synchronize()
-        for call in range(3):
-            rows.fill_(float("nan"))
-            torch.cuda.synchronize()
-            eng.decompose_dev(xd.data_ptr(), np.float32, n, B, n, m, rows.data_ptr(), None, None)
-            s = eng.summary(B)
-            for b in range(B):
-                nr = refs[b]["rows"].shape[0]
-                assert int(s["n_rows"][b]) == nr
-                assert_bits_equal(rows[b, :nr].cpu().numpy(), refs[b]["rows"], "call %d, signal %d, device repair %s" % (call, b, device_repair))
-        if device_repair:
-            assert eng.device_repairs >= B and bool((valid == 1).all())
-        else:
-            assert eng.fuse_repeats == 1          # the first call only: the engine left the pipelined form behind
-        eng.close()
 
 
 def test_a_captured_fused_call_survives_a_workspace_change(P, torch, oracle):
