@@ -33,6 +33,7 @@
 #include "itd_nak.hpp"
 #include "itd_wpe.hpp"
 #include "itd_meitd.hpp"
+#include "itd_policy.hpp"
 
 #ifndef ITD_TILE
 #define ITD_TILE 512
@@ -62,7 +63,7 @@ __global__ void k_init_state(SigState *st, int batch, int32_t *gsum, int64_t gsu
 
 // ---- device-visible validity and the device-side repair (itd_set_valid_flags, itd_set_device_repair) ----
 // One thread per signal, behind the last launch of a decomposition: the fused levels' verdict merged into the signal's state (what
-// kf_verdict does on the host when the summary is read), then valid[b] = 1 if the rows in the caller's buffer are final; need[b] = 1
+// read_states does on the host when the summary is read), then valid[b] = 1 if the rows in the caller's buffer are final; need[b] = 1
 // if the optimistic forms fell short for this signal (fused levels refused, fused level 0 out of reach, resident form met a
 // non-finite value) and a level-by-level run would repair it.  A NaN in the caller's signal is neither (the host repeats such a
 // call the way the reference runs it): valid = 0, need = 0.
@@ -146,7 +147,20 @@ __global__ void k_widen_idx(const int32_t *__restrict__ src, int64_t *__restrict
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < cnt) dst[i] = src[i];
 }
+static_assert(FormPolicy::kRangeTiles == kKcTiles && FormPolicy::kFailCapacity == kKfFailCapacity && FormPolicy::kFailWait == kKfFailWait,
+              "itd_policy.hpp restates the fused levels' geometry and fail bits");
 }  // namespace
+
+// The record of the last decomposition enqueued: what itd_get_summary reads back, repeats or repairs, and itd_get_timing, ... refer to
+struct LastCall {
+    int32_t batch = 0, m = 0; int64_t n = 0; hipStream_t stream = nullptr;                              // the call's arguments
+    const void *x = nullptr; bool x_f32 = false; int64_t x_stride = 0; double *rows = nullptr, *bases = nullptr;
+    bool fused = false, resident = false;   // fused level 0; the one-workgroup form (k_resident)
+    bool nan_input = false;        // the NaN-input repeat (k_nan_level0): its results follow the reference
+    bool kf = false;               // fused sparse levels whose verdict is still to be drawn
+    int kf_level = 0, kf_cap = 0;  // their first level and cap (0: all levels fused)
+    int kf_form = 0, kf_cap_form = 0;   // ... as enqueued (itd_get_last_fuse_level / _cap): stay when a summary has drawn the verdict
+};
 
 struct itd_engine {
     int device = 0;
@@ -187,9 +201,7 @@ struct itd_engine {
     hipStream_t aux_stream[3] = {nullptr, nullptr, nullptr};   // the others besides the caller's, created on demand
     hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
 
-    int32_t resident_mode = ITD_RESIDENT_AUTO;   // short signals as one workgroup each, one launch (itd_set_resident_mode)
-    int32_t resident_off_left = 0;  // automatic mode: decompositions still to run level by level after a resident call met a non-finite value
-    int32_t resident_repeats = 0;   // how often itd_get_summary had to repeat a resident call level by level
+    FormPolicy policy;              // which form each call takes, what the summaries have taught (itd_policy.hpp)
     bool resident_attr[12] = {};
     bool nak_small_attr = false;    // hipFuncSetAttribute done for k_nak_small<true>
     bool meitd_attr[2] = {};        // ... for k_meitd_small<false / true>
@@ -203,42 +215,17 @@ struct itd_engine {
     void *d_kf = nullptr; size_t kf_bytes = 0;
     std::vector<void *> kf_retired;  // earlier, smaller workspaces: a captured graph may still hold their pointers — kept until the engine is destroyed
     KfWs kf{};                       // pointers into d_kf, for signal 0
-    int32_t fuse_mode = ITD_FUSE_AUTO, fuse_level = 0, fuse_off_left = 0, fuse_repeats = 0;   // fuse_level 0: automatic (kf_first_level)
-    int32_t fuse_off_span = 16;                      // calls that run level by level after the next whole-call refusal: doubles with every refusal that
-                                                     // follows a back-off directly (a workload the fused form cannot deliver — periodic, collapsing input —
-                                                     // pays one wasted attempt in 17, then 33, ... 1025 calls), back to 16 after a delivered call
-    bool fuse_probe = false;                         // the call being summarised was the first fused attempt after a back-off
-    // capped fused levels: a workload whose fused form fails at the same level every time keeps the fused form for the levels in front of it
-    int32_t fuse_cap = 0;                            // itd_set_fuse_cap: the first level NOT fused (0 = whatever the engine has learned)
-    int32_t fuse_cap_auto = 0;                       // learned from a refusal's KfSig::fail_lev (0 = none)
-    int32_t fuse_cap_calls = 0;                      // delivered calls under the learned cap since the last probe
-    int32_t fuse_cap_span = 16;                      // ... after this many the next call tries all levels again (a probe); doubles, up to 1024,
-                                                     // every time a probe is refused at the learned level again
-    int last_kf_cap = 0, last_kf_cap_form = 0;       // the cap of the last call (as enqueued: itd_get_last_fuse_cap; 0 = all levels fused)
-    bool kf_force_tickets = false;                   // a halo wait was given up on this engine (kKfFailWait): workgroup ids are tickets from then on
-    bool fuse_level2_off = false;                    // automatic first fused level: a level-2 list has outgrown its workgroup, level 3 from then on
-    bool fuse_no_memory = false;                     // the fused levels' workspace could not be allocated: level by level from then on
     // device-visible validity / device-side repair (itd_set_valid_flags, itd_set_device_repair)
     int32_t *valid_dev = nullptr;                    // the caller's [batch] words, written behind every decomposition; NULL = none
     bool device_repair = false;
     int32_t *d_need = nullptr;                       // [max_batch] which signals the repair's launches work on
     int32_t *d_valid_own = nullptr;                  // [max_batch] (the repair needs the words even if the caller gave none)
     bool last_device_repair = false;                 // the last call carried its repair: the summary has nothing to repeat
-    int64_t device_repairs = 0;                      // signals the device-side repair has re-run (counted when a summary is read)
-    int32_t fuse_range = 0;                          // tiles per knot-side workgroup: 0 = automatic, or 16 / 32 / 64 (itd_set_fuse_range)
-    int32_t kf_shrink = 0;                           // automatic: how often a list has outgrown a workgroup (each time halves the range, down to 16 tiles)
     int64_t kf_resident_wgs = 0;                     // knot-side workgroups the device holds at once (occupancy query at creation of the workspace)
-    int64_t fuse_min_samples = (int64_t)2 << 20;   // automatic mode: samples per launch sequence from which the fused form pays
-    int64_t fuse_signal_repairs = 0;   // signals itd_get_summary has re-run on their own (a few of a batch refused the fused form)
-    bool last_kf = false;
-    int last_kf_level = 0;         // the first fused level of that call
-    int last_kf_form = 0;          // ... as enqueued (itd_get_last_fuse_level): stays when a summary has drawn the verdict (last_kf = false then)
     // fault injection into the fused levels' workspace (itd_debug_kf_fault; tests only): kind < 0 = none
     int32_t fault_kind = -1, fault_level = 0, fault_where = 0, fault_slot = 0, fault_delta = 0;
     int32_t fault_sig = 0;         // the signal of the batch the fault lands in (itd_debug_kf_fault_signal)
     int32_t spline_solver = ITD_SPLINE_AUTO;   // FITPACK flavour: serial bit-level sweep or the parallel moment form (itd_set_spline_solver)
-    int32_t l0_mode = ITD_LEVEL0_AUTO;   // how level 0 finds its knots (itd_set_level0_mode)
-    int32_t l0_records_left = 0;   // automatic mode: decompositions still to run record-driven after a fused launch fell short
     int64_t ws_bytes = 0;
     // host-convenience staging (grow only)
     void *d_cub = nullptr; size_t cub_bytes = 0;          // cubic variant: per-signal jobs + K, bf, b (3 arrays of idx+2 doubles each);
@@ -260,16 +247,7 @@ struct itd_engine {
     int64_t kept_n = 0; int32_t kept_nb = -1;   // what itd_get_last_baselines_host can still deliver (-1: nothing)
     // last run
     bool ran = false;
-    int32_t last_batch = 0, last_m = 0;
-    int64_t last_n = 0;
-    hipStream_t last_stream = nullptr;
-    const void *last_x = nullptr;      // the last decomposition's arguments: itd_get_summary repeats it record-driven when the
-    bool last_x_f32 = false;           // fused level-0 launch fell short of a tile's halo knots
-    int64_t last_x_stride = 0;
-    double *last_rows = nullptr, *last_bases = nullptr;
-    bool last_fused = false;
-    bool last_resident = false;        // the last run was the one-workgroup form (k_resident)
-    bool last_nan_input = false;       // the last run was the NaN-input repeat (k_nan_level0): its results follow the reference
+    LastCall last;
     int32_t nan_input_mode = ITD_NAN_INPUT_FOLLOW;   // itd_set_nan_input_mode
     // timing
     bool timing = false;
@@ -356,53 +334,13 @@ int chunk_of(const itd_engine *e, int64_t n, int32_t batch)
     return (int)std::min<int64_t>(std::min<int64_t>(c, kMaxGridY), batch);   // a chunk's signals are the launches' grid.y
 }
 
+// samples per launch sequence: what the policy's automatic choices of the fused levels go by
+inline int64_t seq_samples(const itd_engine *e, int64_t n, int32_t batch) { return (int64_t)std::min<int32_t>(chunk_of(e, n, batch), batch) * n; }
+
 // The workspace of the fused sparse levels (itd_knotfirst.hpp), allocated at the first call that takes that path.  Per signal and
 // knot-side workgroup (kKcTiles tiles): a slab of table entries (32 B per knot and level: kKcSlab of them) and one 256-byte
 // boundary record per level; per level and tile the knots' flag words and the tile's first table index; per tile the near-tie flag words.
 constexpr int kKfLevels = ITD_MAX_ITERATION + 3;
-// tiles per knot-side workgroup: its LDS holds kKcCapH candidates at the hand-over level — the first fused level's knots of its tiles
-// (typically 0.036 / 0.012 n at levels 2 / 3: 18 / 6 per tile, 1180 / 400 per 64-tile range) plus the sticky ones — and kKcCap from
-// the level after it; a call that a list outgrew halves the ranges of the calls after it
-inline int kf_tiles_per_wg(const itd_engine *e, int first_fused_level)
-{
-    (void)first_fused_level;
-    if (e->fuse_range) return e->fuse_range;
-    return std::max(kKcTiles / 4, kKcTiles >> e->kf_shrink);
-}
-// The first fused level.  Automatic: level 2 where a launch sequence covers at least 2^22 samples — one level launch less (-63 us
-// at 2^24) for a sample pass that writes one more row (+22) and a knot side that starts on a 2.6 x longer list (+14): one signal of
-// 2^22 / 2^23 / 2^24 samples 153 / 225 / 377 us against 160 / 243 / 404 from level 3, but 102 against 98 at 2^20
-// (profiles/r05/fuse_level_probe.txt) — unless a level-2 list has outgrown its workgroup on this engine (denser knots than the
-// hand-over layout's 1720 per 64 tiles): level 3 then, before the ranges are halved.
-inline int kf_first_level(const itd_engine *e, int64_t n, int32_t batch)
-{
-    if (e->fuse_level) return e->fuse_level;
-    const int64_t seq = (int64_t)std::min<int32_t>(chunk_of(e, n, batch), batch) * n;
-    return (seq >= ((int64_t)1 << 22) && !e->fuse_level2_off) ? 2 : 3;
-}
-// What the engine's NEXT calls do after fused levels refused with the failure bits `bits` (host-side repeat and device-side repair
-// alike).  A list that outgrew its workgroup: the automatic first fused level goes from 2 to 3, after that the ranges are halved
-// (down to 16 tiles) — the calls stay fused: returns true.  A halo wait given up with nothing else wrong (the grid was not resident
-// at once after all: other work on the device): tickets from now on.  Anything else (verification, non-finite knot data): false —
-// the caller lets the next calls run level by level for a while.
-bool kf_back_off(itd_engine *e, int bits, int level)
-{
-    if (bits & kKfFailCapacity) {
-        if (!e->fuse_level && level == 2 && !e->fuse_level2_off) { e->fuse_level2_off = true; return true; }
-        if (!e->fuse_range && kf_tiles_per_wg(e, level) > kKcTiles / 4) { ++e->kf_shrink; return true; }
-        return false;
-    }
-    if (bits == kKfFailWait && !e->kf_force_tickets) { e->kf_force_tickets = true; return true; }
-    return false;
-}
-// the engine's next calls run level by level: 16 of them after a first refusal, twice as many after every refusal of the probing
-// call that follows a back-off (up to 1024)
-void kf_levels_off(itd_engine *e)
-{
-    if (e->fuse_probe) e->fuse_off_span = std::min(e->fuse_off_span * 2, 1024);
-    e->fuse_off_left = e->fuse_off_span;
-    e->fuse_probe = false;
-}
 int ensure_kf_ws(itd_engine *e, int tpw, bool may_allocate)
 {
     const size_t wgs = (size_t)(e->max_tiles + tpw - 1) / tpw;
@@ -517,7 +455,7 @@ KfWs kf_chunk_ws(const itd_engine *e, const DecomposePlan<Tin> &p, const int b0,
     w.tpw = p.kf_tpw; w.wgs = p.kf_wgs; w.nb = nb;
     // (ids from blockIdx only where the whole grid is resident at once — with S streams in flight each launch may count on its share
     //  of the device only)
-    w.ticketed = ((int64_t)w.wgs * nb * p.S > e->kf_resident_wgs || e->kf_force_tickets) ? 1 : 0;
+    w.ticketed = e->policy.tickets((int64_t)w.wgs * nb * p.S, e->kf_resident_wgs) ? 1 : 0;
     w.dbg_kind = e->fault_kind; w.dbg_lev = e->fault_level; w.dbg_wg = e->fault_where; w.dbg_slot = e->fault_slot; w.dbg_delta = e->fault_delta;
     w.dbg_sig = e->fault_sig - b0;               // (relative to this launch's first signal; outside it: no workgroup matches)
     const size_t B0 = (size_t)b0;
@@ -653,6 +591,19 @@ int claim_state_set(itd_engine *e, int32_t batch, int64_t gs_extent, bool nan_in
     return set;
 }
 
+// The record of the call just enqueued (e->last): its arguments, every form off; the caller sets what its form adds
+template <typename Tin>
+LastCall &record_call(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int64_t x_stride, int32_t M, double *rows, double *bases,
+                      hipStream_t st)
+{
+    LastCall &c = e->last;
+    e->ran = true;
+    c.batch = batch; c.m = M; c.n = n; c.stream = st;
+    c.x = x; c.x_f32 = sizeof(Tin) == 4; c.x_stride = x_stride; c.rows = rows; c.bases = bases;
+    c.fused = c.resident = c.nan_input = c.kf = false;
+    return c;
+}
+
 template <typename Tin>
 int enqueue_decompose(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int64_t x_stride, int32_t M,
                       double *rows, double *bases_user, hipStream_t st, bool fuse0, bool nan_input = false, bool kf = false,
@@ -667,34 +618,27 @@ int enqueue_decompose(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int
     DecomposePlan<Tin> p;
     p.x = x; p.x_stride = x_stride; p.n = n; p.M = M; p.rows = rows; p.bases = bases_user; p.fuse0 = fuse0; p.nan_input = nan_input;
     // kf: levels L0 .. max_iteration + 1 run fused (itd_knotfirst.hpp): one launch per level only for levels 0 .. L0 - 1
-    p.L0 = kf_first_level(e, n, batch);
-    if (!e->fuse_level && p.L0 > M) p.L0 = 2;               // (automatic: few levels asked for)
+    p.L0 = e->policy.first_level(seq_samples(e, n, batch), M);
     kf = kf && fuse0 && p.L0 >= 2 && p.L0 <= M && n < ((int64_t)1 << 31) - 65536;
     // a call that is being captured into a graph must be complete in itself (the graph may be replayed any number of times) and
     // cannot allocate: a captured call on an engine whose fused workspace does not exist yet runs level by level
     hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(st, &cap_status);
     const bool capturing = cap_status != hipStreamCaptureStatusNone;
-    p.kf_tpw = kf_tiles_per_wg(e, p.L0);
+    p.kf_tpw = e->policy.tiles_per_wg();
     if (kf && capturing && ensure_kf_ws(e, p.kf_tpw, false) != ITD_OK) kf = false;
     if (kf) {
         const int rc = ensure_kf_ws(e, p.kf_tpw, true);
-        if (rc == ITD_ERR_NOMEM && e->fuse_mode != ITD_FUSE_ONLY) {
+        if (rc == ITD_ERR_NOMEM && e->policy.workspace_unavailable()) {
             // no room for the fused levels' workspace (136 B x max_n / 8 + 136 B per tile and level, per signal): this engine stays
             // level by level — the result is the same
             (void)hipGetLastError();
-            e->fuse_no_memory = true;
             kf = false;
         } else if (rc) return rc;
     }
     p.kf = kf;
     // capped fused levels: levels L0 .. cap - 1 fused, cap .. M + 1 one launch each behind a scan of the baseline the sample pass leaves
-    p.cap = 0;
-    if (kf) {
-        p.cap = e->fuse_cap ? e->fuse_cap : e->fuse_cap_auto;                            // (fuse_cap -1 = never: falls out below)
-        if (p.cap > 0 && !e->fuse_cap && e->fuse_cap_calls >= e->fuse_cap_span) p.cap = 0;   // (a learned cap is probed now and then: workloads change)
-        if (p.cap < p.L0 + 2 || p.cap > M + 1) p.cap = 0;                                // (fewer than two fused levels are not worth a knot side; beyond the call's levels: no cap)
-    }
+    p.cap = kf ? e->policy.cap(p.L0, M) : 0;
     p.Mk = p.cap ? p.cap - 2 : M;               // the knot side's "max_iteration": its levels are L0 .. Mk + 1
     p.n_tiles = (int)tiles_of(n);
     p.n_groups = groups_of(p.n_tiles);
@@ -754,12 +698,9 @@ int enqueue_decompose(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int
         else e->ev_tag[(size_t)span_pair] = -1;           // nothing instrumented in this call
     }
     HIP_TRY(e, hipGetLastError());
-    e->ran = true;
-    e->last_batch = batch; e->last_m = M; e->last_n = n; e->last_stream = st;
-    e->last_x = x; e->last_x_f32 = sizeof(Tin) == 4; e->last_x_stride = x_stride; e->last_rows = rows; e->last_bases = bases_user;
-    e->last_fused = fuse0; e->last_resident = false; e->last_nan_input = nan_input;
-    e->last_kf = kf; e->last_kf_level = p.L0; e->last_kf_cap = kf ? p.cap : 0;
-    if (!repair_need) { e->last_kf_form = kf ? p.L0 : 0; e->last_kf_cap_form = kf ? p.cap : 0; }
+    LastCall &c = record_call(e, x, n, batch, x_stride, M, rows, bases_user, st);
+    c.fused = fuse0; c.nan_input = nan_input; c.kf = kf; c.kf_level = p.L0; c.kf_cap = kf ? p.cap : 0;
+    if (!repair_need) { c.kf_form = kf ? p.L0 : 0; c.kf_cap_form = c.kf_cap; }   // (what itd_get_last_fuse_level / _cap report)
     return ITD_OK;
 }
 
@@ -767,18 +708,6 @@ int enqueue_decompose(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int
 // in LDS (itd_resident.hpp).  Optimistic: the kernel handles finite data only and raises SigState::res_fail
 // otherwise; itd_get_summary then repeats the call level by level.  The kernel initialises the states it works on itself
 // and leaves the other set's states as k_finalize would (the group sums are not touched).
-bool want_fused(itd_engine *e);
-bool want_resident(itd_engine *e, int64_t n)
-{
-    if (n > kResidentMax || e->resident_mode == ITD_RESIDENT_OFF) return false;
-    if (e->resident_mode == ITD_RESIDENT_ONLY) return true;
-    // an engine that was told how to run its level 0 / its launches, or that is being timed launch by launch, means the
-    // level-by-level form
-    if (e->l0_mode != ITD_LEVEL0_AUTO || e->timing) return false;
-    if (e->resident_off_left > 0) { --e->resident_off_left; return false; }
-    return true;
-}
-
 template <typename Tin>
 int enqueue_resident(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int64_t x_stride, int32_t M, double *rows,
                      double *bases_user, hipStream_t st)
@@ -811,9 +740,9 @@ int enqueue_resident(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int6
         const hipError_t arc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kResidentLdsMax);
         if (arc != hipSuccess) {     // a device / runtime that does not grant it: this engine runs level by level from now on
             (void)hipGetLastError();
-            if (e->resident_mode == ITD_RESIDENT_ONLY) return fail_hip(e, arc, "hipFuncSetAttribute(k_resident, MaxDynamicSharedMemorySize)");
-            e->resident_mode = ITD_RESIDENT_OFF;
-            return enqueue_decompose<Tin>(e, x, n, batch, x_stride, M, rows, bases_user, st, want_fused(e));
+            if (e->policy.resident_mode == ITD_RESIDENT_ONLY) return fail_hip(e, arc, "hipFuncSetAttribute(k_resident, MaxDynamicSharedMemorySize)");
+            e->policy.resident_unavailable();
+            return enqueue_decompose<Tin>(e, x, n, batch, x_stride, M, rows, bases_user, st, e->policy.level0_fused());
         }
         e->resident_attr[inst] = true;
     }
@@ -829,38 +758,9 @@ int enqueue_resident(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int6
     e->dirty_sig[set] = std::max(e->dirty_sig[set], batch);
     if (cap == hipStreamCaptureStatusNone && batch >= e->dirty_sig[set ^ 1]) e->dirty_sig[set ^ 1] = 0;
     e->cur_set = set;
-    e->ran = true;
-    e->last_batch = batch;
-    e->last_m = M;
-    e->last_n = n;
-    e->last_stream = st;
-    e->last_x = x;
-    e->last_x_f32 = sizeof(Tin) == 4;
-    e->last_x_stride = x_stride;
-    e->last_rows = rows;
-    e->last_bases = bases_user;
-    e->last_fused = false;
-    e->last_resident = true;
-    e->last_kf = false;
-    e->last_kf_form = 0;
-    e->last_nan_input = false;
+    record_call(e, x, n, batch, x_stride, M, rows, bases_user, st).resident = true;
+    e->last.kf_form = 0;
     return ITD_OK;
-}
-
-// The sparse levels fused (itd_knotfirst.hpp)?  Automatic: when a launch sequence covers enough samples for its launches to be
-// memory bound — the fused form trades traffic for launches (18 instead of 10 at 8 levels), and below ~2^22.5 samples per
-// sequence every launch is bound by its ~6.5 us boundary: measured one signal of 2^16 / 2^20 / 2^22 / 2^23 samples 64 / 88 / 180 /
-// 305 us level by level against 102 / 116 / 191 / 277 us fused (tools/fuse_threshold.py) —, the fused level 0 (it flags the input's
-// exact ties), no per-launch timing; not while a recent call had to be repeated level by level (smooth or quantised input
-// keeps failing the verification: workloads tend to be homogeneous).
-bool want_kf(itd_engine *e, int64_t n, int32_t batch, int32_t M, bool fuse0)
-{
-    if (e->fuse_mode == ITD_FUSE_OFF || !fuse0 || M < 2 || (e->fuse_level && e->fuse_level > M)) return false;
-    if (e->fuse_mode == ITD_FUSE_ONLY) return true;
-    if (n < 65536 || e->l0_mode != ITD_LEVEL0_AUTO || e->fuse_no_memory) return false;
-    if ((int64_t)std::min<int32_t>(chunk_of(e, n, batch), batch) * n < e->fuse_min_samples) return false;
-    if (e->fuse_off_left > 0) { if (--e->fuse_off_left == 0) e->fuse_probe = true; return false; }
-    return true;
 }
 
 template <typename Tin>
@@ -868,10 +768,11 @@ int enqueue_any(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int64_t x
                 double *bases_user, hipStream_t st)
 {
     int rc;
-    if (want_resident(e, n)) rc = enqueue_resident<Tin>(e, x, n, batch, x_stride, M, rows, bases_user, st);
+    if (e->policy.resident(n <= kResidentMax, e->timing)) rc = enqueue_resident<Tin>(e, x, n, batch, x_stride, M, rows, bases_user, st);
     else {
-        const bool f0 = want_fused(e);
-        rc = enqueue_decompose<Tin>(e, x, n, batch, x_stride, M, rows, bases_user, st, f0, false, want_kf(e, n, batch, M, f0));
+        const bool f0 = e->policy.level0_fused();
+        rc = enqueue_decompose<Tin>(e, x, n, batch, x_stride, M, rows, bases_user, st, f0, false,
+                                    e->policy.fused_levels(n, seq_samples(e, n, batch), M, f0));
     }
     e->last_device_repair = false;
     if (rc || (!e->valid_dev && !e->device_repair)) return rc;
@@ -880,7 +781,7 @@ int enqueue_any(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int64_t x
     SigState *state_a = e->d_state + (size_t)e->cur_set * e->max_batch;
     int32_t *valid = e->valid_dev ? e->valid_dev : e->d_valid_own;
     const int follow = e->nan_input_mode == ITD_NAN_INPUT_FOLLOW ? 1 : 0;
-    k_verdict<<<vb, 64, 0, st>>>(state_a, batch, e->last_kf ? e->kf.sig : nullptr, e->last_kf_level, follow, valid, e->device_repair ? e->d_need : nullptr);
+    k_verdict<<<vb, 64, 0, st>>>(state_a, batch, e->last.kf ? e->kf.sig : nullptr, e->last.kf_level, follow, valid, e->device_repair ? e->d_need : nullptr);
     if (e->device_repair) {
         // the same call level by level (record-driven level 0: any knot spacing), guarded per signal by d_need: rows_dev is final
         // when the stream has drained, with no host synchronisation in between
@@ -891,16 +792,6 @@ int enqueue_any(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int64_t x
     }
     HIP_TRY(e, hipGetLastError());
     return ITD_OK;
-}
-
-// how the next decomposition's level 0 finds its knots: fused (one pass over the signal) unless the engine was told
-// otherwise or a recent fused launch fell short (smooth input: the following decompositions go record-driven directly)
-bool want_fused(itd_engine *e)
-{
-    if (e->l0_mode == ITD_LEVEL0_RECORDS) return false;
-    if (e->l0_mode == ITD_LEVEL0_FUSED) return true;
-    if (e->l0_records_left > 0) { --e->l0_records_left; return false; }
-    return true;
 }
 
 int check_args(itd_engine *e, const void *x, int64_t n, int32_t batch, int64_t x_stride, int32_t M, const void *rows)
@@ -1221,62 +1112,169 @@ int itd_decompose_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t bat
                                stream ? (hipStream_t)stream : e->own_stream);
 }
 
+namespace {
+// The recorded call `c` again, level by level unless fuse0, on its signals b0 .. b0 + batch - 1 into their rows (and baselines)
+int enqueue_again(itd_engine *e, const LastCall c, int b0, int32_t batch, bool fuse0, bool nan_input)
+{
+    const int64_t rs = (int64_t)(c.m + 2) * c.n;
+    double *rows = c.rows + (int64_t)b0 * rs, *bases = c.bases ? c.bases + (int64_t)b0 * rs : nullptr;
+    return c.x_f32 ? enqueue_decompose<float>(e, (const float *)c.x + (int64_t)b0 * c.x_stride, c.n, batch, c.x_stride, c.m, rows, bases, c.stream, fuse0, nan_input)
+                   : enqueue_decompose<double>(e, (const double *)c.x + (int64_t)b0 * c.x_stride, c.n, batch, c.x_stride, c.m, rows, bases, c.stream, fuse0, nan_input);
+}
+
 // The signals of the last call whose fused levels reported a failure (h_state[b].kf_fail), each run again on its own: level by level,
 // record-driven level 0, into its own rows (and baselines) of the caller's buffers; its state replaces h_state[b].  The engine's
 // record of the last call (what a later itd_get_summary, itd_get_timing, ... refer to) is put back afterwards.
 int repair_signals(itd_engine *e, int B)
 {
-    const auto keep_batch = e->last_batch; const auto keep_m = e->last_m; const auto keep_n = e->last_n; const auto keep_stream = e->last_stream;
-    const void *keep_x = e->last_x; const bool keep_f32 = e->last_x_f32; const auto keep_xs = e->last_x_stride;
-    double *keep_rows = e->last_rows, *keep_bases = e->last_bases;
-    const bool keep_fused = e->last_fused; const int keep_kfl = e->last_kf_level, keep_form = e->last_kf_form;
+    const LastCall keep = e->last;
     const bool keep_timing = e->timing;
     const int main_set = e->cur_set;
     const int64_t main_gs = e->dirty_gs[main_set];
     e->timing = false;                       // (the repairs are not part of any timed launch class)
-    const int64_t rs = (int64_t)(keep_m + 2) * keep_n;
     int rc = ITD_OK;
     for (int b = 0; b < B && rc == ITD_OK; ++b) {
         if (!e->h_state[b].kf_fail) continue;
-        double *rows_b = keep_rows + (int64_t)b * rs, *bases_b = keep_bases ? keep_bases + (int64_t)b * rs : nullptr;
-        rc = keep_f32 ? enqueue_decompose<float>(e, (const float *)keep_x + (int64_t)b * keep_xs, keep_n, 1, keep_xs, keep_m, rows_b, bases_b, keep_stream, false)
-                      : enqueue_decompose<double>(e, (const double *)keep_x + (int64_t)b * keep_xs, keep_n, 1, keep_xs, keep_m, rows_b, bases_b, keep_stream, false);
+        rc = enqueue_again(e, keep, b, 1, false, false);
         if (rc) break;
         // (stream ordered: the copy leaves before the next repair's last launch puts this state set back into its initial state)
-        if (hipMemcpyAsync(&e->h_state[b], e->d_state + (size_t)e->cur_set * e->max_batch, sizeof(SigState), hipMemcpyDeviceToHost, keep_stream) != hipSuccess) { rc = ITD_ERR_HIP; break; }
-        ++e->fuse_signal_repairs;
+        if (hipMemcpyAsync(&e->h_state[b], e->d_state + (size_t)e->cur_set * e->max_batch, sizeof(SigState), hipMemcpyDeviceToHost, keep.stream) != hipSuccess) { rc = ITD_ERR_HIP; break; }
+        ++e->policy.fuse_signal_repairs;
     }
-    if (hipStreamSynchronize(keep_stream) != hipSuccess && rc == ITD_OK) rc = ITD_ERR_HIP;
+    if (hipStreamSynchronize(keep.stream) != hipSuccess && rc == ITD_OK) rc = ITD_ERR_HIP;
     e->timing = keep_timing;
     // The call's state set on the device becomes what the host now knows (fused verdicts and repaired signals merged), and the
-    // engine's current set again: a later itd_get_summary of this call reads it as it stands (last_kf = false: nothing left to
+    // engine's current set again: a later itd_get_summary of this call reads it as it stands (last.kf = false: nothing left to
     // draw or repair); the other set was last used by a one-signal repair.
     if (rc == ITD_OK) {
         for (int b = 0; b < B; ++b) e->h_state[b].kf_fail = 0;
-        if (hipMemcpyAsync(e->d_state + (size_t)main_set * e->max_batch, e->h_state, sizeof(SigState) * (size_t)B, hipMemcpyHostToDevice, keep_stream) != hipSuccess ||
-            hipStreamSynchronize(keep_stream) != hipSuccess) rc = ITD_ERR_HIP;
+        if (hipMemcpyAsync(e->d_state + (size_t)main_set * e->max_batch, e->h_state, sizeof(SigState) * (size_t)B, hipMemcpyHostToDevice, keep.stream) != hipSuccess ||
+            hipStreamSynchronize(keep.stream) != hipSuccess) rc = ITD_ERR_HIP;
     }
     e->cur_set = main_set;
-    e->dirty_sig[main_set] = std::max(e->dirty_sig[main_set], keep_batch);
+    e->dirty_sig[main_set] = std::max(e->dirty_sig[main_set], keep.batch);
     e->dirty_sig[main_set ^ 1] = std::max(e->dirty_sig[main_set ^ 1], 1);
     e->dirty_gs[main_set] = std::max(e->dirty_gs[main_set], main_gs);
-    e->dirty_gs[main_set ^ 1] = std::max<int64_t>(e->dirty_gs[main_set ^ 1], (int64_t)groups_of((int)tiles_of(keep_n)) * kGsumPitch);
-    e->last_batch = keep_batch; e->last_m = keep_m; e->last_n = keep_n; e->last_stream = keep_stream; e->last_x = keep_x; e->last_x_f32 = keep_f32;
-    e->last_x_stride = keep_xs; e->last_rows = keep_rows; e->last_bases = keep_bases; e->last_fused = keep_fused; e->last_kf = false;
-    e->last_kf_level = keep_kfl; e->last_kf_form = keep_form; e->last_resident = false; e->last_nan_input = false;
+    e->dirty_gs[main_set ^ 1] = std::max<int64_t>(e->dirty_gs[main_set ^ 1], (int64_t)groups_of((int)tiles_of(keep.n)) * kGsumPitch);
+    e->last = keep;            // (kf_cap keeps the fused call's cap: unread once kf is false)
+    e->last.kf = false;
+    e->last.kf_cap_form = 0;   // (as the repairs left it: itd_get_last_fuse_cap reports 0 after a summary that repaired signals)
     return rc;
 }
 
-// The verdict of the fused sparse levels, drawn from the heads of their KfSig into the signals' states as the host sees them
-// (no launch of its own behind the sample pass): kf_sig_verdict for every signal.
-void kf_verdict(itd_engine *e, int B)
+// ---- the steps of itd_get_summary, in its order; each returns ITD_OK or the error that ends the summary ----
+
+// The signals' states of the last call, and the verdict of its fused sparse levels drawn from the heads of their KfSig into the
+// states as the host sees them (no launch of its own behind the sample pass)
+int read_states(itd_engine *e, int B)
+{
+    HIP_TRY(e, hipMemcpyAsync(e->h_state, e->d_state + (size_t)e->cur_set * e->max_batch, sizeof(SigState) * (size_t)B, hipMemcpyDeviceToHost, e->last.stream));
+    if (e->last.kf) {
+        if (!e->h_kf) HIP_TRY(e, hipHostMalloc((void **)&e->h_kf, kKfSigHead * (size_t)e->max_batch));
+        HIP_TRY(e, hipMemcpy2DAsync(e->h_kf, kKfSigHead, e->kf.sig, sizeof(KfSig), kKfSigHead, (size_t)B, hipMemcpyDeviceToHost, e->last.stream));
+    }
+    HIP_TRY(e, hipStreamSynchronize(e->last.stream));
+    KfSig ks;
+    for (int b = 0; e->last.kf && b < B; ++b) { memcpy(&ks, e->h_kf + (size_t)b * kKfSigHead, kKfSigHead); kf_sig_verdict(ks, e->last.kf_level, e->h_state[b]); }
+    return ITD_OK;
+}
+
+// The call carried its own repair (itd_set_device_repair): nothing to repeat here; count what it re-ran and let the policy learn
+void count_device_repairs(itd_engine *e, int B)
+{
+    if (!e->last_device_repair) return;
+    int fixed = 0, why = 0;
+    for (int b = 0; b < B; ++b) if (e->h_state[b].skip < 0) { ++fixed; why |= -e->h_state[b].skip; }
+    e->last_device_repair = false;      // (a second summary of the same call counts nothing)
+    e->policy.device_repaired(fixed, why, FormPolicy::many(fixed, B), e->last.kf_level);
+}
+
+// the same call again, whole, and its states read back
+int repeat_call(itd_engine *e, int B, bool fuse0, bool nan_input)
+{
+    const int rc = enqueue_again(e, e->last, 0, B, fuse0, nan_input);
+    if (rc) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->h_state, e->d_state + (size_t)e->cur_set * e->max_batch, sizeof(SigState) * (size_t)B, hipMemcpyDeviceToHost, e->last.stream));
+    HIP_TRY(e, hipStreamSynchronize(e->last.stream));
+    return ITD_OK;
+}
+
+// The one-workgroup form handles finite data only: a NaN / infinity in the input or in a baseline (a leading or trailing plateau,
+// ITD.py:115-116) raised res_fail.  Repeat the call level by level — those kernels carry the reference's NaN rules.
+int repeat_resident(itd_engine *e, int B)
+{
+    if (!e->last.resident) return ITD_OK;
+    if (!std::any_of(e->h_state, e->h_state + B, [](const SigState &s) { return s.res_fail != 0; })) return ITD_OK;
+    if (!e->policy.resident_failed()) {
+        snprintf(e->err, sizeof(e->err), "resident form: a non-finite sample or baseline (ITD_RESIDENT_ONLY forbids the level-by-level repeat)");
+        return ITD_ERR_HIP;
+    }
+    return repeat_call(e, B, e->policy.level0_fused(), false);
+}
+
+// A signal of the call holds a NaN.  The reference runs such input through detect_peaks' NaN branch and overwrites the NaNs with
+// +inf (ITD.py:46-51, 64-68); the launches so far evaluated plain rules.  Repeat the call with the level 0 that follows the
+// reference (k_nan_level0); SigState::in_nan stays set and tells it which signals are concerned.
+int repeat_nan_input(itd_engine *e, int B)
+{
+    if (e->last.nan_input || e->nan_input_mode != ITD_NAN_INPUT_FOLLOW) return ITD_OK;
+    const bool any = std::any_of(e->h_state, e->h_state + B, [](const SigState &s) { return s.in_nan != 0; });
+    return any ? repeat_call(e, B, false, true) : ITD_OK;
+}
+
+// The fused sparse levels deliver the reference's result or report that they cannot (SigState::kf_fail: the sample pass found a
+// knot the knot side had missed, a list / table outgrew its workspace, non-finite knot data, too many exact ties).  A few signals of
+// a batch: each of them is run again on its own, level by level (record-driven level 0: any knot spacing), into its rows — the rest
+// of the batch keeps its fused result.  Many, or a single signal: the whole call is repeated level by level.
+int settle_fused_levels(itd_engine *e, int B)
+{
+    if (!e->last.kf) return ITD_OK;
+    int nfail = 0, bits = 0, fail_lev = 99;
+    for (int b = 0; b < B; ++b) {
+        if (!e->h_state[b].kf_fail) continue;
+        ++nfail;
+        bits |= e->h_state[b].kf_fail;
+        fail_lev = std::min<int>(fail_lev, reinterpret_cast<const KfSig *>(e->h_kf + (size_t)b * kKfSigHead)->fail_lev);
+    }
+    if (!nfail) { e->policy.fused_levels_delivered(e->last.kf_cap != 0, e->last.m); return ITD_OK; }
+    const auto what = e->policy.fused_levels_refused(bits, fail_lev, e->last.kf_level, e->last.kf_cap, e->last.m, FormPolicy::many(nfail, B));
+    if (what == FormPolicy::Refusal::Fail) {
+        snprintf(e->err, sizeof(e->err), "fused sparse levels: not the reference's result (fail bits 0x%x: 1 verification, 2 capacity, 4 non-finite, 8 ties, 16 halo wait); ITD_FUSE_ONLY forbids the level-by-level repeat", bits);
+        return ITD_ERR_HIP;
+    }
+    return what == FormPolicy::Refusal::RepairSignals ? repair_signals(e, B) : repeat_call(e, B, e->policy.level0_fused(), false);
+}
+
+// The fused level-0 launch reaches kReach windows beyond a tile for its halo knots; a signal smoother than that (knots more than
+// ~4000 samples apart at level 0) raised l0_fail: repeat the call record-driven (k_scan0 + records)
+int repeat_level0(itd_engine *e, int B)
+{
+    if (!e->last.fused) return ITD_OK;
+    if (!std::any_of(e->h_state, e->h_state + B, [](const SigState &s) { return s.l0_fail && !s.in_nan; })) return ITD_OK;
+    if (!e->policy.level0_fell_short()) {
+        snprintf(e->err, sizeof(e->err), "fused level 0: a tile's halo knots lie beyond its reach (ITD_LEVEL0_FUSED forbids the record-driven repeat)");
+        return ITD_ERR_HIP;
+    }
+    return repeat_call(e, B, false, false);
+}
+
+void fill_summary(const itd_engine *e, int B, int32_t *n_rows, int32_t *n_baselines, int32_t *stop_reason, int64_t *knot_counts,
+                  int32_t *nan_levels)
 {
     for (int b = 0; b < B; ++b) {
-        KfSig ks;
-        memcpy(&ks, e->h_kf + (size_t)b * kKfSigHead, kKfSigHead);
-        kf_sig_verdict(ks, e->last_kf_level, e->h_state[b]);
+        const SigState &s = e->h_state[b];
+        // ITD.py:404-416, counter = stop_level-1: rows[0:counter+1], baselines[0:counter-1] after the increment;
+        // ITD.py:418-426, counter = max_iteration+1: rows and baselines[0:counter] (last row zero)
+        const int rows = s.fin_stopped ? s.fin_stop_level : e->last.m + 2;
+        if (n_rows) n_rows[b] = rows;
+        if (n_baselines) n_baselines[b] = s.fin_stopped ? rows - 1 : rows;
+        if (stop_reason) stop_reason[b] = s.fin_stopped ? ITD_STOP_NATURAL : ITD_STOP_TIMEOUT;
+        if (knot_counts)
+            for (int j = 0; j <= ITD_MAX_ROWS; ++j) knot_counts[(size_t)b * (ITD_MAX_ROWS + 1) + j] = s.m[j];
+        if (nan_levels) nan_levels[b] = (s.in_nan && !e->last.nan_input) ? -2 : -1;
     }
 }
+}  // namespace
 
 int itd_get_summary(itd_engine *e, int32_t *n_rows, int32_t *n_baselines, int32_t *stop_reason,
                     int64_t *knot_counts, int32_t *nan_levels)
@@ -1284,161 +1282,21 @@ int itd_get_summary(itd_engine *e, int32_t *n_rows, int32_t *n_baselines, int32_
     if (!e) return ITD_ERR_INVALID_ARG;
     if (!e->ran) return ITD_ERR_NOT_RUN;
     DevGuard g(e->device);
-    const int B = e->last_batch;
-    HIP_TRY(e, hipMemcpyAsync(e->h_state, e->d_state + (size_t)e->cur_set * e->max_batch, sizeof(SigState) * (size_t)B, hipMemcpyDeviceToHost, e->last_stream));
-    if (e->last_kf) {
-        if (!e->h_kf) HIP_TRY(e, hipHostMalloc((void **)&e->h_kf, kKfSigHead * (size_t)e->max_batch));
-        HIP_TRY(e, hipMemcpy2DAsync(e->h_kf, kKfSigHead, e->kf.sig, sizeof(KfSig), kKfSigHead, (size_t)B, hipMemcpyDeviceToHost, e->last_stream));
-    }
-    HIP_TRY(e, hipStreamSynchronize(e->last_stream));
-    if (e->last_kf) kf_verdict(e, B);
-    if (e->last_device_repair) {
-        // the call carried its own repair (itd_set_device_repair): nothing to repeat here; count what it re-ran and let the engine's
-        // next calls start the way that would have delivered (workloads tend to be homogeneous) — as the host-side repeats do
-        int fixed = 0, why = 0;
-        for (int b = 0; b < B; ++b) if (e->h_state[b].skip < 0) { ++fixed; why |= -e->h_state[b].skip; }
-        e->device_repairs += fixed;
-        e->last_device_repair = false;      // (a second summary of the same call counts nothing)
-        if (fixed && (B < 8 || fixed * 8 > B)) {
-            if ((why & 1) && !kf_back_off(e, (why >> 3) & 31, e->last_kf_level)) kf_levels_off(e);
-            if (why & 2) e->l0_records_left = 16;
-            if (why & 4) e->resident_off_left = 16;
-        }
-    }
-    auto any_nan_input = [&]() {
-        for (int b = 0; b < B; ++b) if (e->h_state[b].in_nan) return true;
-        return false;
-    };
-    auto repeat = [&](bool f0, bool nan_in) {   // the same call again, level by level
-        const int rc = e->last_x_f32
-            ? enqueue_decompose<float>(e, (const float *)e->last_x, e->last_n, B, e->last_x_stride, e->last_m, e->last_rows, e->last_bases, e->last_stream, f0, nan_in)
-            : enqueue_decompose<double>(e, (const double *)e->last_x, e->last_n, B, e->last_x_stride, e->last_m, e->last_rows, e->last_bases, e->last_stream, f0, nan_in);
-        if (rc) return rc;
-        HIP_TRY(e, hipMemcpyAsync(e->h_state, e->d_state + (size_t)e->cur_set * e->max_batch, sizeof(SigState) * (size_t)B, hipMemcpyDeviceToHost, e->last_stream));
-        HIP_TRY(e, hipStreamSynchronize(e->last_stream));
-        return (int)ITD_OK;
-    };
-    if (e->last_resident) {
-        // the one-workgroup form handles finite data only: a NaN / infinity in the input or in a baseline (a leading or
-        // trailing plateau, ITD.py:115-116) raised res_fail.  Repeat the call level by level — those kernels carry the
-        // reference's NaN rules — and let the engine's next decompositions start that way: workloads tend to be homogeneous
-        bool redo = false;
-        for (int b = 0; b < B; ++b) redo = redo || e->h_state[b].res_fail;
-        if (redo) {
-            if (e->resident_mode == ITD_RESIDENT_ONLY) {
-                snprintf(e->err, sizeof(e->err), "resident form: a non-finite sample or baseline (ITD_RESIDENT_ONLY forbids the level-by-level repeat)");
-                return ITD_ERR_HIP;
-            }
-            ++e->resident_repeats;
-            e->resident_off_left = 16;
-            const int rc = repeat(want_fused(e), false);
-            if (rc) return rc;
-        }
-    }
-    if (!e->last_nan_input && e->nan_input_mode == ITD_NAN_INPUT_FOLLOW && any_nan_input()) {
-        // A signal of the call holds a NaN.  The reference runs such input through detect_peaks' NaN branch and overwrites the
-        // NaNs with +inf (ITD.py:46-51, 64-68); the launches so far evaluated plain rules.  Repeat the call with the level 0
-        // that follows the reference (k_nan_level0); SigState::in_nan stays set and tells it which signals are concerned.
-        const int rc = repeat(false, true);
-        if (rc) return rc;
-    }
-    if (e->last_kf) {
-        // the fused sparse levels deliver the reference's result or report that they cannot (SigState::kf_fail: the sample pass
-        // found a knot the knot side had missed, a list / table outgrew its workspace, non-finite knot data, too many exact ties).
-        // A few signals of a batch: each of them is run again on its own, level by level (record-driven level 0: any knot
-        // spacing), into its rows — the rest of the batch keeps its fused result.  Many, or a single signal: the whole call is
-        // repeated level by level and the engine's next decompositions start that way.
-        int nfail = 0;
-        for (int b = 0; b < B; ++b) nfail += e->h_state[b].kf_fail != 0;
-        if (!nfail) {      // delivered: the back-off starts over
-            e->fuse_off_span = 16; e->fuse_probe = false;
-            if (!e->fuse_cap && e->fuse_cap_auto) {
-                if (e->last_kf_cap) ++e->fuse_cap_calls;
-                else if (e->last_m + 1 >= e->fuse_cap_auto) { e->fuse_cap_auto = 0; e->fuse_cap_calls = 0; e->fuse_cap_span = 16; }   // the probe without the cap was delivered: the workload has changed
-            }
-        }
-        if (nfail) {
-            if (e->fuse_mode == ITD_FUSE_ONLY) {
-                int code = 0;
-                for (int b = 0; b < B; ++b) code |= e->h_state[b].kf_fail;
-                snprintf(e->err, sizeof(e->err), "fused sparse levels: not the reference's result (fail bits 0x%x: 1 verification, 2 capacity, 4 non-finite, 8 ties, 16 halo wait); ITD_FUSE_ONLY forbids the level-by-level repeat", code);
-                return ITD_ERR_HIP;
-            }
-            // a list that outgrew its workgroup (dense knots): the calls after this one hand over a level later or run with half the
-            // tiles per workgroup (kf_back_off)
-            int bits = 0;
-            for (int b = 0; b < B; ++b) bits |= e->h_state[b].kf_fail;
-            const bool can_shrink = kf_back_off(e, bits, e->last_kf_level);
-            if (B >= 8 && nfail * 8 <= B) {
-                const int rc = repair_signals(e, B);
-                if (rc) return rc;
-            } else {
-                ++e->fuse_repeats;
-                // Where did it fail?  A workload whose fused form fails at the same level every time (periodic input whose baseline collapses
-                // there: BASELINE configs[4]'s substitute clip at level 8) keeps the fused form for the levels in front of it: the engine's
-                // next calls cap their fused levels at the lowest level anything failed at (KfSig::fail_lev) and run the rest level by level
-                bool capped_next = false;
-                if (!e->fuse_cap && !(bits & (kKfFailCapacity | kKfFailWait))) {
-                    int fl = 99;
-                    for (int b = 0; b < B; ++b)
-                        if (e->h_state[b].kf_fail) fl = std::min<int>(fl, reinterpret_cast<const KfSig *>(e->h_kf + (size_t)b * kKfSigHead)->fail_lev);
-                    const int L0 = e->last_kf_level;
-                    if (fl >= L0 + 2 && fl <= e->last_m + 1 && (e->last_kf_cap == 0 || fl < e->last_kf_cap)) {
-                        // (a refused PROBE — the cap was known, this call tried without it —: the next probe comes later)
-                        e->fuse_cap_span = (e->fuse_cap_auto && !e->last_kf_cap) ? std::min(e->fuse_cap_span * 2, 1024) : 16;
-                        e->fuse_cap_auto = fl; e->fuse_cap_calls = 0; capped_next = true;
-                    } else { e->fuse_cap_auto = 0; e->fuse_cap_span = 16; }
-                }
-                if (!can_shrink && !capped_next) kf_levels_off(e);
-                const int rc = repeat(want_fused(e), false);
-                if (rc) return rc;
-            }
-        }
-    }
-    if (e->last_fused) {
-        // the fused level-0 launch reaches kReach windows beyond a tile for its halo knots; a signal smoother than that
-        // (knots more than ~4000 samples apart at level 0) raised l0_fail: repeat the call record-driven (k_scan0 + records),
-        // and let the next decompositions of this engine start record-driven — workloads tend to be homogeneous
-        bool fell_short = false;
-        for (int b = 0; b < B; ++b) fell_short = fell_short || (e->h_state[b].l0_fail && !e->h_state[b].in_nan);
-        if (fell_short) {
-            if (e->l0_mode == ITD_LEVEL0_FUSED) {
-                snprintf(e->err, sizeof(e->err), "fused level 0: a tile's halo knots lie beyond its reach (ITD_LEVEL0_FUSED forbids the record-driven repeat)");
-                return ITD_ERR_HIP;
-            }
-            e->l0_records_left = 16;
-            const int rc = repeat(false, false);
-            if (rc) return rc;
-        }
-    }
-    for (int b = 0; b < B; ++b) {
-        const SigState &s = e->h_state[b];
-        int rows, nb, why;
-        if (s.fin_stopped) {           // ITD.py:404-416, counter = stop_level-1
-            const int c = s.fin_stop_level - 1;
-            rows = c + 1;
-            nb = c;                    // baselines[0:counter-1] after the increment
-            why = ITD_STOP_NATURAL;
-        } else {                       // ITD.py:418-426, counter = max_iteration+1
-            rows = e->last_m + 2;
-            nb = e->last_m + 2;        // baselines[0:counter] (last row zero)
-            why = ITD_STOP_TIMEOUT;
-        }
-        if (n_rows) n_rows[b] = rows;
-        if (n_baselines) n_baselines[b] = nb;
-        if (stop_reason) stop_reason[b] = why;
-        if (knot_counts)
-            for (int j = 0; j <= ITD_MAX_ROWS; ++j) knot_counts[(size_t)b * (ITD_MAX_ROWS + 1) + j] = s.m[j];
-        if (nan_levels) nan_levels[b] = (s.in_nan && !e->last_nan_input) ? -2 : -1;
-    }
+    const int B = e->last.batch;
+    int rc = read_states(e, B);
+    if (rc) return rc;
+    count_device_repairs(e, B);
+    // each repeat also lets the engine's next calls start the way it runs: workloads tend to be homogeneous
+    if ((rc = repeat_resident(e, B)) || (rc = repeat_nan_input(e, B)) || (rc = settle_fused_levels(e, B)) || (rc = repeat_level0(e, B)))
+        return rc;
+    fill_summary(e, B, n_rows, n_baselines, stop_reason, knot_counts, nan_levels);
     return ITD_OK;
 }
 
 int itd_set_level0_mode(itd_engine *e, int32_t mode)
 {
     if (!e || mode < ITD_LEVEL0_AUTO || mode > ITD_LEVEL0_FUSED) return ITD_ERR_INVALID_ARG;
-    e->l0_mode = mode;
-    e->l0_records_left = 0;
+    e->policy.set_level0_mode(mode);
     return ITD_OK;
 }
 
@@ -1470,12 +1328,11 @@ int itd_get_last_baselines_host(itd_engine *e, double *baselines_host, int64_t n
 int itd_set_resident_mode(itd_engine *e, int32_t mode)
 {
     if (!e || mode < ITD_RESIDENT_AUTO || mode > ITD_RESIDENT_ONLY) return ITD_ERR_INVALID_ARG;
-    e->resident_mode = mode;
-    e->resident_off_left = 0;
+    e->policy.set_resident_mode(mode);
     return ITD_OK;
 }
 
-int itd_get_resident_repeats(const itd_engine *e) { return e ? e->resident_repeats : -1; }
+int itd_get_resident_repeats(const itd_engine *e) { return e ? e->policy.resident_repeats : -1; }
 
 int itd_set_valid_flags(itd_engine *e, int32_t *valid_dev)
 {
@@ -1491,23 +1348,19 @@ int itd_set_device_repair(itd_engine *e, int32_t on)
     return ITD_OK;
 }
 
-int64_t itd_get_device_repairs(const itd_engine *e) { return e ? e->device_repairs : -1; }
+int64_t itd_get_device_repairs(const itd_engine *e) { return e ? e->policy.device_repairs : -1; }
 
 int itd_set_fuse_range(itd_engine *e, int32_t tiles)
 {
     if (!e || (tiles != 0 && tiles != 16 && tiles != 32 && tiles != 64)) return ITD_ERR_INVALID_ARG;
-    e->fuse_range = tiles;
-    e->kf_shrink = 0;
+    e->policy.set_fuse_range(tiles);
     return ITD_OK;
 }
 
 int itd_set_fuse_mode(itd_engine *e, int32_t mode)
 {
     if (!e || mode < ITD_FUSE_AUTO || mode > ITD_FUSE_ONLY) return ITD_ERR_INVALID_ARG;
-    e->fuse_mode = mode;
-    e->fuse_off_left = 0;
-    e->fuse_off_span = 16;
-    e->fuse_probe = false;
+    e->policy.set_fuse_mode(mode);
     return ITD_OK;
 }
 
@@ -1515,15 +1368,14 @@ int itd_set_fuse_level(itd_engine *e, int32_t first_fused_level)
 {
     // (level 1's launch completes the signal's own knot count, and a level-1 list would not fit the workspace: 2 at least)
     if (!e || (first_fused_level != 0 && (first_fused_level < 2 || first_fused_level > ITD_MAX_ITERATION))) return ITD_ERR_INVALID_ARG;
-    e->fuse_level = first_fused_level;
-    e->fuse_level2_off = false;
+    e->policy.set_fuse_level(first_fused_level);
     return ITD_OK;
 }
 
 int itd_set_fuse_min_samples(itd_engine *e, int64_t samples)
 {
     if (!e || samples < 0) return ITD_ERR_INVALID_ARG;
-    e->fuse_min_samples = samples;
+    e->policy.set_fuse_min_samples(samples);
     return ITD_OK;
 }
 
@@ -1559,17 +1411,14 @@ int itd_debug_kf_fault_signal(itd_engine *e, int32_t signal)
 int itd_set_fuse_cap(itd_engine *e, int32_t first_level_not_fused)
 {
     if (!e || first_level_not_fused < -1 || first_level_not_fused > ITD_MAX_ITERATION + 1 || (first_level_not_fused > 0 && first_level_not_fused < 4)) return ITD_ERR_INVALID_ARG;
-    e->fuse_cap = first_level_not_fused;
-    e->fuse_cap_auto = 0;
-    e->fuse_cap_calls = 0;
-    e->fuse_cap_span = 16;
+    e->policy.set_fuse_cap(first_level_not_fused);
     return ITD_OK;
 }
-int itd_get_last_fuse_cap(const itd_engine *e) { return !e ? -1 : (e->ran && e->last_kf_form ? e->last_kf_cap_form : 0); }
+int itd_get_last_fuse_cap(const itd_engine *e) { return !e ? -1 : (e->ran && e->last.kf_form ? e->last.kf_cap_form : 0); }
 
-int itd_get_fuse_repeats(const itd_engine *e) { return e ? e->fuse_repeats : -1; }
-int itd_get_last_fuse_level(const itd_engine *e) { return !e ? -1 : (e->ran && e->last_kf_form ? e->last_kf_form : 0); }
-int64_t itd_get_fuse_signal_repairs(const itd_engine *e) { return e ? e->fuse_signal_repairs : -1; }
+int itd_get_fuse_repeats(const itd_engine *e) { return e ? e->policy.fuse_repeats : -1; }
+int itd_get_last_fuse_level(const itd_engine *e) { return !e ? -1 : (e->ran && e->last.kf_form ? e->last.kf_form : 0); }
+int64_t itd_get_fuse_signal_repairs(const itd_engine *e) { return e ? e->policy.fuse_signal_repairs : -1; }
 
 int itd_set_resident_window(itd_engine *e, int32_t segments)
 {
@@ -2895,7 +2744,7 @@ int itd_get_kernel_timing_samples(itd_engine *e, int32_t which, double *ms_out, 
     if (!e || which < 0 || which > ITD_TIME_KF_KNOTS || cap < 0 || (cap > 0 && !ms_out)) return ITD_ERR_INVALID_ARG;
     if (!e->ran || !e->timing) return ITD_ERR_NOT_RUN;
     DevGuard g(e->device);
-    HIP_TRY(e, hipStreamSynchronize(e->last_stream));
+    HIP_TRY(e, hipStreamSynchronize(e->last.stream));
     int cnt = 0;
     for (int k = 0; k < e->n_timed; ++k) {
         if (e->ev_tag[(size_t)k] != which) continue;
@@ -2915,7 +2764,7 @@ int itd_get_step_periods(itd_engine *e, double *ms_out, int32_t cap, int32_t *co
     if (!e || cap < 0 || (cap > 0 && !ms_out)) return ITD_ERR_INVALID_ARG;
     if (!e->ran || !e->timing) return ITD_ERR_NOT_RUN;
     DevGuard g(e->device);
-    HIP_TRY(e, hipStreamSynchronize(e->last_stream));
+    HIP_TRY(e, hipStreamSynchronize(e->last.stream));
     int cnt = 0, prev = -1;
     for (int k = 0; k < e->n_timed; ++k) {
         if (e->ev_tag[(size_t)k] != ITD_TIME_EXTRACT_L0) continue;
@@ -2938,7 +2787,7 @@ int itd_get_kernel_timing(itd_engine *e, int32_t which, double *ms_total, int32_
     if (!e || which < 0 || which > ITD_TIME_KF_KNOTS) return ITD_ERR_INVALID_ARG;
     if (!e->ran || !e->timing) return ITD_ERR_NOT_RUN;
     DevGuard g(e->device);
-    HIP_TRY(e, hipStreamSynchronize(e->last_stream));
+    HIP_TRY(e, hipStreamSynchronize(e->last.stream));
     double tot = 0.0;
     int cnt = 0;
     for (int k = 0; k < e->n_timed; ++k) {

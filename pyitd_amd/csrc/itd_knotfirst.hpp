@@ -137,7 +137,7 @@ struct KfSig {
 constexpr size_t kKfSigHead = (8 + (kMaxLevels + 2)) * sizeof(int32_t);
 static_assert(offsetof(KfSig, acc_mlev) == kKfSigHead, "KfSig layout");
 
-// The verdict of the fused levels for one signal, drawn from the head of its KfSig into the signal's state (the host's kf_verdict when
+// The verdict of the fused levels for one signal, drawn from the head of its KfSig into the signal's state (the host's read_states when
 // the summary is read, the device's k_verdict behind the call): the knot counts of the fused levels and the stop, or kf_fail — the
 // sample pass found a knot the knot side had missed, a list outgrew its workspace, non-finite knot data, too many exact ties.
 // Reads only fields inside the head (the host holds nothing else).
