@@ -473,6 +473,23 @@ int itd_copy(itd_engine *e, void *dst, const void *src, int64_t bytes, int32_t k
  * construction, not by the two log2 agreeing.  Synchronous. */
 int itd_meitd_small_f64(itd_engine *e, double *rows_dev, int64_t n, double wpemax, int32_t *result_host, void *probe_log_host,
                         int32_t log_cap, void *stream);
+/* The same loop on a BATCH of signals of one length, one workgroup per signal, all of them in one launch (up to 65535 signals per
+ * launch; more: one launch per 65535), under the same eligibility rule (3 <= n <= 8192 and the parallel-in-knots solver setting;
+ * otherwise ITD_ERR_INVALID_ARG).  Signal b's rows are the 50 rows above at rows_dev + b * rows_stride (rows_stride >= 50 * n
+ * elements).  x_host (optional): batch signals of n float64, copied into row 5 of their blocks first (one copy per launch); NULL: the
+ * rows already hold them.  result_host [batch][24]: each signal's words as itd_meitd_small_f64's result_host.  probe_logs_host
+ * [batch][log_cap] entries: each signal's log as itd_meitd_small_f64's, filled up to min(its probes, log_cap, 1024).
+ * xitd_sums_host / xitd_windows_host [batch][22][6] (both or neither): for a signal with status 0, XITD's entropy sums (MEITD.py:536-549)
+ * of its kept high rows, its kept low rows and its residual, in that order — row by row what itd_wpe3_f64 returns for that row; the
+ * other signals' entries and the rows behind the residual are undefined.  The per-signal workspace is the engine's own, apart from a pending decomposition's.  Synchronous. */
+int itd_meitd_batch_f64(itd_engine *e, double *rows_dev, int64_t n, int32_t batch, int64_t rows_stride, const double *x_host, double wpemax,
+                        int32_t *result_host, void *probe_logs_host, int32_t log_cap, double *xitd_sums_host, int64_t *xitd_windows_host,
+                        void *stream);
+/* rows of n float64, row r at src_dev + offsets_host[r] (0 <= offset <= src_elems - n, checked), one after the other into dst_dev
+ * [rows][n]: one upload of the table, one launch; dst_host (optional, [rows][n]): then one download of dst_dev — how the batch's
+ * components leave the device.  Synchronous. */
+int itd_gather_rows_f64(itd_engine *e, const double *src_dev, int64_t src_elems, const int64_t *offsets_host, int64_t rows, int64_t n,
+                        double *dst_dev, double *dst_host, void *stream);
 /* crossways_itd_baseline_extract(data), siftED2D.ipynb cell 1, for `planes` images of rows x cols float64 (the ensemble
  * members of retrieve_statistical_image_component go through in one call): the operator over every row, then over every
  * column of that; over every column, then every row of that; the mean of the two.  Transposes and the mean run on the GPU. */

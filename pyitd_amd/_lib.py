@@ -62,6 +62,8 @@ ABI = {
     "itd_subtract_f64": (_INT, [_P, _P, _P, _P, _I64, _P]),
     "itd_copy": (_INT, [_P, _P, _P, _I64, _I32, _I32, _P]),
     "itd_meitd_small_f64": (_INT, [_P, _P, _I64, ctypes.c_double, _P, _P, _I32, _P]),
+    "itd_meitd_batch_f64": (_INT, [_P, _P, _I64, _I32, _I64, _P, ctypes.c_double, _P, _P, _I32, _P, _P, _P]),
+    "itd_gather_rows_f64": (_INT, [_P, _P, _I64, _P, _I64, _I64, _P, _P, _P]),
     "itd_crossways_f64": (_INT, [_P, _P, _I32, _I32, _I32, _I32, _P, _P]),
     "itd_crossways_host_f64": (_INT, [_P, _P, _I32, _I32, _I32, _I32, _P]),
     "itd_instantaneous_f64": (_INT, [_P, _P, _I64, _P, _P, _P, _P]),

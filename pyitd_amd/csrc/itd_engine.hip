@@ -205,6 +205,7 @@ struct itd_engine {
     bool resident_attr[12] = {};
     bool nak_small_attr = false;    // hipFuncSetAttribute done for k_nak_small<true>
     bool meitd_attr[2] = {};        // ... for k_meitd_small<false / true>
+    bool meitd_batch_attr[2] = {};  // ... for k_meitd_batch<false / true>
     // a few scalars per call come back to the host in MEITD's operators (counts, six sums): 256 bytes of pinned host memory that the
     // GPU writes directly (mapped, coherent) — no copy behind the launch, just the stream's synchronisation (a pageable destination
     // cost ~15 us per call: 110 calls per MEITD run)
@@ -237,6 +238,8 @@ struct itd_engine {
     void *d_sp = nullptr; size_t sp_bytes = 0;            // spline flavour (batched): lists, counts, records, group sums, states,
                                                           // ordered knot lists, totals, fit arrays, metadata
     double *d_sp2 = nullptr; size_t sp2_bytes = 0;        // 2-D consumers: three planes of scratch
+    void *d_mb = nullptr; size_t mb_bytes = 0;            // MEITD over a batch (itd_meitd_batch_f64): per-signal results, solver arrays, logs, XITD sums
+    int64_t *d_rowtab = nullptr; size_t rowtab_bytes = 0; // itd_gather_rows_f64: the row table
     char *d_wpe = nullptr; size_t wpe_bytes = 0;          // weighted permutation entropy: the segments' sums
     void *d_io_x = nullptr; size_t io_x_bytes = 0;
     void *d_iq_avg = nullptr; size_t iq_avg_bytes = 0;   // the I/Q form of the cubic operator: the components' mean series
@@ -972,7 +975,7 @@ void itd_engine_destroy(itd_engine *e)
     (void)hipFree(e->d_hcounts); (void)hipFree(e->d_hrecs); (void)hipFree(e->d_hgsum); (void)hipFree(e->d_hstate);
     (void)hipFree(e->d_io_x); (void)hipFree(e->d_io_rows); (void)hipFree(e->d_io_bases); (void)hipFree(e->d_iq_avg);
     (void)hipFree(e->d_cub); (void)hipFree(e->d_cub_e); (void)hipFree(e->d_dw); (void)hipFree(e->d_bw); (void)hipFree(e->d_kf); for (void *q : e->kf_retired) (void)hipFree(q); (void)hipFree(e->d_flag); (void)hipFree(e->d_need); (void)hipFree(e->d_valid_own);
-    (void)hipFree(e->d_sp); (void)hipFree(e->d_sp2); (void)hipFree(e->d_wpe);
+    (void)hipFree(e->d_sp); (void)hipFree(e->d_sp2); (void)hipFree(e->d_wpe); (void)hipFree(e->d_mb); (void)hipFree(e->d_rowtab);
     if (e->h_state) (void)hipHostFree(e->h_state);
     if (e->h_kf) (void)hipHostFree(e->h_kf);
     for (int k = 0; k < 2; ++k) if (e->h_pin[k]) (void)hipHostFree(e->h_pin[k]);
@@ -2481,6 +2484,123 @@ int itd_meitd_small_f64(itd_engine *e, double *rows_dev, int64_t n, double wpema
     memcpy(result_host, &ho, sizeof(MeitdOut));
     const int32_t got = result_host[4] < log_cap ? result_host[4] : log_cap;
     if (got > 0) HIP_TRY(e, hipMemcpy(probe_log_host, dlog, (size_t)(got < kMeitdLogCap ? got : kMeitdLogCap) * sizeof(MeitdProbe), hipMemcpyDeviceToHost));
+    return ITD_OK;
+}
+
+// MEITD's selection loop on a batch of short device-resident signals, one workgroup per signal (itd_meitd.hpp: k_meitd_batch).
+// Synchronous; launches of at most kMaxGridY signals.  The per-signal scratch is the engine's d_mb, apart from every other workspace;
+// above kMeitdBatchKeepBytes it is freed when the call returns.
+constexpr size_t kMeitdBatchKeepBytes = (size_t)64 << 20;
+int itd_meitd_batch_f64(itd_engine *e, double *rows_dev, int64_t n, int32_t batch, int64_t rows_stride, const double *x_host, double wpemax,
+                        int32_t *result_host, void *probe_logs_host, int32_t log_cap, double *xitd_sums_host, int64_t *xitd_windows_host,
+                        void *stream)
+{
+    if (!e || !rows_dev || !result_host || n < 3 || n > kNakSmallMax || batch < 1 || log_cap < 0 || (log_cap > 0 && !probe_logs_host))
+        return ITD_ERR_INVALID_ARG;
+    if (rows_stride < (int64_t)(kMeitdWork + 2 * kMeitdKept) * n || (!xitd_sums_host) != (!xitd_windows_host)) return ITD_ERR_INVALID_ARG;
+    // (the same rule as itd_meitd_small_f64: where the host-driven loop's extractions take the parallel-in-knots form)
+    if (!(e->spline_solver == ITD_SPLINE_PARALLEL || (e->spline_solver == ITD_SPLINE_AUTO && n >= 1024))) return ITD_ERR_INVALID_ARG;
+    DevGuard g(e->device);
+    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
+    const int64_t L = n + 2;
+    const int grid_max = batch < kMaxGridY ? batch : kMaxGridY;
+    const bool xitd = xitd_sums_host != nullptr;
+    const size_t idx_b = (((size_t)L * sizeof(int32_t)) + 255) & ~(size_t)255;
+    const size_t sig_b = idx_b + ((6 * (size_t)L * sizeof(double) + 255) & ~(size_t)255);
+    const size_t out_b = (((size_t)grid_max * sizeof(MeitdOut)) + 255) & ~(size_t)255;
+    const size_t log_b = (size_t)grid_max * kMeitdLogCap * sizeof(MeitdProbe);
+    const size_t xs_b = xitd ? (size_t)grid_max * kMeitdKept * 6 * (sizeof(double) + sizeof(long long)) : 0;
+    const size_t x_b = x_host ? (((size_t)grid_max * (size_t)n * sizeof(double)) + 255) & ~(size_t)255 : 0;
+    // (the logs are packed, as far as the longest reaches, behind everything else before they go to the host: log_b more)
+    int rc = grow(e, &e->d_mb, &e->mb_bytes, out_b + log_b + xs_b + (size_t)grid_max * sig_b + x_b + log_b);
+    if (rc) return rc;
+    MeitdOut *dout = (MeitdOut *)e->d_mb;
+    MeitdProbe *dlog = (MeitdProbe *)((char *)e->d_mb + out_b);
+    double *dxw = xitd ? (double *)((char *)e->d_mb + out_b + log_b) : nullptr;
+    long long *dxc = xitd ? (long long *)(dxw + (size_t)grid_max * kMeitdKept * 6) : nullptr;
+    char *ws = (char *)e->d_mb + out_b + log_b + xs_b;
+    double *dx = x_host ? (double *)(ws + (size_t)grid_max * sig_b) : nullptr;
+    MeitdProbe *dpack = (MeitdProbe *)(ws + (size_t)grid_max * sig_b + x_b);
+    const size_t nak_lds = 4 * (size_t)L * sizeof(double);
+    const bool in_lds = nak_lds <= kNakSmallLdsMax;
+    const size_t lds = in_lds && nak_lds > kMeitdWpeLds ? nak_lds : kMeitdWpeLds;   // (as itd_meitd_small_f64)
+    if (!e->meitd_batch_attr[in_lds]) {
+        const void *fn = in_lds ? reinterpret_cast<const void *>(&k_meitd_batch<true>) : reinterpret_cast<const void *>(&k_meitd_batch<false>);
+        HIP_TRY(e, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(in_lds ? kNakSmallLdsMax : kMeitdWpeLds)));
+        e->meitd_batch_attr[in_lds] = true;
+    }
+    const int32_t cap = log_cap < kMeitdLogCap ? log_cap : kMeitdLogCap;
+    std::vector<MeitdOut> ho((size_t)grid_max);
+    std::vector<MeitdProbe> hlog;
+    for (int32_t b0 = 0; b0 < batch; b0 += grid_max) {
+        const int32_t G = batch - b0 < grid_max ? batch - b0 : grid_max;
+        double *rows = rows_dev + (size_t)b0 * (size_t)rows_stride;
+        // (the signals as one contiguous copy; each workgroup moves its own into row 5 of its block)
+        if (x_host) HIP_TRY(e, hipMemcpyAsync(dx, x_host + (size_t)b0 * (size_t)n, (size_t)G * (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+        if (in_lds)
+            k_meitd_batch<true><<<(unsigned)G, kNakSmallThreads, lds, st>>>(dx, rows, rows_stride, (int)n, wpemax, ws, (int64_t)sig_b, (int64_t)idx_b, L, dlog, dout, dxw, dxc);
+        else
+            k_meitd_batch<false><<<(unsigned)G, kNakSmallThreads, lds, st>>>(dx, rows, rows_stride, (int)n, wpemax, ws, (int64_t)sig_b, (int64_t)idx_b, L, dlog, dout, dxw, dxc);
+        HIP_TRY(e, hipGetLastError());
+        HIP_TRY(e, hipMemcpyAsync(ho.data(), dout, (size_t)G * sizeof(MeitdOut), hipMemcpyDeviceToHost, st));
+        HIP_TRY(e, hipStreamSynchronize(st));
+        int32_t most = 0;
+        for (int32_t b = 0; b < G; ++b) {
+            memcpy(result_host + ((size_t)b0 + b) * 24, &ho[(size_t)b], sizeof(MeitdOut));
+            most = ho[(size_t)b].probes > most ? ho[(size_t)b].probes : most;
+        }
+        most = most < cap ? most : cap;
+        // (every signal's log as far as the longest one reaches: packed on the device, then one copy)
+        if (most > 0) {
+            HIP_TRY(e, hipMemcpy2DAsync(dpack, (size_t)most * sizeof(MeitdProbe), dlog, kMeitdLogCap * sizeof(MeitdProbe), (size_t)most * sizeof(MeitdProbe),
+                                        (size_t)G, hipMemcpyDeviceToDevice, st));
+            hlog.resize((size_t)G * (size_t)most);
+            HIP_TRY(e, hipMemcpyAsync(hlog.data(), dpack, hlog.size() * sizeof(MeitdProbe), hipMemcpyDeviceToHost, st));
+        }
+        if (xitd) {
+            static_assert(sizeof(long long) == sizeof(int64_t), "XITD's window counts are 64-bit on both sides");
+            HIP_TRY(e, hipMemcpyAsync(xitd_sums_host + (size_t)b0 * kMeitdKept * 6, dxw, (size_t)G * kMeitdKept * 6 * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIP_TRY(e, hipMemcpyAsync(xitd_windows_host + (size_t)b0 * kMeitdKept * 6, dxc, (size_t)G * kMeitdKept * 6 * sizeof(long long), hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(e, hipStreamSynchronize(st));
+        for (int32_t b = 0; most > 0 && b < G; ++b)
+            memcpy((char *)probe_logs_host + ((size_t)b0 + b) * log_cap * sizeof(MeitdProbe), hlog.data() + (size_t)b * most, (size_t)most * sizeof(MeitdProbe));
+    }
+    if (e->mb_bytes > kMeitdBatchKeepBytes) {      // (a large batch's workspace does not stay allocated behind the call)
+        HIP_TRY(e, hipFree(e->d_mb));
+        e->d_mb = nullptr;
+        e->mb_bytes = 0;
+    }
+    return ITD_OK;
+}
+
+__global__ void k_gather_rows(const double *__restrict__ src, const int64_t *__restrict__ tab, int64_t rows, int64_t n, double *__restrict__ dst)
+{
+    for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
+        const double *s = src + tab[r];
+        double *d = dst + r * n;
+        for (int64_t i = threadIdx.x; i < n; i += blockDim.x) d[i] = s[i];
+    }
+}
+
+// rows of n float64 at element offsets of src_dev, one after the other into dst_dev: one upload of the table, one launch; then (dst_host)
+// one download through the pinned bounce buffers.  Synchronous.
+int itd_gather_rows_f64(itd_engine *e, const double *src_dev, int64_t src_elems, const int64_t *offsets_host, int64_t rows, int64_t n,
+                        double *dst_dev, double *dst_host, void *stream)
+{
+    if (!e || !src_dev || !offsets_host || !dst_dev || rows < 0 || rows > INT32_MAX || n < 1 || src_elems < n) return ITD_ERR_INVALID_ARG;
+    for (int64_t r = 0; r < rows; ++r)
+        if (offsets_host[r] < 0 || offsets_host[r] > src_elems - n) return ITD_ERR_INVALID_ARG;
+    if (rows == 0) return ITD_OK;
+    DevGuard g(e->device);
+    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
+    int rc = grow(e, &e->d_rowtab, &e->rowtab_bytes, (size_t)rows * sizeof(int64_t));
+    if (rc) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->d_rowtab, offsets_host, (size_t)rows * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    k_gather_rows<<<(unsigned)(rows < 65536 ? rows : 65536), 256, 0, st>>>(src_dev, e->d_rowtab, rows, n, dst_dev);
+    HIP_TRY(e, hipGetLastError());
+    if (dst_host) return copy_to_host(e, dst_host, dst_dev, (size_t)rows * (size_t)n * sizeof(double), st);
+    HIP_TRY(e, hipStreamSynchronize(st));
     return ITD_OK;
 }
 

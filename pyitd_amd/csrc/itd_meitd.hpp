@@ -50,7 +50,14 @@ struct MeitdCtx {
 };
 struct MeitdProbed { double wpe; int count, status; };
 
+// The operators below are instantiated per kernel (Tag 0: both k_meitd_small, 1 / 2: k_meitd_batch<false / true>), their static LDS
+// variables with them.  The compiler gives a variable that non-kernel functions of several kernels reach a place through a per-kernel
+// offset table, except for one set of kernels it keeps in a common struct at fixed addresses: k_meitd_small's pair holds that place as
+// before, the batched kernels' variables are reached from one kernel each (fixed addresses too), and k_meitd_small's code stays
+// what it was before the batched kernel existed.
+
 // (normalised entropy, extrema count) of a row: MEITD.py:346-351 / :373-378
+template <int Tag>
 __device__ __noinline__ MeitdProbed meitd_probe(MeitdCtx &c, int r)
 {
     constexpr int NT = kNakSmallThreads;
@@ -66,7 +73,7 @@ __device__ __noinline__ MeitdProbed meitd_probe(MeitdCtx &c, int r)
     int kn, nanf;
     long long t_sum = 0;
     const int probes = c.probes;
-    wpe3_pass<NT>(c.row(r), 0, (int64_t)c.n - 2, c.s_dyn, c.s_dyn + kWpeChunk + 2, s, cw, kn, nanf, &t_sum);
+    wpe3_pass<NT, Tag>(c.row(r), 0, (int64_t)c.n - 2, c.s_dyn, c.s_dyn + kWpeChunk + 2, s, cw, kn, nanf, &t_sum);
     const long long t1 = (long long)wall_clock64();
     if (tid < 6) { s_w[tid] = s; s_c[tid] = cw; }
     if (kn) atomicAdd(&s_k[0], kn);
@@ -111,6 +118,7 @@ __device__ __noinline__ MeitdProbed meitd_probe(MeitdCtx &c, int r)
 }
 
 // matlab_detect_peaks(v).size + matlab_detect_peaks(-v).size: ITD.py:59 on v and on -v, raw differences, samples 1 .. n-2
+template <int Tag>
 __device__ __noinline__ int meitd_count(MeitdCtx &c, int r)
 {
     constexpr int NT = kNakSmallThreads;
@@ -138,14 +146,14 @@ __device__ __noinline__ int meitd_count(MeitdCtx &c, int r)
 }
 
 // itd_baseline_extract (MEITD.py:303-338): src -> (rot, base; rot < 0: not wanted); returns the knot count of the produced baseline if asked for
-template <bool LDS>
+template <bool LDS, int Tag>
 __device__ __noinline__ int meitd_extract(MeitdCtx &c, int src, int base, int rot, int want_bcount)
 {
     const long long t0 = (long long)wall_clock64();
     __syncthreads();
     int res[4];
     long long t_ph[8] = {};
-    nak_small_body<LDS>(c.row(src), c.n, 0, c.e, c.K, c.dpg, c.M, c.cpg, c.subg, c.rhsg, c.row(base), rot >= 0 ? c.row(rot) : nullptr, want_bcount,
+    nak_small_body<LDS, Tag>(c.row(src), c.n, 0, c.e, c.K, c.dpg, c.M, c.cpg, c.subg, c.rhsg, c.row(base), rot >= 0 ? c.row(rot) : nullptr, want_bcount,
                         c.s_dyn, res, t_ph);
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -159,6 +167,7 @@ __device__ __noinline__ int meitd_extract(MeitdCtx &c, int src, int base, int ro
 }
 
 // dst = a - b (b < 0: dst = a; a < 0: dst = 0): MEITD.py:453 and the rows' assignments
+template <int Tag>
 __device__ __noinline__ void meitd_rowop(MeitdCtx &c, int dst, int a, int b)
 {
     constexpr int NT = kNakSmallThreads;
@@ -170,12 +179,29 @@ __device__ __noinline__ void meitd_rowop(MeitdCtx &c, int dst, int a, int b)
     if (threadIdx.x == 0) c.t_op[3] += (long long)wall_clock64() - t0;
 }
 
-template <bool LDS>
-__global__ __launch_bounds__(kNakSmallThreads) void k_meitd_small(double *__restrict__ rows, int n, double wpemax, int32_t *__restrict__ e,
-                                                                 double *__restrict__ K, double *__restrict__ dpg, double *__restrict__ M,
-                                                                 double *__restrict__ cpg, double *__restrict__ subg, double *__restrict__ rhsg,
-                                                                 MeitdProbe *__restrict__ log, MeitdOut *__restrict__ out /* both device memory: the host copies them
-                                                                                                                          behind the launch (milliseconds long) */)
+// XITD's entropy sums of one row (MEITD.py:536-549 orders the components by weighted_permutation_entropy(row, 3, True)): the six
+// weighted sums and window counts of wpe3_pass over the whole row — what itd_wpe3_f64 returns for it, bit for bit (the order of a
+// pattern's additions does not depend on the thread count); the entropy itself is drawn on the host
+template <int Tag>
+__device__ __noinline__ void meitd_sums(MeitdCtx &c, int r, double *__restrict__ w, long long *__restrict__ cw)
+{
+    constexpr int NT = kNakSmallThreads;
+    __syncthreads();
+    double s;
+    long long k;
+    int kn, nanf;
+    wpe3_pass<NT, Tag>(c.row(r), 0, (int64_t)c.n - 2, c.s_dyn, c.s_dyn + kWpeChunk + 2, s, k, kn, nanf);
+    if (threadIdx.x < 6) { w[threadIdx.x] = s; cw[threadIdx.x] = k; }
+}
+
+// The loop on the rows of one signal, for the kNakSmallThreads threads of one workgroup: k_meitd_small (one signal) and k_meitd_batch
+// (one signal per workgroup) both run it.  xw / xc (NULL: not wanted): after a delivered loop, XITD's sums (meitd_sums) of the kept
+// high rows, the kept low rows and the residual, in that order, kMeitdKept rows of 6 at most.
+template <bool LDS, int Tag>
+__device__ __forceinline__ void meitd_run(double *__restrict__ rows, int n, double wpemax, int32_t *__restrict__ e, double *__restrict__ K,
+                                          double *__restrict__ dpg, double *__restrict__ M, double *__restrict__ cpg, double *__restrict__ subg,
+                                          double *__restrict__ rhsg, MeitdProbe *__restrict__ log, MeitdOut *__restrict__ out,
+                                          double *__restrict__ xw, long long *__restrict__ xc)
 {
     extern __shared__ double s_dyn[];
     __shared__ MeitdCtx c;
@@ -193,19 +219,19 @@ __global__ __launch_bounds__(kNakSmallThreads) void k_meitd_small(double *__rest
     auto give = [&](int r) { free_rows = (free_rows & ~(15u << (4 * nfree))) | ((unsigned)r << (4 * nfree)); ++nfree; };
     auto proper_of = [&](double wpe) { return (wpe < wpemax && !(wpe < 0.2)) ? 1 : 0; };     // MEITD.py:364 / :387
     auto probe = [&](int r, double &wpe, int &count) {
-        const MeitdProbed p = meitd_probe(c, r);
+        const MeitdProbed p = meitd_probe<Tag>(c, r);
         wpe = p.wpe; count = p.count;
         if (p.status) status = p.status;
     };
-    auto count_knots = [&](int r) { const int k = meitd_count(c, r); if (k < 0) status = -k; return k < 0 ? 0 : k; };
+    auto count_knots = [&](int r) { const int k = meitd_count<Tag>(c, r); if (k < 0) status = -k; return k < 0 ? 0 : k; };
     auto extract = [&](int src, int base, int rot, bool want_bcount) {
-        const int k = meitd_extract<LDS>(c, src, base, rot, want_bcount ? 1 : 0);
+        const int k = meitd_extract<LDS, Tag>(c, src, base, rot, want_bcount ? 1 : 0);
         if (k < 0) status = -k;
         return k < 0 ? 0 : k;
     };
-    auto assign = [&](int dst, int src) { meitd_rowop(c, dst, src, -1); };
-    auto zero = [&](int dst) { meitd_rowop(c, dst, -1, -1); };
-    auto subtract_into = [&](int a, int b) { meitd_rowop(c, a, a, b); };                     // a = a - b (MEITD.py:453)
+    auto assign = [&](int dst, int src) { meitd_rowop<Tag>(c, dst, src, -1); };
+    auto zero = [&](int dst) { meitd_rowop<Tag>(c, dst, -1, -1); };
+    auto subtract_into = [&](int a, int b) { meitd_rowop<Tag>(c, a, a, b); };                     // a = a - b (MEITD.py:453)
     // determine_if_first_is_proper_rotation(src) into the rows rot / base (base < 0: not wanted); (wpe, cnt) = probe(src)
     auto determine = [&](int src, int rot, int base, double wpe, int cnt) {
         if (cnt < 5) {
@@ -298,6 +324,46 @@ __global__ __launch_bounds__(kNakSmallThreads) void k_meitd_small(double *__rest
         out->probes = c.probes; out->extractions = c.extractions; out->steps = steps; out->pad = 0;
         for (int q = 0; q < 16; ++q) out->ticks[q] = (int32_t)c.t_op[q];
     }
+    if (xw && status == kMeitdOk) {                               // (uniform: every thread holds the same status and counts)
+        const int rows_n = n_high + n_low + 1 < kMeitdKept ? n_high + n_low + 1 : kMeitdKept;
+        for (int k = 0; k < rows_n; ++k) {
+            const int r = k < n_high ? kMeitdWork + k : k < n_high + n_low ? kMeitdWork + kMeitdKept + (k - n_high) : x;
+            meitd_sums<Tag>(c, r, xw + 6 * k, xc + 6 * k);
+        }
+    }
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(kNakSmallThreads) void k_meitd_small(double *__restrict__ rows, int n, double wpemax, int32_t *__restrict__ e,
+                                                                 double *__restrict__ K, double *__restrict__ dpg, double *__restrict__ M,
+                                                                 double *__restrict__ cpg, double *__restrict__ subg, double *__restrict__ rhsg,
+                                                                 MeitdProbe *__restrict__ log, MeitdOut *__restrict__ out /* both device memory: the host copies them
+                                                                                                                          behind the launch (milliseconds long) */)
+{
+    meitd_run<LDS, 0>(rows, n, wpemax, e, K, dpg, M, cpg, subg, rhsg, log, out, nullptr, nullptr);
+}
+
+// One signal per workgroup (blockIdx.x): signal b's 50 rows at rows + b * rows_stride (x: NULL, or the signals, n apart, which the
+// workgroup first copies into row 5 of its block), its solver arrays in its own slice of `ws`
+// (sig_bytes per signal: the knot indices in the first idx_bytes, then six arrays of L doubles), its log at log + b * kMeitdLogCap,
+// its result at out[b], XITD's sums (xw, xc: NULL = not wanted) at b * kMeitdKept * 6.  The workgroups share nothing.
+template <bool LDS>
+__global__ __launch_bounds__(kNakSmallThreads) void k_meitd_batch(const double *__restrict__ x, double *__restrict__ rows, int64_t rows_stride, int n, double wpemax,
+                                                                 char *__restrict__ ws, int64_t sig_bytes, int64_t idx_bytes, int64_t L,
+                                                                 MeitdProbe *__restrict__ log, MeitdOut *__restrict__ out,
+                                                                 double *__restrict__ xw, long long *__restrict__ xc)
+{
+    const int64_t b = blockIdx.x;
+    if (x) {
+        const double *xb = x + b * n;
+        double *r5 = rows + b * rows_stride + 5 * (int64_t)n;
+        for (int i = threadIdx.x; i < n; i += kNakSmallThreads) r5[i] = xb[i];
+        __syncthreads();
+    }
+    char *sw = ws + b * sig_bytes;
+    double *arr = reinterpret_cast<double *>(sw + idx_bytes);
+    meitd_run<LDS, LDS ? 2 : 1>(rows + b * rows_stride, n, wpemax, reinterpret_cast<int32_t *>(sw), arr, arr + L, arr + 2 * L, arr + 3 * L, arr + 4 * L,
+                   arr + 5 * L, log + b * kMeitdLogCap, out + b, xw ? xw + b * kMeitdKept * 6 : nullptr, xc ? xc + b * kMeitdKept * 6 : nullptr);
 }
 
 }  // namespace itd

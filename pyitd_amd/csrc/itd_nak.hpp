@@ -194,7 +194,7 @@ constexpr size_t kNakSmallLdsMax = 156 * 1024;
 // The operator's body, for the kNakSmallThreads threads of one workgroup (k_nak_small below; k_meitd_small, itd_meitd.hpp, runs it
 // once per extraction of its loop).  s_dyn: 4 x (n + 2) doubles of LDS when LDS.  Comes back with res = {knots, NaN seen, valid,
 // knots of the produced baseline (want_bcount)} in every thread.  The caller puts a barrier between two uses.
-template <bool LDS>
+template <bool LDS, int Tag = 0>      // (Tag: a kernel of its own gets LDS variables of its own — see itd_meitd.hpp)
 __device__ __forceinline__ void nak_small_body(const double *__restrict__ x, int n, int min_extrema, int32_t *__restrict__ e,
                                                double *__restrict__ K, double *__restrict__ dpg, double *__restrict__ M,
                                                double *__restrict__ cpg, double *__restrict__ subg, double *__restrict__ rhsg,

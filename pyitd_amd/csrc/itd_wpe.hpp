@@ -51,7 +51,7 @@ constexpr int kWpeThreads = 256;
 // LDS).  Threads 0..5 come back with their pattern's sum and window count in (s, c); every thread with its share of kn — the number
 // of windows whose MIDDLE sample is a knot of x (ITD.py:59 on x and on -x, raw differences: what the count-only detection counts for
 // samples 1 .. n-2) — and nanf, whether it saw a NaN.  The order of every pattern's additions does not depend on NT.
-template <int NT>
+template <int NT, int Tag = 0>        // (Tag: as nak_small_body's, itd_nak.hpp)
 __device__ __forceinline__ void wpe3_pass(const double *__restrict__ x, int64_t lo, int64_t hi, double *__restrict__ s_x, double *__restrict__ s_l,
                                           double &s, long long &c, int &kn, int &nanf, long long *prof = nullptr)
 {

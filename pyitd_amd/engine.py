@@ -434,6 +434,32 @@ class Engine:
         self._check(self._L.itd_meitd_small_f64(self._h, rows_ptr, n, float(wpemax), _np_ptr(res), _np_ptr(log), len(log), stream))
         return res, log[:min(int(res[4]), len(log))]
 
+    def meitd_batch_dev(self, rows_ptr, n, batch, rows_stride, wpemax, x=None, xitd=False, stream=None):
+        """The same loop on `batch` signals, one workgroup each, in one launch (include/pyitd_hip.h: itd_meitd_batch_f64): signal b's
+        50 rows at rows_ptr + 8 * b * rows_stride; x (optional, float64[batch, n]) is copied into row 5 of every block first.  Returns
+        (result[batch, 24] as meitd_small_dev's, logs[batch, 1024] — signal b's first min(result[b, 4], 1024) entries are its log —,
+        and with xitd XITD's sums and window counts [batch, 22, 6] of each delivered signal's high rows, low rows and residual, else
+        None, None)."""
+        res = np.zeros((batch, 24), np.int32)
+        logs = np.empty((batch, 1024), self.MEITD_PROBE)
+        xw = np.zeros((batch, 22, 6), np.float64) if xitd else None
+        xc = np.zeros((batch, 22, 6), np.int64) if xitd else None
+        if x is not None:
+            x = np.ascontiguousarray(x, dtype=np.float64)
+            if x.shape != (batch, n):
+                raise ValueError("meitd_batch_dev: x must be [batch, n]")
+        self._check(self._L.itd_meitd_batch_f64(self._h, rows_ptr, n, batch, rows_stride, _np_ptr(x), float(wpemax), _np_ptr(res),
+                                                _np_ptr(logs), logs.shape[1], _np_ptr(xw), _np_ptr(xc), stream))
+        return res, logs, xw, xc
+
+    def gather_rows_dev(self, src_ptr, src_elems, offsets, n, dst_ptr, out=None, stream=None):
+        """rows of n float64 at the element offsets `offsets` of src_ptr (a buffer of src_elems), one after the other into dst_ptr;
+        out (optional, a C-contiguous float64[len(offsets), n]): then downloaded into it."""
+        tab = np.ascontiguousarray(offsets, dtype=np.int64)
+        if out is not None and (out.dtype != np.float64 or not out.flags["C_CONTIGUOUS"] or out.shape != (len(tab), n)):
+            raise ValueError("gather_rows_dev: out must be a C-contiguous float64[%d, %d]" % (len(tab), n))
+        self._check(self._L.itd_gather_rows_f64(self._h, src_ptr, src_elems, _np_ptr(tab), len(tab), n, dst_ptr, _np_ptr(out), stream))
+
     def subtract_dev(self, a_ptr, b_ptr, out_ptr, count, stream=None):
         self._check(self._L.itd_subtract_f64(self._h, a_ptr, b_ptr, out_ptr, count, stream))
 

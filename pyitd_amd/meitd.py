@@ -151,6 +151,8 @@ def release(device=None):
     with _lock:
         for key in [k for k in _work if device is None or k == int(device)]:
             _work.pop(key).buf.free()
+        for key in [k for k in _batch_rows if device is None or k == int(device)]:
+            _batch_rows.pop(key).free()
 
 
 def _done(w):
@@ -361,6 +363,14 @@ def MEITD(data, max_iteration=40, WPEMAX=0.6, device=0, solver="auto"):
     return high, low, residual
 
 
+def _xitd_early(data, device):
+    """XITD of a signal with fewer than 4 extrema (MEITD.py:411-413): zeros, zeros and the data, ordered by their entropy"""
+    zero = numpy.zeros(len(data))
+    rotations = numpy.vstack((numpy.vstack((zero, zero)), data))
+    ent = [weighted_permutation_entropy(rotations[i, :], order=3, normalize=True, device=device) for i in range(3)]
+    return rotations[numpy.argsort(ent), :]
+
+
 def XITD(data, device=0, solver="auto"):
     """MEITD.py:536-549 — MEITD's components and residual, ordered by their entropy (taken on the device rows).  solver: see MEITD."""
     data = numpy.ascontiguousarray(numpy.asarray(data).astype(dtype=numpy.float64))
@@ -368,10 +378,7 @@ def XITD(data, device=0, solver="auto"):
         wk = _work_for(len(data), device, solver)
         r = _meitd(wk, data, 0.6)                        # upstream passes its WPEMAX estimate where max_iteration goes (:541)
         if r is None:
-            zero = numpy.zeros(len(data))
-            rotations = numpy.vstack((numpy.vstack((zero, zero)), data))
-            ent = [weighted_permutation_entropy(rotations[i, :], order=3, normalize=True, device=device) for i in range(3)]
-            return rotations[numpy.argsort(ent), :]
+            return _xitd_early(data, device)
         n_high, n_low, x = r
         rows = [wk.kept(wk.high0, k) for k in range(n_high)] + [wk.kept(wk.low0, k) for k in range(n_low)] + [x]
         ent = [wk.entropy(p) for p in rows]
@@ -381,3 +388,129 @@ def XITD(data, device=0, solver="auto"):
         wk.give(x)
         _done(wk)
     return out
+
+
+# ---- many short signals of one length: MEITD_batch / XITD_batch ------------------------------------------------------------------
+_batch_rows = {}                   # device -> DeviceBuffer of a batch's rows, kept between calls up to _CACHE_MAX_BYTES
+_BATCH_BYTES = 1 << 30             # the default chunk keeps a launch's device memory (rows and the engine's scratch) at about this many bytes
+_GRID_MAX = 65535                  # signals per launch of itd_meitd_batch_f64
+last_batch = {}                    # the last MEITD_batch / XITD_batch: launches, status counts, signals handed back, ...
+
+
+def _batch_bytes(n):
+    """device bytes per signal of a batch: its (6 + 2 * 22) rows of n float64, and its share of itd_meitd_batch_f64's workspace —
+    knot indices and six solver arrays of n + 2, the signal's staging copy, XITD's sums, the result, and its probe log twice (1024
+    entries of 88 bytes: the kernel's log and the packed copy that goes to the host), with room for alignment"""
+    return (6 + 2 * _ROWS_KEPT) * n * 8 + 4 * (n + 2) + 6 * 8 * (n + 2) + 8 * n + _ROWS_KEPT * 6 * 16 + 96 + 2 * 1024 * 88 + 1024
+
+
+def _batch_chunk(n):
+    """signals per chunk by default: about _BATCH_BYTES of device memory in all (>= 271 signals for n <= 8192)"""
+    return max(1, min(_GRID_MAX, _BATCH_BYTES // _batch_bytes(n)))
+
+
+def _batch_buffer(nbytes, device):
+    key = int(device)
+    buf = _batch_rows.get(key)
+    if buf is None or buf.nbytes < nbytes:
+        if buf is not None:
+            _batch_rows.pop(key).free()
+        buf = _batch_rows[key] = DeviceBuffer(nbytes, device)
+    return buf
+
+
+def _batch(data, WPEMAX, device, solver, chunk, xitd):
+    global last_batch
+    what = "XITD_batch" if xitd else "MEITD_batch"
+    arr = numpy.asarray(data)
+    if arr.ndim != 2 or arr.shape[1] < 3:
+        raise ValueError("%s: data must be 2-D [B, N] with N >= 3 (got shape %s)" % (what, arr.shape))
+    if chunk is not None and int(chunk) < 1:
+        raise ValueError("%s: chunk must be at least 1" % what)
+    arr = numpy.ascontiguousarray(arr.astype(dtype=numpy.float64))
+    B, n = arr.shape
+    wpemax = 0.6 if xitd else WPEMAX               # (XITD runs MEITD with WPEMAX = 0.6: see XITD)
+
+    def single(x):
+        return XITD(x, device=device, solver=solver) if xitd else MEITD(x, WPEMAX=WPEMAX, device=device, solver=solver)
+
+    stats = last_batch = {"signals": B, "launches": 0, "chunks": 0, "status": {}, "handed_back": 0, "looped": 0}
+    with _lock:
+        if not (3 <= n <= _ONE_LAUNCH_MAX and (solver == "parallel" or (solver == "auto" and n >= 1024))):
+            stats["looped"] = B                    # no one-launch form for this length / solver: the single-signal path, one by one
+            return [single(x) for x in arr]
+        per = (6 + 2 * _ROWS_KEPT) * n             # elements of one signal's rows
+        c = min(B, int(chunk) if chunk is not None else _batch_chunk(n))
+        buf = _batch_buffer(c * per * 8, device)
+        out = []
+        try:
+            for c0 in range(0, B, c):
+                xs = arr[c0:c0 + c]
+                m = len(xs)
+                # (the engine is shared: a single-signal call of the chunk before — a fallback, XITD's entropies of a signal with
+                # fewer than 4 extrema — may have set its solver to something else)
+                eng = _eng(n, device, solver)
+                res, logs, xw, xc = eng.meitd_batch_dev(buf.ptr, n, m, per, wpemax, x=xs, xitd=xitd)
+                stats["chunks"] += 1
+                stats["launches"] += (m + _GRID_MAX - 1) // _GRID_MAX
+                status = res[:, 0]
+                for v, k in zip(*numpy.unique(status, return_counts=True)):
+                    stats["status"][int(v)] = stats["status"].get(int(v), 0) + int(k)
+                # the logged threshold tests of every delivered signal, re-drawn with numpy in one call (as _meitd_one_launch)
+                ok = numpy.flatnonzero(status == 0)
+                if len(ok):
+                    probes = res[ok, 4].astype(numpy.int64)
+                    log = numpy.concatenate([logs[b, :p] for b, p in zip(ok, probes)])
+                    wd = log["wpe"]
+                    agree = _proper_rows(log, wpemax) == ((wd < wpemax) & ~(wd < 0.2))
+                    ok = numpy.setdiff1d(ok, numpy.repeat(ok, probes)[~agree])
+                # one table of the delivered signals' rows (XITD: in the order of their entropies), one gather, one download
+                tab, spans = [], {}
+                for b in ok:
+                    nh, nl, xr = (int(v) for v in res[b, 1:4])
+                    base = int(b) * per
+                    rows = [base + (6 + k) * n for k in range(nh)] + [base + (6 + _ROWS_KEPT + k) * n for k in range(nl)] + [base + xr * n]
+                    if xitd:
+                        ent = [_entropy_from_bins(xw[b, k], xc[b, k], 3, True) for k in range(len(rows))]
+                        rows = [rows[i] for i in numpy.argsort(ent)]
+                    spans[int(b)] = (len(tab), nh, nl)
+                    tab += rows
+                got = numpy.empty((len(tab), n))
+                if tab:
+                    dst = DeviceBuffer(got.nbytes, device)
+                    try:
+                        eng.gather_rows_dev(buf.ptr, m * per, tab, n, dst.ptr, out=got)
+                    finally:
+                        dst.free()
+                for b in range(m):
+                    if b in spans:
+                        r0, nh, nl = spans[b]
+                        out.append(got[r0:r0 + nh + nl + 1] if xitd else (got[r0:r0 + nh], got[r0 + nh:r0 + nh + nl], got[r0 + nh + nl]))
+                    elif status[b] == 1:               # fewer than 4 extrema (MEITD.py:411-413)
+                        x = xs[b].copy()
+                        zero = numpy.zeros(n)
+                        out.append(_xitd_early(x, device) if xitd else (zero, zero, x))
+                    else:                              # not delivered, or a threshold test numpy draws otherwise: the single-signal path
+                        stats["handed_back"] += 1
+                        out.append(single(xs[b]))
+        finally:
+            if buf.nbytes > _CACHE_MAX_BYTES:
+                _batch_rows.pop(int(device)).free()
+    return out
+
+
+def MEITD_batch(data, max_iteration=40, WPEMAX=0.6, device=0, solver="auto", chunk=None):
+    """[MEITD(x, max_iteration, WPEMAX) for x in data] for data[B, N], bit for bit — the same components, the same exception for the
+    first signal that raises — with the loop of every signal in one launch, one workgroup (one CU) per signal
+    (include/pyitd_hip.h: itd_meitd_batch_f64).  A signal the launch does not deliver (a NaN, an extraction scipy would refuse, a
+    threshold test that numpy's log2 draws otherwise) goes through MEITD on its own; the rest keep the launch's result.  Only where
+    MEITD itself takes the one-launch form: N <= 8192 and solver "parallel", or "auto" with N >= 1024.  Other lengths / solvers loop
+    over MEITD signal by signal: correct, not faster.  chunk: signals per launch (default: about 1 GiB of device memory, at least 256
+    signals for N <= 8192); the results do not depend on it.  `last_batch` describes the call."""
+    return _batch(data, WPEMAX, device, solver, chunk, False)
+
+
+def XITD_batch(data, device=0, solver="auto", chunk=None):
+    """[XITD(x) for x in data] for data[B, N], bit for bit: MEITD_batch's launch, which also returns the six entropy sums of every
+    kept row and the residual; the entropies are drawn and ordered here as XITD draws them.  See MEITD_batch."""
+    return _batch(data, 0.6, device, solver, chunk, True)
