@@ -560,6 +560,7 @@ int itd_baseline_extract_cubic_batch_f64(itd_engine *e, const double *x_dev, int
 typedef struct itd_stream itd_stream;   /* opaque; not thread-safe */
 #define ITD_STREAM_CUBIC 0
 #define ITD_STREAM_LINEAR 1
+#define ITD_STREAM_LEVELS 2   /* a levels stream (itd_levels_stream_create); not a kind itd_stream_create takes */
 int itd_stream_create(itd_stream **out, int device_id, int64_t block /* samples, >= 8 */, int32_t channels, int32_t kind,
                       int32_t margin /* cubic: >= 1 */, int32_t shared_knots);
 void itd_stream_destroy(itd_stream *s);
@@ -577,6 +578,38 @@ int itd_stream_push_host_f64(itd_stream *s, const double *block_host, double *ba
 int itd_stream_flush_host_f64(itd_stream *s, double *baseline_host, double *rot_host, int32_t *emitted);
 /* synchronises the device; *status = 0, or 2 if some window since create / reset held a NaN */
 int itd_stream_status(itd_stream *s, int32_t *status);
+
+/* ---- the levels stream: the full multi-level ITD block by block -----------------------------------------------------------
+ * A chain of levels + 1 (M + 1) ITD_STREAM_LINEAR stages: stage 0 runs on the caller's blocks, stage k >= 1 on the baselines
+ * stage k-1 emits.  The rows of block j are the rotations of stages 0 .. M-1 and, as row M, stage M's rotation + baseline
+ * (ITD.py:418-426, the driver's "Out of time!" row): where the whole signal runs to max_iteration = M-1 without a natural
+ * stop these are block j's columns of ITD().itd(x, M-1).  Block j's rows leave on push j+M+1 (blocks and pushes counted from 0;
+ * the minimum: stage k emits block j once it holds block j+1 of its input), so the first M+1 pushes emit nothing; flush emits
+ * one block per call (emitted = 0 once empty, and the stream then starts afresh).  A push between flushes is refused.
+ * Each emitted block comes with exact[c] = 1 where its M+1 rows are certified bit-identical to the whole-signal rows of the
+ * concatenated blocks (a sound, conservative rule; the rule and its argument: itd_stream.hpp, k_stream_levels); a window
+ * holding a NaN is never certified and sets itd_stream_status's bit 2 (the block follows the single-level stream's plain rules).
+ * block >= 8 samples, channels 1 .. 65535, levels 1 .. 21.  Blocks up to 2730 samples (3 blocks <= 8192) take ONE launch per
+ * step (one workgroup per channel holds the window in LDS); longer blocks take a launch sequence (per stage: the batched tier-1
+ * extraction of every channel's window, then one routing / certificate kernel), bit-identical to the one-launch form.
+ * itd_levels_stream_set_sequence(s, 1) forces the sequence form on a short block (0: back to one launch; refused for a long
+ * block); itd_levels_stream_form returns the form in use (0 one launch, 1 sequence, -1 not a levels stream).  Everything is
+ * allocated at create (or, for a forced sequence form, by the setter; ITD_ERR_NOMEM when it does not fit): M+1 rings of 5
+ * blocks and M (M+1) / 2 delayed blocks per channel, plus, for the sequence form, the windows' results (6 blocks per channel).  itd_stream_destroy / reset / status / blocks / last_error apply; the
+ * single-level push / flush entries refuse a levels stream.
+ * Device forms: block_dev [channels][block] at in_stride; rows_dev[c][r][s] at c chan_stride + r row_stride + s (row_stride >=
+ * block, chan_stride >= M row_stride + block when channels > 1), required when the call emits; exact_dev [channels] optional.
+ * They enqueue on `stream` and return.  Host forms: contiguous [channels][block] in, [channels][M+1][block] rows and [channels]
+ * flags out, one synchronisation per call. */
+int itd_levels_stream_create(itd_stream **out, int device_id, int64_t block, int32_t channels, int32_t levels);
+int itd_levels_stream_set_sequence(itd_stream *s, int32_t on);
+int itd_levels_stream_form(const itd_stream *s);
+int itd_levels_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_stride, double *rows_dev, int64_t row_stride,
+                               int64_t chan_stride, uint8_t *exact_dev, int32_t *emitted, void *stream);
+int itd_levels_stream_flush_f64(itd_stream *s, double *rows_dev, int64_t row_stride, int64_t chan_stride, uint8_t *exact_dev,
+                                int32_t *emitted, void *stream);
+int itd_levels_stream_push_host_f64(itd_stream *s, const double *block_host, double *rows_host, uint8_t *exact_host, int32_t *emitted);
+int itd_levels_stream_flush_host_f64(itd_stream *s, double *rows_host, uint8_t *exact_host, int32_t *emitted);
 
 /* ---- introspection for benchmarks -------------------------------------------------------------
  * hipEvent pairs on the launch stream.  Extraction launches are dispatched with their own start/stop events

@@ -99,6 +99,15 @@ struct itd_stream {
     int32_t *d_status = nullptr;    // sticky: |= 2 when a window held a NaN
     double *h_in = nullptr, *h_out = nullptr;   // pinned staging of the host form: [C][L], [2][C][L]
     double *d_in = nullptr, *d_out = nullptr;   // device staging of the host form
+    // levels stream (ITD_STREAM_LEVELS, k_stream_levels in itd_stream.hpp): ring = [C][M+1][5 L]
+    int32_t M = 0, cw = 0, threads = 0;
+    int32_t seq = 0;                // 1: the launch-sequence form (blocks above 2730 samples, or itd_levels_stream_set_sequence)
+    int64_t t = 0, P = -1;          // the next step; the blocks in all once flushing began (-1: pushing)
+    double *delay = nullptr;        // [C][M (M+1) / 2][L]
+    uint8_t *eflags = nullptr;      // [C][M+1][4]
+    uint8_t *d_exact = nullptr, *h_exact = nullptr;   // host form: [C]
+    size_t lds = 0;
+    const void *fn = nullptr;
 };
 
 namespace {
@@ -255,6 +264,8 @@ void itd_stream_destroy(itd_stream *s)
         (void)hipStreamSynchronize(s->eng->own_stream);
         (void)hipFree(s->ring); (void)hipFree(s->scr); (void)hipFree(s->jobs); (void)hipFree(s->arr); (void)hipFree(s->d_status);
         (void)hipFree(s->d_in); (void)hipFree(s->d_out);
+        (void)hipFree(s->delay); (void)hipFree(s->eflags); (void)hipFree(s->d_exact);
+        if (s->h_exact) (void)hipHostFree(s->h_exact);
         if (s->h_in) (void)hipHostFree(s->h_in);
         if (s->h_out) (void)hipHostFree(s->h_out);
         itd_engine_destroy(s->eng);
@@ -267,18 +278,25 @@ int itd_stream_reset(itd_stream *s)
     if (!s) return ITD_ERR_INVALID_ARG;
     DevGuard g(s->eng->device);
     s->pushed = 0;
+    s->t = 0;
+    s->P = -1;
     HIP_TRY(s->eng, hipMemsetAsync(s->d_status, 0, sizeof(int32_t), s->eng->own_stream));
     HIP_TRY(s->eng, hipStreamSynchronize(s->eng->own_stream));
     return ITD_OK;
 }
 
-int64_t itd_stream_blocks(const itd_stream *s) { return s ? s->pushed : -1; }
+int64_t itd_stream_blocks(const itd_stream *s)
+{
+    if (!s) return -1;
+    if (s->kind != ITD_STREAM_LEVELS) return s->pushed;
+    return (s->P < 0 ? s->t : s->P) - std::max<int64_t>(0, s->t - s->M - 1);   // pushed, less the blocks whose rows have left
+}
 const char *itd_stream_last_error(const itd_stream *s) { return s && s->eng ? s->eng->err : "null stream"; }
 
 int itd_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_stride, double *baseline_dev, int64_t baseline_stride,
                         double *rot_dev, int64_t rot_stride, int32_t *emitted, void *stream)
 {
-    if (!s || !block_dev) return ITD_ERR_INVALID_ARG;
+    if (!s || !block_dev || s->kind == ITD_STREAM_LEVELS) return ITD_ERR_INVALID_ARG;
     if (s->C > 1 && (in_stride < s->L || (baseline_dev && baseline_stride < s->L) || (rot_dev && rot_stride < s->L))) return ITD_ERR_INVALID_ARG;
     if (s->pushed >= 1 && !baseline_dev) return ITD_ERR_INVALID_ARG;      // this push emits a block
     DevGuard g(s->eng->device);
@@ -289,7 +307,7 @@ int itd_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_strid
 int itd_stream_flush_f64(itd_stream *s, double *baseline_dev, int64_t baseline_stride, double *rot_dev, int64_t rot_stride,
                          int32_t *emitted, void *stream)
 {
-    if (!s) return ITD_ERR_INVALID_ARG;
+    if (!s || s->kind == ITD_STREAM_LEVELS) return ITD_ERR_INVALID_ARG;
     if (s->pushed >= 1 && !baseline_dev) return ITD_ERR_INVALID_ARG;
     if (s->C > 1 && ((baseline_dev && baseline_stride < s->L) || (rot_dev && rot_stride < s->L))) return ITD_ERR_INVALID_ARG;
     DevGuard g(s->eng->device);
@@ -311,7 +329,7 @@ namespace {
 // host form: pinned staging in and out, ONE synchronisation per call
 int stream_host(itd_stream *s, const double *block_host, double *baseline_host, double *rot_host, int32_t *emitted, bool flush)
 {
-    if (!s || (!flush && !block_host) || !baseline_host) return ITD_ERR_INVALID_ARG;
+    if (!s || (!flush && !block_host) || !baseline_host || s->kind == ITD_STREAM_LEVELS) return ITD_ERR_INVALID_ARG;
     itd_engine *e = s->eng;
     DevGuard g(e->device);
     const size_t cnt = (size_t)s->C * (size_t)s->L;
@@ -356,5 +374,279 @@ int itd_stream_push_host_f64(itd_stream *s, const double *block_host, double *ba
 int itd_stream_flush_host_f64(itd_stream *s, double *baseline_host, double *rot_host, int32_t *emitted)
 {
     return stream_host(s, nullptr, baseline_host, rot_host, emitted, true);
+}
+}  // extern "C"
+
+// ---- the levels stream: itd_levels_stream_* (include/pyitd_hip.h; the kernel, its schedule and the exactness rule:
+//      k_stream_levels in itd_stream.hpp) ------------------------------------------------------------------------------
+namespace {
+
+// the launch-sequence form of one step: the new block into stage 0's ring, then per stage extract_batch of every channel's
+// window and k_levels_route (itd_stream.hpp); a drained stage only lets its delayed rotation leave
+int levels_step_seq(itd_stream *s, const LevelsArgs &a, hipStream_t st)
+{
+    const int64_t L = s->L, ring_stride = (int64_t)(s->M + 1) * 5 * L;
+    const int C = s->C;
+    if (a.in)
+        k_stream_store<<<dim3((unsigned)((L + 255) / 256), C), 256, 0, st>>>(a.in, a.in_stride, s->ring, ring_stride, L, (int)(a.t % 3));
+    LevelsRoute r;
+    r.a = a;
+    r.rw = s->scr;
+    r.bw = s->scr + (int64_t)C * 3 * L;
+    const int64_t jo = a.t - 1 - s->M;
+    const bool out = a.rows && jo >= 0 && (a.P < 0 || jo <= a.P - 1);
+    for (int k = 0; k <= s->M; ++k) {
+        const int64_t j = a.t - 1 - k;
+        const bool active = j >= 0 && (a.P < 0 || j <= a.P - 1);
+        if (!active && !(out && k < s->M)) continue;
+        if (active) {
+            const bool succ = a.P < 0 || j + 1 <= a.P - 1;
+            const int64_t f = j > 0 ? j - 1 : 0, n = (j - f + (succ ? 2 : 1)) * L;
+            const int rc = extract_batch(s->eng, s->ring + (int64_t)k * 5 * L + (f % 3) * L, n, C, ring_stride, s->scr, 3 * L,
+                                         s->scr + (int64_t)C * 3 * L, 3 * L, nullptr, s->d_status, st);
+            if (rc) return rc;
+        }
+        r.k = k;
+        k_levels_route<1024><<<C, 1024, 0, st>>>(r);
+    }
+    HIP_TRY(s->eng, hipGetLastError());
+    return ITD_OK;
+}
+
+// one step of every stage: ONE launch (or the launch sequence).  rows / exact: where the step's emitted block goes (ignored when
+// it emits none)
+int levels_step(itd_stream *s, const double *blk, int64_t in_stride, double *rows, int64_t row_stride, int64_t chan_stride,
+                uint8_t *exact, hipStream_t st)
+{
+    LevelsArgs a;
+    a.in = blk; a.in_stride = in_stride;
+    a.ring = s->ring; a.delay = s->delay; a.eflags = s->eflags;
+    a.rows = rows; a.row_stride = row_stride; a.chan_stride = chan_stride; a.exact = exact;
+    a.status = s->d_status;
+    a.t = s->t; a.P = s->P;
+    a.L = (int)s->L; a.M = s->M; a.cw = s->cw;
+    if (s->seq) {
+        const int rc = levels_step_seq(s, a, st);
+        if (rc) return rc;
+        ++s->t;
+        return ITD_OK;
+    }
+    void *args[] = {&a};
+    HIP_TRY(s->eng, hipLaunchKernel(s->fn, dim3((unsigned)s->C), dim3((unsigned)s->threads), args, s->lds, st));
+    HIP_TRY(s->eng, hipGetLastError());
+    ++s->t;
+    return ITD_OK;
+}
+
+bool levels_rows_ok(const itd_stream *s, double *rows, int64_t row_stride, int64_t chan_stride)
+{
+    if (!rows) return true;
+    if (row_stride < s->L) return false;
+    return s->C == 1 || chan_stride >= (int64_t)s->M * row_stride + s->L;
+}
+
+int levels_push(itd_stream *s, const double *blk, int64_t in_stride, double *rows, int64_t row_stride, int64_t chan_stride,
+                uint8_t *exact, int32_t *emitted, hipStream_t st)
+{
+    const bool emits = s->t >= s->M + 1;
+    const int rc = levels_step(s, blk, in_stride, emits ? rows : nullptr, row_stride, chan_stride, exact, st);
+    if (rc) return rc;
+    if (emitted) *emitted = emits ? 1 : 0;
+    return ITD_OK;
+}
+
+// one block per call: the steps behind the last push until one emits (a stream of fewer than M+1 blocks has emitted none yet)
+int levels_flush(itd_stream *s, double *rows, int64_t row_stride, int64_t chan_stride, uint8_t *exact, int32_t *emitted,
+                 hipStream_t st)
+{
+    if (emitted) *emitted = 0;
+    if (s->P < 0 && s->t == 0) return ITD_OK;      // empty: nothing to run
+    if (s->P < 0) s->P = s->t;
+    for (;;) {
+        const int64_t jo = s->t - 1 - s->M;
+        if (jo > s->P - 1) {            // empty
+            s->t = 0;
+            s->P = -1;
+            return ITD_OK;
+        }
+        const int rc = levels_step(s, nullptr, 0, jo >= 0 ? rows : nullptr, row_stride, chan_stride, exact, st);
+        if (rc) return rc;
+        if (jo >= 0) {
+            if (emitted) *emitted = 1;
+            if (jo == s->P - 1) { s->t = 0; s->P = -1; }   // the last block: the stream starts afresh
+            return ITD_OK;
+        }
+    }
+}
+
+// the launch-sequence form's window results [2][C][3 L] and extract_batch's workspace, at create / when the form is forced
+int levels_seq_alloc(itd_stream *s)
+{
+    if (s->scr) return ITD_OK;
+    const size_t bytes = 2 * (size_t)s->C * 3 * (size_t)s->L * sizeof(double);
+    hipError_t hrc = hipMalloc((void **)&s->scr, bytes);
+    if (hrc != hipSuccess) {
+        (void)hipGetLastError();
+        s->scr = nullptr;
+        return hrc == hipErrorOutOfMemory ? ITD_ERR_NOMEM : fail_hip(s->eng, hrc, "hipMalloc(levels stream scratch)");
+    }
+    poison(s->scr, bytes);
+    BatchWs w;
+    const int rc = batch_workspace(s->eng, 3 * s->L, std::min<int32_t>(s->C, kMaxGridY), w);
+    if (rc) return rc;
+    HIP_TRY(s->eng, hipDeviceSynchronize());
+    return ITD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int itd_levels_stream_create(itd_stream **out, int device_id, int64_t block, int32_t channels, int32_t levels)
+{
+    if (!out) return ITD_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (block < 8 || 3 * block >= (int64_t)INT32_MAX - 65536 || channels < 1 || channels > kMaxGridY) return ITD_ERR_INVALID_ARG;
+    if (levels < 1 || levels > ITD_MAX_ROWS - 1) return ITD_ERR_INVALID_ARG;
+    itd_stream *s = new (std::nothrow) itd_stream();
+    if (!s) return ITD_ERR_NOMEM;
+    int rc = itd_engine_create(&s->eng, device_id, 3 * block, 1);
+    if (rc) { delete s; return rc; }
+    s->L = block; s->C = channels; s->kind = ITD_STREAM_LEVELS; s->M = levels;
+    DevGuard g(device_id);
+    hipError_t hrc = hipSuccess;
+    if (3 * block <= kResidentMax) {
+        // the one-launch geometry of a three-block window (k_resident's classes) and its window of by-rank knot slots
+        const int n3 = (int)(3 * block);
+        int cw = std::min(resident_auto_window(n3), resident_pad(n3));
+        while (resident_lds_bytes(n3, cw) > kResidentLdsMax) cw -= 64;
+        const int cls = n3 <= 256 ? 0 : n3 <= 512 ? 1 : n3 <= 1024 ? 2 : n3 <= 2048 ? 3 : n3 <= 4096 ? 4 : 5;
+        s->cw = cw;
+        s->lds = resident_lds_bytes(n3, cw);
+        s->threads = cls == 5 ? 1024 : 64 << cls;
+        s->fn = cls == 0 ? reinterpret_cast<const void *>(&k_stream_levels<64, 4>)
+              : cls == 1 ? reinterpret_cast<const void *>(&k_stream_levels<128, 4>)
+              : cls == 2 ? reinterpret_cast<const void *>(&k_stream_levels<256, 4>)
+              : cls == 3 ? reinterpret_cast<const void *>(&k_stream_levels<512, 4>)
+              : cls == 4 ? reinterpret_cast<const void *>(&k_stream_levels<1024, 4>)
+                         : reinterpret_cast<const void *>(&k_stream_levels<1024, 8>);
+        hrc = hipFuncSetAttribute(s->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kResidentLdsMax);
+    } else {
+        s->seq = 1;                 // the window does not fit one workgroup's LDS: the launch sequence
+    }
+    const size_t C = (size_t)channels, L = (size_t)block, R = (size_t)levels + 1;
+    const size_t ring_b = C * R * 5 * L * sizeof(double), delay_b = C * ((size_t)levels * R / 2) * L * sizeof(double);
+    if (hrc == hipSuccess) hrc = hipMalloc((void **)&s->ring, ring_b);
+    if (hrc == hipSuccess) hrc = hipMalloc((void **)&s->delay, delay_b);
+    if (hrc == hipSuccess) hrc = hipMalloc((void **)&s->eflags, C * R * 4);
+    if (hrc == hipSuccess) hrc = hipMalloc((void **)&s->d_status, 64);
+    if (hrc == hipSuccess) hrc = hipMemset(s->d_status, 0, 64);
+    // the host form's staging: [C][L] in, [C][M+1][L] rows and [C] flags out
+    if (hrc == hipSuccess) hrc = hipMalloc((void **)&s->d_in, C * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = hipMalloc((void **)&s->d_out, C * R * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = hipMalloc((void **)&s->d_exact, C);
+    if (hrc == hipSuccess) hrc = hipHostMalloc((void **)&s->h_in, C * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = hipHostMalloc((void **)&s->h_out, C * R * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = hipHostMalloc((void **)&s->h_exact, C);
+    if (hrc == hipSuccess) {
+        poison(s->ring, ring_b); poison(s->delay, delay_b); poison(s->eflags, C * R * 4);
+        poison(s->d_in, C * L * sizeof(double)); poison(s->d_out, C * R * L * sizeof(double)); poison(s->d_exact, C);
+    }
+    if (hrc == hipSuccess) hrc = hipDeviceSynchronize();     // (the fills ran on the null stream)
+    if (hrc != hipSuccess) {
+        const bool oom = hrc == hipErrorOutOfMemory;
+        (void)hipGetLastError();
+        itd_stream_destroy(s);
+        return oom ? ITD_ERR_NOMEM : ITD_ERR_HIP;
+    }
+    if (s->seq && (rc = levels_seq_alloc(s)) != ITD_OK) {
+        itd_stream_destroy(s);
+        return rc;
+    }
+    *out = s;
+    return ITD_OK;
+}
+
+int itd_levels_stream_set_sequence(itd_stream *s, int32_t on)
+{
+    if (!s || s->kind != ITD_STREAM_LEVELS || (on != 0 && on != 1)) return ITD_ERR_INVALID_ARG;
+    if (!on && !s->fn) return ITD_ERR_INVALID_ARG;        // the block is too long for the one-launch form
+    if (on) {
+        DevGuard g(s->eng->device);
+        const int rc = levels_seq_alloc(s);
+        if (rc) return rc;
+    }
+    s->seq = on;
+    return ITD_OK;
+}
+
+int itd_levels_stream_form(const itd_stream *s) { return s && s->kind == ITD_STREAM_LEVELS ? s->seq : -1; }
+
+int itd_levels_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_stride, double *rows_dev, int64_t row_stride,
+                               int64_t chan_stride, uint8_t *exact_dev, int32_t *emitted, void *stream)
+{
+    if (!s || !block_dev || s->kind != ITD_STREAM_LEVELS) return ITD_ERR_INVALID_ARG;
+    if (s->P >= 0) return ITD_ERR_INVALID_ARG;                               // flushing: drain or reset first
+    if (s->C > 1 && in_stride < s->L) return ITD_ERR_INVALID_ARG;
+    if (s->t >= s->M + 1 && !rows_dev) return ITD_ERR_INVALID_ARG;          // this push emits a block
+    if (!levels_rows_ok(s, rows_dev, row_stride, chan_stride)) return ITD_ERR_INVALID_ARG;
+    DevGuard g(s->eng->device);
+    return levels_push(s, block_dev, in_stride, rows_dev, row_stride, chan_stride, exact_dev, emitted,
+                       stream ? (hipStream_t)stream : s->eng->own_stream);
+}
+
+int itd_levels_stream_flush_f64(itd_stream *s, double *rows_dev, int64_t row_stride, int64_t chan_stride, uint8_t *exact_dev,
+                                int32_t *emitted, void *stream)
+{
+    if (!s || s->kind != ITD_STREAM_LEVELS) return ITD_ERR_INVALID_ARG;
+    if (itd_stream_blocks(s) > 0 && !rows_dev) return ITD_ERR_INVALID_ARG;  // this flush emits a block
+    if (!levels_rows_ok(s, rows_dev, row_stride, chan_stride)) return ITD_ERR_INVALID_ARG;
+    DevGuard g(s->eng->device);
+    return levels_flush(s, rows_dev, row_stride, chan_stride, exact_dev, emitted, stream ? (hipStream_t)stream : s->eng->own_stream);
+}
+
+}  // extern "C"
+
+namespace {
+// host form: pinned staging in and out, ONE synchronisation per call
+int levels_host(itd_stream *s, const double *block_host, double *rows_host, uint8_t *exact_host, int32_t *emitted, bool flush)
+{
+    if (!s || s->kind != ITD_STREAM_LEVELS || (!flush && !block_host) || !rows_host) return ITD_ERR_INVALID_ARG;
+    if (!flush && s->P >= 0) return ITD_ERR_INVALID_ARG;
+    itd_engine *e = s->eng;
+    DevGuard g(e->device);
+    const size_t cnt = (size_t)s->C * (size_t)s->L, R = (size_t)s->M + 1;
+    hipStream_t st = e->own_stream;
+    int32_t em = 0;
+    int rc;
+    if (flush) rc = levels_flush(s, s->d_out, s->L, (int64_t)R * s->L, s->d_exact, &em, st);
+    else {
+        memcpy(s->h_in, block_host, cnt * sizeof(double));
+        HIP_TRY(e, hipMemcpyAsync(s->d_in, s->h_in, cnt * sizeof(double), hipMemcpyHostToDevice, st));
+        rc = levels_push(s, s->d_in, s->L, s->d_out, s->L, (int64_t)R * s->L, s->d_exact, &em, st);
+    }
+    if (rc) return rc;
+    if (em) {
+        HIP_TRY(e, hipMemcpyAsync(s->h_out, s->d_out, R * cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(e, hipMemcpyAsync(s->h_exact, s->d_exact, (size_t)s->C, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(e, hipStreamSynchronize(st));
+    if (em) {
+        memcpy(rows_host, s->h_out, R * cnt * sizeof(double));
+        if (exact_host) memcpy(exact_host, s->h_exact, (size_t)s->C);
+    }
+    if (emitted) *emitted = em;
+    return ITD_OK;
+}
+}  // namespace
+
+extern "C" {
+int itd_levels_stream_push_host_f64(itd_stream *s, const double *block_host, double *rows_host, uint8_t *exact_host, int32_t *emitted)
+{
+    return levels_host(s, block_host, rows_host, exact_host, emitted, false);
+}
+int itd_levels_stream_flush_host_f64(itd_stream *s, double *rows_host, uint8_t *exact_host, int32_t *emitted)
+{
+    return levels_host(s, nullptr, rows_host, exact_host, emitted, true);
 }
 }  // extern "C"

@@ -80,6 +80,144 @@ __device__ __forceinline__ double res_load(__amdgpu_buffer_rsrc_t r, int i, cons
     return (double)__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, i * 4, 0, 0));
 }
 
+// ---- the per-level body of the one-workgroup kernels, k_resident (below) and k_stream_levels (itd_stream.hpp) ---------------
+// Both expand these statement macros, so a block-wise extraction is the resident arithmetic itself.  Macros, not functions:
+// k_resident compiles to the same instructions as before they were shared (a function boundary changes the optimiser's order
+// and with it the registers and schedule).  In scope at the expansion: W, SPT, WPL, tid, wave, lane, n, np2, Q, xs, Xk, Bk, Sk,
+// ends, bal, pre, ek, xr[], and
+//   ITD_RES_FLAGS    cs (cs[1] = 1: the array holds a NaN).  Knot flags of xs (interior samples 1 .. n-2, ITD.py:44-59, 87-98,
+//                    plain comparisons) into bal[], one word per 64 samples; the caller puts a barrier behind it
+//   ITD_RES_PREFIX   the level's end samples into ends[], the exclusive prefix of the wavefront's own words into pre[], the
+//                    knot count into a new `const int total`
+//   ITD_RES_PASSES   m (knots), cw.  One tier-1 extraction (ITD.py:79-121) of xr[] / xs in passes of cw segments: the baseline
+//                    replaces the input in xs; EMIT runs for every sample i (input xr[j], baseline b).  Ends with a barrier.
+#define ITD_RES_FLAGS \
+_Pragma("unroll")                                                                                                                                               \
+        for (int j = 0; j < SPT; ++j) {                                                                                                                         \
+            const int q = wave + W * j, i = q * 64 + lane;                                                                                                      \
+            if (q < Q) {                                                                                                                                        \
+                const double c = xs[i];                                                                                                                         \
+                /* dx[i-1], dx[i] (ITD.py:44); the reads next to the signal's ends stay inside xs (word 0 starts at sample 0, the */                            \
+                /* padding ends the last word) and only interior samples can flag */                                                                            \
+                const double d0 = c - ((ITD_RES_ABL & 128) ? 0.5 : xs[i > 0 ? i - 1 : 0]), d1 = ((ITD_RES_ABL & 128) ? 0.25 : xs[i < np2 - 1 ? i + 1 : i]) - c; \
+                const bool f = ((d1 > 0.0 && d0 <= 0.0) || (d1 < 0.0 && d0 >= 0.0)) && i >= 1 && i <= n - 2;  /* valley of x or of -x (ITD.py:59, 87-88) */     \
+                const unsigned long long bw = __ballot(f);                                                                                                      \
+                const unsigned long long bb = __ballot(c != c);                                                                                                 \
+                if (lane == 0) {                                                                                                                                \
+                    bal[q] = bw;                                                                                                                                \
+                    if (bb) cs[1] = 1;                                                                                                                          \
+                }                                                                                                                                               \
+            }                                                                                                                                                   \
+        }
+
+#define ITD_RES_PREFIX \
+        if (tid == 0) {  /* read by this thread (knot list) and, behind the knot list's barrier, by everybody (knot values) */         \
+            ends[0] = xs[0];                                                                                                           \
+            ends[1] = xs[1];                                                                                                           \
+            ends[2] = xs[n - 2];                                                                                                       \
+            ends[3] = xs[n - 1];                                                                                                       \
+        }                                                                                                                              \
+        /* inclusive prefix over the 64 lanes on the DPP path (no LDS round trips): Hillis-Steele inside the rows of 16 lanes */       \
+        /* (row_shr 1, 2, 4, 8: a lane without a source inside its row keeps the 0 it is given), then row 0's / rows 0-1's */          \
+        /* totals into the rows behind them (row_bcast:15 to rows 1 and 3, row_bcast:31 to rows 2 and 3).  A lane totals WPL words. */ \
+        const int c0 = WPL * lane < Q ? __popcll(bal[WPL * lane]) : 0;                                                                 \
+        const int c1 = (WPL == 2 && 2 * lane + 1 < Q) ? __popcll(bal[2 * lane + 1]) : 0;                                               \
+        const int cnt = c0 + c1;                                                                                                       \
+        int inc = cnt;                                                                                                                 \
+        if (!(ITD_RES_ABL & 2)) {                                                                                                      \
+            inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, false);                                                        \
+            inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, false);                                                        \
+            inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, false);                                                        \
+            inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xf, 0xf, false);                                                        \
+            inc += __builtin_amdgcn_update_dpp(0, inc, 0x142, 0xa, 0xf, false);                                                        \
+            inc += __builtin_amdgcn_update_dpp(0, inc, 0x143, 0xc, 0xf, false);                                                        \
+        }                                                                                                                              \
+        /* the prefixes of the wavefront's own words (nobody else reads them: no barrier) */                                           \
+        const int excl = inc - cnt;                                                                                                    \
+        const int w0 = WPL * lane;                                                                                                     \
+        if (w0 < Q && (w0 % W) == wave) pre[w0] = excl;                                                                                \
+        if (WPL == 2 && w0 + 1 < Q && ((w0 + 1) % W) == wave) pre[w0 + 1] = excl + c0;                                                 \
+        const int total = __builtin_amdgcn_readlane(inc, 63);
+
+#define ITD_RES_PASSES(EMIT) \
+        for (int k0 = 0; k0 <= m; k0 += cw) {                                                                                                       \
+            const int kend = k0 + cw < m + 1 ? k0 + cw : m + 1;                                                                                     \
+            /* nothing derived from the lane / wavefront index is carried across the passes (registers) */                                          \
+            int lane_p = lane, wave_p = wave;                                                                                                       \
+            asm volatile("" : "+v"(lane_p), "+s"(wave_p));                                                                                          \
+            /* -- ordered knot list (knots by rank 1 .. m; the two ends are knots 0 and m+1, ITD.py:93-98) */                                       \
+_Pragma("unroll")                                                                                                                                   \
+            for (int j = 0; j < SPT; ++j) {                                                                                                         \
+                const int q = wave_p + W * j, i = q * 64 + lane_p;                                                                                  \
+                if (q < Q && !(ITD_RES_ABL & 16)) {                                                                                                 \
+                    const unsigned long long bw = bal[q];                                                                                           \
+                    if ((bw >> lane_p) & 1ull) {                                                                                                    \
+                        const int k = pre[q] + __popcll(bw & ((1ull << lane_p) - 1ull)) + 1;                                                        \
+                        if (k >= k0 - 1 && k <= kend + 1) {                                                                                         \
+                            ek[k - k0 + 1] = (unsigned short)i;                                                                                     \
+                            Xk[k - k0 + 1] = xr[j];                                                                                                 \
+                        }                                                                                                                           \
+                    }                                                                                                                               \
+                }                                                                                                                                   \
+            }                                                                                                                                       \
+            if (tid == 0) {                                                                                                                         \
+                if (k0 <= 1) {  /* knot 0: ITD.py:96 */                                                                                             \
+                    ek[1 - k0] = 0;                                                                                                                 \
+                    Xk[1 - k0] = ends[0];                                                                                                           \
+                }                                                                                                                                   \
+                if (kend + 1 >= m + 1) {  /* knot m+1: ITD.py:98 */                                                                                 \
+                    ek[m + 1 - k0 + 1] = (unsigned short)(n - 1);                                                                                   \
+                    Xk[m + 1 - k0 + 1] = ends[3];                                                                                                   \
+                }                                                                                                                                   \
+            }                                                                                                                                       \
+            __syncthreads();                                                                                                                        \
+            /* -- knot values (ITD.py:100-110) and slopes (ITD.py:115-116; 0/0 on an end segment is the reference's NaN: the */                     \
+            /*    next scan catches it).  A wavefront takes 64 consecutive knots and the 63 segments between them — B_{k+1} comes */                \
+            /*    from the next lane — so consecutive chunks overlap by one knot and no barrier separates values from slopes */                     \
+            for (int cidx = wave_p; k0 + 63 * cidx <= kend && !(ITD_RES_ABL & 1); cidx += W) {                                                      \
+                const int k = k0 + 63 * cidx + lane_p, sl = k - k0 + 1;                                                                             \
+                double v = 0.0, x0 = 0.0, xp1 = 0.0;                                                                                                \
+                if (k <= kend) {                                                                                                                    \
+                    x0 = Xk[sl];                                                                                                                    \
+                    if (k == 0) {                                                                                                                   \
+                        v = (ends[0] + ends[1]) / 2.0;  /* numpy.mean(x[:2]) */                                                                     \
+                        xp1 = Xk[sl + 1];                                                                                                           \
+                    } else if (k == m + 1) {                                                                                                        \
+                        v = (ends[2] + ends[3]) / 2.0;  /* numpy.mean(x[-2:]) */                                                                    \
+                    } else {                                                                                                                        \
+                        const int e0 = ek[sl - 1], e1 = ek[sl], e2 = ek[sl + 1];                                                                    \
+                        const double xm1 = Xk[sl - 1];                                                                                              \
+                        xp1 = Xk[sl + 1];                                                                                                           \
+                        const double frac = (double)(e1 - e0) / (double)(e2 - e0);  /* (int_ratio here: no difference, profiles/r05/experiments) */ \
+                        const double t = frac * (xp1 - xm1);                                                                                        \
+                        const double u = xm1 + t;                                                                                                   \
+                        v = 0.5 * u + 0.5 * x0;                                                                                                     \
+                    }                                                                                                                               \
+                    Bk[sl] = v;                                                                                                                     \
+                }                                                                                                                                   \
+                const double vn = __shfl_down(v, 1, 64);                                                                                            \
+                if (lane_p < 63 && k < kend) Sk[sl] = (vn - v) / (xp1 - x0);                                                                        \
+            }                                                                                                                                       \
+            __syncthreads();                                                                                                                        \
+            /* -- map (ITD.py:112-117) of the samples whose segment lies in the window: the baseline replaces the signal in LDS; */                 \
+            /*    EMIT: what the kernel does with sample i (input xr[j], baseline b) */                                                             \
+_Pragma("unroll")                                                                                                                                   \
+            for (int j = 0; j < SPT; ++j) {                                                                                                         \
+                const int q = wave_p + W * j, i = q * 64 + lane_p;                                                                                  \
+                if (q < Q) {                                                                                                                        \
+                    const int k = pre[q] + __popcll(bal[q] & ((2ull << lane_p) - 1ull));  /* knots at or before the sample */                       \
+                    if (k >= k0 && k < kend) {                                                                                                      \
+                        const int sl = k - k0 + 1;                                                                                                  \
+                        const double b = (ITD_RES_ABL & 32) ? xr[j] * 0.75 + k : (i >= n - 1) ? 0.0 : Bk[sl] + Sk[sl] * (xr[j] - Xk[sl]);           \
+                        xs[i] = b;                                                                                                                  \
+                        EMIT;                                                                                                                       \
+                    }                                                                                                                               \
+                }                                                                                                                                   \
+            }                                                                                                                                       \
+            __syncthreads();                                                                                                                        \
+        }
+
+
 template <typename Tin, int TH, int SPT>
 __global__ __launch_bounds__(TH, SPT == 4 ? ITD_RES_MINW : 4) void k_resident(const Tin *__restrict__ xin, int64_t x_stride, int n, int M, int cw,
                                                    int nan_follow /* a NaN in the caller's signal: 1 = the reference's rules (below), 0 = leave (res_fail) */,
@@ -169,23 +307,7 @@ __global__ __launch_bounds__(TH, SPT == 4 ? ITD_RES_MINW : 4) void k_resident(co
         int *cs = ctl + 4 * (n_scans & 1), *co = ctl + 4 * ((n_scans & 1) ^ 1);   // this scan's counters, the previous scan's
         ++n_scans;
         if (tid == 0) co[1] = co[2] = co[3] = 0;   // last read before the barriers of the phases in between
-#pragma unroll
-        for (int j = 0; j < SPT; ++j) {
-            const int q = wave + W * j, i = q * 64 + lane;
-            if (q < Q) {
-                const double c = xs[i];
-                // dx[i-1], dx[i] (ITD.py:44); the reads next to the signal's ends stay inside xs (word 0 starts at sample 0, the
-                // padding ends the last word) and only interior samples can flag
-                const double d0 = c - ((ITD_RES_ABL & 128) ? 0.5 : xs[i > 0 ? i - 1 : 0]), d1 = ((ITD_RES_ABL & 128) ? 0.25 : xs[i < np2 - 1 ? i + 1 : i]) - c;
-                const bool f = ((d1 > 0.0 && d0 <= 0.0) || (d1 < 0.0 && d0 >= 0.0)) && i >= 1 && i <= n - 2;   // valley of x or of -x (ITD.py:59, 87-88)
-                const unsigned long long bw = __ballot(f);
-                const unsigned long long bb = __ballot(c != c);
-                if (lane == 0) {
-                    bal[q] = bw;
-                    if (bb) cs[1] = 1;
-                }
-            }
-        }
+        ITD_RES_FLAGS;
         __syncthreads();
         const bool has_nan = cs[1] != 0;
         if (has_nan) {
@@ -243,33 +365,7 @@ __global__ __launch_bounds__(TH, SPT == 4 ? ITD_RES_MINW : 4) void k_resident(co
             if (lane == 0 && acc) atomicAdd(&cs[3], acc);
             __syncthreads();
         }
-        if (tid == 0) {   // read by this thread (knot list) and, behind the knot list's barrier, by everybody (knot values)
-            ends[0] = xs[0];
-            ends[1] = xs[1];
-            ends[2] = xs[n - 2];
-            ends[3] = xs[n - 1];
-        }
-        // inclusive prefix over the 64 lanes on the DPP path (no LDS round trips): Hillis-Steele inside the rows of 16 lanes
-        // (row_shr 1, 2, 4, 8: a lane without a source inside its row keeps the 0 it is given), then row 0's / rows 0-1's
-        // totals into the rows behind them (row_bcast:15 to rows 1 and 3, row_bcast:31 to rows 2 and 3).  A lane totals WPL words.
-        const int c0 = WPL * lane < Q ? __popcll(bal[WPL * lane]) : 0;
-        const int c1 = (WPL == 2 && 2 * lane + 1 < Q) ? __popcll(bal[2 * lane + 1]) : 0;
-        const int cnt = c0 + c1;
-        int inc = cnt;
-        if (!(ITD_RES_ABL & 2)) {
-            inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, false);
-            inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, false);
-            inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, false);
-            inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xf, 0xf, false);
-            inc += __builtin_amdgcn_update_dpp(0, inc, 0x142, 0xa, 0xf, false);
-            inc += __builtin_amdgcn_update_dpp(0, inc, 0x143, 0xc, 0xf, false);
-        }
-        // the prefixes of the wavefront's own words (nobody else reads them: no barrier)
-        const int excl = inc - cnt;
-        const int w0 = WPL * lane;
-        if (w0 < Q && (w0 % W) == wave) pre[w0] = excl;
-        if (WPL == 2 && w0 + 1 < Q && ((w0 + 1) % W) == wave) pre[w0 + 1] = excl + c0;
-        const int total = __builtin_amdgcn_readlane(inc, 63);
+        ITD_RES_PREFIX;
         m_stop = has_nan ? cs[2] + cs[3] : total;
         return total;
     };
@@ -292,86 +388,12 @@ __global__ __launch_bounds__(TH, SPT == 4 ? ITD_RES_MINW : 4) void k_resident(co
         const __amdgpu_buffer_rsrc_t r_base = tile_rsrc(bases_s ? bases_s + (int64_t)(c <= M ? c : 0) * n : nullptr, bases_s ? (int64_t)n * 8 : 0);
         // ---- passes over the level's ranks: segments k0 .. kend-1 (segment k = samples e_k <= i < e_{k+1}); the window's
         //      slots hold the knots k0-1 .. kend+1, slot = k - k0 + 1 -------------------------------------------------------
-        for (int k0 = 0; k0 <= m; k0 += cw) {
-            const int kend = k0 + cw < m + 1 ? k0 + cw : m + 1;
-            // nothing derived from the lane / wavefront index is carried across the passes (registers)
-            int lane_p = lane, wave_p = wave;
-            asm volatile("" : "+v"(lane_p), "+s"(wave_p));
-            // -- ordered knot list (knots by rank 1 .. m; the two ends are knots 0 and m+1, ITD.py:93-98)
-#pragma unroll
-            for (int j = 0; j < SPT; ++j) {
-                const int q = wave_p + W * j, i = q * 64 + lane_p;
-                if (q < Q && !(ITD_RES_ABL & 16)) {
-                    const unsigned long long bw = bal[q];
-                    if ((bw >> lane_p) & 1ull) {
-                        const int k = pre[q] + __popcll(bw & ((1ull << lane_p) - 1ull)) + 1;
-                        if (k >= k0 - 1 && k <= kend + 1) {
-                            ek[k - k0 + 1] = (unsigned short)i;
-                            Xk[k - k0 + 1] = xr[j];
-                        }
-                    }
-                }
-            }
-            if (tid == 0) {
-                if (k0 <= 1) {                   // knot 0: ITD.py:96
-                    ek[1 - k0] = 0;
-                    Xk[1 - k0] = ends[0];
-                }
-                if (kend + 1 >= m + 1) {         // knot m+1: ITD.py:98
-                    ek[m + 1 - k0 + 1] = (unsigned short)(n - 1);
-                    Xk[m + 1 - k0 + 1] = ends[3];
-                }
-            }
-            __syncthreads();
-            // -- knot values (ITD.py:100-110) and slopes (ITD.py:115-116; 0/0 on an end segment is the reference's NaN: the
-            //    next scan catches it).  A wavefront takes 64 consecutive knots and the 63 segments between them — B_{k+1} comes
-            //    from the next lane — so consecutive chunks overlap by one knot and no barrier separates values from slopes
-            for (int cidx = wave_p; k0 + 63 * cidx <= kend && !(ITD_RES_ABL & 1); cidx += W) {
-                const int k = k0 + 63 * cidx + lane_p, sl = k - k0 + 1;
-                double v = 0.0, x0 = 0.0, xp1 = 0.0;
-                if (k <= kend) {
-                    x0 = Xk[sl];
-                    if (k == 0) {
-                        v = (ends[0] + ends[1]) / 2.0;               // numpy.mean(x[:2])
-                        xp1 = Xk[sl + 1];
-                    } else if (k == m + 1) {
-                        v = (ends[2] + ends[3]) / 2.0;               // numpy.mean(x[-2:])
-                    } else {
-                        const int e0 = ek[sl - 1], e1 = ek[sl], e2 = ek[sl + 1];
-                        const double xm1 = Xk[sl - 1];
-                        xp1 = Xk[sl + 1];
-                        const double frac = (double)(e1 - e0) / (double)(e2 - e0);      // (int_ratio here: no difference, profiles/r05/experiments)
-                        const double t = frac * (xp1 - xm1);
-                        const double u = xm1 + t;
-                        v = 0.5 * u + 0.5 * x0;
-                    }
-                    Bk[sl] = v;
-                }
-                const double vn = __shfl_down(v, 1, 64);
-                if (lane_p < 63 && k < kend) Sk[sl] = (vn - v) / (xp1 - x0);
-            }
-            __syncthreads();
-            // -- map (ITD.py:112-117) of the samples whose segment lies in the window: the baseline replaces the signal in LDS;
-            //    rotation = x - baseline (ITD.py:119) leaves at once unless this is the extraction behind the last requested
-            //    one (its row is never the rotation)
-#pragma unroll
-            for (int j = 0; j < SPT; ++j) {
-                const int q = wave_p + W * j, i = q * 64 + lane_p;
-                if (q < Q) {
-                    const int k = pre[q] + __popcll(bal[q] & ((2ull << lane_p) - 1ull));   // knots at or before the sample
-                    if (k >= k0 && k < kend) {
-                        const int sl = k - k0 + 1;
-                        const double b = (ITD_RES_ABL & 32) ? xr[j] * 0.75 + k : (i >= n - 1) ? 0.0 : Bk[sl] + Sk[sl] * (xr[j] - Xk[sl]);
-                        xs[i] = b;
-                        if (c <= M && !(ITD_RES_ABL & 8)) {
-                            res_store(r_row, i, xr[j] - b);
-                            if (bases_s) res_store(r_base, i, b);
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-        }
+        ITD_RES_PASSES(if (c <= M && !(ITD_RES_ABL & 8)) {
+            // rotation = x - baseline (ITD.py:119) leaves at once unless this is the extraction behind the last requested one
+            // (its row is never the rotation)
+            res_store(r_row, i, xr[j] - b);
+            if (bases_s) res_store(r_base, i, b);
+        });
         // ---- the pending baseline's stop test = the next level's scan (ITD.py:400-404) -------------------------------
         m = scan(false, r_base, bases_s && c <= M);
         if (tid == 0) st->m[c + 1] = m_stop;

@@ -169,3 +169,122 @@ def blockwise(x, block, kind="cubic", margin=8, shared_knots=False, device=0):
         return (rot[0], base[0]) if flat else (rot, base)
     base = numpy.concatenate(outs, axis=1)
     return base[0] if flat else base
+
+
+class LevelsStream:
+    """The full multi-level ITD block by block (itd_levels_stream_* in include/pyitd_hip.h): a chain of levels + 1 tier-1
+    stages, stage k >= 1 on the baselines of stage k-1; every step is ONE launch on the GPU for blocks up to 2730 samples, a launch
+    sequence (bit-identical) for longer ones.
+
+        st = LevelsStream(1024, levels=8)
+        for block in blocks:
+            out = st.push(block)         # None for the first levels + 1 pushes, then (rows[levels+1, block], exact)
+        while (out := st.flush()) is not None: ...
+
+    rows 0 .. M-1 of a block are its rotations of stages 0 .. M-1, row M stage M's rotation + baseline (ITD.py:418-426); block j
+    leaves on push j + M + 1.  exact[c] = 1 certifies that the block's rows equal the whole-signal rows of
+    ITD().itd(x, max_iteration=M-1) of the concatenated blocks, bit for bit (where that run does not stop naturally).  A window
+    holding a NaN is never certified and sets status() bit 2."""
+
+    def __init__(self, block, levels, channels=1, device=0):
+        if block < 8 or 3 * block >= 2 ** 31 - 65536:
+            raise ValueError("block must be at least 8 samples (and 3 blocks below 2^31)")
+        if not 1 <= levels <= 21:
+            raise ValueError("levels must be 1 .. 21")
+        if not 1 <= channels <= 65535:
+            raise ValueError("channels must be 1 .. 65535")
+        self._L = _lib.load()
+        h = ctypes.c_void_p()
+        rc = self._L.itd_levels_stream_create(ctypes.byref(h), int(device), int(block), int(channels), int(levels))
+        if rc:
+            raise ITDError(rc, "itd_levels_stream_create(block=%d, channels=%d, levels=%d)" % (block, channels, levels))
+        self._h = h
+        self.block, self.levels, self.channels, self.device = int(block), int(levels), int(channels), int(device)
+
+    @property
+    def form(self):
+        """'one-launch' (blocks up to 2730 samples) or 'sequence' (longer blocks, or forced)"""
+        return "sequence" if self._L.itd_levels_stream_form(self._h) == 1 else "one-launch"
+
+    def force_sequence(self, on=True):
+        """Run every step as the launch sequence even where one launch would do (bit-identical; for comparing the forms)."""
+        self._check(self._L.itd_levels_stream_set_sequence(self._h, 1 if on else 0))
+
+    close = Stream.close
+    __del__ = Stream.__del__
+    _check = Stream._check
+    blocks_held = Stream.blocks_held
+    reset = Stream.reset
+    status = Stream.status
+
+    # ---- device buffers (raw pointers; asynchronous on `stream`) ----------------------------------------------------
+    def push_dev(self, block_ptr, in_stride, rows_ptr, row_stride, chan_stride, exact_ptr=None, stream=None):
+        """Store one block of every channel; True if a block's rows (and flags) were written."""
+        em = ctypes.c_int32(0)
+        self._check(self._L.itd_levels_stream_push_f64(self._h, block_ptr, in_stride, rows_ptr, row_stride, chan_stride,
+                                                       exact_ptr, ctypes.byref(em), stream))
+        return bool(em.value)
+
+    def flush_dev(self, rows_ptr, row_stride, chan_stride, exact_ptr=None, stream=None):
+        em = ctypes.c_int32(0)
+        self._check(self._L.itd_levels_stream_flush_f64(self._h, rows_ptr, row_stride, chan_stride, exact_ptr,
+                                                        ctypes.byref(em), stream))
+        return bool(em.value)
+
+    # ---- numpy in -> numpy out (one synchronisation per call) ----------------------------------------------------------
+    def _out(self, rows, exact, flat):
+        ex = exact.astype(bool)
+        return (rows[0], ex[0]) if flat else (rows, ex)
+
+    def push(self, samples):
+        """samples [channels, block] (or [block] for one channel).  None, or (rows[channels, levels+1, block], exact[channels])
+        with the channel axis dropped for 1-D input."""
+        x = numpy.ascontiguousarray(samples, dtype=numpy.float64)
+        flat = x.ndim == 1
+        x2 = x.reshape(1, -1) if flat else x
+        if x2.shape != (self.channels, self.block):
+            raise ValueError("expected blocks of shape (%d, %d)" % (self.channels, self.block))
+        rows = numpy.empty((self.channels, self.levels + 1, self.block))
+        exact = numpy.zeros(self.channels, dtype=numpy.uint8)
+        em = ctypes.c_int32(0)
+        self._check(self._L.itd_levels_stream_push_host_f64(self._h, _np_ptr(x2), _np_ptr(rows), _np_ptr(exact),
+                                                            ctypes.byref(em)))
+        return self._out(rows, exact, flat) if em.value else None
+
+    def flush(self, flat=None):
+        """The next block still held (one per call); None once the stream is empty."""
+        rows = numpy.empty((self.channels, self.levels + 1, self.block))
+        exact = numpy.zeros(self.channels, dtype=numpy.uint8)
+        em = ctypes.c_int32(0)
+        self._check(self._L.itd_levels_stream_flush_host_f64(self._h, _np_ptr(rows), _np_ptr(exact), ctypes.byref(em)))
+        if not em.value:
+            return None
+        return self._out(rows, exact, self.channels == 1 if flat is None else flat)
+
+
+def blockwise_itd(x, block, levels, device=0):
+    """Run x[channels, n_blocks * block] (or [n]) through a LevelsStream.  Returns (rows[channels, levels+1, n],
+    exact[channels, n_blocks]) (no channel axis for 1-D input)."""
+    x = numpy.asarray(x, dtype=numpy.float64)
+    flat = x.ndim == 1
+    x2 = x.reshape(1, -1) if flat else x
+    C, n = x2.shape
+    if n % block or n < block:
+        raise ValueError("the length must be a multiple of the block")
+    st = LevelsStream(block, levels, C, device)
+    outs = []
+    try:
+        for k in range(n // block):
+            r = st.push(x2[:, k * block:(k + 1) * block])
+            if r is not None:
+                outs.append(r)
+        while True:
+            r = st.flush(flat=False)
+            if r is None:
+                break
+            outs.append(r)
+    finally:
+        st.close()
+    rows = numpy.concatenate([o[0] for o in outs], axis=2)
+    exact = numpy.stack([o[1] for o in outs], axis=1)
+    return (rows[0], exact[0]) if flat else (rows, exact)
