@@ -17,23 +17,29 @@ fresh children (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set per child) and rel
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` (WORLD_SIZE already in the environment) the
 process IS one rank.
 
-Printed JSON (one line, rank 0): the driver contract + "roofline" — the dominant kernel: with the sparse levels fused (the
-default for this workload) k_kf_apply, the one pass over the samples for levels 2 .. 8 (8 B read + 7 x 8 B written per sample);
-with --no-fuse k_extract<double> (24 B per sample and level) — timed with the launch's own hipEvents on the launch stream
-inside the timed region, + the per-kernel fractions + "cpu_baseline" (the C oracle = single-thread port of the reference
-algorithm, timed on this box's host at N = 1) and the other CPU legs SURVEY 8d lists (all host cores over independent signals,
-numpy restatement, numba restatement).  A step whose fused levels refuse is repeated level by level when
-its summary is read: the headline checks for that behind its timed region and times again level by level if it happened; the
-batch legs and the N > 1 path read the summary inside every step.
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs if asked and prints
+one JSON line (rank 0): the driver contract + "roofline" — the dominant kernel: with the sparse levels fused (the default for this
+workload) k_kf_apply, the one pass over the samples for levels 2 .. 8 (8 B read + 7 x 8 B written per sample); with --no-fuse
+k_extract<double> (24 B per sample and level) — timed with the launch's own hipEvents on the launch stream inside the timed region,
++ the per-kernel fractions.  A step whose fused levels refuse is repeated level by level when its summary is
+read: the headline checks for that behind its timed region and times again level by level if it happened; the N > 1 path reads the
+summary inside every step.
 `--dump-outputs DIR` writes what the headline's last timed step computed (a fixed sample of the rows, the per-signal summary) to
 DIR/<name>.npy; the input is the same from run to run, so two builds can be compared output for output.
 The headline has an untimed warm-up of its own (--warm-ms of its own steps, then the W warm-up steps), so it does not depend on any
-other leg.  At N = 1 the line also carries, all timed AFTER the headline and skipped by --no-extra: "config3_batch" (BASELINE
-configs[2], 1024 x 2^20 signals), "short_signal_batches" (4096 x 4096 and 60 000 x 256 samples through the resident form and level by
-level), "mid_size_signals" (single signals of 2^16 .. 2^20 samples, BASELINE configs[0]'s chirp among them), "f_rows" (the SURVEY 8f
-operators: cubic baseline at 2^24, instantaneous step, totalextract2d on 512 x 512 beside the reference's recorded 10.1457 s, MEITD on a
-golden signal, block-wise microseconds per block), "config5_audio" (BASELINE configs[4] on --wav PATH or the substitute clip) and
-"headline_on_quantised_2p24".
+other leg.
+`--full` (N = 1) adds everything else the benchmark measures or checks, all of it after the headline's timed region except the first:
+the roofline's "traffic" measured by PMC in two profiled child runs before this process touches the GPU (--no-live-traffic skips
+them), "step_time_distribution" (a second region of back-to-back steps), "cpu_baseline" (the C oracle = single-thread port of the
+reference algorithm, timed on the host) and the other CPU legs SURVEY 8d lists (all host cores over independent signals, numpy
+restatement, numba restatement) with "parity" against the C oracle (--no-cpu-baseline skips them), and, skipped by --no-extra:
+"config3_batch" (BASELINE configs[2], 1024 x 2^20 signals; its batch legs read the summary inside every step),
+"short_signal_batches" (4096 x 4096 and 60 000 x 256 samples through the resident form and level by level), "mid_size_signals"
+(single signals of 2^16 .. 2^20 samples, BASELINE configs[0]'s chirp among them), "many_mid_size_signals" (64 and 256 such signals
+as one batch call and over a pool of engines), "f_rows" (the SURVEY 8f operators: cubic baseline at 2^24, instantaneous step,
+totalextract2d on 512 x 512 beside the reference's recorded 10.1457 s, MEITD on a golden signal, block-wise microseconds per block),
+"config5_audio" (BASELINE configs[4] on --wav PATH or the substitute clip; with --wav it runs under --no-extra too),
+"headline_on_quantised_2p24" and "headline_with_valid_flags".
 """
 import argparse
 import json
@@ -469,27 +475,28 @@ def run_rank(args):
         samples = {k: eng.kernel_timing_samples(t) * 1e3 for k, t in (("ext", TIME_EXTRACT), ("l0", TIME_EXTRACT_L0), ("kfa", TIME_KF_APPLY),
                                                                        ("kfk", TIME_KF_KNOTS), ("dec", TIME_DECOMPOSE))}
         eng.set_timing(0)
-        # The distribution of the per-step time: >= 64 further back-to-back steps in which only each step's level-0 launch carries
-        # events (one completion signal per step); the period from one step's first dispatch to the next one's, device timestamps
+        # --full: the distribution of the per-step time: >= 64 further back-to-back steps in which only each step's level-0 launch
+        # carries events (one completion signal per step); the period from one step's first dispatch to the next one's, device timestamps
         step_dist = None
-        try:
-            extra = max(64, args.steps)
-            eng.set_timing_mode(1)
-            eng.set_timing(extra + 1, stride=1)
-            for _ in range(extra + 1):
-                step()
-            sync()
-            per = eng.step_periods() * 1e3
-            eng.set_timing(0)
-            eng.set_timing_mode(0)
-            if len(per) >= 8:
-                step_dist = {"steps": int(len(per)), "mean_us": round(float(per.mean()), 2), "median_us": round(float(np.median(per)), 2),
-                             "p10_us": round(float(np.percentile(per, 10)), 2), "p90_us": round(float(np.percentile(per, 90)), 2),
-                             "min_us": round(float(per.min()), 2), "max_us": round(float(per.max()), 2),
-                             "how": "a second region of back-to-back steps behind the timed one; period between consecutive steps' first "
-                                    "dispatches (hipExtLaunchKernel start events on the level-0 launch only)"}
-        except Exception as ex:  # noqa: BLE001
-            step_dist = {"error": repr(ex)[:160]}
+        if args.full:
+            try:
+                extra = max(64, args.steps)
+                eng.set_timing_mode(1)
+                eng.set_timing(extra + 1, stride=1)
+                for _ in range(extra + 1):
+                    step()
+                sync()
+                per = eng.step_periods() * 1e3
+                eng.set_timing(0)
+                eng.set_timing_mode(0)
+                if len(per) >= 8:
+                    step_dist = {"steps": int(len(per)), "mean_us": round(float(per.mean()), 2), "median_us": round(float(np.median(per)), 2),
+                                 "p10_us": round(float(np.percentile(per, 10)), 2), "p90_us": round(float(np.percentile(per, 90)), 2),
+                                 "min_us": round(float(per.min()), 2), "max_us": round(float(per.max()), 2),
+                                 "how": "a second region of back-to-back steps behind the timed one; period between consecutive steps' first "
+                                        "dispatches (hipExtLaunchKernel start events on the level-0 launch only)"}
+            except Exception as ex:  # noqa: BLE001
+                step_dist = {"error": repr(ex)[:160]}
     else:
         timing = None
         samples = None
@@ -694,10 +701,11 @@ def run_rank(args):
             "per_gpu": True,
             "reference_flow_equivalent_GBps_per_gpu": round(algorithmic_bytes_per_sample(LEVELS) * float(n) * sb.n_local * args.steps / elapsed / 1e9, 1),
         }
-        out["cpu_baseline"] = None   # timed on rank 0 at N = 1 only (the N = 1 line of the same build carries all four CPU legs)
-    if world == 1 and not stub and not args.no_cpu_baseline:
+        out["cpu_baseline"] = None   # timed on rank 0 at N = 1 only (the N = 1 --full line of the same build carries all four CPU legs)
+    full = world == 1 and not stub and args.full       # everything below measures or checks something beyond the headline
+    if full and not args.no_cpu_baseline:
         out.update(cpu_legs(x_host, n, M, summ, rows, args))
-    if world == 1 and not stub and not args.no_extra and args.log2n == LOG2N:
+    if full and not args.no_extra and args.log2n == LOG2N:
         # informational legs, all timed AFTER the headline (never at its cost: each in its own try)
         del rows, x
         torch.cuda.empty_cache()
@@ -709,13 +717,13 @@ def run_rank(args):
             except Exception as ex:  # noqa: BLE001
                 out[key] = {"error": repr(ex)[:200]}
     wav = args.wav or os.environ.get("PYITD_WAV")
-    if world == 1 and not stub and (wav or not args.no_extra):
+    if full and (wav or not args.no_extra):
         # BASELINE configs[4]: the operator's wav, or the substitute clip the tests use (tests/golden/radio8000_input.npz)
         try:
             out["config5_audio"] = audio_leg(torch, dev, wav)
         except Exception as ex:  # noqa: BLE001
             out["config5_audio"] = {"error": repr(ex)[:200], "input": wav or "substitute clip"}
-    if world == 1 and not stub and not args.no_extra and args.log2n == LOG2N:
+    if full and not args.no_extra and args.log2n == LOG2N:
         # the headline signal rounded to 16 bits: exact ties everywhere, the fused sparse levels refuse it — what the refusal path costs
         try:
             out["headline_on_quantised_2p24"] = quantised_leg(torch, dev, x_host, n, M)
@@ -1361,8 +1369,12 @@ def main():
     ap.add_argument("--batch", type=int, default=1024, help="N > 1: signals per GPU (weak scaling: the batch grows with N)")
     ap.add_argument("--total-batch", type=int, default=0, help="N > 1: a FIXED batch over all GPUs instead (strong scaling; SURVEY 8d config 4: 8192), "
                                                               "balanced contiguous shards; `scaling` = \"strong\"")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the informational BASELINE configs[2] leg (1024 x 2^20 signals)")
+    ap.add_argument("--full", action="store_true", help="N = 1: besides the headline, everything else the benchmark measures or checks: PMC "
+                                                        "traffic, the step-time distribution, the CPU baselines and the parity check, "
+                                                        "the informational legs (see the module's docstring); the --no-* options below trim it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and the parity check")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the informational legs (config3_batch and the others "
+                                                            "timed after the headline) and the live PMC traffic")
     ap.add_argument("--try-rccl", action="store_true",
                     help="with --rehearse-one-gpu: ask for RCCL first all the same (two ranks on one GPU: it refuses, which exercises "
                          "the fallback of the control plane to gloo)")
@@ -1373,24 +1385,28 @@ def main():
     ap.add_argument("--warm-ms", type=float, default=150.0, help="untimed warm-up of the headline's own step before the W warm-up steps (ms)")
     ap.add_argument("--spawn-timeout", type=int, default=900, help="plain --gpus N: seconds until the parent kills its ranks")
     ap.add_argument("--pg-timeout", type=int, default=120, help="seconds a rank waits for the process group / a collective")
-    ap.add_argument("--wav", default=None, help="BASELINE configs[4] on a user-supplied wav (mono / first channel, float32 in [-1, 1], "
-                                                "numpy.resize to 2^22, 10 levels): adds config5_audio to the line (also: PYITD_WAV)")
+    ap.add_argument("--wav", default=None, help="with --full: BASELINE configs[4] on a user-supplied wav (mono / first channel, float32 in "
+                                                "[-1, 1], numpy.resize to 2^22, 10 levels) as the config5_audio leg, also under --no-extra "
+                                                "(also: PYITD_WAV)")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)   # CPU test of the launcher only
-    ap.add_argument("--no-live-traffic", action="store_true", help="N = 1: do not measure roofline.traffic in this run (two PMC passes of "
-                                                                      "a 3-step child run, ~40 s, before the timed region); --no-extra implies it")
+    ap.add_argument("--no-live-traffic", action="store_true", help="with --full, N = 1: do not measure roofline.traffic in this run (two PMC "
+                                                                      "passes of a 3-step child run before the timed region); --no-extra implies it")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64, at most 64 MB in all: "
                          "a fixed sample of the rows' positions and the per-signal summary; N > 1: rank 0's shard)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.wav and not args.full:
+        ap.error("--wav picks the input of the config5_audio leg, which only a --full run measures: add --full")
     if args.gpus > 1 and not args.stub and not args.rehearse_one_gpu:
         rc = preflight(args)
         if rc:
             return rc
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args)
-    if args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not (args.stub or args.no_extra or args.no_live_traffic or args.no_fuse):
+    if args.full and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not (args.stub or args.no_extra or args.no_live_traffic
+                                                                                             or args.no_fuse):
         global LIVE_TRAFFIC
         LIVE_TRAFFIC = measure_traffic_live()
     return run_rank(args)

@@ -99,3 +99,10 @@ def test_dump_outputs_writes_the_summary_as_float64(tmp_path):
 def test_steps_below_one_are_refused():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub", "--steps", "0"], capture_output=True, text=True, timeout=120)
     assert p.returncode == 2 and "--steps" in p.stderr
+
+
+def test_wav_without_full_is_refused():
+    """--wav picks the input of config5_audio, a leg that only a --full run measures: a plain run with it starts nothing."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub", "--wav", "clip.wav"], capture_output=True, text=True,
+                       timeout=120)
+    assert p.returncode == 2 and "--full" in p.stderr

@@ -1,6 +1,6 @@
 #!/bin/bash
 # One GPU session that collects a round's evidence into gpurun_out/<tag>/ (copied into profiles/<round>/ afterwards):
-#   the -m gpu suite's log; bench.py in the driver's form and with 200 steps; rocprofv3 --kernel-trace --stats of the driver's form;
+#   the -m gpu suite's log; bench.py --full and with 200 steps; rocprofv3 --kernel-trace --stats of the headline;
 #   the PMC traffic passes (tools/traffic.sh); the knot side's phase profile (variants/libprof.so, built with -DITD_PROF=1, if present);
 #   the delivery rates of the fused levels by signal family; fuzz slices (default mode, batches, everything fused from level 3 / 2);
 #   the suite again in the fused levels' other modes (tools/suite_modes.sh).
@@ -17,7 +17,7 @@ f=$(find $O/prof -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp "$f" $O
 bash tools/traffic.sh $tag > $O/traffic_summary.txt 2>&1; tail -1 $O/traffic_summary.txt | cut -c1-400
 # (the line in the driver's form reads the traffic record of THIS build: traffic_stale false)
 cp gpurun_out/traffic.json profiles/traffic.json
-timeout -k 10 900 python bench.py > $O/bench_default_form.json 2> $O/bench_default_form.err || exit 1
+timeout -k 10 900 python bench.py --full > $O/bench_default_form.json 2> $O/bench_default_form.err || exit 1
 if [ -f variants/libprof.so ]; then PYITD_HIP_LIB=variants/libprof.so timeout -k 10 200 python tools/knots_prof.py > $O/knots_phase_profile.txt 2>&1 || exit 1; fi
 timeout -k 10 900 python tools/kf_rates.py 12 11 > $O/kf_delivery_rates.txt 2>&1 || exit 1; tail -2 $O/kf_delivery_rates.txt
 FUZZ_MIN_N=65536 PYITD_FUSE_MIN=65536 timeout -k 10 600 python tools/fuzz_parity.py 3000 601 > $O/fuzz_3000_long_fused.txt 2>&1 || exit 1; tail -1 $O/fuzz_3000_long_fused.txt

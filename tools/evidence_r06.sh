@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round 6's evidence in three GPU sessions (tools/evidence.sh's steps, regrouped so that each call stays well inside gpurun's limit):
-#   bash tools/evidence_r06.sh core   the -m gpu log; bench.py in the driver's form (live PMC traffic), with 200 steps, under rocprofv3
+#   bash tools/evidence_r06.sh core   the -m gpu log; bench.py --full (live PMC traffic), with 200 steps, under rocprofv3
 #                                     --kernel-trace --stats; the recorded traffic passes (profiles/traffic.json); a batch timeline
 #   bash tools/evidence_r06.sh modes  the suite in the fused levels' other modes
 #   bash tools/evidence_r06.sh fuzz   delivery rates by signal family; fuzz slices (fused long signals from level 3 / 2, capped, default, batches, pipelined batches)
@@ -17,7 +17,7 @@ core)
   rm -rf $O/prof
   bash tools/traffic.sh r06 > $O/traffic_summary.txt 2>&1; tail -1 $O/traffic_summary.txt | cut -c1-400
   cp gpurun_out/traffic.json profiles/traffic.json; cp gpurun_out/traffic.json $O/traffic.json; rm -rf gpurun_out/traffic_r06
-  timeout -k 10 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default_form.json 2> $O/bench_default_form.err || exit 1
+  timeout -k 10 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_default_form.json 2> $O/bench_default_form.err || exit 1
   bash tools/pipeline_trace.sh r06 "64 0 3 2 0" "64 1 3 2 0" || exit 1
   timeout -k 10 300 python tools/pipeline_sweep.py 1024 20 0,8 > $O/pipeline_sweep_1024.txt 2>&1 || exit 1; tail -4 $O/pipeline_sweep_1024.txt
   python - <<PY
