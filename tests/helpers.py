@@ -120,3 +120,36 @@ def coarse(x):
     every near tie as candidates; with ties at most samples their lists outgrow a workgroup's capacity and they refuse — the one
     family of inputs (beside NaN-producing ones) that still takes the level-by-level repeat since round 4."""
     return (np.round(np.asarray(x, dtype=np.float64) * 3) / 4.0).astype(np.asarray(x).dtype)
+
+
+class DevArrays:
+    """Named device arrays carved out of one pyitd_amd.engine.DeviceBuffer (256-byte aligned), each uploaded from a host array
+    (sentinels included) and read back whole through the engine's own stream: what the tests of the device-pointer entries use."""
+
+    def __init__(self, eng, **arrays):
+        from pyitd_amd.engine import DeviceBuffer
+        self.eng, self.host, self.off = eng, {}, {}
+        total = 0
+        for k, a in arrays.items():
+            self.host[k] = np.ascontiguousarray(a)
+            self.off[k] = total
+            total += (self.host[k].nbytes + 255) // 256 * 256
+        self.buf = DeviceBuffer(max(total, 256))
+        for k in arrays:
+            self.put(k, self.host[k])
+
+    def ptr(self, k):
+        return self.buf.ptr + self.off[k]
+
+    def put(self, k, a):
+        a = np.ascontiguousarray(a, dtype=self.host[k].dtype)
+        assert a.shape == self.host[k].shape
+        self.eng.copy(self.ptr(k), a.ctypes.data, a.nbytes, 1, wait=True)
+
+    def get(self, k):
+        out = np.empty_like(self.host[k])
+        self.eng.copy(out.ctypes.data, self.ptr(k), out.nbytes, 0, wait=True)
+        return out
+
+    def free(self):
+        self.buf.free()

@@ -115,3 +115,43 @@ def test_meitd_mirror_keeps_the_reference_surface():
     p = inspect.signature(meitd.MEITD).parameters
     assert list(p)[:3] == ["data", "max_iteration", "WPEMAX"] and p["max_iteration"].default == 40 and p["WPEMAX"].default == 0.6
     assert list(inspect.signature(meitd.XITD).parameters)[:1] == ["data"]
+
+
+def test_single_signal_device_entries_reject_a_null_engine(lib):
+    """The single-signal device-pointer and float32 entries: a NULL engine is ITD_ERR_INVALID_ARG (1), decided before any HIP call;
+    itd_engine_device(NULL) is -1."""
+    m = ctypes.c_int64()
+    k = (ctypes.c_int32 * 1)()
+    assert lib.itd_baseline_extract_f64(None, None, 100, None, None, None, ctypes.byref(m), None) == 1
+    assert lib.itd_baseline_extract_f32(None, None, 100, None, None, None, ctypes.byref(m), None) == 1
+    assert lib.itd_detect_f64(None, None, 100, 0, None, ctypes.byref(m), None) == 1
+    assert lib.itd_detect_f32(None, None, 100, 0, None, ctypes.byref(m), None) == 1
+    assert lib.itd_baseline_extract_cubic_f64(None, None, 100, None, 0, None, ctypes.byref(m), None) == 1
+    assert lib.itd_baseline_extract_cubic_f32(None, None, 100, None, 0, None, ctypes.byref(m), None) == 1
+    assert lib.itd_baseline_extract_iq_f64(None, None, 100, None, 0, None, ctypes.byref(m), None) == 1
+    assert lib.itd_baseline_extract_spline_f64(None, None, 100, 1, 100, 0, None, 100, None, 100, k, None) == 1
+    assert lib.itd_crossways_f64(None, None, 1, 8, 8, 10, None, None) == 1
+    assert lib.itd_instantaneous_f64(None, None, 100, None, None, None, None) == 1
+    assert lib.itd_engine_device(None) == -1
+
+
+# Entries of the C ABI that no test and no Python wrapper needs to name.  Empty: every entry is reached; a name added here needs a
+# reason (say, a debugging hook that only a tool under tools/ calls).
+ABI_UNREACHED_ALLOWED = {}
+
+
+def test_every_abi_entry_is_reached_by_a_test_or_a_wrapper():
+    """Each name of pyitd_amd._lib.ABI appears in a file under tests/ or in a wrapper module of pyitd_amd (not _lib.py, which
+    only declares the prototypes): an entry that nothing calls can regress unnoticed."""
+    from pyitd_amd._lib import ABI
+    texts = []
+    for dirpath, _, files in os.walk(os.path.join(ROOT, "tests")):
+        for f in files:
+            if f.endswith((".py", ".c", ".cpp", ".h")) and f != os.path.basename(__file__):
+                texts.append(open(os.path.join(dirpath, f)).read())
+    pkg = os.path.join(ROOT, "pyitd_amd")
+    texts += [open(os.path.join(pkg, f)).read() for f in os.listdir(pkg) if f.endswith(".py") and f != "_lib.py"]
+    blob = "\n".join(texts)
+    unreached = sorted(n for n in ABI if n not in ABI_UNREACHED_ALLOWED and not re.search(r"\b%s\b" % n, blob))
+    assert not unreached, "C ABI entries called by no test and no wrapper: %s" % unreached
+    assert set(ABI_UNREACHED_ALLOWED) <= set(ABI), "the allowlist names entries that no longer exist"
