@@ -533,6 +533,45 @@ int itd_baseline_extract_cubic_batch_f64(itd_engine *e, const double *x_dev, int
                                          const int32_t *extrema_dev, int64_t extrema_stride, int64_t idx, double *baseline_dev,
                                          int64_t baseline_stride, int32_t *info_dev, void *stream);
 
+/* ---- the ITD-Fourier cascade (itd_fourier_decomposition.py:131-303) and its FFT ---------------------------------------------
+ * itd_debug_fft_f64 (tests): `batch` transforms of n complex float64 points (interleaved re, im; transform b at 2 b n doubles) from
+ *   in_dev into out_dev (may be in_dev): inverse 0 = numpy.fft.fft, 1 = numpy.fft.ifft (scaled by 1 / n).  n <= 8192: one
+ *   workgroup per transform in LDS; n = n1 n2 with n1, n2 <= 8192: four steps; any other n: Bluestein over a power of two
+ *   M >= 2n - 1 (M <= 2^26, else ITD_ERR_INVALID_ARG).  Synchronous.
+ * itd_fourier_mode_any_f64 / itd_fourier_mode_valid_f64: fourier_mode_decomposition_any (:171-209) / _valid (:131-168) of `rows` real
+ *   rows of n >= 4 samples (row r at rows_dev + r row_stride) as one batched operator: forward FFT, the selector's decision and its
+ *   masked spectrum xn in complex64 values (xn[mina:minb] = X[mina:minb], xn[-minb:-mina] = X[-minb:-mina] literally: empty when
+ *   mina == 0, not the Hermitian mirror), the full complex inverse of xn; its real part into modes_dev (row r at modes_dev +
+ *   r mode_stride; zeros for a rejection).  rec_dev (optional) [rows][8]: status (1 mode, 0 rejected), peak_max, first_peak,
+ *   last_peak, mina, minb, 0, 0 (-1: not reached).  Asynchronous on `stream`.
+ * itd_fourier_cascade_f64: itd_fourier_decomposition (:212-255; lean = 0) or itd_fourier_decomposition_lean (:258-303; lean = 1) of
+ *   `batch` signals of n samples (signal b at x_dev + b x_stride; never written).  The band plan is the caller's: `bands` knot lists
+ *   of itd_sine_wrapper (:33-47: find_extrema of the band's sine), back to back in knots_host, list k with idx_host[k] + 1 entries
+ *   as for itd_baseline_extract_cubic_f64 (2 <= idx <= n - 1, every entry < n); it is kept on the device per engine while
+ *   (n, sample_rate, lists) stay the same.  A round runs the bands, the selector _any on every row but the residual, the mode test
+ *   (not np.allclose(mode, 0): some |mode| > 1e-8), row -= mode, and the next signal as the sum of the rows in row order; a
+ *   signal whose round finds no mode leaves the loop.  One host synchronisation per round.
+ *   rows_dev [batch][bands + 1][n]: the final rows (rotations less their modes, then the residual); at the cap (a round with modes
+ *   numbered max_rounds >= 1) the rows of that round.  acc_dev (lean) [batch][bands][n]: the modes accumulated per row.
+ *   rounds_host [batch]: rounds that found modes (the reference's iteration - 1); capped_host: stopped at the cap; modes_host:
+ *   modes found.  ITD_ERR_NONFINITE if a signal holds a NaN.  Synchronous.
+ * itd_fourier_cascade_host_f64: the same on host arrays (x_host [batch][n]).
+ * itd_fourier_modes_f64: the last cascade's modes in the order found (round, then signal, then row): modes_dst [count][n] (host if
+ *   to_host, else device; NULL: records only; a lean call keeps no modes) and records_host [count][8]: signal, round, source row,
+ *   peak_max, first_peak, last_peak, mina, minb. */
+int itd_debug_fft_f64(itd_engine *e, const double *in_dev, double *out_dev, int64_t n, int32_t batch, int32_t inverse);
+int itd_fourier_mode_any_f64(itd_engine *e, const double *rows_dev, int64_t n, int64_t rows, int64_t row_stride, double *modes_dev,
+                             int64_t mode_stride, int32_t *rec_dev, void *stream);
+int itd_fourier_mode_valid_f64(itd_engine *e, const double *rows_dev, int64_t n, int64_t rows, int64_t row_stride, double *modes_dev,
+                               int64_t mode_stride, int32_t *rec_dev, void *stream);
+int itd_fourier_cascade_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t batch, int64_t x_stride, double sample_rate,
+                            int32_t bands, const int64_t *knots_host, const int64_t *idx_host, int32_t lean, int32_t max_rounds,
+                            double *rows_dev, double *acc_dev, int32_t *rounds_host, int32_t *capped_host, int64_t *modes_host);
+int itd_fourier_cascade_host_f64(itd_engine *e, const double *x_host, int64_t n, int32_t batch, double sample_rate, int32_t bands,
+                                 const int64_t *knots_host, const int64_t *idx_host, int32_t lean, int32_t max_rounds, double *rows_host,
+                                 double *acc_host, int32_t *rounds_host, int32_t *capped_host, int64_t *modes_host);
+int itd_fourier_modes_f64(itd_engine *e, double *modes_dst, int64_t count, int32_t *records_host, int32_t to_host);
+
 /* ---- block-wise (streaming) operation for unbounded signals (ABI revision 6) ------------------------------
  * The recipe of the comment at itd.cpp:31-38 — "use a circular buffer with modulous tracking to rotate the samples / re-assess
  * extrema in the entire buffer every iteration / use from the last extrema in the first buffer to the first extrema in the last

@@ -13,10 +13,14 @@ from .itd import (ITD, baseline_knot_estimation, detect_knots, detect_peaks, fin
                   itd_baseline_extract, itd_baseline_extract_cubic, itd_baseline_extract_fast, itd_baseline_extract_iq, itd_batch, itd_levels,
                   itd_sine_wrapper, matlab_detect_peaks, release_engines)
 
+from .fourier import (fourier_mode_decomposition_any, fourier_mode_decomposition_valid, itd_fourier_decomposition,
+                      itd_fourier_decomposition_batch, itd_fourier_decomposition_lean)
 from .spline import (crossways_itd_baseline_extract, itd_baseline_extract_modified, itd_baseline_extract_rows,
                      itd_baseline_extract_spline, mad, retrieve_statistical_image_component, totalextract2d)
 
 __all__ = ["itd_baseline_extract_modified", "itd_baseline_extract_spline", "itd_baseline_extract_rows", "mad",
            "crossways_itd_baseline_extract", "retrieve_statistical_image_component", "totalextract2d", "ITD", "ITDError", "Engine", "build", "itd", "itd_levels", "itd_batch", "itd_baseline_extract", "detect_peaks",
            "matlab_detect_peaks", "detect_knots", "baseline_knot_estimation", "isin", "find_extrema", "generate_sine_wave",
-           "itd_baseline_extract_fast", "itd_baseline_extract_cubic", "itd_baseline_extract_iq", "itd_sine_wrapper", "release_engines", "instantaneous"]
+           "itd_baseline_extract_fast", "itd_baseline_extract_cubic", "itd_baseline_extract_iq", "itd_sine_wrapper", "release_engines", "instantaneous",
+           "fourier_mode_decomposition_any", "fourier_mode_decomposition_valid", "itd_fourier_decomposition",
+           "itd_fourier_decomposition_lean", "itd_fourier_decomposition_batch"]

@@ -71,6 +71,12 @@ ABI = {
     "itd_baseline_extract_batch_f64": (_INT, [_P, _P, _I64, _I32, _I64, _P, _I64, _P, _I64, _P, _P]),
     "itd_detect_batch_f64": (_INT, [_P, _P, _I64, _I32, _I64, _I32, _P, _I64, _P, _P]),
     "itd_baseline_extract_cubic_batch_f64": (_INT, [_P, _P, _I64, _I32, _I64, _P, _I64, _I64, _P, _I64, _P, _P]),
+    "itd_debug_fft_f64": (_INT, [_P, _P, _P, _I64, _I32, _I32]),
+    "itd_fourier_mode_any_f64": (_INT, [_P, _P, _I64, _I64, _I64, _P, _I64, _P, _P]),
+    "itd_fourier_mode_valid_f64": (_INT, [_P, _P, _I64, _I64, _I64, _P, _I64, _P, _P]),
+    "itd_fourier_cascade_f64": (_INT, [_P, _P, _I64, _I32, _I64, ctypes.c_double, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "itd_fourier_cascade_host_f64": (_INT, [_P, _P, _I64, _I32, ctypes.c_double, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "itd_fourier_modes_f64": (_INT, [_P, _P, _I64, _P, _I32]),
     "itd_stream_create": (_INT, [ctypes.POINTER(_P), _INT, _I64, _I32, _I32, _I32, _I32]),
     "itd_stream_destroy": (None, [_P]),
     "itd_stream_reset": (_INT, [_P]),

@@ -34,6 +34,7 @@
 #include "itd_wpe.hpp"
 #include "itd_meitd.hpp"
 #include "itd_policy.hpp"
+#include "itd_fft.hpp"
 
 #ifndef ITD_TILE
 #define ITD_TILE 512
@@ -248,6 +249,22 @@ struct itd_engine {
     void *h_pin[2] = {nullptr, nullptr};   // host-form calls: pinned bounce buffers of the pipelined device -> host copy (copy_to_host)
     bool host_keep_bases = false;      // itd_set_host_keep_baselines: host-form calls leave their baselines in d_io_bases
     int64_t kept_n = 0; int32_t kept_nb = -1;   // what itd_get_last_baselines_host can still deliver (-1: nothing)
+    // the FFT and the ITD-Fourier cascade (itd_fft.hpp, itd_fourier.inc), all grown on demand
+    bool fft_attr = false;                                // hipFuncSetAttribute done for k_fft_lds
+    void *d_fft_x = nullptr; size_t fft_x_bytes = 0;      // the selectors' spectra
+    void *d_fft_y = nullptr; size_t fft_y_bytes = 0;      // four-step: the column transforms
+    void *d_fft_a = nullptr; size_t fft_a_bytes = 0;      // Bluestein: the padded chirped rows
+    void *d_fft_b = nullptr; size_t fft_b_bytes = 0;      // Bluestein: the chirp's spectrum for fft_chirp_n
+    int64_t fft_chirp_n = 0;
+    void *d_fft_rec = nullptr; size_t fft_rec_bytes = 0;  // selector records when the caller wants none
+    void *d_fc = nullptr; size_t fc_bytes = 0;            // cascade: signals, band scratch, rows, modes, records, flags
+    void *d_fio = nullptr; size_t fio_bytes = 0;          // cascade host form: its input, rows and accumulators (not d_io_*)
+    double *d_fmodes = nullptr; size_t fmodes_bytes = 0;  // cascade: the mode arena of the last call (non-lean)
+    int64_t fmodes_count = 0, fmodes_n = 0; bool fmodes_lean = false;
+    std::vector<int32_t> frec;                            // cascade: [fmodes_count][8] records of the last call
+    int32_t *d_fplan = nullptr; size_t fplan_bytes = 0;   // cascade: the band plan's knot lists (int32), for fplan_n / fplan_sr
+    int64_t fplan_n = 0; double fplan_sr = 0.0;
+    std::vector<int64_t> fplan_host, fplan_idx;
     // last run
     bool ran = false;
     LastCall last;
@@ -976,6 +993,8 @@ void itd_engine_destroy(itd_engine *e)
     (void)hipFree(e->d_io_x); (void)hipFree(e->d_io_rows); (void)hipFree(e->d_io_bases); (void)hipFree(e->d_iq_avg);
     (void)hipFree(e->d_cub); (void)hipFree(e->d_cub_e); (void)hipFree(e->d_dw); (void)hipFree(e->d_bw); (void)hipFree(e->d_kf); for (void *q : e->kf_retired) (void)hipFree(q); (void)hipFree(e->d_flag); (void)hipFree(e->d_need); (void)hipFree(e->d_valid_own);
     (void)hipFree(e->d_sp); (void)hipFree(e->d_sp2); (void)hipFree(e->d_wpe); (void)hipFree(e->d_mb); (void)hipFree(e->d_rowtab);
+    (void)hipFree(e->d_fft_x); (void)hipFree(e->d_fft_y); (void)hipFree(e->d_fft_a); (void)hipFree(e->d_fft_b); (void)hipFree(e->d_fft_rec);
+    (void)hipFree(e->d_fc); (void)hipFree(e->d_fio); (void)hipFree(e->d_fmodes); (void)hipFree(e->d_fplan);
     if (e->h_state) (void)hipHostFree(e->h_state);
     if (e->h_kf) (void)hipHostFree(e->h_kf);
     for (int k = 0; k < 2; ++k) if (e->h_pin[k]) (void)hipHostFree(e->h_pin[k]);
@@ -2925,3 +2944,4 @@ int itd_get_kernel_timing(itd_engine *e, int32_t which, double *ms_total, int32_
 }  // extern "C"
 
 #include "itd_engine_batch.inc"
+#include "itd_fourier.inc"
