@@ -191,7 +191,8 @@ struct itd_engine {
     int32_t dirty_sig[2] = {0, 0};
     int64_t dirty_gs[2] = {0, 0};
     // workspace of the single-level helpers (itd_detect_*, itd_baseline_extract_*): one signal, apart from the
-    // decomposition's, so a helper call never disturbs a decomposition that is still in flight or not yet summarised
+    // decomposition's, so a helper call never disturbs a decomposition that is still in flight or not yet summarised;
+    // with d_lists, d_kidx and d_total the fixed buffers that helper_ws() presents as a KnotWs (no allocation after create)
     int32_t *d_hcounts = nullptr;  // [2][tiles]
     TileRec *d_hrecs = nullptr;    // [2][tiles]
     int32_t *d_hgsum = nullptr;    // [3][groups*pitch]
@@ -234,10 +235,10 @@ struct itd_engine {
                                                           // also staging of the NaN-input helper path and the instantaneous step
     int32_t *d_cub_e = nullptr; size_t cub_e_bytes = 0;   // cubic variant: the caller's knots narrowed to int32 (host form)
     int32_t *d_flag = nullptr;                            // [1] device-side argument check
-    void *d_dw = nullptr; size_t dw_bytes = 0;            // batched knot detection (DetectWs): cubic batch, detect batch, streams
-    void *d_bw = nullptr; size_t bw_bytes = 0;            // batched single-level tier-1 extraction (BatchWs)
-    void *d_sp = nullptr; size_t sp_bytes = 0;            // spline flavour (batched): lists, counts, records, group sums, states,
-                                                          // ordered knot lists, totals, fit arrays, metadata
+    // three arenas a KnotWs is carved from (knot_workspace), apart so that operators used in one call do not share one
+    void *d_dw = nullptr; size_t dw_bytes = 0;            // batched knot detection: cubic batch, detect batch, counts, streams
+    void *d_bw = nullptr; size_t bw_bytes = 0;            // batched single-level tier-1 extraction (a k_extract behind the scan)
+    void *d_sp = nullptr; size_t sp_bytes = 0;            // spline flavour (batched): the scan's parts, fit arrays, metadata
     double *d_sp2 = nullptr; size_t sp2_bytes = 0;        // 2-D consumers: three planes of scratch
     void *d_mb = nullptr; size_t mb_bytes = 0;            // MEITD over a batch (itd_meitd_batch_f64): per-signal results, solver arrays, logs, XITD sums
     int64_t *d_rowtab = nullptr; size_t rowtab_bytes = 0; // itd_gather_rows_f64: the row table
@@ -318,6 +319,9 @@ struct DevGuard {
 };
 
 inline int64_t tiles_of(int64_t n) { return (n + T - 1) / T; }
+
+// the stream a call works on: the caller's, or the engine's own
+inline hipStream_t stream_of(const itd_engine *e, void *stream) { return stream ? (hipStream_t)stream : e->own_stream; }
 
 // hipEvent pairs on the launch stream around selected launches (bench instrumentation, off by default)
 // a pair of events for a launch that records them itself (hipExtLaunchKernel)
@@ -1120,8 +1124,7 @@ int itd_decompose_f32(itd_engine *e, const float *x_dev, int64_t n, int32_t batc
     int rc = check_args(e, x_dev, n, batch, x_stride, max_iteration, rows_dev);
     if (rc) return rc;
     DevGuard g(e->device);
-    return enqueue_any<float>(e, x_dev, n, batch, x_stride, max_iteration, rows_dev, baselines_dev,
-                              stream ? (hipStream_t)stream : e->own_stream);
+    return enqueue_any<float>(e, x_dev, n, batch, x_stride, max_iteration, rows_dev, baselines_dev, stream_of(e, stream));
 }
 
 int itd_decompose_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t batch, int64_t x_stride,
@@ -1130,8 +1133,7 @@ int itd_decompose_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t bat
     int rc = check_args(e, x_dev, n, batch, x_stride, max_iteration, rows_dev);
     if (rc) return rc;
     DevGuard g(e->device);
-    return enqueue_any<double>(e, x_dev, n, batch, x_stride, max_iteration, rows_dev, baselines_dev,
-                               stream ? (hipStream_t)stream : e->own_stream);
+    return enqueue_any<double>(e, x_dev, n, batch, x_stride, max_iteration, rows_dev, baselines_dev, stream_of(e, stream));
 }
 
 namespace {
@@ -1521,52 +1523,162 @@ int decompose_host(itd_engine *e, const Tin *x_host, int64_t n, int32_t M, doubl
     return nanlv != -1 ? ITD_ERR_NONFINITE : ITD_OK;
 }
 
-// level-0 knot scan of one device signal into the workspace of batch slot 0; optional ordered list in d_kidx
-// nan_xm: the scanned signal holds a NaN (found by a first scan, SigState::in_nan kept): the knot set the reference's NaN
-// branch gives (k_nan_level0), and — if non-null — the mutated float64 copy of the signal
-template <typename Tin>
-int scan_level0(itd_engine *e, const Tin *x, int64_t n, int mode, bool compact, hipStream_t st, int64_t tail_value = -1,
-                bool nan_follow = false, double *nan_xm = nullptr)
+// ---------------------------------------------------------------------------------------------
+// The knot scan every single-level operator starts with: what it works on (KnotWs: carved from one of the engine's arenas, or
+// the fixed one-signal buffers seen as one), its launches (knot_scan), the record-driven level-0 extraction behind it
+// (extract_level0) and its totals on the host (fetch_totals).
+// ---------------------------------------------------------------------------------------------
+struct KnotWs {
+    int32_t *lists, *counts, *gsum, *kidx, *totals, *tbase;   // a part that was not asked for is NULL
+    TileRec *recs;
+    SigState *state;
+    int64_t kidx_stride;      // kidx[b] = [lead slot, knots, tail]; totals[b] = {knot count, the signal holds a NaN}
+    int64_t half, third;      // elements between the two count / record buffers, between the three group-sum buffers
+    int64_t gsum_zero;        // group-sum elements a scan zeroes first: one buffer, or all three (a k_extract behind the scan)
+    int n_tiles, n_groups;
+    int init_pad;             // blocks the initialising launch has beyond what it needs (the fixed buffers' launch always had one)
+};
+// the optional parts: per-tile lists (the fast pair keeps its flag words there), ordered lists and totals, the knots in front of
+// every tile (k_compact), and the second count / record buffer with group-sum buffers two and three
+enum : int { kWsLists = 1, kWsOrdered = 2, kWsTbase = 4, kWsExtract = 8, kWsDetect = kWsLists | kWsOrdered | kWsTbase };
+
+// a KnotWs for `batch` signals of n samples from a grow-only arena, `tail` bytes for the caller behind it (*tail_out)
+int knot_workspace(itd_engine *e, void **arena, size_t *have, int64_t n, int batch, int parts, KnotWs &w, size_t tail = 0,
+                   char **tail_out = nullptr)
 {
-    const int n_tiles = (int)tiles_of(n);
-    const dim3 grid_t(n_tiles, 1), blk(kWave);
-    // the helpers' own state, counts, records and group sums: a decomposition's workspace is never touched
-    k_init_state<<<(unsigned)std::min<int64_t>((3 * e->hgsum_third + 255) / 256 + 1, 2048), 256, 0, st>>>(e->d_hstate, 1, e->d_hgsum,
-                                                                                                   3 * e->hgsum_third, nan_follow ? 1 : 0);
-    if constexpr (std::is_same<Tin, double>::value) {
-        if (!nan_follow && compact && (mode == (int)kCpp || mode == (int)kZeroCross)) {       // the short pair (itd_detect_fast.hpp)
-            unsigned long long *fw = reinterpret_cast<unsigned long long *>(e->d_lists);
-            if (mode == (int)kCpp) k_detect_fast<(int)kCpp><<<grid_t, blk, 0, st>>>(x, n, n, n_tiles, e->d_hcounts, fw, e->d_hgsum, e->d_hstate);
-            else k_detect_fast<(int)kZeroCross><<<grid_t, blk, 0, st>>>(x, n, n, n_tiles, e->d_hcounts, fw, e->d_hgsum, e->d_hstate);
-            k_compact_fast<<<grid_t, blk, 0, st>>>(fw, e->d_hcounts, e->d_hgsum, n_tiles, n, e->d_kidx, e->max_n + 2, e->d_total, e->d_hstate,
-                                                   tail_value, e->d_hcounts + e->max_tiles, 1);
-            HIP_TRY(e, hipGetLastError());
-            return ITD_OK;
-        }
-    }
-    if (nan_follow)
-        k_nan_level0<Tin, T><<<grid_t, blk, 0, st>>>(x, n, n, n_tiles, nan_xm, n, e->d_hcounts, e->d_hrecs, e->d_hgsum, e->d_hstate,
-                                                     mode, compact ? e->d_lists : nullptr);
+    w.n_tiles = (int)tiles_of(n);
+    w.n_groups = groups_of(w.n_tiles);
+    w.kidx_stride = n + 2;
+    w.half = (int64_t)batch * w.n_tiles;
+    w.third = (int64_t)batch * w.n_groups * kGsumPitch;
+    const size_t bufs = parts & kWsExtract ? 2 : 1, gbufs = parts & kWsExtract ? 3 : 1, B = (size_t)batch, tiles = (size_t)w.half;
+    w.gsum_zero = (int64_t)gbufs * w.third;
+    w.init_pad = 0;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_lists = parts & kWsLists ? al(tiles * T * sizeof(int32_t)) : 0, b_tbase = parts & kWsTbase ? al(tiles * sizeof(int32_t)) : 0;
+    const size_t b_counts = al(bufs * tiles * sizeof(int32_t)), b_recs = al(bufs * tiles * sizeof(TileRec));
+    const size_t b_gsum = al(gbufs * (size_t)w.third * sizeof(int32_t)), b_state = al(B * sizeof(SigState));
+    const size_t b_kidx = parts & kWsOrdered ? al(B * (size_t)w.kidx_stride * sizeof(int32_t)) : 0, b_tot = parts & kWsOrdered ? al(B * 2 * sizeof(int32_t)) : 0;
+    const int rc = grow(e, arena, have, b_lists + b_counts + b_recs + b_gsum + b_state + b_kidx + b_tot + b_tbase + tail);
+    if (rc) return rc;
+    char *p = (char *)*arena;
+    auto take = [&p](size_t b) { char *q = b ? p : nullptr; p += b; return q; };
+    w.lists = (int32_t *)take(b_lists);
+    w.counts = (int32_t *)take(b_counts);
+    w.recs = (TileRec *)take(b_recs);
+    w.gsum = (int32_t *)take(b_gsum);
+    w.state = (SigState *)take(b_state);
+    w.kidx = (int32_t *)take(b_kidx);
+    w.totals = (int32_t *)take(b_tot);
+    w.tbase = (int32_t *)take(b_tbase);
+    if (tail_out) *tail_out = p;
+    return ITD_OK;
+}
+
+// the engine's fixed one-signal buffers as a KnotWs: the helpers' own state, counts, records and group sums (a decomposition's
+// workspace is never touched), nothing to allocate.  The second half of the count buffer receives every tile's knot base.
+KnotWs helper_ws(const itd_engine *e, int64_t n)
+{
+    KnotWs w;
+    w.n_tiles = (int)tiles_of(n);
+    w.n_groups = groups_of(w.n_tiles);
+    w.lists = e->d_lists; w.counts = e->d_hcounts; w.recs = e->d_hrecs; w.gsum = e->d_hgsum; w.state = e->d_hstate;
+    w.kidx = e->d_kidx; w.kidx_stride = e->max_n + 2; w.totals = e->d_total;
+    w.half = e->max_tiles; w.third = e->hgsum_third;
+    w.tbase = w.counts + w.half;
+    w.gsum_zero = 3 * e->hgsum_third;
+    w.init_pad = 1;
+    return w;
+}
+
+// the scan's first launch: states and group sums (keep_in_nan: the NaN-input repeat needs to know which signals hold one)
+void scan_init(const KnotWs &w, int batch, bool keep_in_nan, hipStream_t st)
+{
+    const int64_t blocks = std::max<int64_t>((w.gsum_zero + 255) / 256 + w.init_pad, (batch + 255) / 256);
+    k_init_state<<<(unsigned)std::min<int64_t>(blocks, 2048), 256, 0, st>>>(w.state, batch, w.gsum, w.gsum_zero, keep_in_nan ? 1 : 0);
+}
+
+// the scan's last launch when ordered lists are wanted.  kidx_out = NULL: into the workspace's lists with a leading slot (what the
+// cubic kernels and the stream's selection read); else the caller's [batch][kidx_out_stride] array without one (itd_detect_batch_*).
+// fast: from the flag words of the short pair (itd_detect_fast.hpp)
+void scan_compact(const KnotWs &w, int64_t n, int batch, bool fast, int64_t tail_value, int32_t *kidx_out, int64_t kidx_out_stride,
+                  hipStream_t st)
+{
+    const dim3 grid_t(w.n_tiles, batch), blk(kWave);
+    int32_t *kidx = kidx_out ? kidx_out : w.kidx;
+    const int64_t stride = kidx_out ? kidx_out_stride : w.kidx_stride;
+    const int lead = kidx_out ? 0 : 1;
+    if (fast)
+        k_compact_fast<<<grid_t, blk, 0, st>>>(reinterpret_cast<const unsigned long long *>(w.lists), w.counts, w.gsum, w.n_tiles, n, kidx,
+                                               stride, w.totals, w.state, tail_value, w.tbase, lead);
     else
-    k_detect<Tin, T><<<grid_t, blk, 0, st>>>(x, n, n, n_tiles, mode, compact ? e->d_lists : nullptr, e->d_hcounts,
-                                              e->d_hrecs, e->d_hgsum, e->d_hstate);
-    if (compact)
-        // (the second half of the helpers' count buffer receives every tile's knot base: the instantaneous-frequency step uses it)
-        k_compact<T><<<grid_t, blk, 0, st>>>(e->d_lists, e->d_hcounts, e->d_hgsum, n_tiles, n, e->d_kidx, e->max_n + 2,
-                                              e->d_total, e->d_hstate, tail_value, e->d_hcounts + e->max_tiles);
+        k_compact<T><<<grid_t, blk, 0, st>>>(w.lists, w.counts, w.gsum, w.n_tiles, n, kidx, stride, w.totals, w.state, tail_value, w.tbase, lead);
+}
+
+// Level-0 knots of `batch` signals (batch <= 65535: grid.y) by predicate `mode`, no host synchronisation.  after: what is wanted
+// behind the detection — nothing (counts, records and group sums for a k_extract), totals[b] only, or the ordered lists too.
+// nan_follow: the scanned signals hold a NaN (found by a first scan, SigState::in_nan kept): the knot set the reference's NaN
+// branch gives (k_nan_level0), and — if nan_xm is non-null — the mutated float64 copy of the signal
+enum KnotAfter { kScanOnly, kScanTotals, kScanOrdered };
+template <typename Tin>
+int knot_scan(itd_engine *e, const KnotWs &w, const Tin *x, int64_t x_stride, int64_t n, int batch, int mode, KnotAfter after, hipStream_t st,
+              int64_t tail_value = -1, bool nan_follow = false, double *nan_xm = nullptr, int32_t *kidx_out = nullptr, int64_t kidx_out_stride = 0)
+{
+    const dim3 grid_t(w.n_tiles, batch), blk(kWave);
+    int32_t *lists = after == kScanOrdered ? w.lists : nullptr;
+    scan_init(w, batch, nan_follow, st);
+    bool fast = false;
+    if constexpr (std::is_same<Tin, double>::value) {
+        // the two predicates without NaN rules and without an extraction behind them: the short pair (itd_detect_fast.hpp); the
+        // tiles' flag words live where the general pair keeps its per-tile position lists
+        fast = !nan_follow && after == kScanOrdered && (mode == (int)kCpp || mode == (int)kZeroCross);
+        unsigned long long *fw = reinterpret_cast<unsigned long long *>(w.lists);
+        if (fast && mode == (int)kCpp) k_detect_fast<(int)kCpp><<<grid_t, blk, 0, st>>>(x, x_stride, n, w.n_tiles, w.counts, fw, w.gsum, w.state);
+        else if (fast) k_detect_fast<(int)kZeroCross><<<grid_t, blk, 0, st>>>(x, x_stride, n, w.n_tiles, w.counts, fw, w.gsum, w.state);
+    }
+    if (!fast && nan_follow)
+        k_nan_level0<Tin, T><<<grid_t, blk, 0, st>>>(x, x_stride, n, w.n_tiles, nan_xm, n, w.counts, w.recs, w.gsum, w.state, mode, lists);
+    else if (!fast)
+        k_detect<Tin, T><<<grid_t, blk, 0, st>>>(x, x_stride, n, w.n_tiles, mode, lists, w.counts, w.recs, w.gsum, w.state);
+    if (after == kScanOrdered) scan_compact(w, n, batch, fast, tail_value, kidx_out, kidx_out_stride, st);
+    else if (after == kScanTotals) k_batch_totals<<<(batch + 3) / 4, 256, 0, st>>>(w.gsum, w.n_groups, batch, w.state, w.totals);
     HIP_TRY(e, hipGetLastError());
     return ITD_OK;
 }
 
-// the knot total of the last helper scan; d_total[1] = the scanned signal held a NaN (the reference's detect_peaks would
-// take its NaN branch and write +inf into the caller's array: rejected, like NaN input of a decomposition)
-int fetch_total(itd_engine *e, hipStream_t st, int64_t *m_host, bool nan_is_error = true)
+// the record-driven level-0 extraction behind a scan (ITD.py:79-121; keep_nan: the baseline as computed): rewrites the per-tile
+// lists' counts and records into the workspace's second buffers
+template <typename Tin>
+void extract_level0(const KnotWs &w, const Tin *x, int64_t x_stride, int64_t n, int batch, double *rot, int64_t rot_stride, double *base,
+                    int64_t base_stride, hipStream_t st)
 {
-    int32_t m32[2] = {0, 0};
-    HIP_TRY(e, hipMemcpyAsync(m32, e->d_total, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    k_extract<Tin, T, false, kRankCap0, kTilesPerWave><<<dim3((w.n_tiles + kTilesPerWave - 1) / kTilesPerWave, batch), kWave, 0, st>>>(
+        x, x_stride, n, w.n_tiles, batch, w.counts, w.counts + w.half, w.recs, w.recs + w.half, w.gsum, w.gsum + w.third, w.gsum + 2 * w.third,
+        rot, rot_stride, base, base_stride, w.state, 0, 1);
+}
+
+// totals[b] = {knot count, the signal held a NaN} of `batch` signals: synchronises, fills counts_out (optional).  A NaN: the
+// reference's detect_peaks would take its NaN branch and write +inf into the caller's array — rejected, like NaN input of a
+// decomposition, unless the caller follows that branch itself (nan_is_error = false)
+int fetch_totals(itd_engine *e, const int32_t *totals, int batch, int32_t *counts_out, hipStream_t st, bool nan_is_error = true)
+{
+    std::vector<int32_t> tot((size_t)batch * 2);
+    HIP_TRY(e, hipMemcpyAsync(tot.data(), totals, tot.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(e, hipStreamSynchronize(st));
-    *m_host = m32[0];
-    return (m32[1] && nan_is_error) ? ITD_ERR_NONFINITE : ITD_OK;
+    bool nan_in = false;
+    for (int b = 0; b < batch; ++b) {
+        if (counts_out) counts_out[b] = tot[2 * (size_t)b];
+        nan_in = nan_in || tot[2 * (size_t)b + 1] != 0;
+    }
+    return nan_in && nan_is_error ? ITD_ERR_NONFINITE : ITD_OK;
+}
+// the knot total of the last one-signal scan (nothing is written where the copy fails)
+int fetch_total(itd_engine *e, const KnotWs &w, hipStream_t st, int64_t *m_host, bool nan_is_error = true)
+{
+    int32_t m32 = 0;
+    const int rc = fetch_totals(e, w.totals, 1, &m32, st, nan_is_error);
+    if (rc == ITD_OK || rc == ITD_ERR_NONFINITE) *m_host = m32;
+    return rc;
 }
 
 // the three knot sets of the reference's own detect functions follow its NaN branch when the signal holds a NaN
@@ -1582,21 +1694,18 @@ int extract_dev(itd_engine *e, const Tin *x, int64_t n, double *rot, double *bas
     if (!e || !x || !rot || !base) return ITD_ERR_INVALID_ARG;
     if (n < 3 || n > e->max_n) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    const int n_tiles = (int)tiles_of(n);
-    const bool want_list = m_host || knots || want_sync;
-    int rc = scan_level0<Tin>(e, x, n, (int)kKnots, want_list, st);   // the ordered list must be taken before
-    if (rc) return rc;                                                 // k_extract rewrites the per-tile lists
-    k_extract<Tin, T, false, kRankCap0, kTilesPerWave><<<dim3((n_tiles + kTilesPerWave - 1) / kTilesPerWave), kWave, 0, st>>>(x, n, n, n_tiles, 1, e->d_hcounts,
-                                                      e->d_hcounts + e->max_tiles, e->d_hrecs, e->d_hrecs + e->max_tiles,
-                                                      e->d_hgsum, e->d_hgsum + e->hgsum_third, e->d_hgsum + 2 * e->hgsum_third,
-                                                      rot, n, base, n, e->d_hstate, 0, 1);
+    const KnotWs w = helper_ws(e, n);
+    const KnotAfter after = m_host || knots || want_sync ? kScanOrdered : kScanOnly;
+    int rc = knot_scan<Tin>(e, w, x, n, n, 1, (int)kKnots, after, st);   // the ordered list must be taken before
+    if (rc) return rc;                                                    // k_extract rewrites the per-tile lists
+    extract_level0<Tin>(w, x, n, n, 1, rot, n, base, n, st);
     HIP_TRY(e, hipGetLastError());
-    if (want_list) {
+    if (after == kScanOrdered) {
         int64_t m = 0;
-        rc = fetch_total(e, st, &m, !nan_follows(e, (int)kKnots));
+        rc = fetch_total(e, w, st, &m, !nan_follows(e, (int)kKnots));
         if (rc) return rc;
         int32_t has_nan = 0;
-        HIP_TRY(e, hipMemcpy(&has_nan, e->d_total + 1, sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(e, hipMemcpy(&has_nan, w.totals + 1, sizeof(int32_t), hipMemcpyDeviceToHost));
         if (took_nan_path) *took_nan_path = has_nan != 0;
         if (has_nan) {
             // NaN in the signal: again, the way the reference runs it (ITD.py:87-88 over :46-51, 64-68): the mutated float64 copy
@@ -1604,18 +1713,16 @@ int extract_dev(itd_engine *e, const Tin *x, int64_t n, double *rot, double *bas
             rc = grow(e, &e->d_cub, &e->cub_bytes, (size_t)n * sizeof(double));
             if (rc) return rc;
             double *xm = (double *)e->d_cub;
-            rc = scan_level0<Tin>(e, x, n, (int)kKnots, want_list, st, -1, true, xm);
+            rc = knot_scan<Tin>(e, w, x, n, n, 1, (int)kKnots, after, st, -1, true, xm);
             if (rc) return rc;
-            k_extract<double, T, false, kRankCap0, kTilesPerWave><<<dim3((n_tiles + kTilesPerWave - 1) / kTilesPerWave), kWave, 0, st>>>(
-                xm, n, n, n_tiles, 1, e->d_hcounts, e->d_hcounts + e->max_tiles, e->d_hrecs, e->d_hrecs + e->max_tiles, e->d_hgsum,
-                e->d_hgsum + e->hgsum_third, e->d_hgsum + 2 * e->hgsum_third, rot, n, base, n, e->d_hstate, 0, 1);
+            extract_level0<double>(w, xm, n, n, 1, rot, n, base, n, st);
             HIP_TRY(e, hipGetLastError());
-            rc = fetch_total(e, st, &m, false);
+            rc = fetch_total(e, w, st, &m, false);
             if (rc) return rc;
         }
         if (m_host) *m_host = m;
         if (knots && m > 0) {
-            HIP_TRY(e, hipMemcpyAsync(knots, e->d_kidx + 1, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(e, hipMemcpyAsync(knots, w.kidx + 1, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToDevice, st));
             HIP_TRY(e, hipStreamSynchronize(st));
         }
     }
@@ -1628,22 +1735,23 @@ int detect_dev(itd_engine *e, const Tin *x, int64_t n, int32_t mode, int32_t *id
     if (!e || !x || !count) return ITD_ERR_INVALID_ARG;
     if (n < 3 || n > e->max_n || mode < 0 || mode > 4) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    int rc = scan_level0<Tin>(e, x, n, mode, true, st);
+    const KnotWs w = helper_ws(e, n);
+    int rc = knot_scan<Tin>(e, w, x, n, n, 1, mode, kScanOrdered, st);
     if (rc) return rc;
-    rc = fetch_total(e, st, count, !nan_follows(e, mode));
+    rc = fetch_total(e, w, st, count, !nan_follows(e, mode));
     if (rc) return rc;
     if (nan_follows(e, mode)) {
         int32_t has_nan = 0;
-        HIP_TRY(e, hipMemcpy(&has_nan, e->d_total + 1, sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(e, hipMemcpy(&has_nan, w.totals + 1, sizeof(int32_t), hipMemcpyDeviceToHost));
         if (has_nan) {   // the reference's NaN branch (ITD.py:46-51, 64-68; numba_accelerated_itd.py:28-49)
-            rc = scan_level0<Tin>(e, x, n, mode, true, st, -1, true, nullptr);
+            rc = knot_scan<Tin>(e, w, x, n, n, 1, mode, kScanOrdered, st, -1, true);
             if (rc) return rc;
-            rc = fetch_total(e, st, count, false);
+            rc = fetch_total(e, w, st, count, false);
             if (rc) return rc;
         }
     }
     if (idx && *count > 0) {
-        HIP_TRY(e, hipMemcpyAsync(idx, e->d_kidx + 1, sizeof(int32_t) * (size_t)*count, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(e, hipMemcpyAsync(idx, w.kidx + 1, sizeof(int32_t) * (size_t)*count, hipMemcpyDeviceToDevice, st));
         HIP_TRY(e, hipStreamSynchronize(st));
     }
     return ITD_OK;
@@ -1672,16 +1780,14 @@ int itd_baseline_extract_f64(itd_engine *e, const double *x_dev, int64_t n, doub
                              int32_t *knots_dev, int64_t *m_host, void *stream)
 {
     if (!e) return ITD_ERR_INVALID_ARG;
-    return extract_dev<double>(e, x_dev, n, rot_dev, base_dev, knots_dev, m_host,
-                               stream ? (hipStream_t)stream : e->own_stream, false);
+    return extract_dev<double>(e, x_dev, n, rot_dev, base_dev, knots_dev, m_host, stream_of(e, stream), false);
 }
 
 int itd_baseline_extract_f32(itd_engine *e, const float *x_dev, int64_t n, double *rot_dev, double *base_dev,
                              int32_t *knots_dev, int64_t *m_host, void *stream)
 {
     if (!e) return ITD_ERR_INVALID_ARG;
-    return extract_dev<float>(e, x_dev, n, rot_dev, base_dev, knots_dev, m_host,
-                              stream ? (hipStream_t)stream : e->own_stream, false);
+    return extract_dev<float>(e, x_dev, n, rot_dev, base_dev, knots_dev, m_host, stream_of(e, stream), false);
 }
 
 int itd_baseline_extract_host_f64(itd_engine *e, const double *x_host, int64_t n, double *rot_host, double *base_host,
@@ -1706,12 +1812,13 @@ int itd_baseline_extract_host_f64(itd_engine *e, const double *x_host, int64_t n
     HIP_TRY(e, hipMemcpyAsync(rot_host, d_rot, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(e, hipMemcpyAsync(base_host, d_base, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
     if (knots_host && m > 0) {
-        k_widen_idx<<<(unsigned)((m + 255) / 256), 256, 0, st>>>(e->d_kidx + 1, d_k64, m);
+        k_widen_idx<<<(unsigned)((m + 255) / 256), 256, 0, st>>>(helper_ws(e, n).kidx + 1, d_k64, m);
         HIP_TRY(e, hipMemcpyAsync(knots_host, d_k64, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     }
     if (bk_host) {
         // (a signal that holds NaNs: the knot values of the mutated copy, as the reference computes them after detect_peaks' write)
-        k_knot_values<double><<<(unsigned)((m + 2 + 255) / 256), 256, 0, st>>>(nan_path ? (const double *)e->d_cub : (const double *)e->d_io_x, n, e->d_kidx, (int)m, d_bk);
+        const double *xk = nan_path ? (const double *)e->d_cub : (const double *)e->d_io_x;
+        k_knot_values<double><<<(unsigned)((m + 2 + 255) / 256), 256, 0, st>>>(xk, n, helper_ws(e, n).kidx, (int)m, d_bk);
         HIP_TRY(e, hipMemcpyAsync(bk_host, d_bk, (size_t)(m + 2) * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(e, hipStreamSynchronize(st));
@@ -1723,14 +1830,14 @@ int itd_detect_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t mode, 
                    void *stream)
 {
     if (!e) return ITD_ERR_INVALID_ARG;
-    return detect_dev<double>(e, x_dev, n, mode, idx_dev, count_host, stream ? (hipStream_t)stream : e->own_stream);
+    return detect_dev<double>(e, x_dev, n, mode, idx_dev, count_host, stream_of(e, stream));
 }
 
 int itd_detect_f32(itd_engine *e, const float *x_dev, int64_t n, int32_t mode, int32_t *idx_dev, int64_t *count_host,
                    void *stream)
 {
     if (!e) return ITD_ERR_INVALID_ARG;
-    return detect_dev<float>(e, x_dev, n, mode, idx_dev, count_host, stream ? (hipStream_t)stream : e->own_stream);
+    return detect_dev<float>(e, x_dev, n, mode, idx_dev, count_host, stream_of(e, stream));
 }
 
 int itd_detect_host_f64(itd_engine *e, const double *x_host, int64_t n, int32_t mode, int64_t *idx_host,
@@ -1750,7 +1857,7 @@ int itd_detect_host_f64(itd_engine *e, const double *x_host, int64_t n, int32_t 
     if (rc) return rc;
     if (idx_host && m > 0) {
         int64_t *d_k64 = (int64_t *)e->d_io_rows;
-        k_widen_idx<<<(unsigned)((m + 255) / 256), 256, 0, st>>>(e->d_kidx + 1, d_k64, m);
+        k_widen_idx<<<(unsigned)((m + 255) / 256), 256, 0, st>>>(helper_ws(e, n).kidx + 1, d_k64, m);
         HIP_TRY(e, hipMemcpyAsync(idx_host, d_k64, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(e, hipStreamSynchronize(st));
     }
@@ -1790,7 +1897,7 @@ int itd_knot_values_f64(itd_engine *e, const double *x_dev, int64_t n, const int
     if (n < 2 || n >= (int64_t)INT32_MAX || m < 0 || m > n) return ITD_ERR_INVALID_ARG;
     if (m == 0) return ITD_OK;
     DevGuard g(e->device);
-    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
+    hipStream_t st = stream_of(e, stream);
     k_knot_values<double><<<(unsigned)((m + 2 + 255) / 256), 256, 0, st>>>(x_dev, n, extrema_dev, (int)m, bk_dev, 1);
     HIP_TRY(e, hipGetLastError());
     return ITD_OK;
@@ -1803,75 +1910,13 @@ int itd_knot_values_f64(itd_engine *e, const double *x_dev, int64_t n, const int
 // itd_fourier_decomposition.py:49-122 = itd.cpp:156-239.  Single-level operator; synchronous like the other helpers.
 // ---------------------------------------------------------------------------------------------
 namespace {
-// Batched knot detection into a workspace of its own (grow-only): per-tile lists, counts, records, group sums, per-signal
-// states, the ordered knot lists kidx[b] = [lead slot, knots, tail] and totals[b] = {knot count, the signal holds a NaN}.
-struct DetectWs {
-    int32_t *lists, *counts, *gsum, *kidx, *totals, *tbase;
-    TileRec *recs;
-    SigState *state;
-    int64_t kidx_stride;
-    int n_tiles, n_groups;
-};
-int detect_workspace(itd_engine *e, int64_t n, int batch, DetectWs &w)
-{
-    w.n_tiles = (int)tiles_of(n);
-    w.n_groups = groups_of(w.n_tiles);
-    w.kidx_stride = n + 2;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t B = (size_t)batch, tiles = B * (size_t)w.n_tiles;
-    const size_t b_lists = al(tiles * T * sizeof(int32_t)), b_counts = al(tiles * sizeof(int32_t)), b_recs = al(tiles * sizeof(TileRec));
-    const size_t b_gsum = al(B * (size_t)w.n_groups * kGsumPitch * sizeof(int32_t)), b_state = al(B * sizeof(SigState));
-    const size_t b_kidx = al(B * (size_t)w.kidx_stride * sizeof(int32_t)), b_tot = al(B * 2 * sizeof(int32_t));
-    const int rc = grow(e, &e->d_dw, &e->dw_bytes, b_lists + 2 * b_counts + b_recs + b_gsum + b_state + b_kidx + b_tot);
-    if (rc) return rc;
-    char *p = (char *)e->d_dw;
-    w.lists = (int32_t *)p; p += b_lists;
-    w.counts = (int32_t *)p; p += b_counts;
-    w.recs = (TileRec *)p; p += b_recs;
-    w.gsum = (int32_t *)p; p += b_gsum;
-    w.state = (SigState *)p; p += b_state;
-    w.kidx = (int32_t *)p; p += b_kidx;
-    w.totals = (int32_t *)p; p += b_tot;
-    w.tbase = (int32_t *)p;          // the knots in front of every tile (k_compact)
-    return ITD_OK;
-}
-// knots of `batch` signals (batch <= 65535: grid.y) by predicate `mode`, ordered, no host synchronisation.  kidx_out = NULL: into
-// the workspace's lists with a leading slot (what the cubic kernels and the stream's selection read); else the caller's
-// [batch][kidx_out_stride] array without one (itd_detect_batch_*)
-int detect_enqueue(itd_engine *e, const double *x, int64_t x_stride, int64_t n, int batch, int mode, int64_t tail_value,
-                   hipStream_t st, DetectWs &w, int32_t *kidx_out = nullptr, int64_t kidx_out_stride = 0, bool want_lists = true)
-{
-    int rc = detect_workspace(e, n, batch, w);
-    if (rc) return rc;
-    const dim3 grid_t(w.n_tiles, batch), blk(kWave);
-    const int64_t ge = (int64_t)batch * w.n_groups * kGsumPitch;
-    k_init_state<<<(unsigned)std::min<int64_t>(std::max<int64_t>((ge + 255) / 256, (batch + 255) / 256), 2048), 256, 0, st>>>(w.state, batch, w.gsum, ge);
-    if (want_lists && (mode == (int)kCpp || mode == (int)kZeroCross)) {
-        // the two predicates without NaN rules and without an extraction behind them: the short pair (itd_detect_fast.hpp); the
-        // tiles' flag words live where the general pair keeps its per-tile position lists
-        unsigned long long *fw = reinterpret_cast<unsigned long long *>(w.lists);
-        if (mode == (int)kCpp) k_detect_fast<(int)kCpp><<<grid_t, blk, 0, st>>>(x, x_stride, n, w.n_tiles, w.counts, fw, w.gsum, w.state);
-        else k_detect_fast<(int)kZeroCross><<<grid_t, blk, 0, st>>>(x, x_stride, n, w.n_tiles, w.counts, fw, w.gsum, w.state);
-        k_compact_fast<<<grid_t, blk, 0, st>>>(fw, w.counts, w.gsum, w.n_tiles, n, kidx_out ? kidx_out : w.kidx,
-                                               kidx_out ? kidx_out_stride : w.kidx_stride, w.totals, w.state, tail_value, w.tbase, kidx_out ? 0 : 1);
-        HIP_TRY(e, hipGetLastError());
-        return ITD_OK;
-    }
-    k_detect<double, T><<<grid_t, blk, 0, st>>>(x, x_stride, n, w.n_tiles, mode, want_lists ? w.lists : nullptr, w.counts, w.recs, w.gsum, w.state);
-    if (want_lists)
-        k_compact<T><<<grid_t, blk, 0, st>>>(w.lists, w.counts, w.gsum, w.n_tiles, n, kidx_out ? kidx_out : w.kidx,
-                                              kidx_out ? kidx_out_stride : w.kidx_stride, w.totals, w.state, tail_value, w.tbase, kidx_out ? 0 : 1);
-    else
-        k_batch_totals<<<(batch + 3) / 4, 256, 0, st>>>(w.gsum, w.n_groups, batch, w.state, w.totals);
-    HIP_TRY(e, hipGetLastError());
-    return ITD_OK;
-}
-
 // The cubic operator over `batch` signals, asynchronous on st.  extrema = NULL: every signal's own knots (itd.cpp:159-169);
 // else the caller's list(s) of idx + 1 entries (e_stride = 0: one list for every signal, itd.cpp:40-44).  *jobs_out: the
-// per-signal jobs on the device (idx used, valid, status) for callers that synchronise afterwards.
+// per-signal jobs on the device (idx used, valid, status) for callers that synchronise afterwards; *knots_out: the detected
+// knots' ordered lists (lead slot in front).
 int cubic_batch(itd_engine *e, const double *x, int64_t n, int batch, int64_t x_stride, const int32_t *extrema, int64_t e_stride,
-                int64_t idx, double *baseline, int64_t b_stride, hipStream_t st, const CubicJob **jobs_out, int *n_jobs_out)
+                int64_t idx, double *baseline, int64_t b_stride, hipStream_t st, const CubicJob **jobs_out, int *n_jobs_out,
+                const int32_t **knots_out = nullptr)
 {
     const int64_t L = (extrema ? idx : n) + 2;                        // entries per knot array
     const size_t jobs_b = (((size_t)batch * sizeof(CubicJob)) + 255) & ~(size_t)255;
@@ -1886,9 +1931,12 @@ int cubic_batch(itd_engine *e, const double *x, int64_t n, int batch, int64_t x_
     int n_jobs;
     int64_t max_count;
     if (!extrema) {
-        DetectWs w;
-        rc = detect_enqueue(e, x, x_stride, n, batch, (int)kCpp, 0 /* e[idx] = 0: the file's static array at first call */, st, w);
+        KnotWs w;
+        rc = knot_workspace(e, &e->d_dw, &e->dw_bytes, n, batch, kWsDetect, w);
+        // (tail 0: e[idx] = 0, the file's static array at first call)
+        if (!rc) rc = knot_scan<double>(e, w, x, x_stride, n, batch, (int)kCpp, kScanOrdered, st, 0);
         if (rc) return rc;
+        if (knots_out) *knots_out = w.kidx;
         n_jobs = batch;
         k_cubic_jobs<<<(batch + 255) / 256, 256, 0, st>>>(jobs, batch, 1, 0, w.totals);
         A.e = w.kidx; A.e_stride = w.kidx_stride; A.job_stride = 1;
@@ -1915,10 +1963,11 @@ int cubic_batch(itd_engine *e, const double *x, int64_t n, int batch, int64_t x_
 // count (find_extrema: including the leading 0 and the extrapolated tail, like the reference's return value)
 int cubic_detect(itd_engine *e, const double *x, int64_t n, int mode, int64_t *count, hipStream_t st)
 {
-    int rc = scan_level0<double>(e, x, n, mode, true, st, mode == (int)kCpp ? 0 : -1);
+    const KnotWs w = helper_ws(e, n);
+    int rc = knot_scan<double>(e, w, x, n, n, 1, mode, kScanOrdered, st, mode == (int)kCpp ? 0 : -1);
     if (rc) return rc;
-    if (mode == (int)kZeroCross) k_zero_cross_tail<<<1, 1, 0, st>>>(e->d_kidx, e->d_total);
-    return fetch_total(e, st, count);
+    if (mode == (int)kZeroCross) k_zero_cross_tail<<<1, 1, 0, st>>>(w.kidx, w.totals);
+    return fetch_total(e, w, st, count);
 }
 
 // one signal, synchronous: ONE host synchronisation, at the end (the job: knot count, validity)
@@ -1930,7 +1979,8 @@ int cubic_dev(itd_engine *e, const double *x, int64_t n, const int32_t *extrema,
     if (extrema && (idx < 2 || idx > n - 1)) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
     const CubicJob *jobs = nullptr;
-    int rc = cubic_batch(e, x, n, 1, n, extrema, 0, idx, baseline, n, st, &jobs, nullptr);
+    const int32_t *kidx = nullptr;
+    int rc = cubic_batch(e, x, n, 1, n, extrema, 0, idx, baseline, n, st, &jobs, nullptr, &kidx);
     if (rc) return rc;
     CubicJob job;
     HIP_TRY(e, hipMemcpyAsync(&job, jobs, sizeof(job), hipMemcpyDeviceToHost, st));
@@ -1938,12 +1988,22 @@ int cubic_dev(itd_engine *e, const double *x, int64_t n, const int32_t *extrema,
     if (job.status == 1) return ITD_ERR_INVALID_ARG;
     if (job.status == 2) return ITD_ERR_NONFINITE;
     if (idx_out) *idx_out = job.idx;
-    if (knots_dev_out) {    // the detected knots (behind the workspace list's leading slot)
-        DetectWs w;
-        rc = detect_workspace(e, n, 1, w);   // no growth: same geometry as the call above
-        if (rc) return rc;
-        *knots_dev_out = w.kidx + 1;
-    }
+    if (knots_dev_out) *knots_dev_out = kidx + 1;    // the detected knots (behind the workspace list's leading slot)
+    return ITD_OK;
+}
+
+// the caller's knot list (host, int64, `count` entries) for the kernels: range-checked on the host copy first (narrowing to int32
+// must not wrap), uploaded into `scratch`, narrowed into d_cub_e
+int stage_extrema(itd_engine *e, const int64_t *extrema_host, int64_t count, int64_t n, int64_t *scratch, hipStream_t st,
+                  const int32_t **dev_out)
+{
+    for (int64_t k = 0; k < count; ++k)
+        if (extrema_host[k] < 0 || extrema_host[k] >= n) return ITD_ERR_INVALID_ARG;
+    const int rc = grow(e, &e->d_cub_e, &e->cub_e_bytes, (size_t)count * sizeof(int32_t));
+    if (rc) return rc;
+    HIP_TRY(e, hipMemcpyAsync(scratch, extrema_host, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    k_narrow_idx<<<(unsigned)((count + 255) / 256), 256, 0, st>>>(scratch, e->d_cub_e, count);
+    *dev_out = e->d_cub_e;
     return ITD_OK;
 }
 }  // namespace
@@ -1954,7 +2014,7 @@ int itd_baseline_extract_cubic_f64(itd_engine *e, const double *x_dev, int64_t n
                                    double *baseline_dev, int64_t *idx_host, void *stream)
 {
     if (!e) return ITD_ERR_INVALID_ARG;
-    return cubic_dev(e, x_dev, n, extrema_dev, idx, baseline_dev, idx_host, stream ? (hipStream_t)stream : e->own_stream);
+    return cubic_dev(e, x_dev, n, extrema_dev, idx, baseline_dev, idx_host, stream_of(e, stream));
 }
 
 int itd_baseline_extract_cubic_f32(itd_engine *e, const float *x_dev, int64_t n, const int32_t *extrema_dev, int64_t idx,
@@ -1963,7 +2023,7 @@ int itd_baseline_extract_cubic_f32(itd_engine *e, const float *x_dev, int64_t n,
     if (!e || !x_dev) return ITD_ERR_INVALID_ARG;
     if (n < 3 || n > e->max_n) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
+    hipStream_t st = stream_of(e, stream);
     int rc = grow(e, &e->d_io_x, &e->io_x_bytes, (size_t)n * sizeof(double));
     if (rc) return rc;
     k_widen_f32<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(x_dev, (double *)e->d_io_x, n);   // float64 arithmetic on the widened signal
@@ -1985,15 +2045,8 @@ int itd_baseline_extract_cubic_host_f64(itd_engine *e, const double *x_host, int
     const int32_t *ek = nullptr;
     if (extrema_host) {
         if (idx < 2 || idx > n - 1) return ITD_ERR_INVALID_ARG;
-        rc = grow(e, &e->d_cub_e, &e->cub_e_bytes, (size_t)(idx + 1) * sizeof(int32_t));
+        rc = stage_extrema(e, extrema_host, idx + 1, n, (int64_t *)(e->d_io_rows + n), st, &ek);
         if (rc) return rc;
-        int64_t *d_e64 = (int64_t *)(e->d_io_rows + n);
-        HIP_TRY(e, hipMemcpyAsync(d_e64, extrema_host, (size_t)(idx + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        // range check on the host copy first: narrowing to int32 must not wrap
-        for (int64_t k = 0; k <= idx; ++k)
-            if (extrema_host[k] < 0 || extrema_host[k] >= n) return ITD_ERR_INVALID_ARG;
-        k_narrow_idx<<<(unsigned)((idx + 1 + 255) / 256), 256, 0, st>>>(d_e64, e->d_cub_e, idx + 1);
-        ek = e->d_cub_e;
     }
     int64_t got = 0;
     const int32_t *knots_dev = nullptr;
@@ -2019,7 +2072,7 @@ int itd_baseline_extract_iq_f64(itd_engine *e, const double *iq_dev, int64_t n, 
     if (n < 3 || n > e->max_n || (reinterpret_cast<uintptr_t>(iq_dev) & 15)) return ITD_ERR_INVALID_ARG;
     if (extrema_dev && (idx < 2 || idx > n - 1)) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
+    hipStream_t st = stream_of(e, stream);
     int rc = grow(e, &e->d_iq_avg, &e->iq_avg_bytes, (size_t)n * sizeof(double));
     if (rc) return rc;
     double *avg = (double *)e->d_iq_avg;
@@ -2027,19 +2080,18 @@ int itd_baseline_extract_iq_f64(itd_engine *e, const double *iq_dev, int64_t n, 
         k_iq_mean<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(iq_dev, n, avg);
         return cubic_dev(e, avg, n, extrema_dev, idx, baseline_dev, idx_host, st);
     }
-    const int n_tiles = (int)tiles_of(n);
-    k_init_state<<<(unsigned)std::min<int64_t>((3 * e->hgsum_third + 255) / 256 + 1, 2048), 256, 0, st>>>(e->d_hstate, 1, e->d_hgsum, 3 * e->hgsum_third, 0);
-    unsigned long long *fw = reinterpret_cast<unsigned long long *>(e->d_lists);
-    k_detect_fast_iq<<<n_tiles, kWave, 0, st>>>(iq_dev, n, n_tiles, e->d_hcounts, fw, e->d_hgsum, e->d_hstate, avg);
+    // the shared scan around a detection kernel of its own (k_detect_fast_iq also writes the mean series)
+    const KnotWs w = helper_ws(e, n);
+    scan_init(w, 1, false, st);
+    k_detect_fast_iq<<<w.n_tiles, kWave, 0, st>>>(iq_dev, n, w.n_tiles, w.counts, reinterpret_cast<unsigned long long *>(w.lists), w.gsum, w.state, avg);
     // the ordered list [lead slot, knots, e[idx] = 0 (itd.cpp's static array at first call)]
-    k_compact_fast<<<dim3(n_tiles, 1), kWave, 0, st>>>(fw, e->d_hcounts, e->d_hgsum, n_tiles, n, e->d_kidx, e->max_n + 2, e->d_total, e->d_hstate, 0,
-                                                       e->d_hcounts + e->max_tiles, 1);
+    scan_compact(w, n, 1, true, 0, nullptr, 0, st);
     int64_t m = 0;
-    rc = fetch_total(e, st, &m);
+    rc = fetch_total(e, w, st, &m);
     if (rc) return rc;
     if (idx_host) *idx_host = m;
     if (m < 2) return ITD_OK;                      // itd.cpp:85-87: the caller's buffer is left alone
-    return cubic_dev(e, avg, n, e->d_kidx + 1, m, baseline_dev, nullptr, st);
+    return cubic_dev(e, avg, n, w.kidx + 1, m, baseline_dev, nullptr, st);
 }
 
 int itd_baseline_extract_iq_host_f64(itd_engine *e, const double *iq_host, int64_t n, const int64_t *extrema_host, int64_t idx,
@@ -2058,13 +2110,8 @@ int itd_baseline_extract_iq_host_f64(itd_engine *e, const double *iq_host, int64
     int64_t *d_e64 = (int64_t *)(e->d_io_rows + n);
     if (extrema_host) {
         if (idx < 2 || idx > n - 1) return ITD_ERR_INVALID_ARG;
-        for (int64_t k = 0; k <= idx; ++k)
-            if (extrema_host[k] < 0 || extrema_host[k] >= n) return ITD_ERR_INVALID_ARG;
-        rc = grow(e, &e->d_cub_e, &e->cub_e_bytes, (size_t)(idx + 1) * sizeof(int32_t));
+        rc = stage_extrema(e, extrema_host, idx + 1, n, d_e64, st, &ek);
         if (rc) return rc;
-        HIP_TRY(e, hipMemcpyAsync(d_e64, extrema_host, (size_t)(idx + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        k_narrow_idx<<<(unsigned)((idx + 1 + 255) / 256), 256, 0, st>>>(d_e64, e->d_cub_e, idx + 1);
-        ek = e->d_cub_e;
     }
     int64_t got = extrema_host ? idx : 0;
     rc = itd_baseline_extract_iq_f64(e, (const double *)e->d_io_x, n, ek, idx, e->d_io_rows, extrema_host ? nullptr : &got, st);
@@ -2072,7 +2119,7 @@ int itd_baseline_extract_iq_host_f64(itd_engine *e, const double *iq_host, int64
     if (idx_out) *idx_out = got;
     if (got >= 2) HIP_TRY(e, hipMemcpyAsync(baseline_host, e->d_io_rows, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
     if (extrema_out_host && !extrema_host && got > 0) {
-        k_widen_idx<<<(unsigned)((got + 255) / 256), 256, 0, st>>>(e->d_kidx + 1, d_e64, got);
+        k_widen_idx<<<(unsigned)((got + 255) / 256), 256, 0, st>>>(helper_ws(e, n).kidx + 1, d_e64, got);
         HIP_TRY(e, hipMemcpyAsync(extrema_out_host, d_e64, (size_t)got * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(e, hipStreamSynchronize(st));
@@ -2097,7 +2144,7 @@ int itd_find_extrema_host_f64(itd_engine *e, const double *s_host, int64_t n, in
     const int64_t idx = m + 2;
     if (idx > n) return ITD_ERR_INVALID_ARG;   // the reference's own array would overflow (every interior sample a crossing)
     int64_t *d_e64 = (int64_t *)e->d_io_rows;
-    k_widen_idx<<<(unsigned)((idx + 255) / 256), 256, 0, st>>>(e->d_kidx, d_e64, idx);
+    k_widen_idx<<<(unsigned)((idx + 255) / 256), 256, 0, st>>>(helper_ws(e, n).kidx, d_e64, idx);
     memset(extrema_host, 0, (size_t)n * sizeof(int64_t));
     HIP_TRY(e, hipMemcpyAsync(extrema_host, d_e64, (size_t)idx * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(e, hipStreamSynchronize(st));
@@ -2111,56 +2158,31 @@ int itd_find_extrema_host_f64(itd_engine *e, const double *s_host, int64_t n, in
 // ---------------------------------------------------------------------------------------------
 }  // extern "C"
 namespace {
+// the knot scan's workspace and, behind it in the same arena, the fit's arrays
 struct SplineWs {
-    int32_t *lists, *counts, *gsum, *kidx, *totals, *tbase;
-    TileRec *recs;
-    SigState *state;
+    KnotWs k;
     double *a, *c;
     SplineMeta *meta;
-    int64_t kidx_stride, lda;
-    int n_tiles, n_groups;
+    int64_t lda;
 };
-int spline_workspace(itd_engine *e, int64_t n, int batch, SplineWs &w)
-{
-    w.n_tiles = (int)tiles_of(n);
-    w.n_groups = groups_of(w.n_tiles);
-    w.kidx_stride = n + 2;
-    w.lda = n + 3;                                   // m <= n + ... data sites: knots <= n - 2, m <= n; 1-based arrays
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t B = (size_t)batch, tiles = B * (size_t)w.n_tiles;
-    const size_t b_lists = al(tiles * T * sizeof(int32_t)), b_counts = al(tiles * sizeof(int32_t)), b_recs = al(tiles * sizeof(TileRec));
-    const size_t b_gsum = al(B * (size_t)w.n_groups * kGsumPitch * sizeof(int32_t)), b_state = al(B * sizeof(SigState));
-    const size_t b_kidx = al(B * (size_t)w.kidx_stride * sizeof(int32_t)), b_tot = al(B * 2 * sizeof(int32_t));
-    const size_t b_a = al(B * 4 * (size_t)w.lda * sizeof(double)), b_c = al(B * (size_t)w.lda * sizeof(double)), b_meta = al(B * sizeof(SplineMeta));
-    const int rc = grow(e, &e->d_sp, &e->sp_bytes, b_lists + b_counts + b_recs + b_gsum + b_state + b_kidx + b_tot + b_a + b_c + b_meta);
-    if (rc) return rc;
-    char *p = (char *)e->d_sp;
-    w.lists = (int32_t *)p; p += b_lists;
-    w.counts = (int32_t *)p; p += b_counts;
-    w.recs = (TileRec *)p; p += b_recs;
-    w.gsum = (int32_t *)p; p += b_gsum;
-    w.state = (SigState *)p; p += b_state;
-    w.kidx = (int32_t *)p; p += b_kidx;
-    w.totals = (int32_t *)p; p += b_tot;
-    w.a = (double *)p; p += b_a;
-    w.c = (double *)p; p += b_c;
-    w.meta = (SplineMeta *)p;
-    return ITD_OK;
-}
 
 // baseline (and optionally rotation) of `batch` contiguous-sample signals; all device pointers; asynchronous on st
 int spline_enqueue(itd_engine *e, const double *x, int64_t n, int batch, int64_t x_stride, int min_extrema, double *base,
                    int64_t base_stride, double *rot, int64_t rot_stride, hipStream_t st, SplineWs &w)
 {
-    int rc = spline_workspace(e, n, batch, w);
+    w.lda = n + 3;                                   // m <= n + ... data sites: knots <= n - 2, m <= n; 1-based arrays
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t B = (size_t)batch, b_a = al(B * 4 * (size_t)w.lda * sizeof(double)), b_c = al(B * (size_t)w.lda * sizeof(double));
+    char *p = nullptr;
+    int rc = knot_workspace(e, &e->d_sp, &e->sp_bytes, n, batch, kWsLists | kWsOrdered, w.k, b_a + b_c + al(B * sizeof(SplineMeta)), &p);
+    if (!rc) rc = knot_scan<double>(e, w.k, x, x_stride, n, batch, (int)kKnots, kScanOrdered, st);
     if (rc) return rc;
-    const dim3 grid_t(w.n_tiles, batch), blk(kWave);
-    const int64_t ge = (int64_t)batch * w.n_groups * kGsumPitch;
-    k_init_state<<<(unsigned)std::min<int64_t>(std::max<int64_t>((ge + 255) / 256, (batch + 255) / 256), 2048), 256, 0, st>>>(w.state, batch, w.gsum, ge);
-    k_detect<double, T><<<grid_t, blk, 0, st>>>(x, x_stride, n, w.n_tiles, (int)kKnots, w.lists, w.counts, w.recs, w.gsum, w.state);
-    k_compact<T><<<grid_t, blk, 0, st>>>(w.lists, w.counts, w.gsum, w.n_tiles, n, w.kidx, w.kidx_stride, w.totals, w.state, -1);
-    k_spline_fit<<<(batch + 63) / 64, 64, 0, st>>>(x, x_stride, n, batch, w.kidx, w.kidx_stride, w.totals, min_extrema, w.a, w.c, w.lda, w.meta);
-    k_spline_eval<<<dim3((unsigned)((n + 255) / 256), batch), 256, 0, st>>>(x, x_stride, n, batch, w.kidx, w.kidx_stride, w.c, w.meta, base,
+    w.a = (double *)p;
+    w.c = (double *)(p + b_a);
+    w.meta = (SplineMeta *)(p + b_a + b_c);
+    const KnotWs &k = w.k;
+    k_spline_fit<<<(batch + 63) / 64, 64, 0, st>>>(x, x_stride, n, batch, k.kidx, k.kidx_stride, k.totals, min_extrema, w.a, w.c, w.lda, w.meta);
+    k_spline_eval<<<dim3((unsigned)((n + 255) / 256), batch), 256, 0, st>>>(x, x_stride, n, batch, k.kidx, k.kidx_stride, w.c, w.meta, base,
                                                                             base_stride, rot, rot_stride);
     HIP_TRY(e, hipGetLastError());
     return ITD_OK;
@@ -2171,8 +2193,9 @@ int spline_enqueue(itd_engine *e, const double *x, int64_t n, int batch, int64_t
 int nak_enqueue(itd_engine *e, const double *x, int64_t n, int batch, int64_t x_stride, int min_extrema, double *base,
                 int64_t base_stride, double *rot, int64_t rot_stride, hipStream_t st, const int32_t **totals_out)
 {
-    DetectWs w;
-    int rc = detect_enqueue(e, x, x_stride, n, batch, (int)kKnots, -1, st, w);     // kidx[b] = [0, knots, n-1]
+    KnotWs w;
+    int rc = knot_workspace(e, &e->d_dw, &e->dw_bytes, n, batch, kWsDetect, w);
+    if (!rc) rc = knot_scan<double>(e, w, x, x_stride, n, batch, (int)kKnots, kScanOrdered, st);     // kidx[b] = [0, knots, n-1]
     if (rc) return rc;
     const int64_t L = n + 2;
     const size_t jobs_b = (((size_t)batch * sizeof(CubicJob)) + 255) & ~(size_t)255;
@@ -2277,19 +2300,6 @@ int nak_small(itd_engine *e, const double *x, int64_t n, int min_extrema, double
     return h[1] ? ITD_ERR_NONFINITE : ITD_OK;
 }
 
-// after spline_enqueue / nak_enqueue: synchronise, fetch the per-signal knot counts, report NaN input
-int spline_finish(itd_engine *e, int batch, const int32_t *totals, int32_t *knots_host, hipStream_t st)
-{
-    std::vector<int32_t> tot((size_t)batch * 2);
-    HIP_TRY(e, hipMemcpyAsync(tot.data(), totals, tot.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(e, hipStreamSynchronize(st));
-    bool nan_in = false;
-    for (int b = 0; b < batch; ++b) {
-        if (knots_host) knots_host[b] = tot[2 * (size_t)b];
-        nan_in = nan_in || tot[2 * (size_t)b + 1] != 0;
-    }
-    return nan_in ? ITD_ERR_NONFINITE : ITD_OK;
-}
 }  // namespace
 extern "C" {
 
@@ -2301,7 +2311,7 @@ int itd_baseline_extract_spline_f64(itd_engine *e, const double *x_dev, int64_t 
     if (n < 3 || n >= (int64_t)INT32_MAX - 8 || batch < 1 || batch > 65535 /* grid.y of its launches */ || min_extrema < 0) return ITD_ERR_INVALID_ARG;
     if (batch > 1 && (x_stride < n || baseline_stride < n || (rot_dev && rot_stride < n))) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
+    hipStream_t st = stream_of(e, stream);
     // few long signals: parallel in the knots; many short rows: one thread per signal, FITPACK's own sweep (bit-level)
     const bool par = e->spline_solver == ITD_SPLINE_PARALLEL || (e->spline_solver == ITD_SPLINE_AUTO && batch < 256 && n >= 1024);
     if (par && batch == 1 && n <= kNakSmallMax) return nak_small(e, x_dev, n, min_extrema, baseline_dev, rot_dev, st, knots_host, nullptr);
@@ -2311,10 +2321,10 @@ int itd_baseline_extract_spline_f64(itd_engine *e, const double *x_dev, int64_t 
     if (par) rc = nak_enqueue(e, x_dev, n, batch, x_stride, min_extrema, baseline_dev, baseline_stride, rot_dev, rot_stride, st, &totals);
     else {
         rc = spline_enqueue(e, x_dev, n, batch, x_stride, min_extrema, baseline_dev, baseline_stride, rot_dev, rot_stride, st, w);
-        totals = w.totals;
+        totals = w.k.totals;
     }
     if (rc) return rc;
-    return spline_finish(e, batch, totals, knots_host, st);
+    return fetch_totals(e, totals, batch, knots_host, st);
 }
 
 int itd_set_spline_solver(itd_engine *e, int32_t solver)
@@ -2347,19 +2357,18 @@ int itd_baseline_extract_spline_host2_f64(itd_engine *e, const double *x_host, i
     HIP_TRY(e, hipMemcpyAsync(d_x, x_host, cnt * sizeof(double), hipMemcpyHostToDevice, st));
     rc = itd_baseline_extract_spline_f64(e, d_x, n, batch, n, min_extrema, d_b, n, rot_host ? d_r : nullptr, n, knots_host, st);
     if (rc) return rc;
-    std::vector<int32_t> tot;
+    KnotWs w;
     if (baseline_knots_host) {
         if (batch > kMaxGridY) return ITD_ERR_INVALID_ARG;
-        DetectWs w;
-        rc = detect_enqueue(e, d_b, n, n, batch, (int)kKnots, -1, st, w, nullptr, 0, false);   // counts only
+        rc = knot_workspace(e, &e->d_dw, &e->dw_bytes, n, batch, kWsDetect, w);
+        if (!rc) rc = knot_scan<double>(e, w, d_b, n, n, batch, (int)kKnots, kScanTotals, st);   // counts only
         if (rc) return rc;
-        tot.resize(2 * (size_t)batch);
-        HIP_TRY(e, hipMemcpyAsync(tot.data(), w.totals, tot.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(e, hipMemcpyAsync(baseline_host, d_b, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
     if (rot_host) HIP_TRY(e, hipMemcpyAsync(rot_host, d_r, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+    // (the call's one synchronisation; a NaN in a baseline is not an error of its own)
+    if (baseline_knots_host) return fetch_totals(e, w.totals, batch, baseline_knots_host, st, false);
     HIP_TRY(e, hipStreamSynchronize(st));
-    if (baseline_knots_host) for (int b = 0; b < batch; ++b) baseline_knots_host[b] = tot[2 * (size_t)b];
     return ITD_OK;
 }
 
@@ -2374,15 +2383,11 @@ int itd_count_knots_host_f64(itd_engine *e, const double *x_host, int64_t n, int
     int rc = grow(e, &e->d_io_x, &e->io_x_bytes, cnt * sizeof(double));
     if (rc) return rc;
     HIP_TRY(e, hipMemcpyAsync(e->d_io_x, x_host, cnt * sizeof(double), hipMemcpyHostToDevice, st));
-    DetectWs w;
-    rc = detect_enqueue(e, (const double *)e->d_io_x, n, n, batch, mode, -1, st, w, nullptr, 0, false);
+    KnotWs w;
+    rc = knot_workspace(e, &e->d_dw, &e->dw_bytes, n, batch, kWsDetect, w);
+    if (!rc) rc = knot_scan<double>(e, w, (const double *)e->d_io_x, n, n, batch, mode, kScanTotals, st);
     if (rc) return rc;
-    std::vector<int32_t> tot(2 * (size_t)batch);
-    HIP_TRY(e, hipMemcpyAsync(tot.data(), w.totals, tot.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(e, hipStreamSynchronize(st));
-    bool nan_in = false;
-    for (int b = 0; b < batch; ++b) { counts_host[b] = tot[2 * (size_t)b]; nan_in = nan_in || tot[2 * (size_t)b + 1]; }
-    return nan_in ? ITD_ERR_NONFINITE : ITD_OK;     // counted under the plain rules: see itd_detect_* for detect_peaks' NaN branch
+    return fetch_totals(e, w.totals, batch, counts_host, st);     // counted under the plain rules: see itd_detect_* for detect_peaks' NaN branch
 }
 
 // ---- MEITD's operators on device-resident signals (MEITD.py:344-534 keeps one signal and its rotations / baselines in a loop:
@@ -2393,25 +2398,20 @@ int itd_count_knots_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t b
     if (!e || !x_dev || !counts_host || n < 3 || batch < 1 || batch > kMaxGridY || mode < 0 || mode > 4) return ITD_ERR_INVALID_ARG;
     if (batch > 1 && x_stride < n) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
-    DetectWs w;
-    int rc = detect_enqueue(e, x_dev, x_stride, n, batch, mode, -1, st, w, nullptr, 0, false);
+    hipStream_t st = stream_of(e, stream);
+    KnotWs w;
+    int rc = knot_workspace(e, &e->d_dw, &e->dw_bytes, n, batch, kWsDetect, w);
+    if (!rc) rc = knot_scan<double>(e, w, x_dev, x_stride, n, batch, mode, kScanTotals, st);
     if (rc) return rc;
-    std::vector<int32_t> tot(2 * (size_t)batch);
-    const bool mapped = 2 * batch <= kSmallWords && small_results(e);       // a few counts: the GPU copies them into the mapped words itself
-    if (mapped) {
-        const int32_t seq = small_next(e);
-        k_copy_words<<<1, 64, 0, st>>>(w.totals, (unsigned long long *)e->d_small, 2 * batch, seq);
-        HIP_TRY(e, hipGetLastError());
-        rc = small_wait(e, seq, 2 * batch, st);
-        if (rc) return rc;
-        for (int i = 0; i < 2 * batch; ++i) tot[(size_t)i] = (int32_t)small_get(e, i);
-    } else {
-        HIP_TRY(e, hipMemcpyAsync(tot.data(), w.totals, tot.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(e, hipStreamSynchronize(st));
-    }
+    if (2 * batch > kSmallWords || !small_results(e)) return fetch_totals(e, w.totals, batch, counts_host, st);
+    // a few counts: the GPU copies them into the mapped words itself
+    const int32_t seq = small_next(e);
+    k_copy_words<<<1, 64, 0, st>>>(w.totals, (unsigned long long *)e->d_small, 2 * batch, seq);
+    HIP_TRY(e, hipGetLastError());
+    rc = small_wait(e, seq, 2 * batch, st);
+    if (rc) return rc;
     bool nan_in = false;
-    for (int b = 0; b < batch; ++b) { counts_host[b] = tot[2 * (size_t)b]; nan_in = nan_in || tot[2 * (size_t)b + 1]; }
+    for (int b = 0; b < batch; ++b) { counts_host[b] = (int32_t)small_get(e, 2 * b); nan_in = nan_in || small_get(e, 2 * b + 1); }
     return nan_in ? ITD_ERR_NONFINITE : ITD_OK;
 }
 
@@ -2422,7 +2422,7 @@ int itd_wpe3_f64(itd_engine *e, const double *x_dev, int64_t n, double *bin_weig
 {
     if (!e || !x_dev || !bin_weights_host || !bin_windows_host || n < 3) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
+    hipStream_t st = stream_of(e, stream);
     const int64_t nw = n - 2;
     const bool exact = nw <= kWpeExactWindows;
     const int64_t seg_len = exact ? nw : kWpeSeg;
@@ -2473,7 +2473,7 @@ int itd_meitd_small_f64(itd_engine *e, double *rows_dev, int64_t n, double wpema
     // (only where the host-driven loop's extractions take the same operator: the parallel-in-knots form of one signal)
     if (!(e->spline_solver == ITD_SPLINE_PARALLEL || (e->spline_solver == ITD_SPLINE_AUTO && n >= 1024))) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
+    hipStream_t st = stream_of(e, stream);
     const int64_t L = n + 2;
     const size_t idx_b = (((size_t)L * sizeof(int32_t)) + 255) & ~(size_t)255, out_b = 256;
     const size_t arr_b = 6 * (size_t)L * sizeof(double);
@@ -2520,7 +2520,7 @@ int itd_meitd_batch_f64(itd_engine *e, double *rows_dev, int64_t n, int32_t batc
     // (the same rule as itd_meitd_small_f64: where the host-driven loop's extractions take the parallel-in-knots form)
     if (!(e->spline_solver == ITD_SPLINE_PARALLEL || (e->spline_solver == ITD_SPLINE_AUTO && n >= 1024))) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
+    hipStream_t st = stream_of(e, stream);
     const int64_t L = n + 2;
     const int grid_max = batch < kMaxGridY ? batch : kMaxGridY;
     const bool xitd = xitd_sums_host != nullptr;
@@ -2612,7 +2612,7 @@ int itd_gather_rows_f64(itd_engine *e, const double *src_dev, int64_t src_elems,
         if (offsets_host[r] < 0 || offsets_host[r] > src_elems - n) return ITD_ERR_INVALID_ARG;
     if (rows == 0) return ITD_OK;
     DevGuard g(e->device);
-    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
+    hipStream_t st = stream_of(e, stream);
     int rc = grow(e, &e->d_rowtab, &e->rowtab_bytes, (size_t)rows * sizeof(int64_t));
     if (rc) return rc;
     HIP_TRY(e, hipMemcpyAsync(e->d_rowtab, offsets_host, (size_t)rows * sizeof(int64_t), hipMemcpyHostToDevice, st));
@@ -2629,7 +2629,7 @@ int itd_wpe_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t order, do
 {
     if (!e || !x_dev || !sums_host || !windows_host || order < 2 || order > kWpeMaxOrder || n < order) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
+    hipStream_t st = stream_of(e, stream);
     const int64_t nw = n - order + 1;
     int nh = 1;
     for (int k = 0; k < order; ++k) nh *= order;
@@ -2675,7 +2675,7 @@ int itd_baseline_extract_spline2_f64(itd_engine *e, const double *x_dev, int64_t
     if (n < 3 || n >= (int64_t)INT32_MAX - 8 || batch < 1 || batch > 65535 || min_extrema < 0) return ITD_ERR_INVALID_ARG;
     if (batch > 1 && (x_stride < n || baseline_stride < n || (rot_dev && rot_stride < n))) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
+    hipStream_t st = stream_of(e, stream);
     const bool par = e->spline_solver == ITD_SPLINE_PARALLEL || (e->spline_solver == ITD_SPLINE_AUTO && batch < 256 && n >= 1024);
     if (par && batch == 1 && n <= kNakSmallMax) return nak_small(e, x_dev, n, min_extrema, baseline_dev, rot_dev, st, knots_host, baseline_knots_host);
     const int32_t *totals = nullptr;
@@ -2684,22 +2684,23 @@ int itd_baseline_extract_spline2_f64(itd_engine *e, const double *x_dev, int64_t
     if (par) rc = nak_enqueue(e, x_dev, n, batch, x_stride, min_extrema, baseline_dev, baseline_stride, rot_dev, rot_stride, st, &totals);
     else {
         rc = spline_enqueue(e, x_dev, n, batch, x_stride, min_extrema, baseline_dev, baseline_stride, rot_dev, rot_stride, st, w);
-        totals = w.totals;
+        totals = w.k.totals;
     }
     if (rc) return rc;
-    if (!baseline_knots_host) return spline_finish(e, batch, totals, knots_host, st);
+    if (!baseline_knots_host) return fetch_totals(e, totals, batch, knots_host, st);
     // (the extraction's totals are read before the counting launches reuse the detection workspace)
-    std::vector<int32_t> tot((size_t)batch * 2), btot((size_t)batch * 2);
+    std::vector<int32_t> tot((size_t)batch * 2);
     HIP_TRY(e, hipMemcpyAsync(tot.data(), totals, tot.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    DetectWs dw;
-    rc = detect_enqueue(e, baseline_dev, baseline_stride, n, batch, (int)kKnots, -1, st, dw, nullptr, 0, false);
+    KnotWs dw;
+    rc = knot_workspace(e, &e->d_dw, &e->dw_bytes, n, batch, kWsDetect, dw);
+    if (!rc) rc = knot_scan<double>(e, dw, baseline_dev, baseline_stride, n, batch, (int)kKnots, kScanTotals, st);
     if (rc) return rc;
-    HIP_TRY(e, hipMemcpyAsync(btot.data(), dw.totals, btot.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(e, hipStreamSynchronize(st));
+    // (one synchronisation for both; the NaN flags that count are the extraction's)
+    rc = fetch_totals(e, dw.totals, batch, baseline_knots_host, st, false);
+    if (rc) return rc;
     bool nan_in = false;
     for (int b = 0; b < batch; ++b) {
         if (knots_host) knots_host[b] = tot[2 * (size_t)b];
-        baseline_knots_host[b] = btot[2 * (size_t)b];
         nan_in = nan_in || tot[2 * (size_t)b + 1] != 0;
     }
     return nan_in ? ITD_ERR_NONFINITE : ITD_OK;
@@ -2710,7 +2711,7 @@ int itd_subtract_f64(itd_engine *e, const double *a_dev, const double *b_dev, do
     if (!e || !a_dev || !b_dev || !out_dev || count < 0) return ITD_ERR_INVALID_ARG;
     if (!count) return ITD_OK;
     DevGuard g(e->device);
-    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
+    hipStream_t st = stream_of(e, stream);
     k_subtract<<<(unsigned)((count + 255) / 256), 256, 0, st>>>(a_dev, b_dev, out_dev, count);
     HIP_TRY(e, hipGetLastError());
     return ITD_OK;
@@ -2722,7 +2723,7 @@ int itd_copy(itd_engine *e, void *dst, const void *src, int64_t bytes, int32_t k
 {
     if (!e || !dst || (!src && kind != 3) || bytes < 0 || kind < 0 || kind > 3) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
+    hipStream_t st = stream_of(e, stream);
     if (bytes) {
         if (kind == 3) HIP_TRY(e, hipMemsetAsync(dst, 0, (size_t)bytes, st));
         else HIP_TRY(e, hipMemcpyAsync(dst, src, (size_t)bytes, kind == 0 ? hipMemcpyDeviceToHost : (kind == 1 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice), st));
@@ -2738,7 +2739,7 @@ int itd_crossways_f64(itd_engine *e, const double *img_dev, int32_t planes, int3
 {
     if (!e || !img_dev || !out_dev || planes < 1 || rows < 3 || cols < 3) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
+    hipStream_t st = stream_of(e, stream);
     const size_t cnt = (size_t)planes * rows * cols;
     int rc = grow(e, &e->d_sp2, &e->sp2_bytes, 3 * cnt * sizeof(double));
     if (rc) return rc;
@@ -2755,7 +2756,7 @@ int itd_crossways_f64(itd_engine *e, const double *img_dev, int32_t planes, int3
             const int nb = (int)std::min<int64_t>(kMaxGridY, sigs - s0);
             const int rc2 = spline_enqueue(e, in + s0 * len, len, nb, len, min_extrema, out + s0 * len, len, nullptr, 0, st, w);
             if (rc2) return rc2;
-            k_or_nan_flags<<<(nb + 255) / 256, 256, 0, st>>>(w.totals, nb, e->d_flag);
+            k_or_nan_flags<<<(nb + 255) / 256, 256, 0, st>>>(w.k.totals, nb, e->d_flag);
         }
         return (int)ITD_OK;
     };
@@ -2804,7 +2805,7 @@ int itd_instantaneous_f64(itd_engine *e, const double *rot_dev, int64_t n, doubl
     if (!e || !rot_dev || (!amp_dev && !phase_dev && !freq_dev)) return ITD_ERR_INVALID_ARG;
     if (n < 3 || n > e->max_n) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
+    hipStream_t st = stream_of(e, stream);
     int64_t m = 0;
     int rc = cubic_detect(e, rot_dev, n, (int)kZeroCross, &m, st);   // ordered zero crossings in d_kidx[1..m]
     if (rc) return rc;
@@ -2814,7 +2815,7 @@ int itd_instantaneous_f64(itd_engine *e, const double *rot_dev, int64_t n, doubl
     HIP_TRY(e, hipMemsetAsync(amp_bits, 0, (size_t)(m + 1) * sizeof(unsigned long long), st));
     static_assert(kTfeTile == T, "k_compact's per-tile bases are per T samples");
     const unsigned blocks = (unsigned)tiles_of(n);
-    const int32_t *tile_base = e->d_hcounts + e->max_tiles;   // crossings in front of every tile (k_compact)
+    const int32_t *tile_base = helper_ws(e, n).tbase;   // crossings in front of every tile (k_compact)
     k_tfe_amplitude<<<blocks, 64, 0, st>>>(rot_dev, n, tile_base, amp_bits);
     k_tfe_phase<<<blocks, 64, 0, st>>>(rot_dev, n, tile_base, amp_bits, amp_dev, phase_dev, freq_dev);
     HIP_TRY(e, hipGetLastError());

@@ -32,33 +32,6 @@ __global__ void k_info_from_jobs(const CubicJob *__restrict__ jobs, int job_stri
     info[b] = j.status == 0 ? j.idx : -j.status;
 }
 
-// workspace of the batched tier-1 extraction: counts / records of two levels, three group-sum buffers, the signals' states
-struct BatchWs {
-    int32_t *counts, *gsum;
-    TileRec *recs;
-    SigState *state;
-    int64_t half, third;
-    int n_tiles, n_groups;
-};
-int batch_workspace(itd_engine *e, int64_t n, int nb, BatchWs &w)
-{
-    w.n_tiles = (int)tiles_of(n);
-    w.n_groups = groups_of(w.n_tiles);
-    w.half = (int64_t)nb * w.n_tiles;
-    w.third = (int64_t)nb * w.n_groups * kGsumPitch;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_counts = al(2 * (size_t)w.half * sizeof(int32_t)), b_recs = al(2 * (size_t)w.half * sizeof(TileRec));
-    const size_t b_gsum = al(3 * (size_t)w.third * sizeof(int32_t)), b_state = al((size_t)nb * sizeof(SigState));
-    const int rc = grow(e, &e->d_bw, &e->bw_bytes, b_counts + b_recs + b_gsum + b_state);
-    if (rc) return rc;
-    char *p = (char *)e->d_bw;
-    w.counts = (int32_t *)p; p += b_counts;
-    w.recs = (TileRec *)p; p += b_recs;
-    w.gsum = (int32_t *)p; p += b_gsum;
-    w.state = (SigState *)p;
-    return ITD_OK;
-}
-
 // one tier-1 extraction (ITD.py:79-121) of every signal of the batch: the record-driven level-0 pair (k_detect, k_extract with
 // keep_nan: the baseline as computed, the NaN -> +inf write belongs to the driver's stop test).  status (optional): |= 2 when a
 // signal holds a NaN (its results then follow the plain rules, not detect_peaks' NaN branch)
@@ -66,19 +39,16 @@ int extract_batch(itd_engine *e, const double *x, int64_t n, int32_t batch, int6
                   double *base, int64_t base_stride, int32_t *info, int32_t *status, hipStream_t st)
 {
     const int chunk = std::min<int32_t>(batch, kMaxGridY);
-    BatchWs w;
-    int rc = batch_workspace(e, n, chunk, w);
+    KnotWs w;   // counts / records of two levels, three group-sum buffers, the signals' states
+    int rc = knot_workspace(e, &e->d_bw, &e->bw_bytes, n, chunk, kWsExtract, w);
     if (rc) return rc;
     for (int b0 = 0; b0 < batch; b0 += chunk) {
         const int nb = std::min(chunk, batch - b0);
-        const int64_t ge = 3 * w.third;
-        k_init_state<<<(unsigned)std::min<int64_t>(std::max<int64_t>((ge + 255) / 256, (nb + 255) / 256), 2048), 256, 0, st>>>(w.state, nb, w.gsum, ge);
         const double *xc = x + (int64_t)b0 * x_stride;
         // (group-sum buffers are laid out for `chunk` signals; a shorter last chunk uses the front of each)
-        k_detect<double, T><<<dim3(w.n_tiles, nb), kWave, 0, st>>>(xc, x_stride, n, w.n_tiles, (int)kKnots, nullptr, w.counts, w.recs, w.gsum, w.state);
-        k_extract<double, T, false, kRankCap0, kTilesPerWave><<<dim3((w.n_tiles + kTilesPerWave - 1) / kTilesPerWave, nb), kWave, 0, st>>>(
-            xc, x_stride, n, w.n_tiles, nb, w.counts, w.counts + w.half, w.recs, w.recs + w.half, w.gsum, w.gsum + w.third, w.gsum + 2 * w.third,
-            rot + (int64_t)b0 * rot_stride, rot_stride, base + (int64_t)b0 * base_stride, base_stride, w.state, 0, 1);
+        rc = knot_scan<double>(e, w, xc, x_stride, n, nb, (int)kKnots, kScanOnly, st);
+        if (rc) return rc;
+        extract_level0<double>(w, xc, x_stride, n, nb, rot + (int64_t)b0 * rot_stride, rot_stride, base + (int64_t)b0 * base_stride, base_stride, st);
         if (info || status) k_info_from_states<<<(nb + 255) / 256, 256, 0, st>>>(w.state, nb, info ? info + b0 : nullptr, status);
     }
     HIP_TRY(e, hipGetLastError());
@@ -131,8 +101,9 @@ int stream_emit(itd_stream *s, int64_t w0, int64_t wl, int64_t lo, int64_t hi, d
     // the window's extrema (itd.cpp:33 "re-assess extrema in the entire buffer every iteration"): channel 0's for everybody
     // (itd.cpp:40-44) or every channel's own
     const int n_lists = s->shared ? 1 : C;
-    DetectWs w;
-    int rc = detect_enqueue(e, win, ring_stride, wl, n_lists, (int)kCpp, 0, st, w);
+    KnotWs w;
+    int rc = knot_workspace(e, &e->d_dw, &e->dw_bytes, wl, n_lists, kWsDetect, w);
+    if (!rc) rc = knot_scan<double>(e, w, win, ring_stride, wl, n_lists, (int)kCpp, kScanOrdered, st, 0);
     if (rc) return rc;
     k_stream_select<<<(n_lists + 63) / 64, 64, 0, st>>>(w.kidx, w.kidx_stride, w.totals, n_lists, (int)lo, (int)hi, s->margin, s->jobs, s->d_status);
     CubicArgs A;
@@ -184,8 +155,7 @@ int itd_baseline_extract_batch_f64(itd_engine *e, const double *x_dev, int64_t n
     if (n < 3 || n >= (int64_t)INT32_MAX - 65536 || batch < 1) return ITD_ERR_INVALID_ARG;
     if (batch > 1 && (x_stride < n || rot_stride < n || base_stride < n)) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    return extract_batch(e, x_dev, n, batch, x_stride, rot_dev, rot_stride, base_dev, base_stride, info_dev, nullptr,
-                         stream ? (hipStream_t)stream : e->own_stream);
+    return extract_batch(e, x_dev, n, batch, x_stride, rot_dev, rot_stride, base_dev, base_stride, info_dev, nullptr, stream_of(e, stream));
 }
 
 int itd_detect_batch_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t batch, int64_t x_stride, int32_t mode, int32_t *idx_dev,
@@ -195,9 +165,10 @@ int itd_detect_batch_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t 
     if (n < 3 || n >= (int64_t)INT32_MAX - 65536 || batch < 1 || batch > kMaxGridY || mode < 0 || mode > 4) return ITD_ERR_INVALID_ARG;
     if (batch > 1 && (x_stride < n || (idx_dev && idx_stride < n - 2))) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
-    DetectWs w;
-    const int rc = detect_enqueue(e, x_dev, x_stride, n, batch, mode, -1, st, w, idx_dev, idx_stride, idx_dev != nullptr);
+    hipStream_t st = stream_of(e, stream);
+    KnotWs w;
+    int rc = knot_workspace(e, &e->d_dw, &e->dw_bytes, n, batch, kWsDetect, w);
+    if (!rc) rc = knot_scan<double>(e, w, x_dev, x_stride, n, batch, mode, idx_dev ? kScanOrdered : kScanTotals, st, -1, false, nullptr, idx_dev, idx_stride);
     if (rc) return rc;
     if (info_dev) k_info_from_totals<<<(batch + 255) / 256, 256, 0, st>>>(w.totals, batch, info_dev);
     HIP_TRY(e, hipGetLastError());
@@ -213,7 +184,7 @@ int itd_baseline_extract_cubic_batch_f64(itd_engine *e, const double *x_dev, int
     if (batch > 1 && (x_stride < n || baseline_stride < n)) return ITD_ERR_INVALID_ARG;
     if (extrema_dev && (idx < 2 || idx > n - 1 || (extrema_stride != 0 && extrema_stride < idx + 1))) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
+    hipStream_t st = stream_of(e, stream);
     const CubicJob *jobs = nullptr;
     int n_jobs = 0;
     const int rc = cubic_batch(e, x_dev, n, batch, x_stride, extrema_dev, extrema_stride, idx, baseline_dev, baseline_stride, st, &jobs, &n_jobs);
@@ -300,8 +271,7 @@ int itd_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_strid
     if (s->C > 1 && (in_stride < s->L || (baseline_dev && baseline_stride < s->L) || (rot_dev && rot_stride < s->L))) return ITD_ERR_INVALID_ARG;
     if (s->pushed >= 1 && !baseline_dev) return ITD_ERR_INVALID_ARG;      // this push emits a block
     DevGuard g(s->eng->device);
-    return stream_push(s, block_dev, in_stride, baseline_dev, baseline_stride, rot_dev, rot_stride, emitted,
-                       stream ? (hipStream_t)stream : s->eng->own_stream);
+    return stream_push(s, block_dev, in_stride, baseline_dev, baseline_stride, rot_dev, rot_stride, emitted, stream_of(s->eng, stream));
 }
 
 int itd_stream_flush_f64(itd_stream *s, double *baseline_dev, int64_t baseline_stride, double *rot_dev, int64_t rot_stride,
@@ -311,7 +281,7 @@ int itd_stream_flush_f64(itd_stream *s, double *baseline_dev, int64_t baseline_s
     if (s->pushed >= 1 && !baseline_dev) return ITD_ERR_INVALID_ARG;
     if (s->C > 1 && ((baseline_dev && baseline_stride < s->L) || (rot_dev && rot_stride < s->L))) return ITD_ERR_INVALID_ARG;
     DevGuard g(s->eng->device);
-    return stream_flush(s, baseline_dev, baseline_stride, rot_dev, rot_stride, emitted, stream ? (hipStream_t)stream : s->eng->own_stream);
+    return stream_flush(s, baseline_dev, baseline_stride, rot_dev, rot_stride, emitted, stream_of(s->eng, stream));
 }
 
 int itd_stream_status(itd_stream *s, int32_t *status)
@@ -491,8 +461,8 @@ int levels_seq_alloc(itd_stream *s)
         return hrc == hipErrorOutOfMemory ? ITD_ERR_NOMEM : fail_hip(s->eng, hrc, "hipMalloc(levels stream scratch)");
     }
     poison(s->scr, bytes);
-    BatchWs w;
-    const int rc = batch_workspace(s->eng, 3 * s->L, std::min<int32_t>(s->C, kMaxGridY), w);
+    KnotWs w;
+    const int rc = knot_workspace(s->eng, &s->eng->d_bw, &s->eng->bw_bytes, 3 * s->L, std::min<int32_t>(s->C, kMaxGridY), kWsExtract, w);
     if (rc) return rc;
     HIP_TRY(s->eng, hipDeviceSynchronize());
     return ITD_OK;
@@ -591,8 +561,7 @@ int itd_levels_stream_push_f64(itd_stream *s, const double *block_dev, int64_t i
     if (s->t >= s->M + 1 && !rows_dev) return ITD_ERR_INVALID_ARG;          // this push emits a block
     if (!levels_rows_ok(s, rows_dev, row_stride, chan_stride)) return ITD_ERR_INVALID_ARG;
     DevGuard g(s->eng->device);
-    return levels_push(s, block_dev, in_stride, rows_dev, row_stride, chan_stride, exact_dev, emitted,
-                       stream ? (hipStream_t)stream : s->eng->own_stream);
+    return levels_push(s, block_dev, in_stride, rows_dev, row_stride, chan_stride, exact_dev, emitted, stream_of(s->eng, stream));
 }
 
 int itd_levels_stream_flush_f64(itd_stream *s, double *rows_dev, int64_t row_stride, int64_t chan_stride, uint8_t *exact_dev,
@@ -602,7 +571,7 @@ int itd_levels_stream_flush_f64(itd_stream *s, double *rows_dev, int64_t row_str
     if (itd_stream_blocks(s) > 0 && !rows_dev) return ITD_ERR_INVALID_ARG;  // this flush emits a block
     if (!levels_rows_ok(s, rows_dev, row_stride, chan_stride)) return ITD_ERR_INVALID_ARG;
     DevGuard g(s->eng->device);
-    return levels_flush(s, rows_dev, row_stride, chan_stride, exact_dev, emitted, stream ? (hipStream_t)stream : s->eng->own_stream);
+    return levels_flush(s, rows_dev, row_stride, chan_stride, exact_dev, emitted, stream_of(s->eng, stream));
 }
 
 }  // extern "C"

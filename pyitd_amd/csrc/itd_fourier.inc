@@ -166,7 +166,7 @@ int select_entry(itd_engine *e, const double *rows_dev, int64_t n, int64_t rows,
     if (n < 4 || n >= (int64_t)INT32_MAX - 65536 || rows < 1) return ITD_ERR_INVALID_ARG;
     if (rows > 1 && (row_stride < n || mode_stride < n)) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
+    hipStream_t st = stream_of(e, stream);
     int32_t *rec = rec_dev;
     if (!rec) {
         const int rc = grow(e, &e->d_fft_rec, &e->fft_rec_bytes, (size_t)rows * 32);
