@@ -34,6 +34,7 @@
 #include "itd_wpe.hpp"
 #include "itd_meitd.hpp"
 #include "itd_policy.hpp"
+#include "itd_memory.hpp"
 #include "itd_fft.hpp"
 
 #ifndef ITD_TILE
@@ -170,19 +171,19 @@ struct itd_engine {
     int64_t max_tiles = 0;
     hipStream_t own_stream = nullptr;
     // workspace
-    int32_t *d_lists = nullptr;    // [tiles][T]  per-tile knot lists, written only for the API helpers (k_compact)
-    int32_t *d_counts = nullptr;   // [2][batch][tiles]  knots per tile, double buffered by level parity
-    TileRec *d_recs = nullptr;     // [2][batch][tiles]  head/tail knot records, double buffered by level parity
+    Buf<int32_t> d_lists;          // [tiles][T]  per-tile knot lists, written only for the API helpers (k_compact)
+    Buf<int32_t> d_counts;         // [2][batch][tiles]  knots per tile, double buffered by level parity
+    Buf<TileRec> d_recs;           // [2][batch][tiles]  head/tail knot records, double buffered by level parity
     int64_t tiles_half = 0;        // elements per counts/recs buffer
-    int32_t *d_gsum = nullptr;     // [2][3][batch][groups*pitch]: per-64-tile knot totals, rotating by level % 3; two sets (below)
+    Buf<int32_t> d_gsum;           // [2][3][batch][groups*pitch]: per-64-tile knot totals, rotating by level % 3; two sets (below)
     int64_t gsum_third = 0;        // elements per buffer
-    int32_t *d_kidx = nullptr;     // [max_n + 2]  ordered knot indices for the API helpers (single signal)
-    int32_t *d_total = nullptr;    // [1] knot total written by k_compact
-    double *d_pp = nullptr;        // [batch][3][pp_pitch] rotating baselines (slot = level % 3)
+    Buf<int32_t> d_kidx;           // [max_n + 2]  ordered knot indices for the API helpers (single signal)
+    Buf<int32_t> d_total;          // [1] knot total written by k_compact
+    Buf<double> d_pp;              // [batch][3][pp_pitch] rotating baselines (slot = level % 3)
     int64_t pp_pitch = 0;          // elements between consecutive slots: max_n + kSlotPad (breaks the power-of-two distance)
-    SigState *d_state = nullptr;   // [2][batch]
-    SigState *h_state = nullptr;   // pinned
-    char *h_kf = nullptr;          // pinned: the heads of the fused levels' KfSig (kKfSigHead bytes per signal), on demand
+    Buf<SigState> d_state;         // [2][batch]
+    Pinned<SigState> h_state;      // [batch]
+    Pinned<char> h_kf;             // the heads of the fused levels' KfSig (kKfSigHead bytes per signal), on demand
     // Per-signal states and group sums exist twice.  A decomposition works on the set the previous one did not use, and its last
     // launch (k_finalize) re-initialises the other set for the call after it: no initialising launch in front of a decomposition,
     // and the summary of the last call stays readable.  dirty_*: the leading part of a set that may not be in its initial state
@@ -193,77 +194,73 @@ struct itd_engine {
     // workspace of the single-level helpers (itd_detect_*, itd_baseline_extract_*): one signal, apart from the
     // decomposition's, so a helper call never disturbs a decomposition that is still in flight or not yet summarised;
     // with d_lists, d_kidx and d_total the fixed buffers that helper_ws() presents as a KnotWs (no allocation after create)
-    int32_t *d_hcounts = nullptr;  // [2][tiles]
-    TileRec *d_hrecs = nullptr;    // [2][tiles]
-    int32_t *d_hgsum = nullptr;    // [3][groups*pitch]
+    Buf<int32_t> d_hcounts;        // [2][tiles]
+    Buf<TileRec> d_hrecs;          // [2][tiles]
+    Buf<int32_t> d_hgsum;          // [3][groups*pitch]
     int64_t hgsum_third = 0;
-    SigState *d_hstate = nullptr;  // [1]
+    Buf<SigState> d_hstate;        // [1]
     int32_t chunk = 0;             // signals per launch sequence of a batched decomposition (0 = automatic, see enqueue_decompose)
     int32_t batch_streams = 2;     // chunks of a batch rotate over this many streams (itd_set_batch_streams): 1 .. kMaxBatchStreams
     hipStream_t aux_stream[3] = {nullptr, nullptr, nullptr};   // the others besides the caller's, created on demand
     hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
 
     FormPolicy policy;              // which form each call takes, what the summaries have taught (itd_policy.hpp)
-    bool resident_attr[12] = {};
-    bool nak_small_attr = false;    // hipFuncSetAttribute done for k_nak_small<true>
-    bool meitd_attr[2] = {};        // ... for k_meitd_small<false / true>
-    bool meitd_batch_attr[2] = {};  // ... for k_meitd_batch<false / true>
+    const void *lds_fn[24] = {}; int lds_fns = 0;   // the kernel instances granted their dynamic LDS on this engine (allow_lds)
     // a few scalars per call come back to the host in MEITD's operators (counts, six sums): 256 bytes of pinned host memory that the
     // GPU writes directly (mapped, coherent) — no copy behind the launch, just the stream's synchronisation (a pageable destination
     // cost ~15 us per call: 110 calls per MEITD run)
-    void *h_small = nullptr, *d_small = nullptr;
+    Pinned<void> h_small; void *d_small = nullptr;   // (d_small: its device address)
     int32_t small_seq = 0;          // the number of the call whose scalars are awaited: every word of a result carries it in its high half (small_put)
-    int32_t resident_window = 0;    // segments per pass over a level's ranks (itd_set_resident_window; 0 = automatic)   // hipFuncSetAttribute done per kernel instance
+    int32_t resident_window = 0;    // segments per pass over a level's ranks (itd_set_resident_window; 0 = automatic)
     // the fused sparse levels (itd_knotfirst.hpp): workspace (allocated at first use), mode, first fused level
-    void *d_kf = nullptr; size_t kf_bytes = 0;
-    std::vector<void *> kf_retired;  // earlier, smaller workspaces: a captured graph may still hold their pointers — kept until the engine is destroyed
+    Buf<void> d_kf;
+    std::vector<Buf<void>> kf_retired;   // earlier, smaller workspaces: a captured graph may still hold their pointers — kept until the engine is destroyed
     KfWs kf{};                       // pointers into d_kf, for signal 0
     // device-visible validity / device-side repair (itd_set_valid_flags, itd_set_device_repair)
     int32_t *valid_dev = nullptr;                    // the caller's [batch] words, written behind every decomposition; NULL = none
     bool device_repair = false;
-    int32_t *d_need = nullptr;                       // [max_batch] which signals the repair's launches work on
-    int32_t *d_valid_own = nullptr;                  // [max_batch] (the repair needs the words even if the caller gave none)
+    Buf<int32_t> d_need;                             // [max_batch] which signals the repair's launches work on
+    Buf<int32_t> d_valid_own;                        // [max_batch] (the repair needs the words even if the caller gave none)
     bool last_device_repair = false;                 // the last call carried its repair: the summary has nothing to repeat
     int64_t kf_resident_wgs = 0;                     // knot-side workgroups the device holds at once (occupancy query at creation of the workspace)
     // fault injection into the fused levels' workspace (itd_debug_kf_fault; tests only): kind < 0 = none
     int32_t fault_kind = -1, fault_level = 0, fault_where = 0, fault_slot = 0, fault_delta = 0;
     int32_t fault_sig = 0;         // the signal of the batch the fault lands in (itd_debug_kf_fault_signal)
     int32_t spline_solver = ITD_SPLINE_AUTO;   // FITPACK flavour: serial bit-level sweep or the parallel moment form (itd_set_spline_solver)
-    int64_t ws_bytes = 0;
+    int64_t ws_total = 0;          // itd_engine_workspace_bytes: the create-time buffers and every fused-levels workspace, retired ones included
     // host-convenience staging (grow only)
-    void *d_cub = nullptr; size_t cub_bytes = 0;          // cubic variant: per-signal jobs + K, bf, b (3 arrays of idx+2 doubles each);
+    Buf<void> d_cub;                                      // cubic variant: per-signal jobs + K, bf, b (3 arrays of idx+2 doubles each);
                                                           // also staging of the NaN-input helper path and the instantaneous step
-    int32_t *d_cub_e = nullptr; size_t cub_e_bytes = 0;   // cubic variant: the caller's knots narrowed to int32 (host form)
-    int32_t *d_flag = nullptr;                            // [1] device-side argument check
+    Buf<int32_t> d_cub_e;                                 // cubic variant: the caller's knots narrowed to int32 (host form)
+    Buf<int32_t> d_flag;                                  // [1] device-side argument check
     // three arenas a KnotWs is carved from (knot_workspace), apart so that operators used in one call do not share one
-    void *d_dw = nullptr; size_t dw_bytes = 0;            // batched knot detection: cubic batch, detect batch, counts, streams
-    void *d_bw = nullptr; size_t bw_bytes = 0;            // batched single-level tier-1 extraction (a k_extract behind the scan)
-    void *d_sp = nullptr; size_t sp_bytes = 0;            // spline flavour (batched): the scan's parts, fit arrays, metadata
-    double *d_sp2 = nullptr; size_t sp2_bytes = 0;        // 2-D consumers: three planes of scratch
-    void *d_mb = nullptr; size_t mb_bytes = 0;            // MEITD over a batch (itd_meitd_batch_f64): per-signal results, solver arrays, logs, XITD sums
-    int64_t *d_rowtab = nullptr; size_t rowtab_bytes = 0; // itd_gather_rows_f64: the row table
-    char *d_wpe = nullptr; size_t wpe_bytes = 0;          // weighted permutation entropy: the segments' sums
-    void *d_io_x = nullptr; size_t io_x_bytes = 0;
-    void *d_iq_avg = nullptr; size_t iq_avg_bytes = 0;   // the I/Q form of the cubic operator: the components' mean series
-    double *d_io_rows = nullptr; size_t io_rows_bytes = 0;
-    double *d_io_bases = nullptr; size_t io_bases_bytes = 0;
-    void *h_pin[2] = {nullptr, nullptr};   // host-form calls: pinned bounce buffers of the pipelined device -> host copy (copy_to_host)
+    Buf<void> d_dw;                                       // batched knot detection: cubic batch, detect batch, counts, streams
+    Buf<void> d_bw;                                       // batched single-level tier-1 extraction (a k_extract behind the scan)
+    Buf<void> d_sp;                                       // spline flavour (batched): the scan's parts, fit arrays, metadata
+    Buf<double> d_sp2;                                    // 2-D consumers: three planes of scratch
+    Buf<void> d_mb;                                       // MEITD over a batch (itd_meitd_batch_f64): per-signal results, solver arrays, logs, XITD sums
+    Buf<int64_t> d_rowtab;                                // itd_gather_rows_f64: the row table
+    Buf<char> d_wpe;                                      // weighted permutation entropy: the segments' sums
+    Buf<void> d_io_x;
+    Buf<void> d_iq_avg;                                  // the I/Q form of the cubic operator: the components' mean series
+    Buf<double> d_io_rows;
+    Buf<double> d_io_bases;
+    Pinned<void> h_pin[2];                 // host-form calls: pinned bounce buffers of the pipelined device -> host copy (copy_to_host)
     bool host_keep_bases = false;      // itd_set_host_keep_baselines: host-form calls leave their baselines in d_io_bases
     int64_t kept_n = 0; int32_t kept_nb = -1;   // what itd_get_last_baselines_host can still deliver (-1: nothing)
     // the FFT and the ITD-Fourier cascade (itd_fft.hpp, itd_fourier.inc), all grown on demand
-    bool fft_attr = false;                                // hipFuncSetAttribute done for k_fft_lds
-    void *d_fft_x = nullptr; size_t fft_x_bytes = 0;      // the selectors' spectra
-    void *d_fft_y = nullptr; size_t fft_y_bytes = 0;      // four-step: the column transforms
-    void *d_fft_a = nullptr; size_t fft_a_bytes = 0;      // Bluestein: the padded chirped rows
-    void *d_fft_b = nullptr; size_t fft_b_bytes = 0;      // Bluestein: the chirp's spectrum for fft_chirp_n
+    Buf<void> d_fft_x;                                    // the selectors' spectra
+    Buf<void> d_fft_y;                                    // four-step: the column transforms
+    Buf<void> d_fft_a;                                    // Bluestein: the padded chirped rows
+    Buf<void> d_fft_b;                                    // Bluestein: the chirp's spectrum for fft_chirp_n
     int64_t fft_chirp_n = 0;
-    void *d_fft_rec = nullptr; size_t fft_rec_bytes = 0;  // selector records when the caller wants none
-    void *d_fc = nullptr; size_t fc_bytes = 0;            // cascade: signals, band scratch, rows, modes, records, flags
-    void *d_fio = nullptr; size_t fio_bytes = 0;          // cascade host form: its input, rows and accumulators (not d_io_*)
-    double *d_fmodes = nullptr; size_t fmodes_bytes = 0;  // cascade: the mode arena of the last call (non-lean)
+    Buf<void> d_fft_rec;                                  // selector records when the caller wants none
+    Buf<void> d_fc;                                       // cascade: signals, band scratch, rows, modes, records, flags
+    Buf<void> d_fio;                                      // cascade host form: its input, rows and accumulators (not d_io_*)
+    Buf<double> d_fmodes;                                 // cascade: the mode arena of the last call (non-lean)
     int64_t fmodes_count = 0, fmodes_n = 0; bool fmodes_lean = false;
     std::vector<int32_t> frec;                            // cascade: [fmodes_count][8] records of the last call
-    int32_t *d_fplan = nullptr; size_t fplan_bytes = 0;   // cascade: the band plan's knot lists (int32), for fplan_n / fplan_sr
+    Buf<int32_t> d_fplan;                                 // cascade: the band plan's knot lists (int32), for fplan_n / fplan_sr
     int64_t fplan_n = 0; double fplan_sr = 0.0;
     std::vector<int64_t> fplan_host, fplan_idx;
     // last run
@@ -286,19 +283,6 @@ struct itd_engine {
 };
 
 namespace {
-
-// PYITD_POISON=1 (a debugging switch of the environment, read once): every workspace the library allocates is filled with 0xFF bytes
-// (NaNs / -1) before its first use, so that a kernel that reads memory nobody wrote fails on every run instead of once in ten
-// thousand — what tools/stream_fuzz.py and the suite are run under in the evidence session.  Off: allocations cost what they cost.
-inline bool poison_on()
-{
-    static const bool on = [] { const char *v = getenv("PYITD_POISON"); return v && *v && *v != '0'; }();
-    return on;
-}
-inline void poison(void *p, size_t bytes)
-{
-    if (p && bytes && poison_on()) { (void)hipMemset(p, 0xFF, bytes); (void)hipDeviceSynchronize(); }   // (a fill on the null stream is not ordered with the engines' non-blocking streams)
-}
 
 int fail_hip(itd_engine *e, hipError_t rc, const char *what)
 {
@@ -375,8 +359,7 @@ int ensure_kf_ws(itd_engine *e, int tpw, bool may_allocate)
         // a larger workspace.  The old one is NOT freed: a hipGraph captured on this engine has its pointers baked into the fused
         // levels' launches and may be replayed at any time (its launches stay self-consistent: geometry and pointers travel
         // together as kernel arguments) — it is retired until itd_engine_destroy; its bytes stay counted
-        e->kf_retired.push_back(e->d_kf);
-        e->d_kf = nullptr;
+        e->kf_retired.push_back(std::move(e->d_kf));
     }
     const size_t B = (size_t)e->max_batch;
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
@@ -384,11 +367,8 @@ int ensure_kf_ws(itd_engine *e, int tpw, bool may_allocate)
     const size_t b_first = al(B * kKfLevels * (size_t)e->max_tiles * 4), b_tf = al(B * kKfLevels * (size_t)e->max_tiles * 64);
     const size_t b_tie = al(B * (size_t)e->max_tiles * 64), b_rec = al(B * kKfLevels * wgs * kKcRecGran * 8);
     const size_t total = b_sig + b_pool + b_first + b_tf + b_tie + b_rec;
-    const hipError_t rc = hipMalloc(&e->d_kf, total);
-    if (rc != hipSuccess) { e->d_kf = nullptr; fail_hip(e, rc, "hipMalloc(fused levels' workspace)"); return rc == hipErrorOutOfMemory ? ITD_ERR_NOMEM : ITD_ERR_HIP; }
-    poison(e->d_kf, total);
-    e->kf_bytes = total;
-    e->ws_bytes += (int64_t)total;
+    const hipError_t rc = e->d_kf.alloc(total, &e->ws_total);
+    if (rc != hipSuccess) { fail_hip(e, rc, "hipMalloc(fused levels' workspace)"); return rc == hipErrorOutOfMemory ? ITD_ERR_NOMEM : ITD_ERR_HIP; }
     char *p = (char *)e->d_kf;
     KfWs &w = e->kf;
     w.sig = (KfSig *)p; p += b_sig;
@@ -728,6 +708,28 @@ int enqueue_decompose(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int
     return ITD_OK;
 }
 
+// More than 64 KB of dynamic LDS has to be asked for, per kernel instance: asked once per engine, which remembers the grant
+hipError_t allow_lds(itd_engine *e, const void *fn, size_t bytes)
+{
+    if (std::find(e->lds_fn, e->lds_fn + e->lds_fns, fn) != e->lds_fn + e->lds_fns) return hipSuccess;
+    const hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (rc == hipSuccess && e->lds_fns < (int)(sizeof(e->lds_fn) / sizeof(e->lds_fn[0]))) e->lds_fn[e->lds_fns++] = fn;
+    return rc;
+}
+
+// The geometry of the one-workgroup kernels (k_resident, k_stream_levels) for n samples.  cls: four samples per thread, 64 threads up
+// to 256 samples ... 1024 threads up to 4096, eight per thread up to 8192 (the per-thread sample loops are unrolled over registers; the
+// wider workgroups hide the phases' latencies better).  cw: the window of by-rank knot slots, automatic (0.4 knots per sample) or
+// what the caller was told, cut to what fits the LDS
+struct WgClass { int cls, threads, cw; size_t lds; };
+inline WgClass wg_class(int n, int window = 0)
+{
+    const int cls = n <= 256 ? 0 : n <= 512 ? 1 : n <= 1024 ? 2 : n <= 2048 ? 3 : n <= 4096 ? 4 : 5;
+    int cw = std::min(window > 0 ? window : resident_auto_window(n), resident_pad(n));
+    while (resident_lds_bytes(n, cw) > kResidentLdsMax) cw -= 64;
+    return {cls, cls == 5 ? 1024 : 64 << cls, cw, resident_lds_bytes(n, cw)};
+}
+
 // Short signals (n <= kResidentMax): the whole decomposition as ONE launch, one workgroup per signal, the signal resident
 // in LDS (itd_resident.hpp).  Optimistic: the kernel handles finite data only and raises SigState::res_fail
 // otherwise; itd_get_summary then repeats the call level by level.  The kernel initialises the states it works on itself
@@ -744,38 +746,25 @@ int enqueue_resident(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int6
     if (bases_user)  // the reference's timeout result keeps an all-zero last baselines row (ITD.py:385,424)
         HIP_TRY(e, hipMemset2DAsync(bases_user + (R - 1) * n, (size_t)rows_stride * sizeof(double), 0,
                                     (size_t)n * sizeof(double), (size_t)batch, st));
-    // the window of by-rank knot slots: automatic (0.4 knots per sample) or what the engine was told, cut to what fits the LDS
-    int cw = e->resident_window > 0 ? e->resident_window : resident_auto_window((int)n);
-    cw = std::min(cw, resident_pad((int)n));
-    while (resident_lds_bytes((int)n, cw) > kResidentLdsMax) cw -= 64;
-    const size_t lds = resident_lds_bytes((int)n, cw);
-    // four samples per thread: 64 threads up to 256 samples ... 1024 threads up to 4096, eight per thread up to 8192 (the
-    // per-thread sample loops are unrolled over registers; the wider workgroups hide the phases' latencies better)
-    const int cls = n <= 256 ? 0 : n <= 512 ? 1 : n <= 1024 ? 2 : n <= 2048 ? 3 : n <= 4096 ? 4 : 5;
-    const int inst = cls + (sizeof(Tin) == 4 ? 0 : 6);
-    const int threads = cls == 5 ? 1024 : 64 << cls;
-    const void *fn = cls == 0 ? reinterpret_cast<const void *>(&k_resident<Tin, 64, 4>)
-                   : cls == 1 ? reinterpret_cast<const void *>(&k_resident<Tin, 128, 4>)
-                   : cls == 2 ? reinterpret_cast<const void *>(&k_resident<Tin, 256, 4>)
-                   : cls == 3 ? reinterpret_cast<const void *>(&k_resident<Tin, 512, 4>)
-                   : cls == 4 ? reinterpret_cast<const void *>(&k_resident<Tin, 1024, 4>)
-                              : reinterpret_cast<const void *>(&k_resident<Tin, 1024, 8>);
-    if (!e->resident_attr[inst]) {   // more than 64 KB of dynamic LDS has to be asked for
-        const hipError_t arc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kResidentLdsMax);
-        if (arc != hipSuccess) {     // a device / runtime that does not grant it: this engine runs level by level from now on
-            (void)hipGetLastError();
-            if (e->policy.resident_mode == ITD_RESIDENT_ONLY) return fail_hip(e, arc, "hipFuncSetAttribute(k_resident, MaxDynamicSharedMemorySize)");
-            e->policy.resident_unavailable();
-            return enqueue_decompose<Tin>(e, x, n, batch, x_stride, M, rows, bases_user, st, e->policy.level0_fused());
-        }
-        e->resident_attr[inst] = true;
+    const WgClass wc = wg_class((int)n, e->resident_window);
+    const void *const inst[6] = {   // by size class
+        reinterpret_cast<const void *>(&k_resident<Tin, 64, 4>),   reinterpret_cast<const void *>(&k_resident<Tin, 128, 4>),
+        reinterpret_cast<const void *>(&k_resident<Tin, 256, 4>),  reinterpret_cast<const void *>(&k_resident<Tin, 512, 4>),
+        reinterpret_cast<const void *>(&k_resident<Tin, 1024, 4>), reinterpret_cast<const void *>(&k_resident<Tin, 1024, 8>)};
+    const void *fn = inst[wc.cls];
+    const hipError_t arc = allow_lds(e, fn, kResidentLdsMax);
+    if (arc != hipSuccess) {     // a device / runtime that does not grant it: this engine runs level by level from now on
+        (void)hipGetLastError();
+        if (e->policy.resident_mode == ITD_RESIDENT_ONLY) return fail_hip(e, arc, "hipFuncSetAttribute(k_resident, MaxDynamicSharedMemorySize)");
+        e->policy.resident_unavailable();
+        return enqueue_decompose<Tin>(e, x, n, batch, x_stride, M, rows, bases_user, st, e->policy.level0_fused());
     }
     const Tin *a_x = x; int64_t a_xs = x_stride, a_rs = rows_stride, a_bs = rows_stride;
-    int a_n = (int)n, a_m = M, a_cw = cw, a_nf = e->nan_input_mode == ITD_NAN_INPUT_FOLLOW ? 1 : 0;
+    int a_n = (int)n, a_m = M, a_cw = wc.cw, a_nf = e->nan_input_mode == ITD_NAN_INPUT_FOLLOW ? 1 : 0;
     double *a_rows = rows, *a_bases = bases_user;
     SigState *a_st = set_state, *a_ot = other_state;
     void *args[] = {&a_x, &a_xs, &a_n, &a_m, &a_cw, &a_nf, &a_rows, &a_rs, &a_bases, &a_bs, &a_st, &a_ot};
-    HIP_TRY(e, hipLaunchKernel(fn, dim3((unsigned)batch), dim3((unsigned)threads), args, lds, st));
+    HIP_TRY(e, hipLaunchKernel(fn, dim3((unsigned)batch), dim3((unsigned)wc.threads), args, wc.lds, st));
     HIP_TRY(e, hipGetLastError());
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(st, &cap);
@@ -828,17 +817,12 @@ int check_args(itd_engine *e, const void *x, int64_t n, int32_t batch, int64_t x
     return ITD_OK;
 }
 
+// a grow-only buffer of the engine made to hold `want` bytes (Buf::reserve), the engine's error text set when that fails
 template <typename Tp>
-int grow(itd_engine *e, Tp **p, size_t *have, size_t want)
+int grow(itd_engine *e, Buf<Tp> &b, size_t want)
 {
-    if (*have >= want) return ITD_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    hipError_t rc = hipMalloc((void **)p, want);
-    if (rc != hipSuccess) { fail_hip(e, rc, "hipMalloc(io)"); return ITD_ERR_NOMEM; }
-    poison(*p, want);
-    *have = want;
+    hipError_t why = hipSuccess;
+    if (b.reserve(want, &why)) { fail_hip(e, why, "hipMalloc(io)"); return ITD_ERR_NOMEM; }
     return ITD_OK;
 }
 
@@ -856,14 +840,10 @@ int copy_to_host(itd_engine *e, void *dst_host, const void *src_dev, size_t byte
         return ITD_OK;
     }
     for (int k = 0; k < 2; ++k)
-        if (!e->h_pin[k]) {
-            const hipError_t rc = hipHostMalloc(&e->h_pin[k], kPinBytes);
-            if (rc != hipSuccess) {   // no pinned memory to be had: the plain path
-                e->h_pin[k] = nullptr;
-                HIP_TRY(e, hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, st));
-                HIP_TRY(e, hipStreamSynchronize(st));
-                return ITD_OK;
-            }
+        if (!e->h_pin[k] && e->h_pin[k].alloc(kPinBytes) != hipSuccess) {   // no pinned memory to be had: the plain path
+            HIP_TRY(e, hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, st));
+            HIP_TRY(e, hipStreamSynchronize(st));
+            return ITD_OK;
         }
     const size_t n_chunks = (bytes + kPinBytes - 1) / kPinBytes;
     std::atomic<size_t> ready{0};                       // chunks whose DMA has completed
@@ -954,28 +934,27 @@ int itd_engine_create(itd_engine **out, int device_id, int64_t max_n, int32_t ma
     e->tiles_half = (int64_t)B * e->max_tiles;
     e->gsum_third = (int64_t)B * max_groups * kGsumPitch;
     hipError_t rc = hipSuccess;
-    auto alloc = [&](void **p, size_t bytes) { if (rc == hipSuccess) { rc = hipMalloc(p, bytes); if (rc == hipSuccess) { e->ws_bytes += (int64_t)bytes; poison(*p, bytes); } } };
-    alloc((void **)&e->d_lists, (size_t)e->max_tiles * T * sizeof(int32_t));   // API helpers only (one signal)
-    alloc((void **)&e->d_counts, 2 * (size_t)e->tiles_half * sizeof(int32_t));
-    alloc((void **)&e->d_recs, 2 * (size_t)e->tiles_half * sizeof(TileRec));
-    alloc((void **)&e->d_gsum, 2 * 3 * (size_t)e->gsum_third * sizeof(int32_t));
-    alloc((void **)&e->d_kidx, (size_t)(max_n + 2) * sizeof(int32_t));
-    alloc((void **)&e->d_total, 64);
+    auto alloc = [&](auto &buf, size_t bytes) { if (rc == hipSuccess) rc = buf.alloc(bytes, &e->ws_total); };   // counted
+    alloc(e->d_lists, (size_t)e->max_tiles * T * sizeof(int32_t));   // API helpers only (one signal)
+    alloc(e->d_counts, 2 * (size_t)e->tiles_half * sizeof(int32_t));
+    alloc(e->d_recs, 2 * (size_t)e->tiles_half * sizeof(TileRec));
+    alloc(e->d_gsum, 2 * 3 * (size_t)e->gsum_third * sizeof(int32_t));
+    alloc(e->d_kidx, (size_t)(max_n + 2) * sizeof(int32_t));
+    alloc(e->d_total, 64);
     e->pp_pitch = max_n + kSlotPad;
-    alloc((void **)&e->d_pp, B * 3 * (size_t)e->pp_pitch * sizeof(double));
-    alloc((void **)&e->d_state, 2 * B * sizeof(SigState));
+    alloc(e->d_pp, B * 3 * (size_t)e->pp_pitch * sizeof(double));
+    alloc(e->d_state, 2 * B * sizeof(SigState));
     e->dirty_sig[0] = e->dirty_sig[1] = max_batch;       // nothing is initialised yet
     e->dirty_gs[0] = e->dirty_gs[1] = e->gsum_third;
     e->hgsum_third = (int64_t)max_groups * kGsumPitch;
-    alloc((void **)&e->d_hcounts, 2 * (size_t)e->max_tiles * sizeof(int32_t));
-    alloc((void **)&e->d_hrecs, 2 * (size_t)e->max_tiles * sizeof(TileRec));
-    alloc((void **)&e->d_hgsum, 3 * (size_t)e->hgsum_third * sizeof(int32_t));
-    alloc((void **)&e->d_hstate, sizeof(SigState));
-    alloc((void **)&e->d_flag, 64);
-    alloc((void **)&e->d_need, sizeof(int32_t) * (size_t)max_batch);
-    alloc((void **)&e->d_valid_own, sizeof(int32_t) * (size_t)max_batch);
-    const size_t st_b = B * sizeof(SigState);
-    if (rc == hipSuccess) rc = hipHostMalloc((void **)&e->h_state, st_b);
+    alloc(e->d_hcounts, 2 * (size_t)e->max_tiles * sizeof(int32_t));
+    alloc(e->d_hrecs, 2 * (size_t)e->max_tiles * sizeof(TileRec));
+    alloc(e->d_hgsum, 3 * (size_t)e->hgsum_third * sizeof(int32_t));
+    alloc(e->d_hstate, sizeof(SigState));
+    alloc(e->d_flag, 64);
+    alloc(e->d_need, sizeof(int32_t) * (size_t)max_batch);
+    alloc(e->d_valid_own, sizeof(int32_t) * (size_t)max_batch);
+    if (rc == hipSuccess) rc = e->h_state.alloc(B * sizeof(SigState));
     if (rc == hipSuccess) rc = hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking);
     if (rc != hipSuccess) {
         const bool oom = (rc == hipErrorOutOfMemory);
@@ -991,18 +970,6 @@ void itd_engine_destroy(itd_engine *e)
     if (!e) return;
     DevGuard g(e->device);
     if (e->own_stream) (void)hipStreamSynchronize(e->own_stream);
-    (void)hipFree(e->d_lists); (void)hipFree(e->d_counts); (void)hipFree(e->d_recs); (void)hipFree(e->d_total);
-    (void)hipFree(e->d_kidx); (void)hipFree(e->d_pp); (void)hipFree(e->d_state); (void)hipFree(e->d_gsum);
-    (void)hipFree(e->d_hcounts); (void)hipFree(e->d_hrecs); (void)hipFree(e->d_hgsum); (void)hipFree(e->d_hstate);
-    (void)hipFree(e->d_io_x); (void)hipFree(e->d_io_rows); (void)hipFree(e->d_io_bases); (void)hipFree(e->d_iq_avg);
-    (void)hipFree(e->d_cub); (void)hipFree(e->d_cub_e); (void)hipFree(e->d_dw); (void)hipFree(e->d_bw); (void)hipFree(e->d_kf); for (void *q : e->kf_retired) (void)hipFree(q); (void)hipFree(e->d_flag); (void)hipFree(e->d_need); (void)hipFree(e->d_valid_own);
-    (void)hipFree(e->d_sp); (void)hipFree(e->d_sp2); (void)hipFree(e->d_wpe); (void)hipFree(e->d_mb); (void)hipFree(e->d_rowtab);
-    (void)hipFree(e->d_fft_x); (void)hipFree(e->d_fft_y); (void)hipFree(e->d_fft_a); (void)hipFree(e->d_fft_b); (void)hipFree(e->d_fft_rec);
-    (void)hipFree(e->d_fc); (void)hipFree(e->d_fio); (void)hipFree(e->d_fmodes); (void)hipFree(e->d_fplan);
-    if (e->h_state) (void)hipHostFree(e->h_state);
-    if (e->h_kf) (void)hipHostFree(e->h_kf);
-    for (int k = 0; k < 2; ++k) if (e->h_pin[k]) (void)hipHostFree(e->h_pin[k]);
-    if (e->h_small) (void)hipHostFree(e->h_small);
     for (auto ev : e->ev) if (ev) (void)hipEventDestroy(ev);
     if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
     for (int k = 0; k < 3; ++k) {
@@ -1010,10 +977,10 @@ void itd_engine_destroy(itd_engine *e)
         if (e->ev_join[k]) (void)hipEventDestroy(e->ev_join[k]);
     }
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-    delete e;
+    delete e;   // (its buffers free themselves: here, with the engine's device current and its streams drained)
 }
 
-int64_t itd_engine_workspace_bytes(const itd_engine *e) { return e ? e->ws_bytes : 0; }
+int64_t itd_engine_workspace_bytes(const itd_engine *e) { return e ? e->ws_total : 0; }
 
 // ---- plain device-memory helpers: a host binding that owns no GPU allocator of its own (numpy callers, the C client) ----
 int itd_dev_alloc(int device_id, int64_t bytes, void **out)
@@ -1194,7 +1161,7 @@ int read_states(itd_engine *e, int B)
 {
     HIP_TRY(e, hipMemcpyAsync(e->h_state, e->d_state + (size_t)e->cur_set * e->max_batch, sizeof(SigState) * (size_t)B, hipMemcpyDeviceToHost, e->last.stream));
     if (e->last.kf) {
-        if (!e->h_kf) HIP_TRY(e, hipHostMalloc((void **)&e->h_kf, kKfSigHead * (size_t)e->max_batch));
+        if (!e->h_kf) HIP_TRY(e, e->h_kf.alloc(kKfSigHead * (size_t)e->max_batch));
         HIP_TRY(e, hipMemcpy2DAsync(e->h_kf, kKfSigHead, e->kf.sig, sizeof(KfSig), kKfSigHead, (size_t)B, hipMemcpyDeviceToHost, e->last.stream));
     }
     HIP_TRY(e, hipStreamSynchronize(e->last.stream));
@@ -1228,7 +1195,7 @@ int repeat_call(itd_engine *e, int B, bool fuse0, bool nan_input)
 int repeat_resident(itd_engine *e, int B)
 {
     if (!e->last.resident) return ITD_OK;
-    if (!std::any_of(e->h_state, e->h_state + B, [](const SigState &s) { return s.res_fail != 0; })) return ITD_OK;
+    if (!std::any_of(e->h_state.get(), e->h_state + B, [](const SigState &s) { return s.res_fail != 0; })) return ITD_OK;
     if (!e->policy.resident_failed()) {
         snprintf(e->err, sizeof(e->err), "resident form: a non-finite sample or baseline (ITD_RESIDENT_ONLY forbids the level-by-level repeat)");
         return ITD_ERR_HIP;
@@ -1242,7 +1209,7 @@ int repeat_resident(itd_engine *e, int B)
 int repeat_nan_input(itd_engine *e, int B)
 {
     if (e->last.nan_input || e->nan_input_mode != ITD_NAN_INPUT_FOLLOW) return ITD_OK;
-    const bool any = std::any_of(e->h_state, e->h_state + B, [](const SigState &s) { return s.in_nan != 0; });
+    const bool any = std::any_of(e->h_state.get(), e->h_state + B, [](const SigState &s) { return s.in_nan != 0; });
     return any ? repeat_call(e, B, false, true) : ITD_OK;
 }
 
@@ -1274,7 +1241,7 @@ int settle_fused_levels(itd_engine *e, int B)
 int repeat_level0(itd_engine *e, int B)
 {
     if (!e->last.fused) return ITD_OK;
-    if (!std::any_of(e->h_state, e->h_state + B, [](const SigState &s) { return s.l0_fail && !s.in_nan; })) return ITD_OK;
+    if (!std::any_of(e->h_state.get(), e->h_state + B, [](const SigState &s) { return s.l0_fail && !s.in_nan; })) return ITD_OK;
     if (!e->policy.level0_fell_short()) {
         snprintf(e->err, sizeof(e->err), "fused level 0: a tile's halo knots lie beyond its reach (ITD_LEVEL0_FUSED forbids the record-driven repeat)");
         return ITD_ERR_HIP;
@@ -1407,11 +1374,11 @@ int itd_debug_int_ratio_check(int device, int32_t max_den, int64_t *mismatches)
 {
     if (!mismatches || max_den < 1) return ITD_ERR_INVALID_ARG;
     DevGuard g(device);
-    unsigned long long *d = nullptr, h = 0;
-    if (hipMalloc(&d, 8) != hipSuccess || hipMemset(d, 0, 8) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipFree(d); return ITD_ERR_HIP; }
+    Buf<unsigned long long> d;
+    unsigned long long h = 0;
+    if (d.alloc(8) != hipSuccess || hipMemset(d, 0, 8) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return ITD_ERR_HIP;
     k_int_ratio_check<<<1024, 256>>>(max_den, d);
     const bool ok = hipMemcpy(&h, d, 8, hipMemcpyDeviceToHost) == hipSuccess;
-    (void)hipFree(d);
     *mismatches = (int64_t)h;
     return ok ? ITD_OK : ITD_ERR_HIP;
 }
@@ -1491,14 +1458,14 @@ int decompose_host(itd_engine *e, const Tin *x_host, int64_t n, int32_t M, doubl
     if (n < 3 || n > e->max_n || M < 0 || M > ITD_MAX_ITERATION) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
     const size_t R = (size_t)M + 2;
-    int rc = grow(e, &e->d_io_x, &e->io_x_bytes, (size_t)n * sizeof(Tin));
+    int rc = grow(e, e->d_io_x, (size_t)n * sizeof(Tin));
     if (rc) return rc;
-    rc = grow(e, &e->d_io_rows, &e->io_rows_bytes, R * (size_t)n * sizeof(double));
+    rc = grow(e, e->d_io_rows, R * (size_t)n * sizeof(double));
     if (rc) return rc;
     const bool dev_bases = bases_host || e->host_keep_bases;
     e->kept_nb = -1;
     if (dev_bases) {
-        rc = grow(e, &e->d_io_bases, &e->io_bases_bytes, R * (size_t)n * sizeof(double));
+        rc = grow(e, e->d_io_bases, R * (size_t)n * sizeof(double));
         if (rc) return rc;
     }
     hipStream_t st = e->own_stream;
@@ -1543,7 +1510,7 @@ struct KnotWs {
 enum : int { kWsLists = 1, kWsOrdered = 2, kWsTbase = 4, kWsExtract = 8, kWsDetect = kWsLists | kWsOrdered | kWsTbase };
 
 // a KnotWs for `batch` signals of n samples from a grow-only arena, `tail` bytes for the caller behind it (*tail_out)
-int knot_workspace(itd_engine *e, void **arena, size_t *have, int64_t n, int batch, int parts, KnotWs &w, size_t tail = 0,
+int knot_workspace(itd_engine *e, Buf<void> &arena, int64_t n, int batch, int parts, KnotWs &w, size_t tail = 0,
                    char **tail_out = nullptr)
 {
     w.n_tiles = (int)tiles_of(n);
@@ -1559,9 +1526,9 @@ int knot_workspace(itd_engine *e, void **arena, size_t *have, int64_t n, int bat
     const size_t b_counts = al(bufs * tiles * sizeof(int32_t)), b_recs = al(bufs * tiles * sizeof(TileRec));
     const size_t b_gsum = al(gbufs * (size_t)w.third * sizeof(int32_t)), b_state = al(B * sizeof(SigState));
     const size_t b_kidx = parts & kWsOrdered ? al(B * (size_t)w.kidx_stride * sizeof(int32_t)) : 0, b_tot = parts & kWsOrdered ? al(B * 2 * sizeof(int32_t)) : 0;
-    const int rc = grow(e, arena, have, b_lists + b_counts + b_recs + b_gsum + b_state + b_kidx + b_tot + b_tbase + tail);
+    const int rc = grow(e, arena, b_lists + b_counts + b_recs + b_gsum + b_state + b_kidx + b_tot + b_tbase + tail);
     if (rc) return rc;
-    char *p = (char *)*arena;
+    char *p = (char *)arena;
     auto take = [&p](size_t b) { char *q = b ? p : nullptr; p += b; return q; };
     w.lists = (int32_t *)take(b_lists);
     w.counts = (int32_t *)take(b_counts);
@@ -1710,7 +1677,7 @@ int extract_dev(itd_engine *e, const Tin *x, int64_t n, double *rot, double *bas
         if (has_nan) {
             // NaN in the signal: again, the way the reference runs it (ITD.py:87-88 over :46-51, 64-68): the mutated float64 copy
             // goes into a staging buffer, the record-driven extraction reads that
-            rc = grow(e, &e->d_cub, &e->cub_bytes, (size_t)n * sizeof(double));
+            rc = grow(e, e->d_cub, (size_t)n * sizeof(double));
             if (rc) return rc;
             double *xm = (double *)e->d_cub;
             rc = knot_scan<Tin>(e, w, x, n, n, 1, (int)kKnots, after, st, -1, true, xm);
@@ -1796,10 +1763,10 @@ int itd_baseline_extract_host_f64(itd_engine *e, const double *x_host, int64_t n
     if (!e || !x_host || !rot_host || !base_host) return ITD_ERR_INVALID_ARG;
     if (n < 3 || n > e->max_n) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    int rc = grow(e, &e->d_io_x, &e->io_x_bytes, (size_t)n * sizeof(double));
+    int rc = grow(e, e->d_io_x, (size_t)n * sizeof(double));
     if (rc) return rc;
     // rows staging: [rot | base | bk(n+2) | knots64(n)]
-    rc = grow(e, &e->d_io_rows, &e->io_rows_bytes, (size_t)(4 * n + 4) * sizeof(double));
+    rc = grow(e, e->d_io_rows, (size_t)(4 * n + 4) * sizeof(double));
     if (rc) return rc;
     hipStream_t st = e->own_stream;
     double *d_rot = e->d_io_rows, *d_base = d_rot + n, *d_bk = d_base + n;
@@ -1846,9 +1813,9 @@ int itd_detect_host_f64(itd_engine *e, const double *x_host, int64_t n, int32_t 
     if (!e || !x_host || !count_host) return ITD_ERR_INVALID_ARG;
     if (n < 3 || n > e->max_n) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    int rc = grow(e, &e->d_io_x, &e->io_x_bytes, (size_t)n * sizeof(double));
+    int rc = grow(e, e->d_io_x, (size_t)n * sizeof(double));
     if (rc) return rc;
-    rc = grow(e, &e->d_io_rows, &e->io_rows_bytes, (size_t)n * sizeof(int64_t));
+    rc = grow(e, e->d_io_rows, (size_t)n * sizeof(int64_t));
     if (rc) return rc;
     hipStream_t st = e->own_stream;
     HIP_TRY(e, hipMemcpyAsync(e->d_io_x, x_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
@@ -1874,9 +1841,9 @@ int itd_knot_values_host_f64(itd_engine *e, const double *x_host, int64_t n, con
         if (extrema_host[k] < 0 || extrema_host[k] >= n) return ITD_ERR_INVALID_ARG;
     if (m == 0) return ITD_OK;
     DevGuard g(e->device);
-    int rc = grow(e, &e->d_io_x, &e->io_x_bytes, (size_t)n * sizeof(double));
+    int rc = grow(e, e->d_io_x, (size_t)n * sizeof(double));
     if (rc) return rc;
-    rc = grow(e, &e->d_io_rows, &e->io_rows_bytes, (size_t)(m + 2) * sizeof(double));
+    rc = grow(e, e->d_io_rows, (size_t)(m + 2) * sizeof(double));
     if (rc) return rc;
     hipStream_t st = e->own_stream;
     std::vector<int32_t> e32((size_t)m + 2);
@@ -1920,7 +1887,7 @@ int cubic_batch(itd_engine *e, const double *x, int64_t n, int batch, int64_t x_
 {
     const int64_t L = (extrema ? idx : n) + 2;                        // entries per knot array
     const size_t jobs_b = (((size_t)batch * sizeof(CubicJob)) + 255) & ~(size_t)255;
-    int rc = grow(e, &e->d_cub, &e->cub_bytes, jobs_b + 3 * (size_t)batch * (size_t)L * sizeof(double));
+    int rc = grow(e, e->d_cub, jobs_b + 3 * (size_t)batch * (size_t)L * sizeof(double));
     if (rc) return rc;
     CubicJob *jobs = (CubicJob *)e->d_cub;
     double *arr = (double *)((char *)e->d_cub + jobs_b);
@@ -1932,7 +1899,7 @@ int cubic_batch(itd_engine *e, const double *x, int64_t n, int batch, int64_t x_
     int64_t max_count;
     if (!extrema) {
         KnotWs w;
-        rc = knot_workspace(e, &e->d_dw, &e->dw_bytes, n, batch, kWsDetect, w);
+        rc = knot_workspace(e, e->d_dw, n, batch, kWsDetect, w);
         // (tail 0: e[idx] = 0, the file's static array at first call)
         if (!rc) rc = knot_scan<double>(e, w, x, x_stride, n, batch, (int)kCpp, kScanOrdered, st, 0);
         if (rc) return rc;
@@ -1999,7 +1966,7 @@ int stage_extrema(itd_engine *e, const int64_t *extrema_host, int64_t count, int
 {
     for (int64_t k = 0; k < count; ++k)
         if (extrema_host[k] < 0 || extrema_host[k] >= n) return ITD_ERR_INVALID_ARG;
-    const int rc = grow(e, &e->d_cub_e, &e->cub_e_bytes, (size_t)count * sizeof(int32_t));
+    const int rc = grow(e, e->d_cub_e, (size_t)count * sizeof(int32_t));
     if (rc) return rc;
     HIP_TRY(e, hipMemcpyAsync(scratch, extrema_host, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, st));
     k_narrow_idx<<<(unsigned)((count + 255) / 256), 256, 0, st>>>(scratch, e->d_cub_e, count);
@@ -2024,7 +1991,7 @@ int itd_baseline_extract_cubic_f32(itd_engine *e, const float *x_dev, int64_t n,
     if (n < 3 || n > e->max_n) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
     hipStream_t st = stream_of(e, stream);
-    int rc = grow(e, &e->d_io_x, &e->io_x_bytes, (size_t)n * sizeof(double));
+    int rc = grow(e, e->d_io_x, (size_t)n * sizeof(double));
     if (rc) return rc;
     k_widen_f32<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(x_dev, (double *)e->d_io_x, n);   // float64 arithmetic on the widened signal
     return cubic_dev(e, (const double *)e->d_io_x, n, extrema_dev, idx, baseline_dev, idx_host, st);
@@ -2037,9 +2004,9 @@ int itd_baseline_extract_cubic_host_f64(itd_engine *e, const double *x_host, int
     if (n < 3 || n > e->max_n) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
     hipStream_t st = e->own_stream;
-    int rc = grow(e, &e->d_io_x, &e->io_x_bytes, (size_t)n * sizeof(double));
+    int rc = grow(e, e->d_io_x, (size_t)n * sizeof(double));
     if (rc) return rc;
-    rc = grow(e, &e->d_io_rows, &e->io_rows_bytes, (size_t)n * sizeof(double) * 2);   // baseline | widened knots
+    rc = grow(e, e->d_io_rows, (size_t)n * sizeof(double) * 2);   // baseline | widened knots
     if (rc) return rc;
     HIP_TRY(e, hipMemcpyAsync(e->d_io_x, x_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
     const int32_t *ek = nullptr;
@@ -2073,7 +2040,7 @@ int itd_baseline_extract_iq_f64(itd_engine *e, const double *iq_dev, int64_t n, 
     if (extrema_dev && (idx < 2 || idx > n - 1)) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
     hipStream_t st = stream_of(e, stream);
-    int rc = grow(e, &e->d_iq_avg, &e->iq_avg_bytes, (size_t)n * sizeof(double));
+    int rc = grow(e, e->d_iq_avg, (size_t)n * sizeof(double));
     if (rc) return rc;
     double *avg = (double *)e->d_iq_avg;
     if (extrema_dev) {
@@ -2101,9 +2068,9 @@ int itd_baseline_extract_iq_host_f64(itd_engine *e, const double *iq_host, int64
     if (n < 3 || n > e->max_n) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
     hipStream_t st = e->own_stream;
-    int rc = grow(e, &e->d_io_x, &e->io_x_bytes, (size_t)n * sizeof(double) * 2);
+    int rc = grow(e, e->d_io_x, (size_t)n * sizeof(double) * 2);
     if (rc) return rc;
-    rc = grow(e, &e->d_io_rows, &e->io_rows_bytes, (size_t)n * sizeof(double) * 2);   // baseline | widened knots
+    rc = grow(e, e->d_io_rows, (size_t)n * sizeof(double) * 2);   // baseline | widened knots
     if (rc) return rc;
     HIP_TRY(e, hipMemcpyAsync(e->d_io_x, iq_host, (size_t)n * sizeof(double) * 2, hipMemcpyHostToDevice, st));
     const int32_t *ek = nullptr;
@@ -2132,9 +2099,9 @@ int itd_find_extrema_host_f64(itd_engine *e, const double *s_host, int64_t n, in
     if (n < 3 || n > e->max_n) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
     hipStream_t st = e->own_stream;
-    int rc = grow(e, &e->d_io_x, &e->io_x_bytes, (size_t)n * sizeof(double));
+    int rc = grow(e, e->d_io_x, (size_t)n * sizeof(double));
     if (rc) return rc;
-    rc = grow(e, &e->d_io_rows, &e->io_rows_bytes, (size_t)(n + 2) * sizeof(int64_t));
+    rc = grow(e, e->d_io_rows, (size_t)(n + 2) * sizeof(int64_t));
     if (rc) return rc;
     HIP_TRY(e, hipMemcpyAsync(e->d_io_x, s_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
     int64_t m = 0;
@@ -2174,7 +2141,7 @@ int spline_enqueue(itd_engine *e, const double *x, int64_t n, int batch, int64_t
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t B = (size_t)batch, b_a = al(B * 4 * (size_t)w.lda * sizeof(double)), b_c = al(B * (size_t)w.lda * sizeof(double));
     char *p = nullptr;
-    int rc = knot_workspace(e, &e->d_sp, &e->sp_bytes, n, batch, kWsLists | kWsOrdered, w.k, b_a + b_c + al(B * sizeof(SplineMeta)), &p);
+    int rc = knot_workspace(e, e->d_sp, n, batch, kWsLists | kWsOrdered, w.k, b_a + b_c + al(B * sizeof(SplineMeta)), &p);
     if (!rc) rc = knot_scan<double>(e, w.k, x, x_stride, n, batch, (int)kKnots, kScanOrdered, st);
     if (rc) return rc;
     w.a = (double *)p;
@@ -2194,12 +2161,12 @@ int nak_enqueue(itd_engine *e, const double *x, int64_t n, int batch, int64_t x_
                 int64_t base_stride, double *rot, int64_t rot_stride, hipStream_t st, const int32_t **totals_out)
 {
     KnotWs w;
-    int rc = knot_workspace(e, &e->d_dw, &e->dw_bytes, n, batch, kWsDetect, w);
+    int rc = knot_workspace(e, e->d_dw, n, batch, kWsDetect, w);
     if (!rc) rc = knot_scan<double>(e, w, x, x_stride, n, batch, (int)kKnots, kScanOrdered, st);     // kidx[b] = [0, knots, n-1]
     if (rc) return rc;
     const int64_t L = n + 2;
     const size_t jobs_b = (((size_t)batch * sizeof(CubicJob)) + 255) & ~(size_t)255;
-    rc = grow(e, &e->d_cub, &e->cub_bytes, jobs_b + 6 * (size_t)batch * (size_t)L * sizeof(double));
+    rc = grow(e, e->d_cub, jobs_b + 6 * (size_t)batch * (size_t)L * sizeof(double));
     if (rc) return rc;
     CubicJob *jobs = (CubicJob *)e->d_cub;
     double *arr = (double *)((char *)e->d_cub + jobs_b);
@@ -2227,7 +2194,7 @@ constexpr int kSmallWords = 32;           // 8-byte words of mapped host memory 
 bool small_results(itd_engine *e)
 {
     if (e->h_small) return e->d_small != nullptr;
-    if (hipHostMalloc(&e->h_small, kSmallWords * 8, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { (void)hipGetLastError(); e->h_small = nullptr; return false; }
+    if (e->h_small.alloc(kSmallWords * 8, nullptr, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { (void)hipGetLastError(); return false; }
     if (hipHostGetDevicePointer(&e->d_small, e->h_small, 0) != hipSuccess) { (void)hipGetLastError(); e->d_small = nullptr; return false; }
     memset(e->h_small, 0, kSmallWords * 8);
     return true;
@@ -2266,7 +2233,7 @@ int nak_small(itd_engine *e, const double *x, int64_t n, int min_extrema, double
 {
     const int64_t L = n + 2;
     const size_t idx_b = (((size_t)L * sizeof(int32_t)) + 255) & ~(size_t)255, out_b = 256;
-    int rc = grow(e, &e->d_cub, &e->cub_bytes, out_b + idx_b + 6 * (size_t)L * sizeof(double));
+    int rc = grow(e, e->d_cub, out_b + idx_b + 6 * (size_t)L * sizeof(double));
     if (rc) return rc;
     const bool mapped = small_results(e);
     int32_t *out = (int32_t *)e->d_cub;
@@ -2276,10 +2243,7 @@ int nak_small(itd_engine *e, const double *x, int64_t n, int min_extrema, double
     unsigned long long *words = mapped ? (unsigned long long *)e->d_small : nullptr;
     const size_t lds = 4 * (size_t)L * sizeof(double);
     if (lds <= kNakSmallLdsMax) {                          // the sweeps' arrays in LDS (more than 64 KB of dynamic LDS has to be asked for)
-        if (!e->nak_small_attr) {
-            HIP_TRY(e, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_nak_small<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kNakSmallLdsMax));
-            e->nak_small_attr = true;
-        }
+        HIP_TRY(e, allow_lds(e, reinterpret_cast<const void *>(&k_nak_small<true>), kNakSmallLdsMax));
         k_nak_small<true><<<1, kNakSmallThreads, lds, st>>>(x, (int)n, min_extrema, idx, arr, arr + L, arr + 2 * L, arr + 3 * L, arr + 4 * L, arr + 5 * L,
                                                              base, rot, baseline_knots_host ? 1 : 0, out, words, seq);
     } else
@@ -2351,7 +2315,7 @@ int itd_baseline_extract_spline_host2_f64(itd_engine *e, const double *x_host, i
     DevGuard g(e->device);
     hipStream_t st = e->own_stream;
     const size_t cnt = (size_t)n * (size_t)batch;
-    int rc = grow(e, &e->d_sp2, &e->sp2_bytes, 3 * cnt * sizeof(double));
+    int rc = grow(e, e->d_sp2, 3 * cnt * sizeof(double));
     if (rc) return rc;
     double *d_x = e->d_sp2, *d_b = d_x + cnt, *d_r = d_b + cnt;
     HIP_TRY(e, hipMemcpyAsync(d_x, x_host, cnt * sizeof(double), hipMemcpyHostToDevice, st));
@@ -2360,7 +2324,7 @@ int itd_baseline_extract_spline_host2_f64(itd_engine *e, const double *x_host, i
     KnotWs w;
     if (baseline_knots_host) {
         if (batch > kMaxGridY) return ITD_ERR_INVALID_ARG;
-        rc = knot_workspace(e, &e->d_dw, &e->dw_bytes, n, batch, kWsDetect, w);
+        rc = knot_workspace(e, e->d_dw, n, batch, kWsDetect, w);
         if (!rc) rc = knot_scan<double>(e, w, d_b, n, n, batch, (int)kKnots, kScanTotals, st);   // counts only
         if (rc) return rc;
     }
@@ -2380,11 +2344,11 @@ int itd_count_knots_host_f64(itd_engine *e, const double *x_host, int64_t n, int
     DevGuard g(e->device);
     hipStream_t st = e->own_stream;
     const size_t cnt = (size_t)n * (size_t)batch;
-    int rc = grow(e, &e->d_io_x, &e->io_x_bytes, cnt * sizeof(double));
+    int rc = grow(e, e->d_io_x, cnt * sizeof(double));
     if (rc) return rc;
     HIP_TRY(e, hipMemcpyAsync(e->d_io_x, x_host, cnt * sizeof(double), hipMemcpyHostToDevice, st));
     KnotWs w;
-    rc = knot_workspace(e, &e->d_dw, &e->dw_bytes, n, batch, kWsDetect, w);
+    rc = knot_workspace(e, e->d_dw, n, batch, kWsDetect, w);
     if (!rc) rc = knot_scan<double>(e, w, (const double *)e->d_io_x, n, n, batch, mode, kScanTotals, st);
     if (rc) return rc;
     return fetch_totals(e, w.totals, batch, counts_host, st);     // counted under the plain rules: see itd_detect_* for detect_peaks' NaN branch
@@ -2400,7 +2364,7 @@ int itd_count_knots_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t b
     DevGuard g(e->device);
     hipStream_t st = stream_of(e, stream);
     KnotWs w;
-    int rc = knot_workspace(e, &e->d_dw, &e->dw_bytes, n, batch, kWsDetect, w);
+    int rc = knot_workspace(e, e->d_dw, n, batch, kWsDetect, w);
     if (!rc) rc = knot_scan<double>(e, w, x_dev, x_stride, n, batch, mode, kScanTotals, st);
     if (rc) return rc;
     if (2 * batch > kSmallWords || !small_results(e)) return fetch_totals(e, w.totals, batch, counts_host, st);
@@ -2429,9 +2393,9 @@ int itd_wpe3_f64(itd_engine *e, const double *x_dev, int64_t n, double *bin_weig
     const int64_t nseg = (nw + seg_len - 1) / seg_len;
     if (nseg > INT32_MAX / 8) return ITD_ERR_INVALID_ARG;
     const size_t out_off = (size_t)nseg * (6 * (sizeof(double) + sizeof(long long)) + 2 * sizeof(int));    // the segments' sums, then the totals
-    int rc = grow(e, &e->d_wpe, &e->wpe_bytes, out_off + 6 * (sizeof(double) + sizeof(long long)) + 2 * sizeof(int));
+    int rc = grow(e, e->d_wpe, out_off + 6 * (sizeof(double) + sizeof(long long)) + 2 * sizeof(int));
     if (rc) return rc;
-    double *part_s = reinterpret_cast<double *>(e->d_wpe);
+    double *part_s = reinterpret_cast<double *>(e->d_wpe.get());
     long long *part_c = reinterpret_cast<long long *>(part_s + (size_t)nseg * 6);
     int *part_k = reinterpret_cast<int *>(part_c + (size_t)nseg * 6);
     double *out_s = reinterpret_cast<double *>(e->d_wpe + out_off);
@@ -2477,7 +2441,7 @@ int itd_meitd_small_f64(itd_engine *e, double *rows_dev, int64_t n, double wpema
     const int64_t L = n + 2;
     const size_t idx_b = (((size_t)L * sizeof(int32_t)) + 255) & ~(size_t)255, out_b = 256;
     const size_t arr_b = 6 * (size_t)L * sizeof(double);
-    int rc = grow(e, &e->d_cub, &e->cub_bytes, out_b + idx_b + arr_b + kMeitdLogCap * sizeof(MeitdProbe));
+    int rc = grow(e, e->d_cub, out_b + idx_b + arr_b + kMeitdLogCap * sizeof(MeitdProbe));
     if (rc) return rc;
     int32_t *idx = (int32_t *)((char *)e->d_cub + out_b);
     double *arr = (double *)((char *)e->d_cub + out_b + idx_b);
@@ -2486,11 +2450,8 @@ int itd_meitd_small_f64(itd_engine *e, double *rows_dev, int64_t n, double wpema
     const size_t nak_lds = 4 * (size_t)L * sizeof(double);
     const bool in_lds = nak_lds <= kNakSmallLdsMax;
     const size_t lds = in_lds && nak_lds > kMeitdWpeLds ? nak_lds : kMeitdWpeLds;   // the two operators take turns in the same bytes
-    if (!e->meitd_attr[in_lds]) {
-        const void *fn = in_lds ? reinterpret_cast<const void *>(&k_meitd_small<true>) : reinterpret_cast<const void *>(&k_meitd_small<false>);
-        HIP_TRY(e, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(in_lds ? kNakSmallLdsMax : kMeitdWpeLds)));
-        e->meitd_attr[in_lds] = true;
-    }
+    HIP_TRY(e, allow_lds(e, in_lds ? reinterpret_cast<const void *>(&k_meitd_small<true>) : reinterpret_cast<const void *>(&k_meitd_small<false>),
+                         in_lds ? kNakSmallLdsMax : kMeitdWpeLds));
     if (in_lds)
         k_meitd_small<true><<<1, kNakSmallThreads, lds, st>>>(rows_dev, (int)n, wpemax, idx, arr, arr + L, arr + 2 * L, arr + 3 * L, arr + 4 * L, arr + 5 * L, dlog, dout);
     else
@@ -2531,7 +2492,7 @@ int itd_meitd_batch_f64(itd_engine *e, double *rows_dev, int64_t n, int32_t batc
     const size_t xs_b = xitd ? (size_t)grid_max * kMeitdKept * 6 * (sizeof(double) + sizeof(long long)) : 0;
     const size_t x_b = x_host ? (((size_t)grid_max * (size_t)n * sizeof(double)) + 255) & ~(size_t)255 : 0;
     // (the logs are packed, as far as the longest reaches, behind everything else before they go to the host: log_b more)
-    int rc = grow(e, &e->d_mb, &e->mb_bytes, out_b + log_b + xs_b + (size_t)grid_max * sig_b + x_b + log_b);
+    int rc = grow(e, e->d_mb, out_b + log_b + xs_b + (size_t)grid_max * sig_b + x_b + log_b);
     if (rc) return rc;
     MeitdOut *dout = (MeitdOut *)e->d_mb;
     MeitdProbe *dlog = (MeitdProbe *)((char *)e->d_mb + out_b);
@@ -2543,11 +2504,8 @@ int itd_meitd_batch_f64(itd_engine *e, double *rows_dev, int64_t n, int32_t batc
     const size_t nak_lds = 4 * (size_t)L * sizeof(double);
     const bool in_lds = nak_lds <= kNakSmallLdsMax;
     const size_t lds = in_lds && nak_lds > kMeitdWpeLds ? nak_lds : kMeitdWpeLds;   // (as itd_meitd_small_f64)
-    if (!e->meitd_batch_attr[in_lds]) {
-        const void *fn = in_lds ? reinterpret_cast<const void *>(&k_meitd_batch<true>) : reinterpret_cast<const void *>(&k_meitd_batch<false>);
-        HIP_TRY(e, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(in_lds ? kNakSmallLdsMax : kMeitdWpeLds)));
-        e->meitd_batch_attr[in_lds] = true;
-    }
+    HIP_TRY(e, allow_lds(e, in_lds ? reinterpret_cast<const void *>(&k_meitd_batch<true>) : reinterpret_cast<const void *>(&k_meitd_batch<false>),
+                         in_lds ? kNakSmallLdsMax : kMeitdWpeLds));
     const int32_t cap = log_cap < kMeitdLogCap ? log_cap : kMeitdLogCap;
     std::vector<MeitdOut> ho((size_t)grid_max);
     std::vector<MeitdProbe> hlog;
@@ -2585,11 +2543,7 @@ int itd_meitd_batch_f64(itd_engine *e, double *rows_dev, int64_t n, int32_t batc
         for (int32_t b = 0; most > 0 && b < G; ++b)
             memcpy((char *)probe_logs_host + ((size_t)b0 + b) * log_cap * sizeof(MeitdProbe), hlog.data() + (size_t)b * most, (size_t)most * sizeof(MeitdProbe));
     }
-    if (e->mb_bytes > kMeitdBatchKeepBytes) {      // (a large batch's workspace does not stay allocated behind the call)
-        HIP_TRY(e, hipFree(e->d_mb));
-        e->d_mb = nullptr;
-        e->mb_bytes = 0;
-    }
+    if (e->d_mb.bytes() > kMeitdBatchKeepBytes) e->d_mb.release();   // (a large batch's workspace does not stay allocated behind the call)
     return ITD_OK;
 }
 
@@ -2613,7 +2567,7 @@ int itd_gather_rows_f64(itd_engine *e, const double *src_dev, int64_t src_elems,
     if (rows == 0) return ITD_OK;
     DevGuard g(e->device);
     hipStream_t st = stream_of(e, stream);
-    int rc = grow(e, &e->d_rowtab, &e->rowtab_bytes, (size_t)rows * sizeof(int64_t));
+    int rc = grow(e, e->d_rowtab, (size_t)rows * sizeof(int64_t));
     if (rc) return rc;
     HIP_TRY(e, hipMemcpyAsync(e->d_rowtab, offsets_host, (size_t)rows * sizeof(int64_t), hipMemcpyHostToDevice, st));
     k_gather_rows<<<(unsigned)(rows < 65536 ? rows : 65536), 256, 0, st>>>(src_dev, e->d_rowtab, rows, n, dst_dev);
@@ -2639,9 +2593,9 @@ int itd_wpe_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t order, do
     const size_t wts_off = ((size_t)nw * sizeof(unsigned short) + 255) / 256 * 256;
     const size_t part_off = wts_off + (size_t)nw * sizeof(double);
     const size_t out_off = part_off + (size_t)nseg * nh * (sizeof(double) + sizeof(long long));
-    int rc = grow(e, &e->d_wpe, &e->wpe_bytes, out_off + (size_t)nh * (sizeof(double) + sizeof(long long)));
+    int rc = grow(e, e->d_wpe, out_off + (size_t)nh * (sizeof(double) + sizeof(long long)));
     if (rc) return rc;
-    unsigned short *hashes = reinterpret_cast<unsigned short *>(e->d_wpe);
+    unsigned short *hashes = reinterpret_cast<unsigned short *>(e->d_wpe.get());
     double *wts = reinterpret_cast<double *>(e->d_wpe + wts_off);
     double *part_s = reinterpret_cast<double *>(e->d_wpe + part_off);
     long long *part_c = reinterpret_cast<long long *>(part_s + (size_t)nseg * nh);
@@ -2692,7 +2646,7 @@ int itd_baseline_extract_spline2_f64(itd_engine *e, const double *x_dev, int64_t
     std::vector<int32_t> tot((size_t)batch * 2);
     HIP_TRY(e, hipMemcpyAsync(tot.data(), totals, tot.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     KnotWs dw;
-    rc = knot_workspace(e, &e->d_dw, &e->dw_bytes, n, batch, kWsDetect, dw);
+    rc = knot_workspace(e, e->d_dw, n, batch, kWsDetect, dw);
     if (!rc) rc = knot_scan<double>(e, dw, baseline_dev, baseline_stride, n, batch, (int)kKnots, kScanTotals, st);
     if (rc) return rc;
     // (one synchronisation for both; the NaN flags that count are the extraction's)
@@ -2741,7 +2695,7 @@ int itd_crossways_f64(itd_engine *e, const double *img_dev, int32_t planes, int3
     DevGuard g(e->device);
     hipStream_t st = stream_of(e, stream);
     const size_t cnt = (size_t)planes * rows * cols;
-    int rc = grow(e, &e->d_sp2, &e->sp2_bytes, 3 * cnt * sizeof(double));
+    int rc = grow(e, e->d_sp2, 3 * cnt * sizeof(double));
     if (rc) return rc;
     double *A = e->d_sp2, *Bq = A + cnt, *C = Bq + cnt;       // scratch planes
     SplineWs w;
@@ -2785,7 +2739,7 @@ int itd_crossways_host_f64(itd_engine *e, const double *img_host, int32_t planes
     DevGuard g(e->device);
     hipStream_t st = e->own_stream;
     const size_t cnt = (size_t)planes * rows * cols;
-    int rc = grow(e, &e->d_io_rows, &e->io_rows_bytes, 2 * cnt * sizeof(double));
+    int rc = grow(e, e->d_io_rows, 2 * cnt * sizeof(double));
     if (rc) return rc;
     double *d_in = e->d_io_rows, *d_out = d_in + cnt;
     HIP_TRY(e, hipMemcpyAsync(d_in, img_host, cnt * sizeof(double), hipMemcpyHostToDevice, st));
@@ -2809,7 +2763,7 @@ int itd_instantaneous_f64(itd_engine *e, const double *rot_dev, int64_t n, doubl
     int64_t m = 0;
     int rc = cubic_detect(e, rot_dev, n, (int)kZeroCross, &m, st);   // ordered zero crossings in d_kidx[1..m]
     if (rc) return rc;
-    rc = grow(e, &e->d_cub, &e->cub_bytes, (size_t)(m + 2) * sizeof(unsigned long long));
+    rc = grow(e, e->d_cub, (size_t)(m + 2) * sizeof(unsigned long long));
     if (rc) return rc;
     unsigned long long *amp_bits = (unsigned long long *)e->d_cub;
     HIP_TRY(e, hipMemsetAsync(amp_bits, 0, (size_t)(m + 1) * sizeof(unsigned long long), st));
@@ -2830,9 +2784,9 @@ int itd_instantaneous_host_f64(itd_engine *e, const double *rot_host, int64_t n,
     if (n < 3 || n > e->max_n) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
     hipStream_t st = e->own_stream;
-    int rc = grow(e, &e->d_io_x, &e->io_x_bytes, (size_t)n * sizeof(double));
+    int rc = grow(e, e->d_io_x, (size_t)n * sizeof(double));
     if (rc) return rc;
-    rc = grow(e, &e->d_io_rows, &e->io_rows_bytes, 3 * (size_t)n * sizeof(double));
+    rc = grow(e, e->d_io_rows, 3 * (size_t)n * sizeof(double));
     if (rc) return rc;
     HIP_TRY(e, hipMemcpyAsync(e->d_io_x, rot_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
     double *d_a = e->d_io_rows, *d_p = d_a + n, *d_f = d_p + n;

@@ -40,7 +40,7 @@ int extract_batch(itd_engine *e, const double *x, int64_t n, int32_t batch, int6
 {
     const int chunk = std::min<int32_t>(batch, kMaxGridY);
     KnotWs w;   // counts / records of two levels, three group-sum buffers, the signals' states
-    int rc = knot_workspace(e, &e->d_bw, &e->bw_bytes, n, chunk, kWsExtract, w);
+    int rc = knot_workspace(e, e->d_bw, n, chunk, kWsExtract, w);
     if (rc) return rc;
     for (int b0 = 0; b0 < batch; b0 += chunk) {
         const int nb = std::min(chunk, batch - b0);
@@ -62,20 +62,20 @@ struct itd_stream {
     int64_t L = 0;
     int32_t C = 1, kind = ITD_STREAM_CUBIC, margin = 8, shared = 0;
     int64_t pushed = 0;             // blocks stored since create / reset / flush
-    double *ring = nullptr;         // [C][5 L]
-    double *scr = nullptr;          // tier-1: rotation and baseline of the window, [2][C][3 L]
-    CubicJob *jobs = nullptr;       // cubic: [C]
-    double *arr = nullptr;          // cubic: K, bf, b, [3][C][3 L + 2]
-    int32_t *d_status = nullptr;    // sticky: |= 2 when a window held a NaN
-    double *h_in = nullptr, *h_out = nullptr;   // pinned staging of the host form: [C][L], [2][C][L]
-    double *d_in = nullptr, *d_out = nullptr;   // device staging of the host form
+    Buf<double> ring;               // [C][5 L]
+    Buf<double> scr;                // tier-1: rotation and baseline of the window, [2][C][3 L]
+    Buf<CubicJob> jobs;             // cubic: [C]
+    Buf<double> arr;                // cubic: K, bf, b, [3][C][3 L + 2]
+    Buf<int32_t> d_status;          // sticky: |= 2 when a window held a NaN
+    Pinned<double> h_in, h_out;     // pinned staging of the host form: [C][L], [2][C][L]
+    Buf<double> d_in, d_out;        // device staging of the host form
     // levels stream (ITD_STREAM_LEVELS, k_stream_levels in itd_stream.hpp): ring = [C][M+1][5 L]
     int32_t M = 0, cw = 0, threads = 0;
     int32_t seq = 0;                // 1: the launch-sequence form (blocks above 2730 samples, or itd_levels_stream_set_sequence)
     int64_t t = 0, P = -1;          // the next step; the blocks in all once flushing began (-1: pushing)
-    double *delay = nullptr;        // [C][M (M+1) / 2][L]
-    uint8_t *eflags = nullptr;      // [C][M+1][4]
-    uint8_t *d_exact = nullptr, *h_exact = nullptr;   // host form: [C]
+    Buf<double> delay;              // [C][M (M+1) / 2][L]
+    Buf<uint8_t> eflags;            // [C][M+1][4]
+    Buf<uint8_t> d_exact; Pinned<uint8_t> h_exact;   // host form: [C]
     size_t lds = 0;
     const void *fn = nullptr;
 };
@@ -102,7 +102,7 @@ int stream_emit(itd_stream *s, int64_t w0, int64_t wl, int64_t lo, int64_t hi, d
     // (itd.cpp:40-44) or every channel's own
     const int n_lists = s->shared ? 1 : C;
     KnotWs w;
-    int rc = knot_workspace(e, &e->d_dw, &e->dw_bytes, wl, n_lists, kWsDetect, w);
+    int rc = knot_workspace(e, e->d_dw, wl, n_lists, kWsDetect, w);
     if (!rc) rc = knot_scan<double>(e, w, win, ring_stride, wl, n_lists, (int)kCpp, kScanOrdered, st, 0);
     if (rc) return rc;
     k_stream_select<<<(n_lists + 63) / 64, 64, 0, st>>>(w.kidx, w.kidx_stride, w.totals, n_lists, (int)lo, (int)hi, s->margin, s->jobs, s->d_status);
@@ -167,7 +167,7 @@ int itd_detect_batch_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t 
     DevGuard g(e->device);
     hipStream_t st = stream_of(e, stream);
     KnotWs w;
-    int rc = knot_workspace(e, &e->d_dw, &e->dw_bytes, n, batch, kWsDetect, w);
+    int rc = knot_workspace(e, e->d_dw, n, batch, kWsDetect, w);
     if (!rc) rc = knot_scan<double>(e, w, x_dev, x_stride, n, batch, mode, idx_dev ? kScanOrdered : kScanTotals, st, -1, false, nullptr, idx_dev, idx_stride);
     if (rc) return rc;
     if (info_dev) k_info_from_totals<<<(batch + 255) / 256, 256, 0, st>>>(w.totals, batch, info_dev);
@@ -209,13 +209,12 @@ int itd_stream_create(itd_stream **out, int device_id, int64_t block, int32_t ch
     s->L = block; s->C = channels; s->kind = kind; s->margin = margin; s->shared = shared_knots ? 1 : 0;
     DevGuard g(device_id);
     const size_t C = (size_t)channels, L = (size_t)block;
-    hipError_t hrc = hipMalloc((void **)&s->ring, C * 5 * L * sizeof(double));
+    hipError_t hrc = s->ring.alloc(C * 5 * L * sizeof(double));
     if (hrc == hipSuccess) hrc = hipMemset(s->ring, 0, C * 5 * L * sizeof(double));
-    if (hrc == hipSuccess && kind == ITD_STREAM_LINEAR) hrc = hipMalloc((void **)&s->scr, 2 * C * 3 * L * sizeof(double));
-    if (hrc == hipSuccess && kind == ITD_STREAM_CUBIC) hrc = hipMalloc((void **)&s->jobs, C * sizeof(CubicJob));
-    if (hrc == hipSuccess && kind == ITD_STREAM_CUBIC) hrc = hipMalloc((void **)&s->arr, 3 * C * (3 * L + 2) * sizeof(double));
-    if (hrc == hipSuccess) { poison(s->scr, 2 * C * 3 * L * sizeof(double)); poison(s->jobs, C * sizeof(CubicJob)); poison(s->arr, 3 * C * (3 * L + 2) * sizeof(double)); }
-    if (hrc == hipSuccess) hrc = hipMalloc((void **)&s->d_status, 64);
+    if (hrc == hipSuccess && kind == ITD_STREAM_LINEAR) hrc = s->scr.alloc(2 * C * 3 * L * sizeof(double));
+    if (hrc == hipSuccess && kind == ITD_STREAM_CUBIC) hrc = s->jobs.alloc(C * sizeof(CubicJob));
+    if (hrc == hipSuccess && kind == ITD_STREAM_CUBIC) hrc = s->arr.alloc(3 * C * (3 * L + 2) * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->d_status.alloc(64);
     if (hrc == hipSuccess) hrc = hipMemset(s->d_status, 0, 64);
     if (hrc == hipSuccess) hrc = hipDeviceSynchronize();     // (the fills ran on the null stream, the stream's launches use a non-blocking one)
     if (hrc != hipSuccess) {
@@ -230,18 +229,11 @@ int itd_stream_create(itd_stream **out, int device_id, int64_t block, int32_t ch
 void itd_stream_destroy(itd_stream *s)
 {
     if (!s) return;
-    if (s->eng) {
-        DevGuard g(s->eng->device);
-        (void)hipStreamSynchronize(s->eng->own_stream);
-        (void)hipFree(s->ring); (void)hipFree(s->scr); (void)hipFree(s->jobs); (void)hipFree(s->arr); (void)hipFree(s->d_status);
-        (void)hipFree(s->d_in); (void)hipFree(s->d_out);
-        (void)hipFree(s->delay); (void)hipFree(s->eflags); (void)hipFree(s->d_exact);
-        if (s->h_exact) (void)hipHostFree(s->h_exact);
-        if (s->h_in) (void)hipHostFree(s->h_in);
-        if (s->h_out) (void)hipHostFree(s->h_out);
-        itd_engine_destroy(s->eng);
-    }
-    delete s;
+    itd_engine *const e = s->eng;   // (never null: a stream whose engine could not be created does not get here)
+    DevGuard g(e->device);
+    (void)hipStreamSynchronize(e->own_stream);
+    delete s;                       // the stream's buffers go before its engine does
+    itd_engine_destroy(e);
 }
 
 int itd_stream_reset(itd_stream *s)
@@ -303,12 +295,14 @@ int stream_host(itd_stream *s, const double *block_host, double *baseline_host, 
     itd_engine *e = s->eng;
     DevGuard g(e->device);
     const size_t cnt = (size_t)s->C * (size_t)s->L;
-    if (!s->h_in) {
-        HIP_TRY(e, hipHostMalloc((void **)&s->h_in, cnt * sizeof(double)));
-        HIP_TRY(e, hipHostMalloc((void **)&s->h_out, 2 * cnt * sizeof(double)));
-        HIP_TRY(e, hipMalloc((void **)&s->d_in, cnt * sizeof(double)));
-        HIP_TRY(e, hipMalloc((void **)&s->d_out, 2 * cnt * sizeof(double)));
-        poison(s->d_in, cnt * sizeof(double)); poison(s->d_out, 2 * cnt * sizeof(double));
+    if (!s->h_in) {   // the staging, at the first host-form call: all four buffers or none
+        Pinned<double> h_in, h_out;
+        Buf<double> d_in, d_out;
+        HIP_TRY(e, h_in.alloc(cnt * sizeof(double)));
+        HIP_TRY(e, h_out.alloc(2 * cnt * sizeof(double)));
+        HIP_TRY(e, d_in.alloc(cnt * sizeof(double)));
+        HIP_TRY(e, d_out.alloc(2 * cnt * sizeof(double)));
+        s->h_in = std::move(h_in); s->h_out = std::move(h_out); s->d_in = std::move(d_in); s->d_out = std::move(d_out);
     }
     hipStream_t st = e->own_stream;
     int32_t em = 0;
@@ -453,18 +447,17 @@ int levels_flush(itd_stream *s, double *rows, int64_t row_stride, int64_t chan_s
 int levels_seq_alloc(itd_stream *s)
 {
     if (s->scr) return ITD_OK;
-    const size_t bytes = 2 * (size_t)s->C * 3 * (size_t)s->L * sizeof(double);
-    hipError_t hrc = hipMalloc((void **)&s->scr, bytes);
+    Buf<double> scr;
+    const hipError_t hrc = scr.alloc(2 * (size_t)s->C * 3 * (size_t)s->L * sizeof(double));
     if (hrc != hipSuccess) {
         (void)hipGetLastError();
-        s->scr = nullptr;
         return hrc == hipErrorOutOfMemory ? ITD_ERR_NOMEM : fail_hip(s->eng, hrc, "hipMalloc(levels stream scratch)");
     }
-    poison(s->scr, bytes);
     KnotWs w;
-    const int rc = knot_workspace(s->eng, &s->eng->d_bw, &s->eng->bw_bytes, 3 * s->L, std::min<int32_t>(s->C, kMaxGridY), kWsExtract, w);
+    const int rc = knot_workspace(s->eng, s->eng->d_bw, 3 * s->L, std::min<int32_t>(s->C, kMaxGridY), kWsExtract, w);
     if (rc) return rc;
     HIP_TRY(s->eng, hipDeviceSynchronize());
+    s->scr = std::move(scr);        // the sequence form is ready only now
     return ITD_OK;
 }
 
@@ -487,41 +480,30 @@ int itd_levels_stream_create(itd_stream **out, int device_id, int64_t block, int
     hipError_t hrc = hipSuccess;
     if (3 * block <= kResidentMax) {
         // the one-launch geometry of a three-block window (k_resident's classes) and its window of by-rank knot slots
-        const int n3 = (int)(3 * block);
-        int cw = std::min(resident_auto_window(n3), resident_pad(n3));
-        while (resident_lds_bytes(n3, cw) > kResidentLdsMax) cw -= 64;
-        const int cls = n3 <= 256 ? 0 : n3 <= 512 ? 1 : n3 <= 1024 ? 2 : n3 <= 2048 ? 3 : n3 <= 4096 ? 4 : 5;
-        s->cw = cw;
-        s->lds = resident_lds_bytes(n3, cw);
-        s->threads = cls == 5 ? 1024 : 64 << cls;
-        s->fn = cls == 0 ? reinterpret_cast<const void *>(&k_stream_levels<64, 4>)
-              : cls == 1 ? reinterpret_cast<const void *>(&k_stream_levels<128, 4>)
-              : cls == 2 ? reinterpret_cast<const void *>(&k_stream_levels<256, 4>)
-              : cls == 3 ? reinterpret_cast<const void *>(&k_stream_levels<512, 4>)
-              : cls == 4 ? reinterpret_cast<const void *>(&k_stream_levels<1024, 4>)
-                         : reinterpret_cast<const void *>(&k_stream_levels<1024, 8>);
-        hrc = hipFuncSetAttribute(s->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kResidentLdsMax);
+        const WgClass wc = wg_class((int)(3 * block));
+        const void *const inst[6] = {   // by size class
+            reinterpret_cast<const void *>(&k_stream_levels<64, 4>),   reinterpret_cast<const void *>(&k_stream_levels<128, 4>),
+            reinterpret_cast<const void *>(&k_stream_levels<256, 4>),  reinterpret_cast<const void *>(&k_stream_levels<512, 4>),
+            reinterpret_cast<const void *>(&k_stream_levels<1024, 4>), reinterpret_cast<const void *>(&k_stream_levels<1024, 8>)};
+        s->cw = wc.cw; s->lds = wc.lds; s->threads = wc.threads; s->fn = inst[wc.cls];
+        hrc = allow_lds(s->eng, s->fn, kResidentLdsMax);
     } else {
         s->seq = 1;                 // the window does not fit one workgroup's LDS: the launch sequence
     }
     const size_t C = (size_t)channels, L = (size_t)block, R = (size_t)levels + 1;
     const size_t ring_b = C * R * 5 * L * sizeof(double), delay_b = C * ((size_t)levels * R / 2) * L * sizeof(double);
-    if (hrc == hipSuccess) hrc = hipMalloc((void **)&s->ring, ring_b);
-    if (hrc == hipSuccess) hrc = hipMalloc((void **)&s->delay, delay_b);
-    if (hrc == hipSuccess) hrc = hipMalloc((void **)&s->eflags, C * R * 4);
-    if (hrc == hipSuccess) hrc = hipMalloc((void **)&s->d_status, 64);
+    if (hrc == hipSuccess) hrc = s->ring.alloc(ring_b);
+    if (hrc == hipSuccess) hrc = s->delay.alloc(delay_b);
+    if (hrc == hipSuccess) hrc = s->eflags.alloc(C * R * 4);
+    if (hrc == hipSuccess) hrc = s->d_status.alloc(64);
     if (hrc == hipSuccess) hrc = hipMemset(s->d_status, 0, 64);
     // the host form's staging: [C][L] in, [C][M+1][L] rows and [C] flags out
-    if (hrc == hipSuccess) hrc = hipMalloc((void **)&s->d_in, C * L * sizeof(double));
-    if (hrc == hipSuccess) hrc = hipMalloc((void **)&s->d_out, C * R * L * sizeof(double));
-    if (hrc == hipSuccess) hrc = hipMalloc((void **)&s->d_exact, C);
-    if (hrc == hipSuccess) hrc = hipHostMalloc((void **)&s->h_in, C * L * sizeof(double));
-    if (hrc == hipSuccess) hrc = hipHostMalloc((void **)&s->h_out, C * R * L * sizeof(double));
-    if (hrc == hipSuccess) hrc = hipHostMalloc((void **)&s->h_exact, C);
-    if (hrc == hipSuccess) {
-        poison(s->ring, ring_b); poison(s->delay, delay_b); poison(s->eflags, C * R * 4);
-        poison(s->d_in, C * L * sizeof(double)); poison(s->d_out, C * R * L * sizeof(double)); poison(s->d_exact, C);
-    }
+    if (hrc == hipSuccess) hrc = s->d_in.alloc(C * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->d_out.alloc(C * R * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->d_exact.alloc(C);
+    if (hrc == hipSuccess) hrc = s->h_in.alloc(C * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->h_out.alloc(C * R * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->h_exact.alloc(C);
     if (hrc == hipSuccess) hrc = hipDeviceSynchronize();     // (the fills ran on the null stream)
     if (hrc != hipSuccess) {
         const bool oom = hrc == hipErrorOutOfMemory;

@@ -27,11 +27,7 @@ fft::Side side(double *p, int64_t es, int64_t bs, int64_t ss, int per, int real)
 // T transforms of n <= 8192 points, nx sub-transforms per transform (blockIdx.x: the four-step's column / row index)
 int fft_lds(itd_engine *e, fft::Side in, fft::Side out, int n, int nx, int64_t T, int inverse, int64_t tw_m, double scale, hipStream_t st)
 {
-    if (!e->fft_attr) {
-        HIP_TRY(e, hipFuncSetAttribute(reinterpret_cast<const void *>(&fft::k_fft_lds<1024>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       fft::kLdsMax * (int)sizeof(double2)));
-        e->fft_attr = true;
-    }
+    HIP_TRY(e, allow_lds(e, reinterpret_cast<const void *>(&fft::k_fft_lds<1024>), fft::kLdsMax * sizeof(double2)));
     fft::LdsArgs a;
     a.in = in; a.out = out; a.n = n; a.inverse = inverse; a.tw_m = tw_m; a.scale = scale;
     for (int64_t t0 = 0; t0 < T; t0 += kMaxGridY) {
@@ -67,7 +63,7 @@ int fft_four_step(itd_engine *e, fft::Side in, fft::Side out, int64_t n, int64_t
 {
     const int64_t n2 = n / n1;
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(T, kFftChunkBytes / (n * 16)));
-    int rc = grow(e, &e->d_fft_y, &e->fft_y_bytes, (size_t)chunk * (size_t)n * 16);
+    int rc = grow(e, e->d_fft_y, (size_t)chunk * (size_t)n * 16);
     if (rc) return rc;
     for (int64_t t0 = 0; t0 < T; t0 += chunk) {
         const int64_t tc = std::min(chunk, T - t0);
@@ -96,7 +92,7 @@ int fft_bluestein(itd_engine *e, fft::Side in, fft::Side out, int64_t n, int64_t
     int rc;
     if (e->fft_chirp_n != n) {          // the chirp's spectrum, once per n
         e->fft_chirp_n = 0;
-        rc = grow(e, &e->d_fft_b, &e->fft_b_bytes, (size_t)M * 16);
+        rc = grow(e, e->d_fft_b, (size_t)M * 16);
         if (rc) return rc;
         fft::k_blue_chirp<<<(unsigned)((M + 255) / 256), 256, 0, st>>>(n, M, (double2 *)e->d_fft_b);
         fft::Side bs = side((double *)e->d_fft_b, 1, 0, M, 1, 0);
@@ -105,7 +101,7 @@ int fft_bluestein(itd_engine *e, fft::Side in, fft::Side out, int64_t n, int64_t
         e->fft_chirp_n = n;
     }
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(T, kFftChunkBytes / (M * 16)));
-    rc = grow(e, &e->d_fft_a, &e->fft_a_bytes, (size_t)chunk * (size_t)M * 16);
+    rc = grow(e, e->d_fft_a, (size_t)chunk * (size_t)M * 16);
     if (rc) return rc;
     double2 *A = (double2 *)e->d_fft_a;
     for (int64_t t0 = 0; t0 < T; t0 += chunk) {
@@ -140,7 +136,7 @@ int fft_exec(itd_engine *e, fft::Side in, fft::Side out, int64_t n, int64_t T, i
 int select_rows(itd_engine *e, fft::Side in, int64_t n, int64_t T, bool valid, fft::Side out, int32_t *rec, hipStream_t st)
 {
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(T, kMaxGridY), kFftChunkBytes / (n * 16)));
-    int rc = grow(e, &e->d_fft_x, &e->fft_x_bytes, (size_t)chunk * (size_t)n * 16);
+    int rc = grow(e, e->d_fft_x, (size_t)chunk * (size_t)n * 16);
     if (rc) return rc;
     for (int64_t t0 = 0; t0 < T; t0 += chunk) {
         const int64_t tc = std::min(chunk, T - t0);
@@ -169,7 +165,7 @@ int select_entry(itd_engine *e, const double *rows_dev, int64_t n, int64_t rows,
     hipStream_t st = stream_of(e, stream);
     int32_t *rec = rec_dev;
     if (!rec) {
-        const int rc = grow(e, &e->d_fft_rec, &e->fft_rec_bytes, (size_t)rows * 32);
+        const int rc = grow(e, e->d_fft_rec, (size_t)rows * 32);
         if (rc) return rc;
         rec = (int32_t *)e->d_fft_rec;
     }
@@ -198,7 +194,7 @@ int fourier_plan(itd_engine *e, int64_t n, double sample_rate, int32_t bands, co
     e->fplan_idx.assign(idx_host, idx_host + bands);
     std::vector<int32_t> narrow(total);
     for (size_t j = 0; j < total; ++j) narrow[j] = (int32_t)knots_host[j];
-    int rc = grow(e, &e->d_fplan, &e->fplan_bytes, total * sizeof(int32_t));
+    int rc = grow(e, e->d_fplan, total * sizeof(int32_t));
     if (rc) return rc;
     HIP_TRY(e, hipMemcpy(e->d_fplan, narrow.data(), total * sizeof(int32_t), hipMemcpyHostToDevice));
     e->fplan_n = n;
@@ -210,16 +206,13 @@ int fourier_plan(itd_engine *e, int64_t n, double sample_rate, int32_t bands, co
 int arena_reserve(itd_engine *e, int64_t n, int64_t count, hipStream_t st)
 {
     const size_t want = (size_t)count * (size_t)n * sizeof(double);
-    if (want <= e->fmodes_bytes) return ITD_OK;
-    const size_t nb = std::max(want, 2 * e->fmodes_bytes);
-    double *p = nullptr;
-    const hipError_t hrc = hipMalloc((void **)&p, nb);
+    if (want <= e->d_fmodes.bytes()) return ITD_OK;
+    Buf<double> p;                  // (the new block is the arena only once the live modes are in it)
+    const hipError_t hrc = p.alloc(std::max(want, 2 * e->d_fmodes.bytes()));
     if (hrc != hipSuccess) { (void)hipGetLastError(); fail_hip(e, hrc, "hipMalloc(mode arena)"); return ITD_ERR_NOMEM; }
     if (e->fmodes_count) HIP_TRY(e, hipMemcpyAsync(p, e->d_fmodes, (size_t)e->fmodes_count * (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
     HIP_TRY(e, hipStreamSynchronize(st));
-    (void)hipFree(e->d_fmodes);
-    e->d_fmodes = p;
-    e->fmodes_bytes = nb;
+    e->d_fmodes = std::move(p);
     return ITD_OK;
 }
 
@@ -230,7 +223,7 @@ int fourier_cascade(itd_engine *e, const double *x, int64_t n, int32_t B, int64_
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t b_sig = al((size_t)B * n * 8), b_rows = al((size_t)B * R * n * 8), b_modes = al((size_t)B * K * n * 8);
     const size_t b_rec = al((size_t)B * K * 32), b_hits = al((size_t)B * K * 4), b_int = al((size_t)B * 4);
-    int rc = grow(e, &e->d_fc, &e->fc_bytes, 3 * b_sig + b_rows + b_modes + b_rec + b_hits + 2 * b_int);
+    int rc = grow(e, e->d_fc, 3 * b_sig + b_rows + b_modes + b_rec + b_hits + 2 * b_int);
     if (rc) return rc;
     char *p = (char *)e->d_fc;
     double *wsig = (double *)p; p += b_sig;
@@ -384,7 +377,7 @@ int itd_fourier_cascade_host_f64(itd_engine *e, const double *x_host, int64_t n,
     if (rc) return rc;
     const size_t xb = (size_t)batch * n * 8, rb = xb * ((size_t)bands + 1), ab = lean ? xb * (size_t)bands : 0;
     // staging of its own: the engine's d_io_* buffers hold what other host forms leave for later (ITD().itd()'s baselines)
-    if ((rc = grow(e, &e->d_fio, &e->fio_bytes, xb + rb + ab))) return rc;
+    if ((rc = grow(e, e->d_fio, xb + rb + ab))) return rc;
     double *d_x = (double *)e->d_fio, *d_rows = d_x + xb / 8, *d_acc = lean ? d_rows + rb / 8 : nullptr;
     hipStream_t st = e->own_stream;
     HIP_TRY(e, hipMemcpyAsync(d_x, x_host, xb, hipMemcpyHostToDevice, st));
