@@ -115,6 +115,21 @@ int itd_decompose_f32(itd_engine *e, const float *x_dev, int64_t n, int32_t batc
 int itd_decompose_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t batch, int64_t x_stride,
                       int32_t max_iteration, double *rows_dev, double *baselines_dev, void *stream);
 
+/* The same decomposition with its rows delivered in float32: rows_dev is [batch][max_iteration+2][n] float32, densely packed.
+ * Every element is the element itd_decompose_f32 / _f64 delivers, converted to float32 (round to nearest even; values below the
+ * float32 normal range become subnormals, values beyond it +-inf) — rotation rows, the natural-stop residual (a copied baseline),
+ * the "Out of time!" residual (rotation + baseline formed in float64, then rounded) and the all-zero row of a stop at c = 0 alike.
+ * The arithmetic is the float64 entries' own: each value is rounded once, where it is stored, and nothing reads a row back (the
+ * baselines travel in the engine's float64 ping-pong pair, exactly as with baselines_dev == NULL — these entries offer no
+ * baselines).  Row traffic and the result buffer halve.  In every other respect the contract is that of itd_decompose_f32 / _f64:
+ * no host synchronisation, itd_get_summary finalises the call (any repeat writes float32 into the same buffer) and reports the same
+ * summary as the float64 call, itd_set_valid_flags / itd_set_device_repair, the NaN-input modes and the timing records apply.
+ * Calls of either row type may follow each other on one engine in any order. */
+int itd_decompose_rows32_f32(itd_engine *e, const float *x_dev, int64_t n, int32_t batch, int64_t x_stride,
+                             int32_t max_iteration, float *rows_dev, void *stream);
+int itd_decompose_rows32_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t batch, int64_t x_stride,
+                             int32_t max_iteration, float *rows_dev, void *stream);
+
 /* Stream-ordered consumers (a kernel of the caller's enqueued behind the decomposition, a replayed hipGraph).
  * The engine runs optimistic forms first — the fused sparse levels, the fused level 0, the resident form of short signals — each
  * of which either delivers the reference's result or REPORTS that it cannot (tied / quantised / very smooth input, non-finite
@@ -299,6 +314,12 @@ int itd_decompose_host_f64(itd_engine *e, const double *x_host, int64_t n, int32
 int itd_decompose_host_f32(itd_engine *e, const float *x_host, int64_t n, int32_t max_iteration,
                            double *rows_host, double *baselines_host, int32_t *n_rows, int32_t *n_baselines,
                            int32_t *stop_reason, int64_t *knot_counts);
+/* ... with float32 rows (itd_decompose_rows32_*): rows_host is [max_iteration+2][n] float32, the copy back is half as long.  No
+ * baselines: itd_set_host_keep_baselines is ignored by these calls (itd_get_last_baselines_host returns ITD_ERR_NOT_RUN after one). */
+int itd_decompose_rows32_host_f32(itd_engine *e, const float *x_host, int64_t n, int32_t max_iteration, float *rows_host,
+                                  int32_t *n_rows, int32_t *stop_reason, int64_t *knot_counts);
+int itd_decompose_rows32_host_f64(itd_engine *e, const double *x_host, int64_t n, int32_t max_iteration, float *rows_host,
+                                  int32_t *n_rows, int32_t *stop_reason, int64_t *knot_counts);
 
 /* The reference keeps the baselines of the last run on the instance (ITD.py:413-414,423-424) but most callers only look at
  * the returned rows: with itd_set_host_keep_baselines(e, 1) a host-form call with baselines_host == NULL still computes the

@@ -33,9 +33,13 @@ ABI = {
     "itd_shard_scatter": (_INT, [_P, _P, _I64, _I64, _I32, _I32, _I32, _I32, _P, _P]),
     "itd_decompose_f32": (_INT, [_P, _P, _I64, _I32, _I64, _I32, _P, _P, _P]),
     "itd_decompose_f64": (_INT, [_P, _P, _I64, _I32, _I64, _I32, _P, _P, _P]),
+    "itd_decompose_rows32_f32": (_INT, [_P, _P, _I64, _I32, _I64, _I32, _P, _P]),
+    "itd_decompose_rows32_f64": (_INT, [_P, _P, _I64, _I32, _I64, _I32, _P, _P]),
     "itd_get_summary": (_INT, [_P, _P, _P, _P, _P, _P]),
     "itd_decompose_host_f64": (_INT, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
     "itd_decompose_host_f32": (_INT, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
+    "itd_decompose_rows32_host_f32": (_INT, [_P, _P, _I64, _I32, _P, _P, _P, _P]),
+    "itd_decompose_rows32_host_f64": (_INT, [_P, _P, _I64, _I32, _P, _P, _P, _P]),
     "itd_baseline_extract_f64": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _P]),
     "itd_baseline_extract_f32": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _P]),
     "itd_baseline_extract_host_f64": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _P]),

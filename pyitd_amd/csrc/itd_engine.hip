@@ -153,10 +153,23 @@ static_assert(FormPolicy::kRangeTiles == kKcTiles && FormPolicy::kFailCapacity =
               "itd_policy.hpp restates the fused levels' geometry and fail bits");
 }  // namespace
 
+// A call's result rows: the caller's buffer and its element type (float64, or float32 for the itd_decompose_rows32_* entries).  The
+// type is a property of the call: it travels with the pointer through every form and every repeat, which therefore writes the same
+// type into the same buffer as the first attempt.  Strides and offsets count elements.
+struct Rows {
+    void *p = nullptr; bool f32 = false;
+    Rows() {}
+    Rows(double *d) : p(d) {}
+    Rows(float *f) : p(f), f32(true) {}
+    Rows(void *q, bool is32) : p(q), f32(is32) {}
+    size_t esz() const { return f32 ? sizeof(float) : sizeof(double); }
+    Rows at(int64_t elems) const { return Rows(static_cast<char *>(p) + elems * (int64_t)esz(), f32); }
+};
+
 // The record of the last decomposition enqueued: what itd_get_summary reads back, repeats or repairs, and itd_get_timing, ... refer to
 struct LastCall {
     int32_t batch = 0, m = 0; int64_t n = 0; hipStream_t stream = nullptr;                              // the call's arguments
-    const void *x = nullptr; bool x_f32 = false; int64_t x_stride = 0; double *rows = nullptr, *bases = nullptr;
+    const void *x = nullptr; bool x_f32 = false; int64_t x_stride = 0; Rows rows; double *bases = nullptr;
     bool fused = false, resident = false;   // fused level 0; the one-workgroup form (k_resident)
     bool nan_input = false;        // the NaN-input repeat (k_nan_level0): its results follow the reference
     bool kf = false;               // fused sparse levels whose verdict is still to be drawn
@@ -407,7 +420,7 @@ hipError_t launch_timed(itd_engine *e, const void *fn, dim3 grid, dim3 block, vo
 template <typename Tin>
 struct DecomposePlan {
     const Tin *x; int64_t x_stride, n, rows_stride; int32_t M;
-    double *rows, *bases;             // bases: the caller's baselines buffer, or NULL (the baselines live in the engine's rotating slots)
+    Rows rows; double *bases;         // bases: the caller's baselines buffer, or NULL (the baselines live in the engine's rotating slots)
     bool fuse0, nan_input, kf;        // fused level 0; the NaN-input repeat (k_nan_level0); fused sparse levels
     int L0, cap, Mk;                  // fused levels L0 .. Mk + 1; cap != 0: levels cap .. M + 1 one launch each behind them
     int n_tiles, n_groups;
@@ -422,7 +435,7 @@ struct ChunkBufs {
     const itd_engine *e;
     int nb, n_tiles; int64_t n, rows_stride;
     hipStream_t st;
-    SigState *state; double *rows, *bases, *pp; int32_t *gsum, *counts; TileRec *recs; unsigned long long *near;
+    SigState *state; Rows rows; double *bases, *pp; int32_t *gsum, *counts; TileRec *recs; unsigned long long *near;
     int32_t *gs(int level) const { return gsum + (int64_t)(level % 3) * e->gsum_third; }      // group sums rotate by level % 3,
     int32_t *cnt(int level) const { return counts + (int64_t)(level & 1) * e->tiles_half; }   // counts and records by level parity
     TileRec *rec(int level) const { return recs + (int64_t)(level & 1) * e->tiles_half; }
@@ -433,18 +446,18 @@ struct ChunkBufs {
 
 // one level launch of a chunk (k_extract): level j's input xin -> rotation rows[j] and baseline j; level j's counts, records and group
 // sums -> level j + 1's (TIES: the launch in front of the fused sparse levels also flags the tiles of its baseline that hold a near tie)
-template <typename TIN, bool FIN, int CAPK, int KTW = kTilesPerWave, bool FUSE = false, bool TIES = false>
+template <typename TIN, bool FIN, int CAPK, int KTW = kTilesPerWave, bool FUSE = false, bool TIES = false, typename TROW = double>
 hipError_t launch_extract(itd_engine *e, const ChunkBufs &c, const TIN *xin, int64_t xs, int j, int pair)
 {
     const TIN *a_x = xin; int64_t a_xs = xs, a_n = c.n, a_rs = c.rows_stride, a_bs = c.base_stride();
     int a_nt = c.n_tiles, a_b = c.nb, a_lvl = j, a_keep = 0;
     const int32_t *a_ci = c.cnt(j), *a_gi = c.gs(j); int32_t *a_co = c.cnt(j + 1), *a_go = c.gs(j + 1), *a_gc = c.gs(j + 2);
     const TileRec *a_ri = c.rec(j); TileRec *a_ro = c.rec(j + 1);
-    double *a_rot = c.rows + (int64_t)j * (c.n + ITD_ROW_PAD), *a_bas = c.base(j);
+    void *a_rot = c.rows.at((int64_t)j * (c.n + ITD_ROW_PAD)).p; double *a_bas = c.base(j);
     SigState *a_st = c.state; unsigned long long *a_tie = TIES ? c.near : nullptr;
     void *args[] = {&a_x, &a_xs, &a_n, &a_nt, &a_b, &a_ci, &a_co, &a_ri, &a_ro, &a_gi, &a_go, &a_gc, &a_rot, &a_rs,
                     &a_bas, &a_bs, &a_st, &a_lvl, &a_keep, &a_tie};
-    return launch_timed(e, reinterpret_cast<const void *>(&k_extract<TIN, T, FIN, CAPK, KTW, FUSE, TIES>),
+    return launch_timed(e, reinterpret_cast<const void *>(&k_extract<TIN, T, FIN, CAPK, KTW, FUSE, TIES, TROW>),
                         dim3((c.n_tiles + KTW - 1) / KTW, c.nb), dim3(kWave), args, c.st, pair);
 }
 
@@ -480,7 +493,7 @@ template <typename Tin>
 int run_chunk(itd_engine *e, const DecomposePlan<Tin> &p, const int b0, const int nb, const hipStream_t cst)
 {
     const int64_t n = p.n, pp3 = 3 * e->pp_pitch;
-    const ChunkBufs c{e, nb, p.n_tiles, n, p.rows_stride, cst, p.state + b0, p.rows + (int64_t)b0 * p.rows_stride,
+    const ChunkBufs c{e, nb, p.n_tiles, n, p.rows_stride, cst, p.state + b0, p.rows.at((int64_t)b0 * p.rows_stride),
                       p.bases ? p.bases + (int64_t)b0 * p.rows_stride : nullptr, e->d_pp + (int64_t)b0 * pp3,
                       p.gsum + (int64_t)b0 * p.n_groups * kGsumPitch, e->d_counts + (int64_t)b0 * p.n_tiles,
                       e->d_recs + (int64_t)b0 * p.n_tiles, p.kf ? e->kf.nearw + (size_t)b0 * p.n_tiles * 8 : nullptr};
@@ -488,7 +501,8 @@ int run_chunk(itd_engine *e, const DecomposePlan<Tin> &p, const int b0, const in
     double *xm_c = c.pp + 2 * e->pp_pitch;   // NaN-input repeat: the mutated signal, one per signal at the slots' stride
     const dim3 blk(kWave);
     // what k_finalize needs (the knot side as well, for the first fused level: its gsum is set there): the rows, the baselines, the other set
-    KfFin fin{c.rows, p.rows_stride, c.bases ? c.bases : c.pp, c.base_stride(), c.bases ? n : e->pp_pitch, c.bases ? 0 : 3, nullptr,
+    const bool r32 = c.rows.f32;     // float32 rows: the same launches, each in its float32 store form
+    KfFin fin{c.rows.p, p.rows_stride, c.bases ? c.bases : c.pp, c.base_stride(), c.bases ? n : e->pp_pitch, c.bases ? 0 : 3, nullptr,
               p.other_state + b0, p.other_gsum + (int64_t)b0 * p.n_groups * kGsumPitch, e->gsum_third};
     // the level launches ja .. jb: extraction j + 1, input = the level-j signal, rotation -> rows[j], baseline -> baseline j
     auto levels = [&](const int ja, const int jb) -> int {
@@ -498,13 +512,16 @@ int run_chunk(itd_engine *e, const DecomposePlan<Tin> &p, const int b0, const in
             const double *in = j ? c.base(j - 1) : nullptr;
             const int64_t is = c.base_stride();
             hipError_t rc;
+#define ITD_LX(TIN, FIN, CAPK, KTW, FUSE, TIES, ...) \
+    (r32 ? launch_extract<TIN, FIN, CAPK, KTW, FUSE, TIES, float>(__VA_ARGS__) : launch_extract<TIN, FIN, CAPK, KTW, FUSE, TIES, double>(__VA_ARGS__))
             if (j == 0) {   // never the last level: M >= 0
-                if (p.nan_input) rc = launch_extract<double, false, kRankCap0>(e, c, xm_c, pp3, 0, pair);
-                else if (p.fuse0) rc = launch_extract<Tin, false, kRankCap0, kFuse0TilesPerWave, true>(e, c, xc, p.x_stride, 0, pair);
-                else rc = launch_extract<Tin, false, kRankCap0>(e, c, xc, p.x_stride, 0, pair);
-            } else if (final_level) rc = launch_extract<double, true, kRankCap>(e, c, in, is, j, pair);
-            else if (p.kf && j == p.L0 - 1) rc = launch_extract<double, false, kRankCap, kTilesPerWave, false, true>(e, c, in, is, j, pair);
-            else rc = launch_extract<double, false, kRankCap>(e, c, in, is, j, pair);
+                if (p.nan_input) rc = ITD_LX(double, false, kRankCap0, kTilesPerWave, false, false, e, c, xm_c, pp3, 0, pair);
+                else if (p.fuse0) rc = ITD_LX(Tin, false, kRankCap0, kFuse0TilesPerWave, true, false, e, c, xc, p.x_stride, 0, pair);
+                else rc = ITD_LX(Tin, false, kRankCap0, kTilesPerWave, false, false, e, c, xc, p.x_stride, 0, pair);
+            } else if (final_level) rc = ITD_LX(double, true, kRankCap, kTilesPerWave, false, false, e, c, in, is, j, pair);
+            else if (p.kf && j == p.L0 - 1) rc = ITD_LX(double, false, kRankCap, kTilesPerWave, false, true, e, c, in, is, j, pair);
+            else rc = ITD_LX(double, false, kRankCap, kTilesPerWave, false, false, e, c, in, is, j, pair);
+#undef ITD_LX
             if (rc != hipSuccess) return fail_hip(e, rc, "hipExtLaunchKernel(k_extract)");
         }
         return ITD_OK;
@@ -514,9 +531,12 @@ int run_chunk(itd_engine *e, const DecomposePlan<Tin> &p, const int b0, const in
         // blocks per signal: a thread of the row fix-up moves 8 samples (four 16-byte accesses) before the grid is widened
         const int fb = (int)std::min<int64_t>(std::max<int64_t>((n + 8 * kFinalizeThreads - 1) / (8 * kFinalizeThreads), 1), 1024);
         const int jf = p.M + 2;      // the level whose input is pending
-        k_finalize<<<dim3(fb, nb), kFinalizeThreads, 0, cst>>>(fin.rows, fin.rows_stride, n, fin.bases, fin.bases_stride, fin.bases_row_pitch,
-                                                               fin.bases_rotate, c.gs(jf), p.n_tiles, jf, c.state, fin.other_state,
-                                                               fin.other_gsum, fin.other_third);
+        if (r32) k_finalize<float><<<dim3(fb, nb), kFinalizeThreads, 0, cst>>>(static_cast<float *>(fin.rows), fin.rows_stride, n, fin.bases, fin.bases_stride,
+                                                                               fin.bases_row_pitch, fin.bases_rotate, c.gs(jf), p.n_tiles, jf, c.state,
+                                                                               fin.other_state, fin.other_gsum, fin.other_third);
+        else k_finalize<double><<<dim3(fb, nb), kFinalizeThreads, 0, cst>>>(static_cast<double *>(fin.rows), fin.rows_stride, n, fin.bases, fin.bases_stride,
+                                                                            fin.bases_row_pitch, fin.bases_rotate, c.gs(jf), p.n_tiles, jf, c.state,
+                                                                            fin.other_state, fin.other_gsum, fin.other_third);
     };
 
     if (p.nan_input) {
@@ -544,7 +564,8 @@ int run_chunk(itd_engine *e, const DecomposePlan<Tin> &p, const int b0, const in
         KfFin a_f = fin;
         a_f.gsum = c.gs(p.L0);
         void *args[] = {&a_w, &a_f, &a_xl, &a_ls, &a_n, &a_m, &a_c, &a_r, &a_st};
-        HIP_TRY(e, launch_timed(e, reinterpret_cast<const void *>(&k_kf_knots<T>), dim3((unsigned)w.wgs * (unsigned)nb), dim3(kKcThreads),
+        const void *knots_fn = r32 ? reinterpret_cast<const void *>(&k_kf_knots<T, float>) : reinterpret_cast<const void *>(&k_kf_knots<T>);
+        HIP_TRY(e, launch_timed(e, knots_fn, dim3((unsigned)w.wgs * (unsigned)nb), dim3(kKcThreads),
                                 args, cst, time_slot(e, ITD_TIME_KF_KNOTS)));
     }
     if (e->fault_kind >= 0 && (e->fault_kind <= 5 || e->fault_kind == 8) && e->fault_level >= p.L0 && e->fault_level - p.L0 < w.nlev &&
@@ -552,9 +573,11 @@ int run_chunk(itd_engine *e, const DecomposePlan<Tin> &p, const int b0, const in
         k_kf_fault<<<1, 64, 0, cst>>>(w, e->fault_sig - b0, e->fault_kind, e->fault_level - p.L0, e->fault_where, e->fault_slot & 0xffff, e->fault_delta);
     {   // the sample pass: verifies the knot side's tables and writes the rows
         KfWs a_w = w; const double *a_xl = xl; int64_t a_xs = xl_stride, a_n = n, a_rs = p.rows_stride, a_bs = p.rows_stride;
-        const TileRec *a_rec = c.rec(p.L0); double *a_rows = c.rows, *a_bases = c.bases;
+        const TileRec *a_rec = c.rec(p.L0); void *a_rows = c.rows.p; double *a_bases = c.bases;
         void *args[] = {&a_w, &a_xl, &a_xs, &a_n, &a_rec, &a_rows, &a_rs, &a_bases, &a_bs};
-        const void *apply_fn = p.cap ? (c.bases ? reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, true, true>) : reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, true>))
+        // (float32 rows come without the caller's baselines: two forms of the sample pass, not four)
+        const void *apply_fn = r32 ? (p.cap ? reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, true, float>) : reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, false, float>)) :
+                               p.cap ? (c.bases ? reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, true, true>) : reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, true>))
                                      : (c.bases ? reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, true, false>) : reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, false>));
         HIP_TRY(e, launch_timed(e, apply_fn, dim3(p.n_tiles + kf_check_blocks(w.wgs), nb), blk, args, cst, time_slot(e, ITD_TIME_KF_APPLY)));
     }
@@ -597,7 +620,7 @@ int claim_state_set(itd_engine *e, int32_t batch, int64_t gs_extent, bool nan_in
 
 // The record of the call just enqueued (e->last): its arguments, every form off; the caller sets what its form adds
 template <typename Tin>
-LastCall &record_call(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int64_t x_stride, int32_t M, double *rows, double *bases,
+LastCall &record_call(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int64_t x_stride, int32_t M, Rows rows, double *bases,
                       hipStream_t st)
 {
     LastCall &c = e->last;
@@ -610,7 +633,7 @@ LastCall &record_call(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int
 
 template <typename Tin>
 int enqueue_decompose(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int64_t x_stride, int32_t M,
-                      double *rows, double *bases_user, hipStream_t st, bool fuse0, bool nan_input = false, bool kf = false,
+                      Rows rows, double *bases_user, hipStream_t st, bool fuse0, bool nan_input = false, bool kf = false,
                       const int32_t *repair_need = nullptr)
 {
     // repair_need: the device-side repair of the call just enqueued (itd_set_device_repair): the same call again, level by level,
@@ -735,7 +758,7 @@ inline WgClass wg_class(int n, int window = 0)
 // otherwise; itd_get_summary then repeats the call level by level.  The kernel initialises the states it works on itself
 // and leaves the other set's states as k_finalize would (the group sums are not touched).
 template <typename Tin>
-int enqueue_resident(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int64_t x_stride, int32_t M, double *rows,
+int enqueue_resident(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int64_t x_stride, int32_t M, Rows rows,
                      double *bases_user, hipStream_t st)
 {
     const int64_t R = (int64_t)M + 2;
@@ -747,11 +770,14 @@ int enqueue_resident(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int6
         HIP_TRY(e, hipMemset2DAsync(bases_user + (R - 1) * n, (size_t)rows_stride * sizeof(double), 0,
                                     (size_t)n * sizeof(double), (size_t)batch, st));
     const WgClass wc = wg_class((int)n, e->resident_window);
-    const void *const inst[6] = {   // by size class
+    const void *const inst[2][6] = {{   // by row type and size class
         reinterpret_cast<const void *>(&k_resident<Tin, 64, 4>),   reinterpret_cast<const void *>(&k_resident<Tin, 128, 4>),
         reinterpret_cast<const void *>(&k_resident<Tin, 256, 4>),  reinterpret_cast<const void *>(&k_resident<Tin, 512, 4>),
-        reinterpret_cast<const void *>(&k_resident<Tin, 1024, 4>), reinterpret_cast<const void *>(&k_resident<Tin, 1024, 8>)};
-    const void *fn = inst[wc.cls];
+        reinterpret_cast<const void *>(&k_resident<Tin, 1024, 4>), reinterpret_cast<const void *>(&k_resident<Tin, 1024, 8>)}, {
+        reinterpret_cast<const void *>(&k_resident<Tin, 64, 4, float>),   reinterpret_cast<const void *>(&k_resident<Tin, 128, 4, float>),
+        reinterpret_cast<const void *>(&k_resident<Tin, 256, 4, float>),  reinterpret_cast<const void *>(&k_resident<Tin, 512, 4, float>),
+        reinterpret_cast<const void *>(&k_resident<Tin, 1024, 4, float>), reinterpret_cast<const void *>(&k_resident<Tin, 1024, 8, float>)}};
+    const void *fn = inst[rows.f32 ? 1 : 0][wc.cls];
     const hipError_t arc = allow_lds(e, fn, kResidentLdsMax);
     if (arc != hipSuccess) {     // a device / runtime that does not grant it: this engine runs level by level from now on
         (void)hipGetLastError();
@@ -761,7 +787,7 @@ int enqueue_resident(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int6
     }
     const Tin *a_x = x; int64_t a_xs = x_stride, a_rs = rows_stride, a_bs = rows_stride;
     int a_n = (int)n, a_m = M, a_cw = wc.cw, a_nf = e->nan_input_mode == ITD_NAN_INPUT_FOLLOW ? 1 : 0;
-    double *a_rows = rows, *a_bases = bases_user;
+    void *a_rows = rows.p; double *a_bases = bases_user;
     SigState *a_st = set_state, *a_ot = other_state;
     void *args[] = {&a_x, &a_xs, &a_n, &a_m, &a_cw, &a_nf, &a_rows, &a_rs, &a_bases, &a_bs, &a_st, &a_ot};
     HIP_TRY(e, hipLaunchKernel(fn, dim3((unsigned)batch), dim3((unsigned)wc.threads), args, wc.lds, st));
@@ -777,7 +803,7 @@ int enqueue_resident(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int6
 }
 
 template <typename Tin>
-int enqueue_any(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int64_t x_stride, int32_t M, double *rows,
+int enqueue_any(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int64_t x_stride, int32_t M, Rows rows,
                 double *bases_user, hipStream_t st)
 {
     int rc;
@@ -1103,12 +1129,31 @@ int itd_decompose_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t bat
     return enqueue_any<double>(e, x_dev, n, batch, x_stride, max_iteration, rows_dev, baselines_dev, stream_of(e, stream));
 }
 
+// float32 rows: the same call in every respect, each row element the float64 one rounded once at its store; no caller's baselines
+int itd_decompose_rows32_f32(itd_engine *e, const float *x_dev, int64_t n, int32_t batch, int64_t x_stride,
+                             int32_t max_iteration, float *rows_dev, void *stream)
+{
+    int rc = check_args(e, x_dev, n, batch, x_stride, max_iteration, rows_dev);
+    if (rc) return rc;
+    DevGuard g(e->device);
+    return enqueue_any<float>(e, x_dev, n, batch, x_stride, max_iteration, rows_dev, nullptr, stream_of(e, stream));
+}
+
+int itd_decompose_rows32_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t batch, int64_t x_stride,
+                             int32_t max_iteration, float *rows_dev, void *stream)
+{
+    int rc = check_args(e, x_dev, n, batch, x_stride, max_iteration, rows_dev);
+    if (rc) return rc;
+    DevGuard g(e->device);
+    return enqueue_any<double>(e, x_dev, n, batch, x_stride, max_iteration, rows_dev, nullptr, stream_of(e, stream));
+}
+
 namespace {
 // The recorded call `c` again, level by level unless fuse0, on its signals b0 .. b0 + batch - 1 into their rows (and baselines)
 int enqueue_again(itd_engine *e, const LastCall c, int b0, int32_t batch, bool fuse0, bool nan_input)
 {
     const int64_t rs = (int64_t)(c.m + 2) * c.n;
-    double *rows = c.rows + (int64_t)b0 * rs, *bases = c.bases ? c.bases + (int64_t)b0 * rs : nullptr;
+    const Rows rows = c.rows.at((int64_t)b0 * rs); double *bases = c.bases ? c.bases + (int64_t)b0 * rs : nullptr;
     return c.x_f32 ? enqueue_decompose<float>(e, (const float *)c.x + (int64_t)b0 * c.x_stride, c.n, batch, c.x_stride, c.m, rows, bases, c.stream, fuse0, nan_input)
                    : enqueue_decompose<double>(e, (const double *)c.x + (int64_t)b0 * c.x_stride, c.n, batch, c.x_stride, c.m, rows, bases, c.stream, fuse0, nan_input);
 }
@@ -1450,8 +1495,8 @@ int itd_set_batch_chunk(itd_engine *e, int32_t signals_per_chunk)
 }  // extern "C"
 
 namespace {
-template <typename Tin>
-int decompose_host(itd_engine *e, const Tin *x_host, int64_t n, int32_t M, double *rows_host, double *bases_host,
+template <typename Tin, typename Trow = double>      // Trow = float: the rows32 host entries (no baselines, kept or returned)
+int decompose_host(itd_engine *e, const Tin *x_host, int64_t n, int32_t M, Trow *rows_host, double *bases_host,
                    int32_t *n_rows, int32_t *n_baselines, int32_t *stop_reason, int64_t *knot_counts)
 {
     if (!e || !x_host || !rows_host) return ITD_ERR_INVALID_ARG;
@@ -1460,9 +1505,9 @@ int decompose_host(itd_engine *e, const Tin *x_host, int64_t n, int32_t M, doubl
     const size_t R = (size_t)M + 2;
     int rc = grow(e, e->d_io_x, (size_t)n * sizeof(Tin));
     if (rc) return rc;
-    rc = grow(e, e->d_io_rows, R * (size_t)n * sizeof(double));
+    rc = grow(e, e->d_io_rows, R * (size_t)n * sizeof(Trow));
     if (rc) return rc;
-    const bool dev_bases = bases_host || e->host_keep_bases;
+    const bool dev_bases = sizeof(Trow) == 8 && (bases_host || e->host_keep_bases);
     e->kept_nb = -1;
     if (dev_bases) {
         rc = grow(e, e->d_io_bases, R * (size_t)n * sizeof(double));
@@ -1470,13 +1515,13 @@ int decompose_host(itd_engine *e, const Tin *x_host, int64_t n, int32_t M, doubl
     }
     hipStream_t st = e->own_stream;
     HIP_TRY(e, hipMemcpyAsync(e->d_io_x, x_host, (size_t)n * sizeof(Tin), hipMemcpyHostToDevice, st));
-    rc = enqueue_any<Tin>(e, (const Tin *)e->d_io_x, n, 1, n, M, e->d_io_rows, dev_bases ? e->d_io_bases : nullptr, st);
+    rc = enqueue_any<Tin>(e, (const Tin *)e->d_io_x, n, 1, n, M, reinterpret_cast<Trow *>(e->d_io_rows.get()), dev_bases ? e->d_io_bases : nullptr, st);
     if (rc) return rc;
     int32_t nr = 0, nb = 0, why = 0, nanlv = -1;
     int64_t kc[ITD_MAX_ROWS + 1];
     rc = itd_get_summary(e, &nr, &nb, &why, kc, &nanlv);
     if (rc) return rc;
-    rc = copy_to_host(e, rows_host, e->d_io_rows, (size_t)nr * n * sizeof(double), st);
+    rc = copy_to_host(e, rows_host, e->d_io_rows, (size_t)nr * n * sizeof(Trow), st);
     if (rc) return rc;
     if (bases_host) {
         rc = copy_to_host(e, bases_host, e->d_io_bases, (size_t)nb * n * sizeof(double), st);
@@ -1733,6 +1778,18 @@ int itd_decompose_host_f64(itd_engine *e, const double *x_host, int64_t n, int32
 {
     return decompose_host<double>(e, x_host, n, max_iteration, rows_host, baselines_host, n_rows, n_baselines,
                                   stop_reason, knot_counts);
+}
+
+int itd_decompose_rows32_host_f32(itd_engine *e, const float *x_host, int64_t n, int32_t max_iteration, float *rows_host,
+                                  int32_t *n_rows, int32_t *stop_reason, int64_t *knot_counts)
+{
+    return decompose_host<float, float>(e, x_host, n, max_iteration, rows_host, nullptr, n_rows, nullptr, stop_reason, knot_counts);
+}
+
+int itd_decompose_rows32_host_f64(itd_engine *e, const double *x_host, int64_t n, int32_t max_iteration, float *rows_host,
+                                  int32_t *n_rows, int32_t *stop_reason, int64_t *knot_counts)
+{
+    return decompose_host<double, float>(e, x_host, n, max_iteration, rows_host, nullptr, n_rows, nullptr, stop_reason, knot_counts);
 }
 
 int itd_decompose_host_f32(itd_engine *e, const float *x_host, int64_t n, int32_t max_iteration, double *rows_host,

@@ -1118,6 +1118,22 @@ __device__ __forceinline__ void tile_store2(__amdgpu_buffer_rsrc_t r, int voff, 
     const D2v d = {a, b};
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(U4, d), r, voff, 0, NT ? kBufNT : 0);
 }
+// the float32 row form (itd_decompose_rows32_*): the lane's two float64 results rounded once, to nearest even, at the store (one
+// b64 per lane: the lane layout, two consecutive samples, gives no wider one).  voff counts 4-byte elements' bytes
+template <bool NT>
+__device__ __forceinline__ void tile_store2(__amdgpu_buffer_rsrc_t r, int voff, float a, float b)
+{
+    using U2 = unsigned __attribute__((ext_vector_type(2)));
+    using F2v = float __attribute__((ext_vector_type(2)));
+    const F2v d = {a, b};
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(U2, d), r, voff, 0, NT ? kBufNT : 0);
+}
+// a result row's store in the row's type: Trow = double as computed, Trow = float rounded here
+template <bool NT, typename Trow>
+__device__ __forceinline__ void row_store2(__amdgpu_buffer_rsrc_t r, int p, double a, double b)
+{
+    tile_store2<NT>(r, p * (int)sizeof(Trow), (Trow)a, (Trow)b);
+}
 
 // ---------------------------------------------------------------------------------------------
 // k_scan0: level-0 knot scan of the caller's signal for a decomposition (the register form of k_detect: knots only, no
@@ -1231,7 +1247,8 @@ __device__ unsigned long long *g_prof_buf;   // [wavefronts][16]
 #else
 #define PROF_MARK(i)
 #endif
-template <typename Tin, int TW, bool FINAL, int CAP, int KT, bool FUSE0 = false, bool TIES = false>
+// Trow: the element type of the rotation row (float: the rows32 entries; the baseline and everything the next level reads stay float64)
+template <typename Tin, int TW, bool FINAL, int CAP, int KT, bool FUSE0 = false, bool TIES = false, typename Trow = double>
 __global__ __launch_bounds__(kWave) void k_extract(const Tin *__restrict__ xin, int64_t x_stride, int64_t n,
                                                      int n_tiles, int batch,
                                                      const int32_t *__restrict__ counts_in,
@@ -1240,7 +1257,7 @@ __global__ __launch_bounds__(kWave) void k_extract(const Tin *__restrict__ xin, 
                                                      TileRec *__restrict__ recs_out,
                                                      const int32_t *__restrict__ gsum_in,
                                                      int32_t *__restrict__ gsum_out, int32_t *__restrict__ gsum_clear,
-                                                     double *__restrict__ rot_out, int64_t rot_stride,
+                                                     Trow *__restrict__ rot_out, int64_t rot_stride,
                                                      double *__restrict__ base_out, int64_t base_stride,
                                                      SigState *__restrict__ state, int level,
                                                      int keep_nan = 0 /* single-level helper: store the baseline as computed (the NaN -> +inf
@@ -1341,13 +1358,13 @@ __global__ __launch_bounds__(kWave) void k_extract(const Tin *__restrict__ xin, 
         const int lane = lane_id();
         const int t = launch_item(blockIdx.x, gridDim.x, level) * KT;
         const int64_t s = (int64_t)t * TW;
-        double *rot_t = rot_out + (int64_t)sig * rot_stride + s;
-        double *bas_t = FINAL ? rot_t : base_out + (int64_t)sig * base_stride + s;
-        const __amdgpu_buffer_rsrc_t r_rot = tile_rsrc(rot_t, (n - s) * 8), r_bas = tile_rsrc(bas_t, FINAL ? 0 : (n - s) * 8);
+        Trow *rot_t = rot_out + (int64_t)sig * rot_stride + s;
+        const void *bas_t = FINAL ? (const void *)rot_t : (const void *)(base_out + (int64_t)sig * base_stride + s);
+        const __amdgpu_buffer_rsrc_t r_rot = tile_rsrc(rot_t, (n - s) * (int64_t)sizeof(Trow)), r_bas = tile_rsrc(bas_t, FINAL ? 0 : (n - s) * 8);
 #pragma unroll
         for (int g = 0; g < G2; ++g) {
             const double a = (double)pre[0].q[g][0] * 0.5 + (double)(pre[0].cb + pre[0].cf + pre[0].specw) + (double)(int)pre[0].own, b = (double)pre[0].q[g][1] * 0.5;
-            tile_store2<(ITD_NT & 1) != 0>(r_rot, (128 * g + 2 * lane) * 8, a, b);
+            row_store2<(ITD_NT & 1) != 0, Trow>(r_rot, 128 * g + 2 * lane, a, b);
             if constexpr (!FINAL) tile_store2<(ITD_NT & 2) != 0>(r_bas, (128 * g + 2 * lane) * 8, b, a);
         }
     };
@@ -1655,10 +1672,10 @@ __global__ __launch_bounds__(kWave) void k_extract(const Tin *__restrict__ xin, 
     }
     // ---- this level's knots inside the tile (the producer's flag words, or FUSE0's own scan); tile-relative ranks, once ----
     const int c = (ITD_ABL_R & 2048) ? 0 : own_c;
-    double *rot_t = rot_out + (int64_t)sig * rot_stride + s;
+    Trow *rot_t = rot_out + (int64_t)sig * rot_stride + s;
     double *bas_t = FINAL ? nullptr : base_out + (int64_t)sig * base_stride + s;
-    const __amdgpu_buffer_rsrc_t r_rot = tile_rsrc32(rot_t, rem, 8);
-    const __amdgpu_buffer_rsrc_t r_bas = tile_rsrc32(FINAL ? rot_t : bas_t, FINAL ? 0 : rem, 8);
+    const __amdgpu_buffer_rsrc_t r_rot = tile_rsrc32(rot_t, rem, sizeof(Trow));   // (in the row's own elements: what lies beyond the row stays clipped)
+    const __amdgpu_buffer_rsrc_t r_bas = tile_rsrc32(FINAL ? (const void *)rot_t : (const void *)bas_t, FINAL ? 0 : rem, 8);
     const bool tail_tile = rem <= TW;       // holds sample n-1 (or runs past it)
     const bool near_end = rem <= TW + 2;    // holds sample n-2 or later
     const bool interior = full && !near_end && t != 0;   // no end-of-signal rule applies to any sample of the tile
@@ -1841,7 +1858,7 @@ __global__ __launch_bounds__(kWave) void k_extract(const Tin *__restrict__ xin, 
                 const double rq = FINAL ? (xo - bo) + bo : xo - bo;
                 xr[g][0] = be;
                 xr[g][1] = bo;
-                tile_store2<(ITD_NT & 1) != 0>(r_rot, p * 8, re, rq);
+                row_store2<(ITD_NT & 1) != 0, Trow>(r_rot, p, re, rq);
                 double se = be, so = bo;
                 if (__builtin_expect(__any(nonfinite(be) || nonfinite(bo)), 0)) {   // rare: the stored baseline is the mutated one, ITD.py:50
                     odd_vals = true;
@@ -1873,7 +1890,7 @@ __global__ __launch_bounds__(kWave) void k_extract(const Tin *__restrict__ xin, 
                 const double rq = FINAL ? (xo - bo) + bo : xo - bo;
                 xr[g][0] = be;
                 xr[g][1] = bo;
-                tile_store2<(ITD_NT & 1) != 0>(r_rot, p * 8, re, rq);   // samples beyond the row are dropped by the bounds check
+                row_store2<(ITD_NT & 1) != 0, Trow>(r_rot, p, re, rq);   // samples beyond the row are dropped by the bounds check
                 double se = be, so = bo;
                 if (__builtin_expect(__any(nonfinite(be) || nonfinite(bo)), 0)) {   // rare: the stored baseline is the mutated one, ITD.py:50
                     odd_vals = true;
@@ -1985,7 +2002,8 @@ __device__ __forceinline__ void sig_state_reset(SigState *st)
 }
 
 constexpr int kFinalizeThreads = 256;
-__global__ __launch_bounds__(kFinalizeThreads) void k_finalize(double *__restrict__ rows, int64_t rows_stride,
+template <typename Trow>       // the rows' element type: the residual row is the float64 baseline, as it is or rounded at the store
+__global__ __launch_bounds__(kFinalizeThreads) void k_finalize(Trow *__restrict__ rows, int64_t rows_stride,
                                                                int64_t n, const double *__restrict__ bases,
                                                                int64_t bases_stride, int64_t bases_row_pitch,
                                                                int bases_rotate, const int32_t *__restrict__ gsum_last,
@@ -2035,7 +2053,7 @@ __global__ __launch_bounds__(kFinalizeThreads) void k_finalize(double *__restric
     }
     if (!stopped) return;
     const int c = stop_level - 1;
-    double *dst = rows + (int64_t)sig * rows_stride + (int64_t)c * n;
+    Trow *dst = rows + (int64_t)sig * rows_stride + (int64_t)c * n;
     // B_c was written by extraction c (level c-1) into baselines row c-1 (rotating slots: (c-1) % 3)
     const double *src = nullptr;
     if (c >= 1) {
@@ -2045,7 +2063,21 @@ __global__ __launch_bounds__(kFinalizeThreads) void k_finalize(double *__restric
     // the copy: 16 bytes per access when both rows allow it (a thread moves several: the grid is sized for >= 4 per thread — with
     // one 8-byte element per thread a batch of short, naturally stopping signals spent most of this launch dispatching wavefronts)
     const int64_t i0 = (int64_t)blockIdx.x * kFinalizeThreads + threadIdx.x, stride = (int64_t)gridDim.x * kFinalizeThreads;
-    if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+    if constexpr (sizeof(Trow) == 4) {
+        // float32 rows: a thread rounds two samples (one 16-byte read) into one 8-byte write when both rows allow it
+        if ((reinterpret_cast<uintptr_t>(dst) & 7) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+            const int64_t n2 = n >> 1;
+            float2 *d2 = reinterpret_cast<float2 *>(dst);
+            const double2 *s2 = reinterpret_cast<const double2 *>(src);
+            for (int64_t i = i0; i < n2; i += stride) {
+                const double2 v = s2 ? s2[i] : make_double2(0.0, 0.0);
+                d2[i] = make_float2((float)v.x, (float)v.y);
+            }
+            if ((n & 1) && i0 == 0) dst[n - 1] = src ? (Trow)src[n - 1] : (Trow)0.0;
+        } else {
+            for (int64_t i = i0; i < n; i += stride) dst[i] = src ? (Trow)src[i] : (Trow)0.0;
+        }
+    } else if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
         const int64_t n2 = n >> 1;
         double2 *d2 = reinterpret_cast<double2 *>(dst);
         const double2 *s2 = reinterpret_cast<const double2 *>(src);

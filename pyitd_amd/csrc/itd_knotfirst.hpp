@@ -166,7 +166,7 @@ __host__ __device__ inline void kf_sig_verdict(const KfSig &ks, int L0, SigState
 // what the knot side's launch needs to do k_finalize's work (itd_kernels.hpp) for the hand-over level: the stop test of that level's
 // input with its row fix-up, and the other set of states / group sums left initialised for the call after this one
 struct KfFin {
-    double *rows; int64_t rows_stride;
+    void *rows; int64_t rows_stride;     // the result's rows in the call's row type (k_kf_knots' Trow), the stride in its elements
     const double *bases; int64_t bases_stride, bases_row_pitch; int32_t bases_rotate;
     const int32_t *gsum;                 // the hand-over level's group sums
     SigState *other_state; int32_t *other_gsum; int64_t other_third;
@@ -278,7 +278,7 @@ __device__ unsigned long long *g_kc_prof;   // [workgroups][64]
 //      starting: a grid that fits the device at once (KfWs::ticketed = 0) takes the id from blockIdx; a larger one hands out
 //      tickets — whoever starts first takes the lowest range, so whatever a resident workgroup waits for has started already
 //      or starts without that workgroup finishing first (dependencies reach a few ranges per level, the device holds hundreds).
-template <int TW>
+template <int TW, typename Trow = double>      // Trow: the element type of the result's rows (the residual row of a signal that stops here)
 __global__ __launch_bounds__(kKcThreads) void k_kf_knots(KfWs ws, KfFin fin, const double *__restrict__ xl, int64_t xl_stride, int64_t n, int max_iteration,
                                                          const int32_t *__restrict__ counts, const TileRec *__restrict__ recs,
                                                          SigState *__restrict__ state)
@@ -378,14 +378,14 @@ __global__ __launch_bounds__(kKcThreads) void k_kf_knots(KfWs ws, KfFin fin, con
     }
     if (stopped) {      // row c = stop_level - 1 of the result is baselines[c-1], or zeros when c = 0: this workgroup's samples of it
         const int c_row = stop_level - 1;
-        double *dst = fin.rows + (int64_t)sig * fin.rows_stride + (int64_t)c_row * n;
+        Trow *dst = static_cast<Trow *>(fin.rows) + (int64_t)sig * fin.rows_stride + (int64_t)c_row * n;
         const double *src = nullptr;
         if (c_row >= 1) {
             const int row = fin.bases_rotate ? ((c_row - 1) % fin.bases_rotate) : (c_row - 1);
             src = fin.bases + (int64_t)sig * fin.bases_stride + (int64_t)row * fin.bases_row_pitch;
         }
         const int64_t lo = (int64_t)t0 * TW, hi = min((int64_t)t1 * TW, n);
-        for (int64_t i = lo + tid; i < hi; i += NT) dst[i] = src ? src[i] : 0.0;
+        for (int64_t i = lo + tid; i < hi; i += NT) dst[i] = src ? (Trow)src[i] : (Trow)0.0;
     }
     if (stopped || odd_input) {                                              // (every workgroup of the signal sees the same)
         if (w == 0 && tid == 0) {
@@ -1022,14 +1022,14 @@ __host__ __device__ constexpr int kf_check_blocks(int wgs) { return (wgs + 1 + 7
 #ifndef ITD_KF_FASTGROUP
 #define ITD_KF_FASTGROUP 1        // A/B builds: 0 = every 128-sample group takes the by-rank path
 #endif
-template <int TW, int CAP, bool BASES, bool PART>      // BASES: the caller wants the baselines too (get_baselines()): a second row store per level
+template <int TW, int CAP, bool BASES, bool PART, typename Trow = double>      // Trow: the rows' element type (float: rounded once, at the store).  BASES: the caller wants the baselines too (get_baselines()): a second row store per level
                                                        // PART: capped fused levels (KfWs::cap): the last fused level's baseline is stored for the level launches behind
 __global__ __launch_bounds__(kWave)
 #if ITD_KF_APPLY_WAVES
 __attribute__((amdgpu_waves_per_eu(ITD_KF_APPLY_WAVES, ITD_KF_APPLY_WAVES)))
 #endif
 void k_kf_apply(KfWs ws, const double *__restrict__ xl, int64_t xl_stride, int64_t n,
-                                                    const TileRec *__restrict__ recs_l0, double *__restrict__ rows, int64_t rows_stride,
+                                                    const TileRec *__restrict__ recs_l0, Trow *__restrict__ rows, int64_t rows_stride,
                                                     double *__restrict__ bases, int64_t bases_stride)
 {
     constexpr int G2 = TW / 128;
@@ -1085,7 +1085,8 @@ void k_kf_apply(KfWs ws, const double *__restrict__ xl, int64_t xl_stride, int64
     const int32_t *first = ws.first + ((size_t)sig * ws.nlev) * n_tiles;
     const unsigned long long *tf = ws.tflags + ((size_t)sig * ws.nlev) * n_tiles * 8;
     const KfEntry *pool = ws.pool + (size_t)sig * ws.wgs_max * kKcSlab;
-    double *rows_s = rows + (int64_t)sig * rows_stride + si;
+    static_assert(!BASES || sizeof(Trow) == 8, "the caller's baselines come with float64 rows only");
+    Trow *rows_s = rows + (int64_t)sig * rows_stride + si;
     double *bases_s = (BASES && bases) ? bases + (int64_t)sig * bases_stride + si : nullptr;
     unsigned long long wcur = lane < 2 * G2 ? tf[(size_t)t * 8 + lane] : 0ull;       // this level's flag words, lane j holds word j
     bool bad = false;            // wave-uniform findings
@@ -1150,11 +1151,11 @@ void k_kf_apply(KfWs ws, const double *__restrict__ xl, int64_t xl_stride, int64
             s_X[r] = en.X; s_B[r] = en.B; s_S[r] = en.S; s_P[r] = en.pos;
         }
         wave_sync();
-        double *row = rows_s + (int64_t)lev * (n + ITD_ROW_PAD);
-        const __amdgpu_buffer_rsrc_t r_row = tile_rsrc32(row, rem, 8);
-        const __amdgpu_buffer_rsrc_t r_bas = tile_rsrc32(bases_s ? bases_s + (int64_t)lev * n : row, (bases_s && (!last || cont)) ? rem : 0, 8);
+        Trow *row = rows_s + (int64_t)lev * (n + ITD_ROW_PAD);
+        const __amdgpu_buffer_rsrc_t r_row = tile_rsrc32(row, rem, sizeof(Trow));
+        const __amdgpu_buffer_rsrc_t r_bas = tile_rsrc32(bases_s ? (const void *)(bases_s + (int64_t)lev * n) : (const void *)row, (bases_s && (!last || cont)) ? rem : 0, 8);
         // (PART, no caller's baselines: the last fused level's baseline goes where the level launch behind expects its input)
-        const __amdgpu_buffer_rsrc_t r_nx = tile_rsrc32((PART && !BASES) ? ws.xnext + (int64_t)sig * ws.xnext_stride + si : row, (PART && !BASES && last && cont) ? rem : 0, 8);
+        const __amdgpu_buffer_rsrc_t r_nx = tile_rsrc32((PART && !BASES) ? (const void *)(ws.xnext + (int64_t)sig * ws.xnext_stride + si) : (const void *)row, (PART && !BASES && last && cont) ? rem : 0, 8);
         int gbase = 0;
         bool nonfin = false;
         if (ITD_KF_VERIFY & 2) {           // V1 for the two tiles that own a virtual knot (rare paths, kept out of the groups' loop)
@@ -1214,7 +1215,7 @@ void k_kf_apply(KfWs ws, const double *__restrict__ xl, int64_t xl_stride, int64
             if (last && natural) { re = xe; ro = xo; }               // row c = baselines[c-1], ITD.py:404-416
             else if (last && !cont) { re = (xe - be) + be; ro = (xo - bo) + bo; }   // "Out of time!": rotation + baseline, ITD.py:420
             else { re = xe - be; ro = xo - bo; }                     // ITD.py:119
-            tile_store2<true>(r_row, p * 8, re, ro);
+            row_store2<true, Trow>(r_row, p, re, ro);
             if constexpr (BASES) tile_store2<true>(r_bas, p * 8, be, bo);      // (without: not even a bounds-checked-away store is issued)
             if constexpr (PART && !BASES) tile_store2<false>(r_nx, p * 8, be, bo);   // (an empty descriptor except at the last level of a capped call)
             nonfin = nonfin || nonfinite(be) || nonfinite(bo);

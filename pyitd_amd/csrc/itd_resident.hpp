@@ -71,6 +71,14 @@ __device__ __forceinline__ void res_store(__amdgpu_buffer_rsrc_t r, int i, doubl
     using U2 = unsigned __attribute__((ext_vector_type(2)));
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(U2, v), r, i * 8, 0, kBufNT);   // result rows are never read again
 }
+// a result row's element in the row's type: float32 rows take the float64 value rounded once, here (one sample per lane, consecutive
+// lanes consecutive samples: a b32 is the layout's own width)
+template <typename Trow>
+__device__ __forceinline__ void res_store_row(__amdgpu_buffer_rsrc_t r, int i, double v)
+{
+    if constexpr (sizeof(Trow) == 8) res_store(r, i, v);
+    else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)v), r, i * 4, 0, kBufNT);
+}
 __device__ __forceinline__ double res_load(__amdgpu_buffer_rsrc_t r, int i, const double *)
 {
     return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, i * 8, 0, 0));
@@ -218,10 +226,10 @@ _Pragma("unroll")                                                               
         }
 
 
-template <typename Tin, int TH, int SPT>
+template <typename Tin, int TH, int SPT, typename Trow = double>
 __global__ __launch_bounds__(TH, SPT == 4 ? ITD_RES_MINW : 4) void k_resident(const Tin *__restrict__ xin, int64_t x_stride, int n, int M, int cw,
                                                    int nan_follow /* a NaN in the caller's signal: 1 = the reference's rules (below), 0 = leave (res_fail) */,
-                                                   double *__restrict__ rows, int64_t rows_stride,
+                                                   Trow *__restrict__ rows, int64_t rows_stride,
                                                    double *__restrict__ bases, int64_t bases_stride,
                                                    SigState *__restrict__ state, SigState *__restrict__ other_state)
 {
@@ -247,7 +255,7 @@ __global__ __launch_bounds__(TH, SPT == 4 ? ITD_RES_MINW : 4) void k_resident(co
 
     SigState *st = state + sig;
     const Tin *x = xin + (int64_t)sig * x_stride;
-    double *rows_s = rows + (int64_t)sig * rows_stride;
+    Trow *rows_s = rows + (int64_t)sig * rows_stride;
     double *bases_s = bases ? bases + (int64_t)sig * bases_stride : nullptr;
     const double inf = __builtin_huge_val();
 
@@ -384,14 +392,14 @@ __global__ __launch_bounds__(TH, SPT == 4 ? ITD_RES_MINW : 4) void k_resident(co
     }
 
     for (int c = 0;; ++c) {
-        const __amdgpu_buffer_rsrc_t r_row = tile_rsrc(rows_s + (int64_t)c * n, (int64_t)n * 8);
+        const __amdgpu_buffer_rsrc_t r_row = tile_rsrc(rows_s + (int64_t)c * n, (int64_t)n * (int64_t)sizeof(Trow));
         const __amdgpu_buffer_rsrc_t r_base = tile_rsrc(bases_s ? bases_s + (int64_t)(c <= M ? c : 0) * n : nullptr, bases_s ? (int64_t)n * 8 : 0);
         // ---- passes over the level's ranks: segments k0 .. kend-1 (segment k = samples e_k <= i < e_{k+1}); the window's
         //      slots hold the knots k0-1 .. kend+1, slot = k - k0 + 1 -------------------------------------------------------
         ITD_RES_PASSES(if (c <= M && !(ITD_RES_ABL & 8)) {
             // rotation = x - baseline (ITD.py:119) leaves at once unless this is the extraction behind the last requested one
             // (its row is never the rotation)
-            res_store(r_row, i, xr[j] - b);
+            res_store_row<Trow>(r_row, i, xr[j] - b);
             if (bases_s) res_store(r_base, i, b);
         });
         // ---- the pending baseline's stop test = the next level's scan (ITD.py:400-404) -------------------------------
@@ -401,7 +409,7 @@ __global__ __launch_bounds__(TH, SPT == 4 ? ITD_RES_MINW : 4) void k_resident(co
 #pragma unroll
             for (int j = 0; j < SPT; ++j) {
                 const int q = wave + W * j, i = q * 64 + lane;
-                if (q < Q) res_store(r_row, i, c == 0 ? 0.0 : xr[j]);
+                if (q < Q) res_store_row<Trow>(r_row, i, c == 0 ? 0.0 : xr[j]);
             }
             if (tid == 0) {
                 st->stop_level = c + 1;
@@ -417,7 +425,7 @@ __global__ __launch_bounds__(TH, SPT == 4 ? ITD_RES_MINW : 4) void k_resident(co
                 if (q < Q) {
                     const double b = xs[i];
                     const double r = xr[j] - b;
-                    res_store(r_row, i, r + b);
+                    res_store_row<Trow>(r_row, i, r + b);
                 }
             }
             return;             // fin_stopped stays 0

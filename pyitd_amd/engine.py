@@ -27,6 +27,20 @@ def _np_ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
+def rows_dtype_of(dtype):
+    """The element type of a decomposition's rows: None / float64 (the default) or float32 (the itd_decompose_rows32_* entries);
+    anything else raises ValueError."""
+    if dtype is None:
+        return np.dtype(np.float64)
+    try:
+        dt = np.dtype(dtype)
+    except TypeError:
+        dt = None
+    if dt is None or dt.kind != "f" or dt.itemsize not in (4, 8):
+        raise ValueError("the rows of a decomposition are float64 or float32, not %r" % (dtype,))
+    return dt
+
+
 class Engine:
     """One engine = one GPU + one workspace sized for (max_n, max_batch).  Not thread-safe."""
 
@@ -82,9 +96,18 @@ class Engine:
 
     # ---- device-resident path ---------------------------------------------------------------
     def decompose_dev(self, x_ptr, dtype, n, batch, x_stride, max_iteration, rows_ptr, baselines_ptr=None,
-                      stream=None):
-        """Enqueue a decomposition of device data (no host sync).  Pointers are ints."""
-        f = self._L.itd_decompose_f32 if np.dtype(dtype) == np.float32 else self._L.itd_decompose_f64
+                      stream=None, rows_dtype=np.float64):
+        """Enqueue a decomposition of device data (no host sync).  Pointers are ints.
+        rows_dtype: float64, or float32 — rows_ptr is then [batch][max_iteration + 2][n] float32, every element the float64 row's
+        rounded once at its store; no baselines in that mode."""
+        f32_in = np.dtype(dtype) == np.float32
+        if rows_dtype_of(rows_dtype) == np.float32:
+            if baselines_ptr:
+                raise ValueError("baselines are not kept with float32 rows")
+            f = self._L.itd_decompose_rows32_f32 if f32_in else self._L.itd_decompose_rows32_f64
+            self._check(f(self._h, x_ptr, n, batch, x_stride, max_iteration, rows_ptr, stream))
+            return
+        f = self._L.itd_decompose_f32 if f32_in else self._L.itd_decompose_f64
         self._check(f(self._h, x_ptr, n, batch, x_stride, max_iteration, rows_ptr, baselines_ptr, stream))
 
     def summary(self, batch):
@@ -225,23 +248,33 @@ class Engine:
         return ms.value, cnt.value
 
     # ---- numpy in -> numpy out ----------------------------------------------------------------
-    def decompose_host(self, x, max_iteration, want_baselines=True, out=None):
+    def decompose_host(self, x, max_iteration, want_baselines=True, out=None, rows_dtype=np.float64):
         """want_baselines: True = copy them back now; False = none; "lazy" = leave them on the device: the result carries
         `n_baselines` and `fetch_baselines()`, valid until this engine's next host-form decomposition.
         out: a caller-owned float64 C-contiguous array of at least (max_iteration + 2, n) the rows are written into (a loop over
-        calls then neither allocates nor releases 8 (max_iteration + 2) n bytes per call)."""
+        calls then neither allocates nor releases 8 (max_iteration + 2) n bytes per call).
+        rows_dtype: float64, or float32 — the rows (and `out`) are float32 then, each element the float64 row's rounded once on the
+        device; the result carries no baselines in that mode, whatever want_baselines says."""
+        rdt = rows_dtype_of(rows_dtype)
         x = np.ascontiguousarray(x)
         if x.dtype != np.float32:
             x = np.ascontiguousarray(x, dtype=np.float64)
         n = x.shape[0]
         R = max_iteration + 2
         if out is None:
-            rows = np.empty((R, n), np.float64)
+            rows = np.empty((R, n), rdt)
         else:
-            if not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.ndim == 2 and out.shape[0] >= R
+            if not (isinstance(out, np.ndarray) and out.dtype == rdt and out.ndim == 2 and out.shape[0] >= R
                     and out.shape[1] == n and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]):
-                raise ValueError("out must be a writable C-contiguous float64 array of shape (>= %d, %d)" % (R, n))
+                raise ValueError("out must be a writable C-contiguous %s array of shape (>= %d, %d)" % (rdt.name, R, n))
             rows = out
+        if rdt == np.float32:
+            n_rows, stop = ctypes.c_int32(0), ctypes.c_int32(0)
+            kc = np.zeros(MAX_ROWS + 1, np.int64)
+            f = self._L.itd_decompose_rows32_host_f32 if x.dtype == np.float32 else self._L.itd_decompose_rows32_host_f64
+            rc = self._check(f(self._h, _np_ptr(x), n, max_iteration, _np_ptr(rows), ctypes.byref(n_rows), ctypes.byref(stop),
+                               _np_ptr(kc)), allow=(ITD_ERR_NONFINITE,))
+            return {"rows": rows[: n_rows.value], "stop": stop.value, "knot_counts": kc, "nonfinite": rc == ITD_ERR_NONFINITE}
         lazy = want_baselines == "lazy"
         self._check(self._L.itd_set_host_keep_baselines(self._h, 1 if lazy else 0))
         bases = np.zeros((R, n), np.float64) if (want_baselines and not lazy) else None

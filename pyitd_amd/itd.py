@@ -12,7 +12,7 @@ fallback — without the library or a GPU these functions raise.
 import numpy
 
 from . import _lib
-from .engine import DETECT_KNOTS, DETECT_PEAKS, DETECT_VALLEYS, STOP_TIMEOUT, Engine
+from .engine import DETECT_KNOTS, DETECT_PEAKS, DETECT_VALLEYS, STOP_TIMEOUT, Engine, rows_dtype_of
 
 _engines = {}
 _pending = None    # weak reference to the ITD instance whose baselines are still on the device (at most one per process)
@@ -145,6 +145,7 @@ class ITD:
         self.rotations = None
         self._baselines = None
         self._fetch = None          # the last run's baselines are still on the device: fetched when first asked for
+        self._rows32 = False        # the last run delivered float32 rows (out_dtype): it kept no baselines
         self.knot_counts = None
         self.stop_reason = None
 
@@ -152,11 +153,15 @@ class ITD:
         # upstream passes a misspelt keyword here (ITD.py:189-190) and cannot run; the intent is clear
         return self.itd(S, max_iteration=max_iterations)
 
-    def itd(self, data, max_iteration: int = 11, out=None):
+    def itd(self, data, max_iteration: int = 11, out=None, out_dtype=None):
         """ITD.py:351-432 — rows 0..c-1 are proper rotations, the last row is the residual.
         out (an addition to the reference's signature): a caller-owned float64 array of at least (max_iteration + 2, len(data))
         the result is written into; the returned array is a view of its first rows.  The reference allocates its [22, N] buffers
-        per call (ITD.py:384-388); a loop over calls that passes `out` pays for that once."""
+        per call (ITD.py:384-388); a loop over calls that passes `out` pays for that once.
+        out_dtype (another addition): None / float64 — the reference's result — or float32: every element of the returned rows is the
+        float64 one rounded once on the GPU (half the row traffic and half the copy back; `out`, if given, is float32 then).  Such a
+        call keeps no baselines: get_baselines() raises after it."""
+        rdt = rows_dtype_of(out_dtype)
         x = _as_signal(data)
         self.DTYPE = numpy.asarray(data).dtype
         n = len(x)
@@ -168,7 +173,7 @@ class ITD:
         m = min(int(max_iteration), _lib.MAX_ITERATION)
         self._fetch = None          # this instance's previous baselines are being replaced: nothing to bring home
         _flush_pending()            # another instance's may still sit in the engine's staging buffer: fetch those first
-        res = _engine_for(n, self.device).decompose_host(x, m, want_baselines="lazy", out=out)
+        res = _engine_for(n, self.device).decompose_host(x, m, want_baselines="lazy", out=out, rows_dtype=rdt)
         if res["nonfinite"]:    # only an engine switched to NAN_INPUT_REJECT gets here
             raise ValueError("the input signal contains NaN")
         if max_iteration > _lib.MAX_ITERATION and res["stop"] == STOP_TIMEOUT:
@@ -178,10 +183,11 @@ class ITD:
         # the reference stores the baselines on the instance (ITD.py:413-414,423-424); here they stay on the GPU until somebody
         # asks (`baselines`, get_baselines()) or the engine's staging buffer is needed again — half the PCIe traffic of a call
         self._baselines = None
-        self._fetch = res["fetch_baselines"]
+        self._rows32 = rdt == numpy.float32
+        self._fetch = res.get("fetch_baselines")
         global _pending
         import weakref
-        _pending = weakref.ref(self)
+        _pending = weakref.ref(self) if self._fetch is not None else None
         self.knot_counts = res["knot_counts"]
         self.stop_reason = "timeout" if res["stop"] == STOP_TIMEOUT else "natural"
         return self.rotations
@@ -205,6 +211,8 @@ class ITD:
         self._fetch = None
 
     def get_baselines(self):
+        if self._rows32 and self._baselines is None:
+            raise ValueError("baselines are not kept by a decomposition with float32 rows (out_dtype=float32)")
         if self.baselines is None:
             raise ValueError("No baselines found. Please, run ITD method or its variant first.")
         return self.baselines
@@ -219,7 +227,14 @@ def _is_torch(x):
     return type(x).__module__.split(".")[0] == "torch"
 
 
-def itd_batch(x, max_iteration: int = 11, keep_baselines: bool = False, device=None):
+def _np_dtype(dtype):
+    """torch.float32 / torch.float64 as numpy's; everything else as given."""
+    if _is_torch(dtype):
+        return {"torch.float32": numpy.float32, "torch.float64": numpy.float64}.get(str(dtype), str(dtype))
+    return dtype
+
+
+def itd_batch(x, max_iteration: int = 11, keep_baselines: bool = False, device=None, out_dtype=None):
     """Decompose a batch of independent signals x[B, N] in one call (device resident, one engine launch sequence
     for the whole batch — the batched form of ITD.itd the reference only has as `numba.prange` over rows,
     siftED2D.ipynb cell 1).
@@ -229,7 +244,12 @@ def itd_batch(x, max_iteration: int = 11, keep_baselines: bool = False, device=N
     Returns a dict: rows [B, max_iteration+2, N] float64 (numpy, or a torch CUDA tensor when x is one), n_rows [B],
     stop [B] (0 natural / 1 timeout), knot_counts [B, 23], and baselines [B, max_iteration+2, N] + n_baselines [B]
     when keep_baselines.  Row r of signal b is valid for r < n_rows[b].
+    out_dtype: None / float64, or float32 (numpy or torch): the rows are float32 then — each element the float64 one rounded once on
+    the GPU, half the result buffer — and baselines are not available (keep_baselines raises ValueError).
     """
+    rdt = rows_dtype_of(_np_dtype(out_dtype))
+    if rdt == numpy.float32 and keep_baselines:
+        raise ValueError("baselines are not kept with float32 rows (out_dtype=float32)")
     if max_iteration < 0 or max_iteration > _lib.MAX_ITERATION:
         raise ValueError("max_iteration must be in 0..20 (the reference's buffers hold 22 rows, ITD.py:384-385)")
     R = max_iteration + 2
@@ -244,12 +264,13 @@ def itd_batch(x, max_iteration: int = 11, keep_baselines: bool = False, device=N
         B, n = xt.shape
         if n < 3:
             raise ValueError("ITD needs at least 3 samples")
-        rows = torch.empty((B, R, n), dtype=torch.float64, device=xt.device)
+        rows = torch.empty((B, R, n), dtype=torch.float32 if rdt == numpy.float32 else torch.float64, device=xt.device)
         bases = torch.zeros((B, R, n), dtype=torch.float64, device=xt.device) if keep_baselines else None
         eng = _batch_engine_for(n, B, dev)
         torch.cuda.synchronize(xt.device)   # the engine runs on its own stream
         eng.decompose_dev(xt.data_ptr(), numpy.float32 if xt.dtype == torch.float32 else numpy.float64, n, B,
-                          xt.stride(0), max_iteration, rows.data_ptr(), bases.data_ptr() if keep_baselines else None, None)
+                          xt.stride(0), max_iteration, rows.data_ptr(), bases.data_ptr() if keep_baselines else None, None,
+                          rows_dtype=rdt)
         s = eng.summary(B)
         if (s["nan_levels"] == -2).any():
             raise ValueError("an input signal contains NaN")
@@ -270,17 +291,18 @@ def itd_batch(x, max_iteration: int = 11, keep_baselines: bool = False, device=N
     if n < 3:
         raise ValueError("ITD needs at least 3 samples")
     d_x = DeviceBuffer(a.nbytes, dev)
-    d_rows = DeviceBuffer(B * R * n * 8, dev)
+    d_rows = DeviceBuffer(B * R * n * rdt.itemsize, dev)
     d_bases = DeviceBuffer(B * R * n * 8, dev) if keep_baselines else None
     try:
         d_x.upload(a)
         eng = _batch_engine_for(n, B, dev)
-        eng.decompose_dev(d_x.ptr, a.dtype, n, B, n, max_iteration, d_rows.ptr, d_bases.ptr if keep_baselines else None, None)
+        eng.decompose_dev(d_x.ptr, a.dtype, n, B, n, max_iteration, d_rows.ptr, d_bases.ptr if keep_baselines else None, None,
+                          rows_dtype=rdt)
         s = eng.summary(B)
         if (s["nan_levels"] == -2).any():
             raise ValueError("an input signal contains NaN")
         out = {"n_rows": s["n_rows"], "stop": s["stop"], "knot_counts": s["knot_counts"],
-               "rows": d_rows.download(numpy.empty((B, R, n), numpy.float64))}
+               "rows": d_rows.download(numpy.empty((B, R, n), rdt))}
         if keep_baselines:
             out["baselines"] = d_bases.download(numpy.empty((B, R, n), numpy.float64))
             out["n_baselines"] = s["n_baselines"]
