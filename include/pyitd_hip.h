@@ -130,6 +130,23 @@ int itd_decompose_rows32_f32(itd_engine *e, const float *x_dev, int64_t n, int32
 int itd_decompose_rows32_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t batch, int64_t x_stride,
                              int32_t max_iteration, float *rows_dev, void *stream);
 
+/* The same decomposition with only the rows the caller names.  rotation_mask: bit r selects rotation row r, 0 <= r <= max_iteration
+ * (a bit above max_iteration is ITD_ERR_INVALID_ARG); want_residual: 0 or 1; S = popcount(rotation_mask) + want_residual >= 1.
+ * rows_dev is [batch][S][n], densely packed (signal stride S * n), float64 or — rows_f32 = 1 — float32 rounded once at the store as
+ * by itd_decompose_rows32_*: the selected rotations in ascending order, the residual's slot last.  With `rows` what
+ * itd_decompose_f32 / _f64 delivers for the same input and n_rows as itd_get_summary reports it: the slot of rotation r holds rows[r]
+ * if r <= n_rows - 2, otherwise its content is unspecified (as rows past n_rows are); the residual's slot holds rows[n_rows - 1]
+ * wherever the stop falls — the copied baseline of a natural stop, the all-zero row of a stop at c = 0, the "Out of time!" row.  A row
+ * that is not selected is stored nowhere: the call moves, and the buffer holds, S rows instead of max_iteration + 2.  The arithmetic,
+ * the knots and the summary (n_rows, stop_reason, knot_counts, nan_levels: those of the full call) are unchanged, and so is the rest
+ * of the contract: no host synchronisation, itd_get_summary finalises the call (every repeat honours the selection and writes into
+ * the same buffer), itd_set_valid_flags / itd_set_device_repair and the NaN-input modes apply, calls of any kind may follow each
+ * other on one engine.  No baselines. */
+int itd_decompose_select_f32(itd_engine *e, const float *x_dev, int64_t n, int32_t batch, int64_t x_stride, int32_t max_iteration,
+                             uint32_t rotation_mask, int32_t want_residual, void *rows_dev, int32_t rows_f32, void *stream);
+int itd_decompose_select_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t batch, int64_t x_stride, int32_t max_iteration,
+                             uint32_t rotation_mask, int32_t want_residual, void *rows_dev, int32_t rows_f32, void *stream);
+
 /* Stream-ordered consumers (a kernel of the caller's enqueued behind the decomposition, a replayed hipGraph).
  * The engine runs optimistic forms first — the fused sparse levels, the fused level 0, the resident form of short signals — each
  * of which either delivers the reference's result or REPORTS that it cannot (tied / quantised / very smooth input, non-finite
@@ -320,6 +337,14 @@ int itd_decompose_rows32_host_f32(itd_engine *e, const float *x_host, int64_t n,
                                   int32_t *n_rows, int32_t *stop_reason, int64_t *knot_counts);
 int itd_decompose_rows32_host_f64(itd_engine *e, const double *x_host, int64_t n, int32_t max_iteration, float *rows_host,
                                   int32_t *n_rows, int32_t *stop_reason, int64_t *knot_counts);
+/* ... with selected rows (itd_decompose_select_*): rows_host is [S][n] float64 or (rows_f32 = 1) float32; all S slots are copied
+ * back, n_rows is the full call's.  No baselines, as with the rows32 forms. */
+int itd_decompose_select_host_f32(itd_engine *e, const float *x_host, int64_t n, int32_t max_iteration, uint32_t rotation_mask,
+                                  int32_t want_residual, void *rows_host, int32_t rows_f32, int32_t *n_rows, int32_t *stop_reason,
+                                  int64_t *knot_counts);
+int itd_decompose_select_host_f64(itd_engine *e, const double *x_host, int64_t n, int32_t max_iteration, uint32_t rotation_mask,
+                                  int32_t want_residual, void *rows_host, int32_t rows_f32, int32_t *n_rows, int32_t *stop_reason,
+                                  int64_t *knot_counts);
 
 /* The reference keeps the baselines of the last run on the instance (ITD.py:413-414,423-424) but most callers only look at
  * the returned rows: with itd_set_host_keep_baselines(e, 1) a host-form call with baselines_host == NULL still computes the

@@ -20,7 +20,7 @@ MAX_ITERATION = 20
 ABI_VERSION = 12
 
 # name -> (restype, argtypes); mirrors include/pyitd_hip.h one to one
-_P, _I64, _I32, _INT = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int
+_P, _I64, _I32, _INT, _U32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int, ctypes.c_uint32
 ABI = {
     "itd_abi_version": (_INT, []),
     "itd_status_string": (ctypes.c_char_p, [_INT]),
@@ -35,11 +35,15 @@ ABI = {
     "itd_decompose_f64": (_INT, [_P, _P, _I64, _I32, _I64, _I32, _P, _P, _P]),
     "itd_decompose_rows32_f32": (_INT, [_P, _P, _I64, _I32, _I64, _I32, _P, _P]),
     "itd_decompose_rows32_f64": (_INT, [_P, _P, _I64, _I32, _I64, _I32, _P, _P]),
+    "itd_decompose_select_f32": (_INT, [_P, _P, _I64, _I32, _I64, _I32, _U32, _I32, _P, _I32, _P]),
+    "itd_decompose_select_f64": (_INT, [_P, _P, _I64, _I32, _I64, _I32, _U32, _I32, _P, _I32, _P]),
     "itd_get_summary": (_INT, [_P, _P, _P, _P, _P, _P]),
     "itd_decompose_host_f64": (_INT, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
     "itd_decompose_host_f32": (_INT, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
     "itd_decompose_rows32_host_f32": (_INT, [_P, _P, _I64, _I32, _P, _P, _P, _P]),
     "itd_decompose_rows32_host_f64": (_INT, [_P, _P, _I64, _I32, _P, _P, _P, _P]),
+    "itd_decompose_select_host_f32": (_INT, [_P, _P, _I64, _I32, _U32, _I32, _P, _I32, _P, _P, _P]),
+    "itd_decompose_select_host_f64": (_INT, [_P, _P, _I64, _I32, _U32, _I32, _P, _I32, _P, _P, _P]),
     "itd_baseline_extract_f64": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _P]),
     "itd_baseline_extract_f32": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _P]),
     "itd_baseline_extract_host_f64": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _P]),

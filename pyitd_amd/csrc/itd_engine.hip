@@ -156,14 +156,22 @@ static_assert(FormPolicy::kRangeTiles == kKcTiles && FormPolicy::kFailCapacity =
 // A call's result rows: the caller's buffer and its element type (float64, or float32 for the itd_decompose_rows32_* entries).  The
 // type is a property of the call: it travels with the pointer through every form and every repeat, which therefore writes the same
 // type into the same buffer as the first attempt.  Strides and offsets count elements.
+// So does a selection (itd_decompose_select_*): sel set, the buffer holds count() packed rows per signal — the rotations of which.mask
+// in ascending order, then the residual if which.res >= 0 — and a row that is not among them is stored nowhere.  Without a selection
+// the map is the identity (row r in slot r, the residual in the row of the stop) and every launch is the one it always was.
 struct Rows {
     void *p = nullptr; bool f32 = false;
+    bool sel = false; RowSel which{0u, -1};
     Rows() {}
     Rows(double *d) : p(d) {}
     Rows(float *f) : p(f), f32(true) {}
     Rows(void *q, bool is32) : p(q), f32(is32) {}
+    Rows(void *q, bool is32, uint32_t mask, bool residual) : p(q), f32(is32), sel(true), which{mask, residual ? __builtin_popcount(mask) : -1} {}
     size_t esz() const { return f32 ? sizeof(float) : sizeof(double); }
-    Rows at(int64_t elems) const { return Rows(static_cast<char *>(p) + elems * (int64_t)esz(), f32); }
+    Rows at(int64_t elems) const { Rows r = *this; r.p = static_cast<char *>(p) + elems * (int64_t)esz(); return r; }
+    int count(int M) const { return sel ? __builtin_popcount(which.mask) + (which.res >= 0 ? 1 : 0) : M + 2; }   // rows per signal
+    // the slot of the row a level launch writes (rotation j, or behind the last requested level the "Out of time!" residual); < 0: none
+    int slot(int j, bool residual) const { return !sel ? j : residual ? which.res : sel_slot(which, j); }
 };
 
 // The record of the last decomposition enqueued: what itd_get_summary reads back, repeats or repairs, and itd_get_timing, ... refer to
@@ -447,13 +455,14 @@ struct ChunkBufs {
 // one level launch of a chunk (k_extract): level j's input xin -> rotation rows[j] and baseline j; level j's counts, records and group
 // sums -> level j + 1's (TIES: the launch in front of the fused sparse levels also flags the tiles of its baseline that hold a near tie)
 template <typename TIN, bool FIN, int CAPK, int KTW = kTilesPerWave, bool FUSE = false, bool TIES = false, typename TROW = double>
-hipError_t launch_extract(itd_engine *e, const ChunkBufs &c, const TIN *xin, int64_t xs, int j, int pair)
+hipError_t launch_extract(itd_engine *e, const ChunkBufs &c, const TIN *xin, int64_t xs, int j, int pair, int slot)
 {
     const TIN *a_x = xin; int64_t a_xs = xs, a_n = c.n, a_rs = c.rows_stride, a_bs = c.base_stride();
     int a_nt = c.n_tiles, a_b = c.nb, a_lvl = j, a_keep = 0;
     const int32_t *a_ci = c.cnt(j), *a_gi = c.gs(j); int32_t *a_co = c.cnt(j + 1), *a_go = c.gs(j + 1), *a_gc = c.gs(j + 2);
     const TileRec *a_ri = c.rec(j); TileRec *a_ro = c.rec(j + 1);
-    void *a_rot = c.rows.at((int64_t)j * (c.n + ITD_ROW_PAD)).p; double *a_bas = c.base(j);
+    // (slot: Rows::slot; none: TROW = NoRow, which stores no row — its pointer is the buffer's own base, a valid address that is never used)
+    void *a_rot = c.rows.at((int64_t)std::max(slot, 0) * (c.n + ITD_ROW_PAD)).p; double *a_bas = c.base(j);
     SigState *a_st = c.state; unsigned long long *a_tie = TIES ? c.near : nullptr;
     void *args[] = {&a_x, &a_xs, &a_n, &a_nt, &a_b, &a_ci, &a_co, &a_ri, &a_ro, &a_gi, &a_go, &a_gc, &a_rot, &a_rs,
                     &a_bas, &a_bs, &a_st, &a_lvl, &a_keep, &a_tie};
@@ -502,8 +511,9 @@ int run_chunk(itd_engine *e, const DecomposePlan<Tin> &p, const int b0, const in
     const dim3 blk(kWave);
     // what k_finalize needs (the knot side as well, for the first fused level: its gsum is set there): the rows, the baselines, the other set
     const bool r32 = c.rows.f32;     // float32 rows: the same launches, each in its float32 store form
+    const bool sel = c.rows.sel;     // a selection: the same launches again, those that store rows in their packed-rows form
     KfFin fin{c.rows.p, p.rows_stride, c.bases ? c.bases : c.pp, c.base_stride(), c.bases ? n : e->pp_pitch, c.bases ? 0 : 3, nullptr,
-              p.other_state + b0, p.other_gsum + (int64_t)b0 * p.n_groups * kGsumPitch, e->gsum_third};
+              p.other_state + b0, p.other_gsum + (int64_t)b0 * p.n_groups * kGsumPitch, e->gsum_third, c.rows.which.res};
     // the level launches ja .. jb: extraction j + 1, input = the level-j signal, rotation -> rows[j], baseline -> baseline j
     auto levels = [&](const int ja, const int jb) -> int {
         for (int j = ja; j <= jb; ++j) {
@@ -512,8 +522,10 @@ int run_chunk(itd_engine *e, const DecomposePlan<Tin> &p, const int b0, const in
             const double *in = j ? c.base(j - 1) : nullptr;
             const int64_t is = c.base_stride();
             hipError_t rc;
+            const int slot = c.rows.slot(j, final_level);    // (a level whose row the selection drops: the form without a row store)
 #define ITD_LX(TIN, FIN, CAPK, KTW, FUSE, TIES, ...) \
-    (r32 ? launch_extract<TIN, FIN, CAPK, KTW, FUSE, TIES, float>(__VA_ARGS__) : launch_extract<TIN, FIN, CAPK, KTW, FUSE, TIES, double>(__VA_ARGS__))
+    (slot < 0 ? launch_extract<TIN, FIN, CAPK, KTW, FUSE, TIES, NoRow>(__VA_ARGS__, slot) : \
+     r32 ? launch_extract<TIN, FIN, CAPK, KTW, FUSE, TIES, float>(__VA_ARGS__, slot) : launch_extract<TIN, FIN, CAPK, KTW, FUSE, TIES, double>(__VA_ARGS__, slot))
             if (j == 0) {   // never the last level: M >= 0
                 if (p.nan_input) rc = ITD_LX(double, false, kRankCap0, kTilesPerWave, false, false, e, c, xm_c, pp3, 0, pair);
                 else if (p.fuse0) rc = ITD_LX(Tin, false, kRankCap0, kFuse0TilesPerWave, true, false, e, c, xc, p.x_stride, 0, pair);
@@ -531,7 +543,13 @@ int run_chunk(itd_engine *e, const DecomposePlan<Tin> &p, const int b0, const in
         // blocks per signal: a thread of the row fix-up moves 8 samples (four 16-byte accesses) before the grid is widened
         const int fb = (int)std::min<int64_t>(std::max<int64_t>((n + 8 * kFinalizeThreads - 1) / (8 * kFinalizeThreads), 1), 1024);
         const int jf = p.M + 2;      // the level whose input is pending
-        if (r32) k_finalize<float><<<dim3(fb, nb), kFinalizeThreads, 0, cst>>>(static_cast<float *>(fin.rows), fin.rows_stride, n, fin.bases, fin.bases_stride,
+        if (sel && r32) k_finalize<float, true><<<dim3(fb, nb), kFinalizeThreads, 0, cst>>>(static_cast<float *>(fin.rows), fin.rows_stride, n, fin.bases, fin.bases_stride,
+                                                                                            fin.bases_row_pitch, fin.bases_rotate, c.gs(jf), p.n_tiles, jf, c.state,
+                                                                                            fin.other_state, fin.other_gsum, fin.other_third, fin.res_slot);
+        else if (sel) k_finalize<double, true><<<dim3(fb, nb), kFinalizeThreads, 0, cst>>>(static_cast<double *>(fin.rows), fin.rows_stride, n, fin.bases, fin.bases_stride,
+                                                                                           fin.bases_row_pitch, fin.bases_rotate, c.gs(jf), p.n_tiles, jf, c.state,
+                                                                                           fin.other_state, fin.other_gsum, fin.other_third, fin.res_slot);
+        else if (r32) k_finalize<float><<<dim3(fb, nb), kFinalizeThreads, 0, cst>>>(static_cast<float *>(fin.rows), fin.rows_stride, n, fin.bases, fin.bases_stride,
                                                                                fin.bases_row_pitch, fin.bases_rotate, c.gs(jf), p.n_tiles, jf, c.state,
                                                                                fin.other_state, fin.other_gsum, fin.other_third);
         else k_finalize<double><<<dim3(fb, nb), kFinalizeThreads, 0, cst>>>(static_cast<double *>(fin.rows), fin.rows_stride, n, fin.bases, fin.bases_stride,
@@ -564,7 +582,8 @@ int run_chunk(itd_engine *e, const DecomposePlan<Tin> &p, const int b0, const in
         KfFin a_f = fin;
         a_f.gsum = c.gs(p.L0);
         void *args[] = {&a_w, &a_f, &a_xl, &a_ls, &a_n, &a_m, &a_c, &a_r, &a_st};
-        const void *knots_fn = r32 ? reinterpret_cast<const void *>(&k_kf_knots<T, float>) : reinterpret_cast<const void *>(&k_kf_knots<T>);
+        const void *knots_fn = sel ? (r32 ? reinterpret_cast<const void *>(&k_kf_knots<T, float, true>) : reinterpret_cast<const void *>(&k_kf_knots<T, double, true>)) :
+                               r32 ? reinterpret_cast<const void *>(&k_kf_knots<T, float>) : reinterpret_cast<const void *>(&k_kf_knots<T>);
         HIP_TRY(e, launch_timed(e, knots_fn, dim3((unsigned)w.wgs * (unsigned)nb), dim3(kKcThreads),
                                 args, cst, time_slot(e, ITD_TIME_KF_KNOTS)));
     }
@@ -574,9 +593,12 @@ int run_chunk(itd_engine *e, const DecomposePlan<Tin> &p, const int b0, const in
     {   // the sample pass: verifies the knot side's tables and writes the rows
         KfWs a_w = w; const double *a_xl = xl; int64_t a_xs = xl_stride, a_n = n, a_rs = p.rows_stride, a_bs = p.rows_stride;
         const TileRec *a_rec = c.rec(p.L0); void *a_rows = c.rows.p; double *a_bases = c.bases;
-        void *args[] = {&a_w, &a_xl, &a_xs, &a_n, &a_rec, &a_rows, &a_rs, &a_bases, &a_bs};
-        // (float32 rows come without the caller's baselines: two forms of the sample pass, not four)
-        const void *apply_fn = r32 ? (p.cap ? reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, true, float>) : reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, false, float>)) :
+        RowSel a_sel = c.rows.which;
+        void *args[] = {&a_w, &a_xl, &a_xs, &a_n, &a_rec, &a_rows, &a_rs, &a_bases, &a_bs, &a_sel};
+        // (float32 rows and selections come without the caller's baselines: two forms of the sample pass each, not four)
+        const void *apply_fn = sel ? (r32 ? (p.cap ? reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, true, float, true>) : reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, false, float, true>))
+                                          : (p.cap ? reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, true, double, true>) : reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, false, double, true>))) :
+                               r32 ? (p.cap ? reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, true, float>) : reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, false, float>)) :
                                p.cap ? (c.bases ? reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, true, true>) : reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, true>))
                                      : (c.bases ? reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, true, false>) : reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, false>));
         HIP_TRY(e, launch_timed(e, apply_fn, dim3(p.n_tiles + kf_check_blocks(w.wgs), nb), blk, args, cst, time_slot(e, ITD_TIME_KF_APPLY)));
@@ -670,7 +692,7 @@ int enqueue_decompose(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int
     p.n_tiles = (int)tiles_of(n);
     p.n_groups = groups_of(p.n_tiles);
     p.kf_wgs = (p.n_tiles + p.kf_tpw - 1) / p.kf_tpw;
-    p.rows_stride = ((int64_t)M + 2) * (n + ITD_ROW_PAD);
+    p.rows_stride = (int64_t)rows.count(M) * (n + ITD_ROW_PAD);
 
     // instrument every timing_stride-th decomposition only: a launch that carries events needs a completion signal of its own
     // (~2 us per launch, measured), the whole-decomposition span two marker records (~5 us each)
@@ -762,7 +784,7 @@ int enqueue_resident(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int6
                      double *bases_user, hipStream_t st)
 {
     const int64_t R = (int64_t)M + 2;
-    const int64_t rows_stride = R * n;
+    const int64_t rows_stride = (int64_t)rows.count(M) * n;      // (the caller's baselines, full calls only, lie R rows apart as well)
     const int set = e->cur_set ^ 1;
     SigState *const set_state = e->d_state + (size_t)set * e->max_batch;
     SigState *const other_state = e->d_state + (size_t)(set ^ 1) * e->max_batch;
@@ -770,14 +792,20 @@ int enqueue_resident(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int6
         HIP_TRY(e, hipMemset2DAsync(bases_user + (R - 1) * n, (size_t)rows_stride * sizeof(double), 0,
                                     (size_t)n * sizeof(double), (size_t)batch, st));
     const WgClass wc = wg_class((int)n, e->resident_window);
-    const void *const inst[2][6] = {{   // by row type and size class
+#define ITD_RES_SEL(TROW) \
+        reinterpret_cast<const void *>(&k_resident<Tin, 64, 4, TROW, true>),   reinterpret_cast<const void *>(&k_resident<Tin, 128, 4, TROW, true>),  \
+        reinterpret_cast<const void *>(&k_resident<Tin, 256, 4, TROW, true>),  reinterpret_cast<const void *>(&k_resident<Tin, 512, 4, TROW, true>),  \
+        reinterpret_cast<const void *>(&k_resident<Tin, 1024, 4, TROW, true>), reinterpret_cast<const void *>(&k_resident<Tin, 1024, 8, TROW, true>)
+    const void *const inst[4][6] = {{   // by row type (then the same with a selection) and size class
         reinterpret_cast<const void *>(&k_resident<Tin, 64, 4>),   reinterpret_cast<const void *>(&k_resident<Tin, 128, 4>),
         reinterpret_cast<const void *>(&k_resident<Tin, 256, 4>),  reinterpret_cast<const void *>(&k_resident<Tin, 512, 4>),
         reinterpret_cast<const void *>(&k_resident<Tin, 1024, 4>), reinterpret_cast<const void *>(&k_resident<Tin, 1024, 8>)}, {
         reinterpret_cast<const void *>(&k_resident<Tin, 64, 4, float>),   reinterpret_cast<const void *>(&k_resident<Tin, 128, 4, float>),
         reinterpret_cast<const void *>(&k_resident<Tin, 256, 4, float>),  reinterpret_cast<const void *>(&k_resident<Tin, 512, 4, float>),
-        reinterpret_cast<const void *>(&k_resident<Tin, 1024, 4, float>), reinterpret_cast<const void *>(&k_resident<Tin, 1024, 8, float>)}};
-    const void *fn = inst[rows.f32 ? 1 : 0][wc.cls];
+        reinterpret_cast<const void *>(&k_resident<Tin, 1024, 4, float>), reinterpret_cast<const void *>(&k_resident<Tin, 1024, 8, float>)},
+        {ITD_RES_SEL(double)}, {ITD_RES_SEL(float)}};
+#undef ITD_RES_SEL
+    const void *fn = inst[(rows.sel ? 2 : 0) + (rows.f32 ? 1 : 0)][wc.cls];
     const hipError_t arc = allow_lds(e, fn, kResidentLdsMax);
     if (arc != hipSuccess) {     // a device / runtime that does not grant it: this engine runs level by level from now on
         (void)hipGetLastError();
@@ -788,8 +816,8 @@ int enqueue_resident(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int6
     const Tin *a_x = x; int64_t a_xs = x_stride, a_rs = rows_stride, a_bs = rows_stride;
     int a_n = (int)n, a_m = M, a_cw = wc.cw, a_nf = e->nan_input_mode == ITD_NAN_INPUT_FOLLOW ? 1 : 0;
     void *a_rows = rows.p; double *a_bases = bases_user;
-    SigState *a_st = set_state, *a_ot = other_state;
-    void *args[] = {&a_x, &a_xs, &a_n, &a_m, &a_cw, &a_nf, &a_rows, &a_rs, &a_bases, &a_bs, &a_st, &a_ot};
+    SigState *a_st = set_state, *a_ot = other_state; RowSel a_sel = rows.which;
+    void *args[] = {&a_x, &a_xs, &a_n, &a_m, &a_cw, &a_nf, &a_rows, &a_rs, &a_bases, &a_bs, &a_st, &a_ot, &a_sel};
     HIP_TRY(e, hipLaunchKernel(fn, dim3((unsigned)batch), dim3((unsigned)wc.threads), args, wc.lds, st));
     HIP_TRY(e, hipGetLastError());
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -841,6 +869,13 @@ int check_args(itd_engine *e, const void *x, int64_t n, int32_t batch, int64_t x
     if (batch > 1 && x_stride < n) return ITD_ERR_INVALID_ARG;
     if (M < 0 || M > ITD_MAX_ITERATION) return ITD_ERR_INVALID_ARG;  // row M+1 must fit in 22 rows (ITD.py:384,421)
     return ITD_OK;
+}
+
+// a selection of rows (itd_decompose_select_*): rotation bits within 0 .. M, the residual flag 0 or 1, one row at least
+bool selection_ok(int32_t M, uint32_t mask, int32_t want_residual)
+{
+    if (M < 0 || M > ITD_MAX_ITERATION || (mask >> (M + 1)) != 0) return false;
+    return (want_residual == 0 || want_residual == 1) && (mask != 0 || want_residual == 1);
 }
 
 // a grow-only buffer of the engine made to hold `want` bytes (Buf::reserve), the engine's error text set when that fails
@@ -1148,11 +1183,34 @@ int itd_decompose_rows32_f64(itd_engine *e, const double *x_dev, int64_t n, int3
     return enqueue_any<double>(e, x_dev, n, batch, x_stride, max_iteration, rows_dev, nullptr, stream_of(e, stream));
 }
 
+// selected rows: the same call in every respect, each selected row's elements those of the full call; the rest is stored nowhere
+int itd_decompose_select_f32(itd_engine *e, const float *x_dev, int64_t n, int32_t batch, int64_t x_stride, int32_t max_iteration,
+                             uint32_t rotation_mask, int32_t want_residual, void *rows_dev, int32_t rows_f32, void *stream)
+{
+    if (!selection_ok(max_iteration, rotation_mask, want_residual) || (rows_f32 != 0 && rows_f32 != 1)) return ITD_ERR_INVALID_ARG;
+    int rc = check_args(e, x_dev, n, batch, x_stride, max_iteration, rows_dev);
+    if (rc) return rc;
+    DevGuard g(e->device);
+    return enqueue_any<float>(e, x_dev, n, batch, x_stride, max_iteration, Rows(rows_dev, rows_f32 != 0, rotation_mask, want_residual != 0),
+                              nullptr, stream_of(e, stream));
+}
+
+int itd_decompose_select_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t batch, int64_t x_stride, int32_t max_iteration,
+                             uint32_t rotation_mask, int32_t want_residual, void *rows_dev, int32_t rows_f32, void *stream)
+{
+    if (!selection_ok(max_iteration, rotation_mask, want_residual) || (rows_f32 != 0 && rows_f32 != 1)) return ITD_ERR_INVALID_ARG;
+    int rc = check_args(e, x_dev, n, batch, x_stride, max_iteration, rows_dev);
+    if (rc) return rc;
+    DevGuard g(e->device);
+    return enqueue_any<double>(e, x_dev, n, batch, x_stride, max_iteration, Rows(rows_dev, rows_f32 != 0, rotation_mask, want_residual != 0),
+                               nullptr, stream_of(e, stream));
+}
+
 namespace {
 // The recorded call `c` again, level by level unless fuse0, on its signals b0 .. b0 + batch - 1 into their rows (and baselines)
 int enqueue_again(itd_engine *e, const LastCall c, int b0, int32_t batch, bool fuse0, bool nan_input)
 {
-    const int64_t rs = (int64_t)(c.m + 2) * c.n;
+    const int64_t rs = (int64_t)c.rows.count(c.m) * c.n;      // (the caller's baselines come with full calls only: the same stride)
     const Rows rows = c.rows.at((int64_t)b0 * rs); double *bases = c.bases ? c.bases + (int64_t)b0 * rs : nullptr;
     return c.x_f32 ? enqueue_decompose<float>(e, (const float *)c.x + (int64_t)b0 * c.x_stride, c.n, batch, c.x_stride, c.m, rows, bases, c.stream, fuse0, nan_input)
                    : enqueue_decompose<double>(e, (const double *)c.x + (int64_t)b0 * c.x_stride, c.n, batch, c.x_stride, c.m, rows, bases, c.stream, fuse0, nan_input);
@@ -1495,19 +1553,23 @@ int itd_set_batch_chunk(itd_engine *e, int32_t signals_per_chunk)
 }  // extern "C"
 
 namespace {
-template <typename Tin, typename Trow = double>      // Trow = float: the rows32 host entries (no baselines, kept or returned)
+// Trow = float: the rows32 host entries (no baselines, kept or returned).  select: the rows of (mask, residual) only, packed — all
+// their slots are copied back, those of rotations the decomposition did not reach with unspecified content; no baselines either
+template <typename Tin, typename Trow = double>
 int decompose_host(itd_engine *e, const Tin *x_host, int64_t n, int32_t M, Trow *rows_host, double *bases_host,
-                   int32_t *n_rows, int32_t *n_baselines, int32_t *stop_reason, int64_t *knot_counts)
+                   int32_t *n_rows, int32_t *n_baselines, int32_t *stop_reason, int64_t *knot_counts,
+                   bool select = false, uint32_t mask = 0, bool residual = false)
 {
+    if (select && !selection_ok(M, mask, residual ? 1 : 0)) return ITD_ERR_INVALID_ARG;
     if (!e || !x_host || !rows_host) return ITD_ERR_INVALID_ARG;
     if (n < 3 || n > e->max_n || M < 0 || M > ITD_MAX_ITERATION) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    const size_t R = (size_t)M + 2;
+    const size_t R = select ? (size_t)Rows(nullptr, false, mask, residual).count(M) : (size_t)M + 2;
     int rc = grow(e, e->d_io_x, (size_t)n * sizeof(Tin));
     if (rc) return rc;
     rc = grow(e, e->d_io_rows, R * (size_t)n * sizeof(Trow));
     if (rc) return rc;
-    const bool dev_bases = sizeof(Trow) == 8 && (bases_host || e->host_keep_bases);
+    const bool dev_bases = sizeof(Trow) == 8 && !select && (bases_host || e->host_keep_bases);
     e->kept_nb = -1;
     if (dev_bases) {
         rc = grow(e, e->d_io_bases, R * (size_t)n * sizeof(double));
@@ -1515,13 +1577,15 @@ int decompose_host(itd_engine *e, const Tin *x_host, int64_t n, int32_t M, Trow 
     }
     hipStream_t st = e->own_stream;
     HIP_TRY(e, hipMemcpyAsync(e->d_io_x, x_host, (size_t)n * sizeof(Tin), hipMemcpyHostToDevice, st));
-    rc = enqueue_any<Tin>(e, (const Tin *)e->d_io_x, n, 1, n, M, reinterpret_cast<Trow *>(e->d_io_rows.get()), dev_bases ? e->d_io_bases : nullptr, st);
+    Rows rows(reinterpret_cast<Trow *>(e->d_io_rows.get()));
+    if (select) rows = Rows(rows.p, rows.f32, mask, residual);
+    rc = enqueue_any<Tin>(e, (const Tin *)e->d_io_x, n, 1, n, M, rows, dev_bases ? e->d_io_bases : nullptr, st);
     if (rc) return rc;
     int32_t nr = 0, nb = 0, why = 0, nanlv = -1;
     int64_t kc[ITD_MAX_ROWS + 1];
     rc = itd_get_summary(e, &nr, &nb, &why, kc, &nanlv);
     if (rc) return rc;
-    rc = copy_to_host(e, rows_host, e->d_io_rows, (size_t)nr * n * sizeof(Trow), st);
+    rc = copy_to_host(e, rows_host, e->d_io_rows, (select ? R : (size_t)nr) * n * sizeof(Trow), st);
     if (rc) return rc;
     if (bases_host) {
         rc = copy_to_host(e, bases_host, e->d_io_bases, (size_t)nb * n * sizeof(double), st);
@@ -1790,6 +1854,28 @@ int itd_decompose_rows32_host_f64(itd_engine *e, const double *x_host, int64_t n
                                   int32_t *n_rows, int32_t *stop_reason, int64_t *knot_counts)
 {
     return decompose_host<double, float>(e, x_host, n, max_iteration, rows_host, nullptr, n_rows, nullptr, stop_reason, knot_counts);
+}
+
+int itd_decompose_select_host_f32(itd_engine *e, const float *x_host, int64_t n, int32_t max_iteration, uint32_t rotation_mask,
+                                  int32_t want_residual, void *rows_host, int32_t rows_f32, int32_t *n_rows, int32_t *stop_reason,
+                                  int64_t *knot_counts)
+{
+    if ((want_residual != 0 && want_residual != 1) || (rows_f32 != 0 && rows_f32 != 1)) return ITD_ERR_INVALID_ARG;
+    return rows_f32 ? decompose_host<float, float>(e, x_host, n, max_iteration, static_cast<float *>(rows_host), nullptr, n_rows, nullptr, stop_reason,
+                                                   knot_counts, true, rotation_mask, want_residual != 0)
+                    : decompose_host<float, double>(e, x_host, n, max_iteration, static_cast<double *>(rows_host), nullptr, n_rows, nullptr, stop_reason,
+                                                    knot_counts, true, rotation_mask, want_residual != 0);
+}
+
+int itd_decompose_select_host_f64(itd_engine *e, const double *x_host, int64_t n, int32_t max_iteration, uint32_t rotation_mask,
+                                  int32_t want_residual, void *rows_host, int32_t rows_f32, int32_t *n_rows, int32_t *stop_reason,
+                                  int64_t *knot_counts)
+{
+    if ((want_residual != 0 && want_residual != 1) || (rows_f32 != 0 && rows_f32 != 1)) return ITD_ERR_INVALID_ARG;
+    return rows_f32 ? decompose_host<double, float>(e, x_host, n, max_iteration, static_cast<float *>(rows_host), nullptr, n_rows, nullptr, stop_reason,
+                                                    knot_counts, true, rotation_mask, want_residual != 0)
+                    : decompose_host<double, double>(e, x_host, n, max_iteration, static_cast<double *>(rows_host), nullptr, n_rows, nullptr, stop_reason,
+                                                     knot_counts, true, rotation_mask, want_residual != 0);
 }
 
 int itd_decompose_host_f32(itd_engine *e, const float *x_host, int64_t n, int32_t max_iteration, double *rows_host,

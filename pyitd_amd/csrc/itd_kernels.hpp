@@ -1128,11 +1128,21 @@ __device__ __forceinline__ void tile_store2(__amdgpu_buffer_rsrc_t r, int voff, 
     const F2v d = {a, b};
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(U2, d), r, voff, 0, NT ? kBufNT : 0);
 }
-// a result row's store in the row's type: Trow = double as computed, Trow = float rounded here
+// A selection of result rows (itd_decompose_select_*) as the kernels see it.  Bit r of mask: rotation row r is stored, in slot
+// popcount(mask below bit r) of the signal's packed rows; a rotation whose bit is clear is stored nowhere.  res: the slot of the
+// residual (behind the rotations' slots, whatever the level of the stop), or -1: not wanted.
+struct RowSel { uint32_t mask; int32_t res; };
+__host__ __device__ inline int sel_slot(RowSel s, int r)
+{
+    return ((s.mask >> r) & 1u) ? __builtin_popcount(s.mask & ((1u << r) - 1u)) : -1;
+}
+// Trow of a launch whose row the selection drops: no row store is issued (the baseline and everything else are as ever)
+struct NoRow {};
+// a result row's store in the row's type: Trow = double as computed, Trow = float rounded here, Trow = NoRow none
 template <bool NT, typename Trow>
 __device__ __forceinline__ void row_store2(__amdgpu_buffer_rsrc_t r, int p, double a, double b)
 {
-    tile_store2<NT>(r, p * (int)sizeof(Trow), (Trow)a, (Trow)b);
+    if constexpr (!std::is_same<Trow, NoRow>::value) tile_store2<NT>(r, p * (int)sizeof(Trow), (Trow)a, (Trow)b);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1247,7 +1257,10 @@ __device__ unsigned long long *g_prof_buf;   // [wavefronts][16]
 #else
 #define PROF_MARK(i)
 #endif
-// Trow: the element type of the rotation row (float: the rows32 entries; the baseline and everything the next level reads stay float64)
+// Trow: the element type of the rotation row (float: the rows32 entries; the baseline and everything the next level reads stay float64;
+// NoRow: a level whose row a selection drops — rot_out is the result buffer's base, a valid address from which a pointer and a
+// descriptor are still formed below (in bytes: sizeof(NoRow) == 1) but through which nothing is ever stored).  A selected row needs no form of its own: rot_out points at its
+// slot and rot_stride is the packed rows' signal stride
 template <typename Tin, int TW, bool FINAL, int CAP, int KT, bool FUSE0 = false, bool TIES = false, typename Trow = double>
 __global__ __launch_bounds__(kWave) void k_extract(const Tin *__restrict__ xin, int64_t x_stride, int64_t n,
                                                      int n_tiles, int batch,
@@ -2002,7 +2015,9 @@ __device__ __forceinline__ void sig_state_reset(SigState *st)
 }
 
 constexpr int kFinalizeThreads = 256;
-template <typename Trow>       // the rows' element type: the residual row is the float64 baseline, as it is or rounded at the store
+// Trow: the rows' element type: the residual row is the float64 baseline, as it is or rounded at the store.  SEL: a selection's
+// packed rows (RowSel): the residual goes to slot res_slot wherever the stop falls, or nowhere (res_slot < 0)
+template <typename Trow, bool SEL = false>
 __global__ __launch_bounds__(kFinalizeThreads) void k_finalize(Trow *__restrict__ rows, int64_t rows_stride,
                                                                int64_t n, const double *__restrict__ bases,
                                                                int64_t bases_stride, int64_t bases_row_pitch,
@@ -2010,7 +2025,8 @@ __global__ __launch_bounds__(kFinalizeThreads) void k_finalize(Trow *__restrict_
                                                                int n_tiles, int level_last,
                                                                SigState *__restrict__ state,
                                                                SigState *__restrict__ other_state = nullptr,
-                                                               int32_t *__restrict__ other_gsum = nullptr, int64_t other_third = 0)
+                                                               int32_t *__restrict__ other_gsum = nullptr, int64_t other_third = 0,
+                                                               int res_slot = 0)
 {
     __shared__ int s_red[kFinalizeThreads / 64];
     const int sig = blockIdx.y;
@@ -2053,7 +2069,8 @@ __global__ __launch_bounds__(kFinalizeThreads) void k_finalize(Trow *__restrict_
     }
     if (!stopped) return;
     const int c = stop_level - 1;
-    Trow *dst = rows + (int64_t)sig * rows_stride + (int64_t)c * n;
+    if constexpr (SEL) { if (res_slot < 0) return; }
+    Trow *dst = rows + (int64_t)sig * rows_stride + (int64_t)(SEL ? res_slot : c) * n;
     // B_c was written by extraction c (level c-1) into baselines row c-1 (rotating slots: (c-1) % 3)
     const double *src = nullptr;
     if (c >= 1) {

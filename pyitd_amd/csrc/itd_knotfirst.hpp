@@ -170,6 +170,7 @@ struct KfFin {
     const double *bases; int64_t bases_stride, bases_row_pitch; int32_t bases_rotate;
     const int32_t *gsum;                 // the hand-over level's group sums
     SigState *other_state; int32_t *other_gsum; int64_t other_third;
+    int32_t res_slot;                    // a selection's packed rows (k_kf_knots' / k_finalize's SEL): the residual's slot, < 0: not wanted
 };
 
 struct KfWs {
@@ -278,7 +279,7 @@ __device__ unsigned long long *g_kc_prof;   // [workgroups][64]
 //      starting: a grid that fits the device at once (KfWs::ticketed = 0) takes the id from blockIdx; a larger one hands out
 //      tickets — whoever starts first takes the lowest range, so whatever a resident workgroup waits for has started already
 //      or starts without that workgroup finishing first (dependencies reach a few ranges per level, the device holds hundreds).
-template <int TW, typename Trow = double>      // Trow: the element type of the result's rows (the residual row of a signal that stops here)
+template <int TW, typename Trow = double, bool SEL = false>      // Trow: the element type of the result's rows (the residual row of a signal that stops here); SEL: that row goes to KfFin::res_slot
 __global__ __launch_bounds__(kKcThreads) void k_kf_knots(KfWs ws, KfFin fin, const double *__restrict__ xl, int64_t xl_stride, int64_t n, int max_iteration,
                                                          const int32_t *__restrict__ counts, const TileRec *__restrict__ recs,
                                                          SigState *__restrict__ state)
@@ -378,14 +379,15 @@ __global__ __launch_bounds__(kKcThreads) void k_kf_knots(KfWs ws, KfFin fin, con
     }
     if (stopped) {      // row c = stop_level - 1 of the result is baselines[c-1], or zeros when c = 0: this workgroup's samples of it
         const int c_row = stop_level - 1;
-        Trow *dst = static_cast<Trow *>(fin.rows) + (int64_t)sig * fin.rows_stride + (int64_t)c_row * n;
+        Trow *dst = static_cast<Trow *>(fin.rows) + (int64_t)sig * fin.rows_stride + (int64_t)(SEL ? max(fin.res_slot, 0) : c_row) * n;
         const double *src = nullptr;
         if (c_row >= 1) {
             const int row = fin.bases_rotate ? ((c_row - 1) % fin.bases_rotate) : (c_row - 1);
             src = fin.bases + (int64_t)sig * fin.bases_stride + (int64_t)row * fin.bases_row_pitch;
         }
         const int64_t lo = (int64_t)t0 * TW, hi = min((int64_t)t1 * TW, n);
-        for (int64_t i = lo + tid; i < hi; i += NT) dst[i] = src ? (Trow)src[i] : (Trow)0.0;
+        if (!SEL || fin.res_slot >= 0)      // (a selection without the residual: the row is written nowhere)
+            for (int64_t i = lo + tid; i < hi; i += NT) dst[i] = src ? (Trow)src[i] : (Trow)0.0;
     }
     if (stopped || odd_input) {                                              // (every workgroup of the signal sees the same)
         if (w == 0 && tid == 0) {
@@ -1022,7 +1024,7 @@ __host__ __device__ constexpr int kf_check_blocks(int wgs) { return (wgs + 1 + 7
 #ifndef ITD_KF_FASTGROUP
 #define ITD_KF_FASTGROUP 1        // A/B builds: 0 = every 128-sample group takes the by-rank path
 #endif
-template <int TW, int CAP, bool BASES, bool PART, typename Trow = double>      // Trow: the rows' element type (float: rounded once, at the store).  BASES: the caller wants the baselines too (get_baselines()): a second row store per level
+template <int TW, int CAP, bool BASES, bool PART, typename Trow = double, bool SEL = false>      // Trow: the rows' element type (float: rounded once, at the store).  SEL: only the rows of `sel`, packed (below).  BASES: the caller wants the baselines too (get_baselines()): a second row store per level
                                                        // PART: capped fused levels (KfWs::cap): the last fused level's baseline is stored for the level launches behind
 __global__ __launch_bounds__(kWave)
 #if ITD_KF_APPLY_WAVES
@@ -1030,7 +1032,7 @@ __attribute__((amdgpu_waves_per_eu(ITD_KF_APPLY_WAVES, ITD_KF_APPLY_WAVES)))
 #endif
 void k_kf_apply(KfWs ws, const double *__restrict__ xl, int64_t xl_stride, int64_t n,
                                                     const TileRec *__restrict__ recs_l0, Trow *__restrict__ rows, int64_t rows_stride,
-                                                    double *__restrict__ bases, int64_t bases_stride)
+                                                    double *__restrict__ bases, int64_t bases_stride, RowSel sel = RowSel{0u, 0})
 {
     constexpr int G2 = TW / 128;
     __shared__ double s_X[CAP + 2], s_B[CAP + 2], s_S[CAP + 2];
@@ -1085,7 +1087,7 @@ void k_kf_apply(KfWs ws, const double *__restrict__ xl, int64_t xl_stride, int64
     const int32_t *first = ws.first + ((size_t)sig * ws.nlev) * n_tiles;
     const unsigned long long *tf = ws.tflags + ((size_t)sig * ws.nlev) * n_tiles * 8;
     const KfEntry *pool = ws.pool + (size_t)sig * ws.wgs_max * kKcSlab;
-    static_assert(!BASES || sizeof(Trow) == 8, "the caller's baselines come with float64 rows only");
+    static_assert(!BASES || (sizeof(Trow) == 8 && !SEL), "the caller's baselines come with all the rows in float64 only");
     Trow *rows_s = rows + (int64_t)sig * rows_stride + si;
     double *bases_s = (BASES && bases) ? bases + (int64_t)sig * bases_stride + si : nullptr;
     unsigned long long wcur = lane < 2 * G2 ? tf[(size_t)t * 8 + lane] : 0ull;       // this level's flag words, lane j holds word j
@@ -1151,8 +1153,13 @@ void k_kf_apply(KfWs ws, const double *__restrict__ xl, int64_t xl_stride, int64
             s_X[r] = en.X; s_B[r] = en.B; s_S[r] = en.S; s_P[r] = en.pos;
         }
         wave_sync();
-        Trow *row = rows_s + (int64_t)lev * (n + ITD_ROW_PAD);
-        const __amdgpu_buffer_rsrc_t r_row = tile_rsrc32(row, rem, sizeof(Trow));
+        // SEL: the level's row is the residual (the signal's last row, whatever its level) or rotation `lev`: its slot of the packed
+        // rows, or none — no store is issued then (wave-uniform), and the descriptor is empty
+        int slot = lev;
+        if constexpr (SEL) slot = (last && (natural || !cont)) ? sel.res : sel_slot(sel, lev);
+        const bool keep = !SEL || slot >= 0;
+        Trow *row = rows_s + (int64_t)(keep ? slot : 0) * (n + ITD_ROW_PAD);
+        const __amdgpu_buffer_rsrc_t r_row = tile_rsrc32(row, keep ? rem : 0, sizeof(Trow));
         const __amdgpu_buffer_rsrc_t r_bas = tile_rsrc32(bases_s ? (const void *)(bases_s + (int64_t)lev * n) : (const void *)row, (bases_s && (!last || cont)) ? rem : 0, 8);
         // (PART, no caller's baselines: the last fused level's baseline goes where the level launch behind expects its input)
         const __amdgpu_buffer_rsrc_t r_nx = tile_rsrc32((PART && !BASES) ? (const void *)(ws.xnext + (int64_t)sig * ws.xnext_stride + si) : (const void *)row, (PART && !BASES && last && cont) ? rem : 0, 8);
@@ -1215,7 +1222,7 @@ void k_kf_apply(KfWs ws, const double *__restrict__ xl, int64_t xl_stride, int64
             if (last && natural) { re = xe; ro = xo; }               // row c = baselines[c-1], ITD.py:404-416
             else if (last && !cont) { re = (xe - be) + be; ro = (xo - bo) + bo; }   // "Out of time!": rotation + baseline, ITD.py:420
             else { re = xe - be; ro = xo - bo; }                     // ITD.py:119
-            row_store2<true, Trow>(r_row, p, re, ro);
+            if (keep) row_store2<true, Trow>(r_row, p, re, ro);
             if constexpr (BASES) tile_store2<true>(r_bas, p * 8, be, bo);      // (without: not even a bounds-checked-away store is issued)
             if constexpr (PART && !BASES) tile_store2<false>(r_nx, p * 8, be, bo);   // (an empty descriptor except at the last level of a capped call)
             nonfin = nonfin || nonfinite(be) || nonfinite(bo);

@@ -226,12 +226,13 @@ _Pragma("unroll")                                                               
         }
 
 
-template <typename Tin, int TH, int SPT, typename Trow = double>
+// SEL: only the rows of `sel` (RowSel, itd_kernels.hpp), packed: a rotation goes to its slot or nowhere, the residual to its slot
+template <typename Tin, int TH, int SPT, typename Trow = double, bool SEL = false>
 __global__ __launch_bounds__(TH, SPT == 4 ? ITD_RES_MINW : 4) void k_resident(const Tin *__restrict__ xin, int64_t x_stride, int n, int M, int cw,
                                                    int nan_follow /* a NaN in the caller's signal: 1 = the reference's rules (below), 0 = leave (res_fail) */,
                                                    Trow *__restrict__ rows, int64_t rows_stride,
                                                    double *__restrict__ bases, int64_t bases_stride,
-                                                   SigState *__restrict__ state, SigState *__restrict__ other_state)
+                                                   SigState *__restrict__ state, SigState *__restrict__ other_state, RowSel sel = RowSel{0u, 0})
 {
     static_assert(TH % 64 == 0 && TH * SPT <= kResidentMax, "geometry");
     constexpr int W = TH / 64;
@@ -392,11 +393,15 @@ __global__ __launch_bounds__(TH, SPT == 4 ? ITD_RES_MINW : 4) void k_resident(co
     }
 
     for (int c = 0;; ++c) {
-        const __amdgpu_buffer_rsrc_t r_row = tile_rsrc(rows_s + (int64_t)c * n, (int64_t)n * (int64_t)sizeof(Trow));
+        // row c: rotation c, then the residual over it if the signal stops here.  SEL: two rows of the packed result, or none
+        const int slot = SEL ? (c <= M ? sel_slot(sel, c) : -1) : c;
+        const bool keep = !SEL || slot >= 0, keep_res = !SEL || sel.res >= 0;
+        const __amdgpu_buffer_rsrc_t r_row = tile_rsrc(rows_s + (int64_t)(keep ? slot : 0) * n, keep ? (int64_t)n * (int64_t)sizeof(Trow) : 0);
+        const __amdgpu_buffer_rsrc_t r_res = SEL ? tile_rsrc(rows_s + (int64_t)(keep_res ? sel.res : 0) * n, keep_res ? (int64_t)n * (int64_t)sizeof(Trow) : 0) : r_row;
         const __amdgpu_buffer_rsrc_t r_base = tile_rsrc(bases_s ? bases_s + (int64_t)(c <= M ? c : 0) * n : nullptr, bases_s ? (int64_t)n * 8 : 0);
         // ---- passes over the level's ranks: segments k0 .. kend-1 (segment k = samples e_k <= i < e_{k+1}); the window's
         //      slots hold the knots k0-1 .. kend+1, slot = k - k0 + 1 -------------------------------------------------------
-        ITD_RES_PASSES(if (c <= M && !(ITD_RES_ABL & 8)) {
+        ITD_RES_PASSES(if (c <= M && keep && !(ITD_RES_ABL & 8)) {
             // rotation = x - baseline (ITD.py:119) leaves at once unless this is the extraction behind the last requested one
             // (its row is never the rotation)
             res_store_row<Trow>(r_row, i, xr[j] - b);
@@ -409,7 +414,7 @@ __global__ __launch_bounds__(TH, SPT == 4 ? ITD_RES_MINW : 4) void k_resident(co
 #pragma unroll
             for (int j = 0; j < SPT; ++j) {
                 const int q = wave + W * j, i = q * 64 + lane;
-                if (q < Q) res_store_row<Trow>(r_row, i, c == 0 ? 0.0 : xr[j]);
+                if (q < Q && keep_res) res_store_row<Trow>(r_res, i, c == 0 ? 0.0 : xr[j]);
             }
             if (tid == 0) {
                 st->stop_level = c + 1;
@@ -422,10 +427,10 @@ __global__ __launch_bounds__(TH, SPT == 4 ? ITD_RES_MINW : 4) void k_resident(co
 #pragma unroll
             for (int j = 0; j < SPT; ++j) {
                 const int q = wave + W * j, i = q * 64 + lane;
-                if (q < Q) {
+                if (q < Q && keep_res) {
                     const double b = xs[i];
                     const double r = xr[j] - b;
-                    res_store_row<Trow>(r_row, i, r + b);
+                    res_store_row<Trow>(r_res, i, r + b);
                 }
             }
             return;             // fin_stopped stays 0

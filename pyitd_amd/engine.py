@@ -41,6 +41,54 @@ def rows_dtype_of(dtype):
     return dt
 
 
+def selection_of(select, max_iteration):
+    """select= of the decompositions as the C entries take it (itd_decompose_select_*): (rotation_mask, want_residual, S).
+    select is a strictly ascending sequence of rotation indices 0 .. max_iteration, -1 in the last place standing for the residual:
+    [2, 3, -1] keeps rotations 2 and 3 and the residual, in that order.  Anything else — an empty sequence, unsorted or repeated
+    indices, an index above max_iteration, -1 anywhere but last, something that is not an integer — raises ValueError."""
+    try:
+        items = list(select)
+    except TypeError:
+        raise ValueError("select must be a sequence of rotation indices, -1 last for the residual, not %r" % (select,))
+    if not items:
+        raise ValueError("select must name at least one row")
+    for v in items:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError("select holds integers (rotation indices, -1 for the residual), not %r" % (v,))
+    items = [int(v) for v in items]
+    residual = items[-1] == -1
+    rot = items[:-1] if residual else items
+    mask = 0
+    for k, r in enumerate(rot):
+        if r == -1:
+            raise ValueError("-1 (the residual) must be the last entry of select")
+        if r < 0 or r > max_iteration:
+            raise ValueError("select: rotation index %d is outside 0..%d (max_iteration)" % (r, max_iteration))
+        if k and r <= rot[k - 1]:
+            raise ValueError("select must be strictly ascending (no repeats), got %r" % (items,))
+        mask |= 1 << r
+    return mask, 1 if residual else 0, len(items)
+
+
+def zero_absent_slots(rows, select, n_rows):
+    """A selected result's slots of rotations the decomposition did not reach (index > n_rows - 2; their content is unspecified)
+    set to zero, in place: rows is [S, n] with n_rows an int, or [B, S, n] with n_rows [B].  x is still the sum of all rotations and the residual."""
+    rot = np.asarray([r for r in select if r != -1], dtype=np.int64)
+    if rows.ndim == 2:
+        for k in np.nonzero(rot > int(n_rows) - 2)[0]:
+            rows[int(k)] = 0
+    else:
+        absent = np.zeros(rows.shape[:2], dtype=bool)       # [B, S]: the residual's slot is never absent
+        absent[:, : len(rot)] = rot[None, :] > (np.asarray(n_rows, dtype=np.int64)[:, None] - 2)
+        if absent.any():                                    # one masked fill (a torch device tensor: one launch)
+            if isinstance(rows, np.ndarray):
+                rows[absent] = 0
+            else:
+                import torch
+                rows[torch.from_numpy(absent).to(rows.device)] = 0
+    return rows
+
+
 class Engine:
     """One engine = one GPU + one workspace sized for (max_n, max_batch).  Not thread-safe."""
 
@@ -96,11 +144,22 @@ class Engine:
 
     # ---- device-resident path ---------------------------------------------------------------
     def decompose_dev(self, x_ptr, dtype, n, batch, x_stride, max_iteration, rows_ptr, baselines_ptr=None,
-                      stream=None, rows_dtype=np.float64):
+                      stream=None, rows_dtype=np.float64, select=None):
         """Enqueue a decomposition of device data (no host sync).  Pointers are ints.
         rows_dtype: float64, or float32 — rows_ptr is then [batch][max_iteration + 2][n] float32, every element the float64 row's
-        rounded once at its store; no baselines in that mode."""
+        rounded once at its store; no baselines in that mode.
+        select: only these rows (selection_of): rows_ptr is [batch][S][n] of rows_dtype, the selected rotations in ascending order and
+        the residual last; nothing else is stored anywhere.  The slot of a rotation above summary()'s n_rows - 2 holds unspecified
+        values.  No baselines either."""
         f32_in = np.dtype(dtype) == np.float32
+        if select is not None:
+            mask, want_res, _ = selection_of(select, max_iteration)
+            r32 = 1 if rows_dtype_of(rows_dtype) == np.float32 else 0
+            if baselines_ptr:
+                raise ValueError("baselines are not kept with selected rows")
+            f = self._L.itd_decompose_select_f32 if f32_in else self._L.itd_decompose_select_f64
+            self._check(f(self._h, x_ptr, n, batch, x_stride, max_iteration, mask, want_res, rows_ptr, r32, stream))
+            return
         if rows_dtype_of(rows_dtype) == np.float32:
             if baselines_ptr:
                 raise ValueError("baselines are not kept with float32 rows")
@@ -248,19 +307,23 @@ class Engine:
         return ms.value, cnt.value
 
     # ---- numpy in -> numpy out ----------------------------------------------------------------
-    def decompose_host(self, x, max_iteration, want_baselines=True, out=None, rows_dtype=np.float64):
+    def decompose_host(self, x, max_iteration, want_baselines=True, out=None, rows_dtype=np.float64, select=None):
         """want_baselines: True = copy them back now; False = none; "lazy" = leave them on the device: the result carries
         `n_baselines` and `fetch_baselines()`, valid until this engine's next host-form decomposition.
         out: a caller-owned float64 C-contiguous array of at least (max_iteration + 2, n) the rows are written into (a loop over
         calls then neither allocates nor releases 8 (max_iteration + 2) n bytes per call).
         rows_dtype: float64, or float32 — the rows (and `out`) are float32 then, each element the float64 row's rounded once on the
-        device; the result carries no baselines in that mode, whatever want_baselines says."""
+        device; the result carries no baselines in that mode, whatever want_baselines says.
+        select: only these rows (selection_of): the result's "rows" (and `out`) are [S, n], the selected rotations in ascending
+        order and the residual last, with "n_rows" the full decomposition's count; the slots of rotations it did not reach
+        (index > n_rows - 2) are zero.  No baselines in that mode either."""
         rdt = rows_dtype_of(rows_dtype)
+        sel = selection_of(select, max_iteration) if select is not None else None
         x = np.ascontiguousarray(x)
         if x.dtype != np.float32:
             x = np.ascontiguousarray(x, dtype=np.float64)
         n = x.shape[0]
-        R = max_iteration + 2
+        R = sel[2] if sel else max_iteration + 2
         if out is None:
             rows = np.empty((R, n), rdt)
         else:
@@ -268,6 +331,14 @@ class Engine:
                     and out.shape[1] == n and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]):
                 raise ValueError("out must be a writable C-contiguous %s array of shape (>= %d, %d)" % (rdt.name, R, n))
             rows = out
+        if sel:
+            n_rows, stop = ctypes.c_int32(0), ctypes.c_int32(0)
+            kc = np.zeros(MAX_ROWS + 1, np.int64)
+            f = self._L.itd_decompose_select_host_f32 if x.dtype == np.float32 else self._L.itd_decompose_select_host_f64
+            rc = self._check(f(self._h, _np_ptr(x), n, max_iteration, sel[0], sel[1], _np_ptr(rows), 1 if rdt == np.float32 else 0,
+                               ctypes.byref(n_rows), ctypes.byref(stop), _np_ptr(kc)), allow=(ITD_ERR_NONFINITE,))
+            return {"rows": zero_absent_slots(rows[:R], list(select), n_rows.value), "n_rows": n_rows.value, "stop": stop.value,
+                    "knot_counts": kc, "nonfinite": rc == ITD_ERR_NONFINITE}
         if rdt == np.float32:
             n_rows, stop = ctypes.c_int32(0), ctypes.c_int32(0)
             kc = np.zeros(MAX_ROWS + 1, np.int64)

@@ -12,7 +12,7 @@ fallback — without the library or a GPU these functions raise.
 import numpy
 
 from . import _lib
-from .engine import DETECT_KNOTS, DETECT_PEAKS, DETECT_VALLEYS, STOP_TIMEOUT, Engine, rows_dtype_of
+from .engine import DETECT_KNOTS, DETECT_PEAKS, DETECT_VALLEYS, STOP_TIMEOUT, Engine, rows_dtype_of, selection_of, zero_absent_slots
 
 _engines = {}
 _pending = None    # weak reference to the ITD instance whose baselines are still on the device (at most one per process)
@@ -146,6 +146,8 @@ class ITD:
         self._baselines = None
         self._fetch = None          # the last run's baselines are still on the device: fetched when first asked for
         self._rows32 = False        # the last run delivered float32 rows (out_dtype): it kept no baselines
+        self._selected = False      # the last run delivered selected rows (select): it kept none either
+        self.n_rows = None          # rows of the last run's full decomposition (what a selection's slots are measured against)
         self.knot_counts = None
         self.stop_reason = None
 
@@ -153,15 +155,23 @@ class ITD:
         # upstream passes a misspelt keyword here (ITD.py:189-190) and cannot run; the intent is clear
         return self.itd(S, max_iteration=max_iterations)
 
-    def itd(self, data, max_iteration: int = 11, out=None, out_dtype=None):
+    def itd(self, data, max_iteration: int = 11, out=None, out_dtype=None, select=None):
         """ITD.py:351-432 — rows 0..c-1 are proper rotations, the last row is the residual.
         out (an addition to the reference's signature): a caller-owned float64 array of at least (max_iteration + 2, len(data))
         the result is written into; the returned array is a view of its first rows.  The reference allocates its [22, N] buffers
         per call (ITD.py:384-388); a loop over calls that passes `out` pays for that once.
         out_dtype (another addition): None / float64 — the reference's result — or float32: every element of the returned rows is the
         float64 one rounded once on the GPU (half the row traffic and half the copy back; `out`, if given, is float32 then).  Such a
-        call keeps no baselines: get_baselines() raises after it."""
+        call keeps no baselines: get_baselines() raises after it.
+        select (a third): only these rows are computed into the result and brought home — a strictly ascending sequence of rotation
+        indices, -1 in the last place for the residual, e.g. [2, 3, -1] or [-1].  The result is [S, N] in that order (`out`, if
+        given, holds at least S rows); rows that are not named are stored nowhere on the GPU.  `n_rows` is the row count of the full
+        decomposition: the slot of a rotation it did not reach (index > n_rows - 2) is zero, so the signal still is the sum of all
+        rotations and the residual.  No baselines.  Composes with out_dtype."""
         rdt = rows_dtype_of(out_dtype)
+        if select is not None:
+            select = list(select) if hasattr(select, "__iter__") else select
+            selection_of(select, min(int(max_iteration), _lib.MAX_ITERATION))
         x = _as_signal(data)
         self.DTYPE = numpy.asarray(data).dtype
         n = len(x)
@@ -173,7 +183,7 @@ class ITD:
         m = min(int(max_iteration), _lib.MAX_ITERATION)
         self._fetch = None          # this instance's previous baselines are being replaced: nothing to bring home
         _flush_pending()            # another instance's may still sit in the engine's staging buffer: fetch those first
-        res = _engine_for(n, self.device).decompose_host(x, m, want_baselines="lazy", out=out, rows_dtype=rdt)
+        res = _engine_for(n, self.device).decompose_host(x, m, want_baselines="lazy", out=out, rows_dtype=rdt, select=select)
         if res["nonfinite"]:    # only an engine switched to NAN_INPUT_REJECT gets here
             raise ValueError("the input signal contains NaN")
         if max_iteration > _lib.MAX_ITERATION and res["stop"] == STOP_TIMEOUT:
@@ -184,6 +194,8 @@ class ITD:
         # asks (`baselines`, get_baselines()) or the engine's staging buffer is needed again — half the PCIe traffic of a call
         self._baselines = None
         self._rows32 = rdt == numpy.float32
+        self._selected = select is not None
+        self.n_rows = res["n_rows"] if select is not None else len(res["rows"])
         self._fetch = res.get("fetch_baselines")
         global _pending
         import weakref
@@ -213,6 +225,8 @@ class ITD:
     def get_baselines(self):
         if self._rows32 and self._baselines is None:
             raise ValueError("baselines are not kept by a decomposition with float32 rows (out_dtype=float32)")
+        if self._selected and self._baselines is None:
+            raise ValueError("baselines are not kept by a decomposition with selected rows (select=)")
         if self.baselines is None:
             raise ValueError("No baselines found. Please, run ITD method or its variant first.")
         return self.baselines
@@ -234,7 +248,7 @@ def _np_dtype(dtype):
     return dtype
 
 
-def itd_batch(x, max_iteration: int = 11, keep_baselines: bool = False, device=None, out_dtype=None):
+def itd_batch(x, max_iteration: int = 11, keep_baselines: bool = False, device=None, out_dtype=None, select=None):
     """Decompose a batch of independent signals x[B, N] in one call (device resident, one engine launch sequence
     for the whole batch — the batched form of ITD.itd the reference only has as `numba.prange` over rows,
     siftED2D.ipynb cell 1).
@@ -246,13 +260,20 @@ def itd_batch(x, max_iteration: int = 11, keep_baselines: bool = False, device=N
     when keep_baselines.  Row r of signal b is valid for r < n_rows[b].
     out_dtype: None / float64, or float32 (numpy or torch): the rows are float32 then — each element the float64 one rounded once on
     the GPU, half the result buffer — and baselines are not available (keep_baselines raises ValueError).
+    select: only these rows, as in ITD.itd — rows is [B, S, N], the selected rotations in ascending order and the residual (-1) last;
+    the result buffer and the row traffic are those of S rows, not of max_iteration + 2.  n_rows stays the full decomposition's: the
+    slot of a rotation signal b did not reach (index > n_rows[b] - 2) is zero.  Baselines are not available with it either.
     """
     rdt = rows_dtype_of(_np_dtype(out_dtype))
+    if select is not None:
+        select = list(select) if hasattr(select, "__iter__") else select
+        if keep_baselines:
+            raise ValueError("baselines are not kept with selected rows (select=)")
     if rdt == numpy.float32 and keep_baselines:
         raise ValueError("baselines are not kept with float32 rows (out_dtype=float32)")
     if max_iteration < 0 or max_iteration > _lib.MAX_ITERATION:
         raise ValueError("max_iteration must be in 0..20 (the reference's buffers hold 22 rows, ITD.py:384-385)")
-    R = max_iteration + 2
+    R = selection_of(select, max_iteration)[2] if select is not None else max_iteration + 2
     if _is_torch(x):
         import torch
         if not x.is_cuda or x.dim() != 2:
@@ -270,10 +291,13 @@ def itd_batch(x, max_iteration: int = 11, keep_baselines: bool = False, device=N
         torch.cuda.synchronize(xt.device)   # the engine runs on its own stream
         eng.decompose_dev(xt.data_ptr(), numpy.float32 if xt.dtype == torch.float32 else numpy.float64, n, B,
                           xt.stride(0), max_iteration, rows.data_ptr(), bases.data_ptr() if keep_baselines else None, None,
-                          rows_dtype=rdt)
+                          rows_dtype=rdt, select=select)
         s = eng.summary(B)
         if (s["nan_levels"] == -2).any():
             raise ValueError("an input signal contains NaN")
+        if select is not None:
+            torch.cuda.synchronize(xt.device)
+            zero_absent_slots(rows, select, s["n_rows"])
         out = {"n_rows": s["n_rows"], "stop": s["stop"], "knot_counts": s["knot_counts"], "rows": rows}
         if keep_baselines:
             out["baselines"] = bases
@@ -297,7 +321,7 @@ def itd_batch(x, max_iteration: int = 11, keep_baselines: bool = False, device=N
         d_x.upload(a)
         eng = _batch_engine_for(n, B, dev)
         eng.decompose_dev(d_x.ptr, a.dtype, n, B, n, max_iteration, d_rows.ptr, d_bases.ptr if keep_baselines else None, None,
-                          rows_dtype=rdt)
+                          rows_dtype=rdt, select=select)
         s = eng.summary(B)
         if (s["nan_levels"] == -2).any():
             raise ValueError("an input signal contains NaN")
@@ -306,6 +330,8 @@ def itd_batch(x, max_iteration: int = 11, keep_baselines: bool = False, device=N
         if keep_baselines:
             out["baselines"] = d_bases.download(numpy.empty((B, R, n), numpy.float64))
             out["n_baselines"] = s["n_baselines"]
+        if select is not None:
+            zero_absent_slots(out["rows"], select, s["n_rows"])
         return out
     finally:
         d_x.free()
