@@ -165,14 +165,26 @@ struct Rows {
     Rows() {}
     Rows(double *d) : p(d) {}
     Rows(float *f) : p(f), f32(true) {}
-    Rows(void *q, bool is32) : p(q), f32(is32) {}
     Rows(void *q, bool is32, uint32_t mask, bool residual) : p(q), f32(is32), sel(true), which{mask, residual ? __builtin_popcount(mask) : -1} {}
     size_t esz() const { return f32 ? sizeof(float) : sizeof(double); }
     Rows at(int64_t elems) const { Rows r = *this; r.p = static_cast<char *>(p) + elems * (int64_t)esz(); return r; }
     int count(int M) const { return sel ? __builtin_popcount(which.mask) + (which.res >= 0 ? 1 : 0) : M + 2; }   // rows per signal
+    int64_t stride(int M, int64_t n) const { return (int64_t)count(M) * (n + ITD_ROW_PAD); }   // elements from one signal's rows to the next's
     // the slot of the row a level launch writes (rotation j, or behind the last requested level the "Out of time!" residual); < 0: none
     int slot(int j, bool residual) const { return !sel ? j : residual ? which.res : sel_slot(which, j); }
 };
+
+// A Rows as the kernels see it: every kernel that stores rows is a template on the element type (Trow) and on whether the rows are a
+// selection's packed ones (SEL).  with_row_form is the one place where a call's runtime description becomes those template arguments:
+// it hands f the form as a tag value, and what f launches names each kernel once, as k<..., typename Form::Trow, Form::SEL>.
+template <typename TROW, bool SELECT>
+struct RowForm { using Trow = TROW; static constexpr bool SEL = SELECT; };
+template <typename F>
+int with_row_form(const Rows &rows, F &&f)
+{
+    if (rows.sel) return rows.f32 ? f(RowForm<float, true>{}) : f(RowForm<double, true>{});
+    return rows.f32 ? f(RowForm<float, false>{}) : f(RowForm<double, false>{});
+}
 
 // The record of the last decomposition enqueued: what itd_get_summary reads back, repeats or repairs, and itd_get_timing, ... refer to
 struct LastCall {
@@ -454,20 +466,24 @@ struct ChunkBufs {
 
 // one level launch of a chunk (k_extract): level j's input xin -> rotation rows[j] and baseline j; level j's counts, records and group
 // sums -> level j + 1's (TIES: the launch in front of the fused sparse levels also flags the tiles of its baseline that hold a near tie)
-template <typename TIN, bool FIN, int CAPK, int KTW = kTilesPerWave, bool FUSE = false, bool TIES = false, typename TROW = double>
+// (slot: Rows::slot.  < 0, a level whose row the selection drops: the form without a row store, TROW = NoRow — its pointer is the buffer's
+// own base, a valid address that is never used)
+template <typename Trow, typename TIN, bool FIN, int CAPK, int KTW = kTilesPerWave, bool FUSE = false, bool TIES = false>
 hipError_t launch_extract(itd_engine *e, const ChunkBufs &c, const TIN *xin, int64_t xs, int j, int pair, int slot)
 {
     const TIN *a_x = xin; int64_t a_xs = xs, a_n = c.n, a_rs = c.rows_stride, a_bs = c.base_stride();
     int a_nt = c.n_tiles, a_b = c.nb, a_lvl = j, a_keep = 0;
     const int32_t *a_ci = c.cnt(j), *a_gi = c.gs(j); int32_t *a_co = c.cnt(j + 1), *a_go = c.gs(j + 1), *a_gc = c.gs(j + 2);
     const TileRec *a_ri = c.rec(j); TileRec *a_ro = c.rec(j + 1);
-    // (slot: Rows::slot; none: TROW = NoRow, which stores no row — its pointer is the buffer's own base, a valid address that is never used)
     void *a_rot = c.rows.at((int64_t)std::max(slot, 0) * (c.n + ITD_ROW_PAD)).p; double *a_bas = c.base(j);
     SigState *a_st = c.state; unsigned long long *a_tie = TIES ? c.near : nullptr;
     void *args[] = {&a_x, &a_xs, &a_n, &a_nt, &a_b, &a_ci, &a_co, &a_ri, &a_ro, &a_gi, &a_go, &a_gc, &a_rot, &a_rs,
                     &a_bas, &a_bs, &a_st, &a_lvl, &a_keep, &a_tie};
-    return launch_timed(e, reinterpret_cast<const void *>(&k_extract<TIN, T, FIN, CAPK, KTW, FUSE, TIES, TROW>),
-                        dim3((c.n_tiles + KTW - 1) / KTW, c.nb), dim3(kWave), args, c.st, pair);
+    const auto launch = [&](auto form) {
+        return launch_timed(e, reinterpret_cast<const void *>(&k_extract<TIN, T, FIN, CAPK, KTW, FUSE, TIES, typename decltype(form)::Trow>),
+                            dim3((c.n_tiles + KTW - 1) / KTW, c.nb), dim3(kWave), args, c.st, pair);
+    };
+    return slot < 0 ? launch(RowForm<NoRow, false>{}) : launch(RowForm<Trow, false>{});
 }
 
 // the fused levels' workspace as one chunk's launches see it: this call's geometry, every pointer offset to the chunk's first signal
@@ -498,9 +514,12 @@ KfWs kf_chunk_ws(const itd_engine *e, const DecomposePlan<Tin> &p, const int b0,
 //   3. without fused levels: k_finalize.  With them: the knot side (k_kf_knots, which does k_finalize's work for the first fused level),
 //      the test-only k_kf_fault and the sample pass (k_kf_apply); behind capped fused levels a scan of the baseline the sample pass
 //      stored (k_clear_gsum, k_scan0), the remaining level launches and k_finalize.
-template <typename Tin>
+// Form: the rows' RowForm (with_row_form): every launch that stores rows is the instance of that form.
+template <typename Form, typename Tin>
 int run_chunk(itd_engine *e, const DecomposePlan<Tin> &p, const int b0, const int nb, const hipStream_t cst)
 {
+    using Trow = typename Form::Trow;
+    constexpr bool SEL = Form::SEL;
     const int64_t n = p.n, pp3 = 3 * e->pp_pitch;
     const ChunkBufs c{e, nb, p.n_tiles, n, p.rows_stride, cst, p.state + b0, p.rows.at((int64_t)b0 * p.rows_stride),
                       p.bases ? p.bases + (int64_t)b0 * p.rows_stride : nullptr, e->d_pp + (int64_t)b0 * pp3,
@@ -510,8 +529,6 @@ int run_chunk(itd_engine *e, const DecomposePlan<Tin> &p, const int b0, const in
     double *xm_c = c.pp + 2 * e->pp_pitch;   // NaN-input repeat: the mutated signal, one per signal at the slots' stride
     const dim3 blk(kWave);
     // what k_finalize needs (the knot side as well, for the first fused level: its gsum is set there): the rows, the baselines, the other set
-    const bool r32 = c.rows.f32;     // float32 rows: the same launches, each in its float32 store form
-    const bool sel = c.rows.sel;     // a selection: the same launches again, those that store rows in their packed-rows form
     KfFin fin{c.rows.p, p.rows_stride, c.bases ? c.bases : c.pp, c.base_stride(), c.bases ? n : e->pp_pitch, c.bases ? 0 : 3, nullptr,
               p.other_state + b0, p.other_gsum + (int64_t)b0 * p.n_groups * kGsumPitch, e->gsum_third, c.rows.which.res};
     // the level launches ja .. jb: extraction j + 1, input = the level-j signal, rotation -> rows[j], baseline -> baseline j
@@ -522,18 +539,14 @@ int run_chunk(itd_engine *e, const DecomposePlan<Tin> &p, const int b0, const in
             const double *in = j ? c.base(j - 1) : nullptr;
             const int64_t is = c.base_stride();
             hipError_t rc;
-            const int slot = c.rows.slot(j, final_level);    // (a level whose row the selection drops: the form without a row store)
-#define ITD_LX(TIN, FIN, CAPK, KTW, FUSE, TIES, ...) \
-    (slot < 0 ? launch_extract<TIN, FIN, CAPK, KTW, FUSE, TIES, NoRow>(__VA_ARGS__, slot) : \
-     r32 ? launch_extract<TIN, FIN, CAPK, KTW, FUSE, TIES, float>(__VA_ARGS__, slot) : launch_extract<TIN, FIN, CAPK, KTW, FUSE, TIES, double>(__VA_ARGS__, slot))
+            const int slot = c.rows.slot(j, final_level);
             if (j == 0) {   // never the last level: M >= 0
-                if (p.nan_input) rc = ITD_LX(double, false, kRankCap0, kTilesPerWave, false, false, e, c, xm_c, pp3, 0, pair);
-                else if (p.fuse0) rc = ITD_LX(Tin, false, kRankCap0, kFuse0TilesPerWave, true, false, e, c, xc, p.x_stride, 0, pair);
-                else rc = ITD_LX(Tin, false, kRankCap0, kTilesPerWave, false, false, e, c, xc, p.x_stride, 0, pair);
-            } else if (final_level) rc = ITD_LX(double, true, kRankCap, kTilesPerWave, false, false, e, c, in, is, j, pair);
-            else if (p.kf && j == p.L0 - 1) rc = ITD_LX(double, false, kRankCap, kTilesPerWave, false, true, e, c, in, is, j, pair);
-            else rc = ITD_LX(double, false, kRankCap, kTilesPerWave, false, false, e, c, in, is, j, pair);
-#undef ITD_LX
+                if (p.nan_input) rc = launch_extract<Trow, double, false, kRankCap0>(e, c, xm_c, pp3, 0, pair, slot);
+                else if (p.fuse0) rc = launch_extract<Trow, Tin, false, kRankCap0, kFuse0TilesPerWave, true>(e, c, xc, p.x_stride, 0, pair, slot);
+                else rc = launch_extract<Trow, Tin, false, kRankCap0>(e, c, xc, p.x_stride, 0, pair, slot);
+            } else if (final_level) rc = launch_extract<Trow, double, true, kRankCap>(e, c, in, is, j, pair, slot);
+            else if (p.kf && j == p.L0 - 1) rc = launch_extract<Trow, double, false, kRankCap, kTilesPerWave, false, true>(e, c, in, is, j, pair, slot);
+            else rc = launch_extract<Trow, double, false, kRankCap>(e, c, in, is, j, pair, slot);
             if (rc != hipSuccess) return fail_hip(e, rc, "hipExtLaunchKernel(k_extract)");
         }
         return ITD_OK;
@@ -543,18 +556,9 @@ int run_chunk(itd_engine *e, const DecomposePlan<Tin> &p, const int b0, const in
         // blocks per signal: a thread of the row fix-up moves 8 samples (four 16-byte accesses) before the grid is widened
         const int fb = (int)std::min<int64_t>(std::max<int64_t>((n + 8 * kFinalizeThreads - 1) / (8 * kFinalizeThreads), 1), 1024);
         const int jf = p.M + 2;      // the level whose input is pending
-        if (sel && r32) k_finalize<float, true><<<dim3(fb, nb), kFinalizeThreads, 0, cst>>>(static_cast<float *>(fin.rows), fin.rows_stride, n, fin.bases, fin.bases_stride,
-                                                                                            fin.bases_row_pitch, fin.bases_rotate, c.gs(jf), p.n_tiles, jf, c.state,
-                                                                                            fin.other_state, fin.other_gsum, fin.other_third, fin.res_slot);
-        else if (sel) k_finalize<double, true><<<dim3(fb, nb), kFinalizeThreads, 0, cst>>>(static_cast<double *>(fin.rows), fin.rows_stride, n, fin.bases, fin.bases_stride,
-                                                                                           fin.bases_row_pitch, fin.bases_rotate, c.gs(jf), p.n_tiles, jf, c.state,
-                                                                                           fin.other_state, fin.other_gsum, fin.other_third, fin.res_slot);
-        else if (r32) k_finalize<float><<<dim3(fb, nb), kFinalizeThreads, 0, cst>>>(static_cast<float *>(fin.rows), fin.rows_stride, n, fin.bases, fin.bases_stride,
-                                                                               fin.bases_row_pitch, fin.bases_rotate, c.gs(jf), p.n_tiles, jf, c.state,
-                                                                               fin.other_state, fin.other_gsum, fin.other_third);
-        else k_finalize<double><<<dim3(fb, nb), kFinalizeThreads, 0, cst>>>(static_cast<double *>(fin.rows), fin.rows_stride, n, fin.bases, fin.bases_stride,
-                                                                            fin.bases_row_pitch, fin.bases_rotate, c.gs(jf), p.n_tiles, jf, c.state,
-                                                                            fin.other_state, fin.other_gsum, fin.other_third);
+        k_finalize<Trow, SEL><<<dim3(fb, nb), kFinalizeThreads, 0, cst>>>(static_cast<Trow *>(fin.rows), fin.rows_stride, n, fin.bases, fin.bases_stride,
+                                                                          fin.bases_row_pitch, fin.bases_rotate, c.gs(jf), p.n_tiles, jf, c.state,
+                                                                          fin.other_state, fin.other_gsum, fin.other_third, fin.res_slot);
     };
 
     if (p.nan_input) {
@@ -582,9 +586,7 @@ int run_chunk(itd_engine *e, const DecomposePlan<Tin> &p, const int b0, const in
         KfFin a_f = fin;
         a_f.gsum = c.gs(p.L0);
         void *args[] = {&a_w, &a_f, &a_xl, &a_ls, &a_n, &a_m, &a_c, &a_r, &a_st};
-        const void *knots_fn = sel ? (r32 ? reinterpret_cast<const void *>(&k_kf_knots<T, float, true>) : reinterpret_cast<const void *>(&k_kf_knots<T, double, true>)) :
-                               r32 ? reinterpret_cast<const void *>(&k_kf_knots<T, float>) : reinterpret_cast<const void *>(&k_kf_knots<T>);
-        HIP_TRY(e, launch_timed(e, knots_fn, dim3((unsigned)w.wgs * (unsigned)nb), dim3(kKcThreads),
+        HIP_TRY(e, launch_timed(e, reinterpret_cast<const void *>(&k_kf_knots<T, Trow, SEL>), dim3((unsigned)w.wgs * (unsigned)nb), dim3(kKcThreads),
                                 args, cst, time_slot(e, ITD_TIME_KF_KNOTS)));
     }
     if (e->fault_kind >= 0 && (e->fault_kind <= 5 || e->fault_kind == 8) && e->fault_level >= p.L0 && e->fault_level - p.L0 < w.nlev &&
@@ -595,12 +597,15 @@ int run_chunk(itd_engine *e, const DecomposePlan<Tin> &p, const int b0, const in
         const TileRec *a_rec = c.rec(p.L0); void *a_rows = c.rows.p; double *a_bases = c.bases;
         RowSel a_sel = c.rows.which;
         void *args[] = {&a_w, &a_xl, &a_xs, &a_n, &a_rec, &a_rows, &a_rs, &a_bases, &a_bs, &a_sel};
-        // (float32 rows and selections come without the caller's baselines: two forms of the sample pass each, not four)
-        const void *apply_fn = sel ? (r32 ? (p.cap ? reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, true, float, true>) : reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, false, float, true>))
-                                          : (p.cap ? reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, true, double, true>) : reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, false, double, true>))) :
-                               r32 ? (p.cap ? reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, true, float>) : reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, false, float>)) :
-                               p.cap ? (c.bases ? reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, true, true>) : reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, true>))
-                                     : (c.bases ? reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, true, false>) : reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, false, false>));
+        const auto apply_of = [&](auto with_bases) {
+            const auto fn = [](auto part) {
+                return reinterpret_cast<const void *>(&k_kf_apply<T, kKfCap, decltype(with_bases)::value, decltype(part)::value, Trow, SEL>);
+            };
+            return p.cap ? fn(std::true_type{}) : fn(std::false_type{});    // (PART: capped fused levels)
+        };
+        const void *apply_fn = apply_of(std::false_type{});
+        // (the caller's baselines come with all the rows in float64 only: the other forms have no BASES instance)
+        if constexpr (std::is_same<Trow, double>::value && !SEL) { if (c.bases) apply_fn = apply_of(std::true_type{}); }
         HIP_TRY(e, launch_timed(e, apply_fn, dim3(p.n_tiles + kf_check_blocks(w.wgs), nb), blk, args, cst, time_slot(e, ITD_TIME_KF_APPLY)));
     }
     if (!p.cap) return ITD_OK;
@@ -692,7 +697,7 @@ int enqueue_decompose(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int
     p.n_tiles = (int)tiles_of(n);
     p.n_groups = groups_of(p.n_tiles);
     p.kf_wgs = (p.n_tiles + p.kf_tpw - 1) / p.kf_tpw;
-    p.rows_stride = (int64_t)rows.count(M) * (n + ITD_ROW_PAD);
+    p.rows_stride = rows.stride(M, n);
 
     // instrument every timing_stride-th decomposition only: a launch that carries events needs a completion signal of its own
     // (~2 us per launch, measured), the whole-decomposition span two marker records (~5 us each)
@@ -730,7 +735,9 @@ int enqueue_decompose(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int
     }
     for (int k = 0; k < n_chunks; ++k) {
         const int b0 = k * p.chunk, lane = k % p.S;
-        const int rc = run_chunk(e, p, b0, std::min(p.chunk, batch - b0), lane == 0 ? st : e->aux_stream[lane - 1]);
+        const int rc = with_row_form(rows, [&](auto form) {
+            return run_chunk<decltype(form)>(e, p, b0, std::min(p.chunk, batch - b0), lane == 0 ? st : e->aux_stream[lane - 1]);
+        });
         if (rc) return rc;
     }
     for (int k = 0; k < p.S - 1; ++k) {
@@ -784,7 +791,7 @@ int enqueue_resident(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int6
                      double *bases_user, hipStream_t st)
 {
     const int64_t R = (int64_t)M + 2;
-    const int64_t rows_stride = (int64_t)rows.count(M) * n;      // (the caller's baselines, full calls only, lie R rows apart as well)
+    const int64_t rows_stride = rows.stride(M, n);      // (the caller's baselines, full calls only, lie R rows apart as well)
     const int set = e->cur_set ^ 1;
     SigState *const set_state = e->d_state + (size_t)set * e->max_batch;
     SigState *const other_state = e->d_state + (size_t)(set ^ 1) * e->max_batch;
@@ -792,20 +799,17 @@ int enqueue_resident(itd_engine *e, const Tin *x, int64_t n, int32_t batch, int6
         HIP_TRY(e, hipMemset2DAsync(bases_user + (R - 1) * n, (size_t)rows_stride * sizeof(double), 0,
                                     (size_t)n * sizeof(double), (size_t)batch, st));
     const WgClass wc = wg_class((int)n, e->resident_window);
-#define ITD_RES_SEL(TROW) \
-        reinterpret_cast<const void *>(&k_resident<Tin, 64, 4, TROW, true>),   reinterpret_cast<const void *>(&k_resident<Tin, 128, 4, TROW, true>),  \
-        reinterpret_cast<const void *>(&k_resident<Tin, 256, 4, TROW, true>),  reinterpret_cast<const void *>(&k_resident<Tin, 512, 4, TROW, true>),  \
-        reinterpret_cast<const void *>(&k_resident<Tin, 1024, 4, TROW, true>), reinterpret_cast<const void *>(&k_resident<Tin, 1024, 8, TROW, true>)
-    const void *const inst[4][6] = {{   // by row type (then the same with a selection) and size class
-        reinterpret_cast<const void *>(&k_resident<Tin, 64, 4>),   reinterpret_cast<const void *>(&k_resident<Tin, 128, 4>),
-        reinterpret_cast<const void *>(&k_resident<Tin, 256, 4>),  reinterpret_cast<const void *>(&k_resident<Tin, 512, 4>),
-        reinterpret_cast<const void *>(&k_resident<Tin, 1024, 4>), reinterpret_cast<const void *>(&k_resident<Tin, 1024, 8>)}, {
-        reinterpret_cast<const void *>(&k_resident<Tin, 64, 4, float>),   reinterpret_cast<const void *>(&k_resident<Tin, 128, 4, float>),
-        reinterpret_cast<const void *>(&k_resident<Tin, 256, 4, float>),  reinterpret_cast<const void *>(&k_resident<Tin, 512, 4, float>),
-        reinterpret_cast<const void *>(&k_resident<Tin, 1024, 4, float>), reinterpret_cast<const void *>(&k_resident<Tin, 1024, 8, float>)},
-        {ITD_RES_SEL(double)}, {ITD_RES_SEL(float)}};
-#undef ITD_RES_SEL
-    const void *fn = inst[(rows.sel ? 2 : 0) + (rows.f32 ? 1 : 0)][wc.cls];
+    const void *fn = nullptr;
+    (void)with_row_form(rows, [&](auto form) {
+        using Trow = typename decltype(form)::Trow;
+        constexpr bool SEL = decltype(form)::SEL;
+        const void *const by_class[6] = {
+            reinterpret_cast<const void *>(&k_resident<Tin, 64, 4, Trow, SEL>),   reinterpret_cast<const void *>(&k_resident<Tin, 128, 4, Trow, SEL>),
+            reinterpret_cast<const void *>(&k_resident<Tin, 256, 4, Trow, SEL>),  reinterpret_cast<const void *>(&k_resident<Tin, 512, 4, Trow, SEL>),
+            reinterpret_cast<const void *>(&k_resident<Tin, 1024, 4, Trow, SEL>), reinterpret_cast<const void *>(&k_resident<Tin, 1024, 8, Trow, SEL>)};
+        fn = by_class[wc.cls];
+        return ITD_OK;
+    });
     const hipError_t arc = allow_lds(e, fn, kResidentLdsMax);
     if (arc != hipSuccess) {     // a device / runtime that does not grant it: this engine runs level by level from now on
         (void)hipGetLastError();
@@ -872,10 +876,22 @@ int check_args(itd_engine *e, const void *x, int64_t n, int32_t batch, int64_t x
 }
 
 // a selection of rows (itd_decompose_select_*): rotation bits within 0 .. M, the residual flag 0 or 1, one row at least
-bool selection_ok(int32_t M, uint32_t mask, int32_t want_residual)
+// and the row type 0 (float64) or 1 (float32).  What the select entries, device and host, test before they look at anything else
+bool selection_ok(int32_t M, uint32_t mask, int32_t want_residual, int32_t rows_f32)
 {
-    if (M < 0 || M > ITD_MAX_ITERATION || (mask >> (M + 1)) != 0) return false;
+    if (M < 0 || M > ITD_MAX_ITERATION || (mask >> (M + 1)) != 0 || (rows_f32 != 0 && rows_f32 != 1)) return false;
     return (want_residual == 0 || want_residual == 1) && (mask != 0 || want_residual == 1);
+}
+
+// The body of the six device entries (itd_decompose_*_f32 / _f64): they differ in the Rows they describe
+template <typename Tin>
+int decompose_dev(itd_engine *e, const Tin *x_dev, int64_t n, int32_t batch, int64_t x_stride, int32_t M, Rows rows, double *bases_dev,
+                  void *stream)
+{
+    const int rc = check_args(e, x_dev, n, batch, x_stride, M, rows.p);
+    if (rc) return rc;
+    DevGuard g(e->device);
+    return enqueue_any<Tin>(e, x_dev, n, batch, x_stride, M, rows, bases_dev, stream_of(e, stream));
 }
 
 // a grow-only buffer of the engine made to hold `want` bytes (Buf::reserve), the engine's error text set when that fails
@@ -1149,68 +1165,48 @@ int itd_shard_scatter(const void *x_root_dev, void *x_local_dev, int64_t n, int6
 int itd_decompose_f32(itd_engine *e, const float *x_dev, int64_t n, int32_t batch, int64_t x_stride,
                       int32_t max_iteration, double *rows_dev, double *baselines_dev, void *stream)
 {
-    int rc = check_args(e, x_dev, n, batch, x_stride, max_iteration, rows_dev);
-    if (rc) return rc;
-    DevGuard g(e->device);
-    return enqueue_any<float>(e, x_dev, n, batch, x_stride, max_iteration, rows_dev, baselines_dev, stream_of(e, stream));
+    return decompose_dev(e, x_dev, n, batch, x_stride, max_iteration, Rows(rows_dev), baselines_dev, stream);
 }
 
 int itd_decompose_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t batch, int64_t x_stride,
                       int32_t max_iteration, double *rows_dev, double *baselines_dev, void *stream)
 {
-    int rc = check_args(e, x_dev, n, batch, x_stride, max_iteration, rows_dev);
-    if (rc) return rc;
-    DevGuard g(e->device);
-    return enqueue_any<double>(e, x_dev, n, batch, x_stride, max_iteration, rows_dev, baselines_dev, stream_of(e, stream));
+    return decompose_dev(e, x_dev, n, batch, x_stride, max_iteration, Rows(rows_dev), baselines_dev, stream);
 }
 
 // float32 rows: the same call in every respect, each row element the float64 one rounded once at its store; no caller's baselines
 int itd_decompose_rows32_f32(itd_engine *e, const float *x_dev, int64_t n, int32_t batch, int64_t x_stride,
                              int32_t max_iteration, float *rows_dev, void *stream)
 {
-    int rc = check_args(e, x_dev, n, batch, x_stride, max_iteration, rows_dev);
-    if (rc) return rc;
-    DevGuard g(e->device);
-    return enqueue_any<float>(e, x_dev, n, batch, x_stride, max_iteration, rows_dev, nullptr, stream_of(e, stream));
+    return decompose_dev(e, x_dev, n, batch, x_stride, max_iteration, Rows(rows_dev), nullptr, stream);
 }
 
 int itd_decompose_rows32_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t batch, int64_t x_stride,
                              int32_t max_iteration, float *rows_dev, void *stream)
 {
-    int rc = check_args(e, x_dev, n, batch, x_stride, max_iteration, rows_dev);
-    if (rc) return rc;
-    DevGuard g(e->device);
-    return enqueue_any<double>(e, x_dev, n, batch, x_stride, max_iteration, rows_dev, nullptr, stream_of(e, stream));
+    return decompose_dev(e, x_dev, n, batch, x_stride, max_iteration, Rows(rows_dev), nullptr, stream);
 }
 
 // selected rows: the same call in every respect, each selected row's elements those of the full call; the rest is stored nowhere
 int itd_decompose_select_f32(itd_engine *e, const float *x_dev, int64_t n, int32_t batch, int64_t x_stride, int32_t max_iteration,
                              uint32_t rotation_mask, int32_t want_residual, void *rows_dev, int32_t rows_f32, void *stream)
 {
-    if (!selection_ok(max_iteration, rotation_mask, want_residual) || (rows_f32 != 0 && rows_f32 != 1)) return ITD_ERR_INVALID_ARG;
-    int rc = check_args(e, x_dev, n, batch, x_stride, max_iteration, rows_dev);
-    if (rc) return rc;
-    DevGuard g(e->device);
-    return enqueue_any<float>(e, x_dev, n, batch, x_stride, max_iteration, Rows(rows_dev, rows_f32 != 0, rotation_mask, want_residual != 0),
-                              nullptr, stream_of(e, stream));
+    if (!selection_ok(max_iteration, rotation_mask, want_residual, rows_f32)) return ITD_ERR_INVALID_ARG;
+    return decompose_dev(e, x_dev, n, batch, x_stride, max_iteration, Rows(rows_dev, rows_f32 != 0, rotation_mask, want_residual != 0), nullptr, stream);
 }
 
 int itd_decompose_select_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t batch, int64_t x_stride, int32_t max_iteration,
                              uint32_t rotation_mask, int32_t want_residual, void *rows_dev, int32_t rows_f32, void *stream)
 {
-    if (!selection_ok(max_iteration, rotation_mask, want_residual) || (rows_f32 != 0 && rows_f32 != 1)) return ITD_ERR_INVALID_ARG;
-    int rc = check_args(e, x_dev, n, batch, x_stride, max_iteration, rows_dev);
-    if (rc) return rc;
-    DevGuard g(e->device);
-    return enqueue_any<double>(e, x_dev, n, batch, x_stride, max_iteration, Rows(rows_dev, rows_f32 != 0, rotation_mask, want_residual != 0),
-                               nullptr, stream_of(e, stream));
+    if (!selection_ok(max_iteration, rotation_mask, want_residual, rows_f32)) return ITD_ERR_INVALID_ARG;
+    return decompose_dev(e, x_dev, n, batch, x_stride, max_iteration, Rows(rows_dev, rows_f32 != 0, rotation_mask, want_residual != 0), nullptr, stream);
 }
 
 namespace {
 // The recorded call `c` again, level by level unless fuse0, on its signals b0 .. b0 + batch - 1 into their rows (and baselines)
 int enqueue_again(itd_engine *e, const LastCall c, int b0, int32_t batch, bool fuse0, bool nan_input)
 {
-    const int64_t rs = (int64_t)c.rows.count(c.m) * c.n;      // (the caller's baselines come with full calls only: the same stride)
+    const int64_t rs = c.rows.stride(c.m, c.n);      // (the caller's baselines come with full calls only: the same stride)
     const Rows rows = c.rows.at((int64_t)b0 * rs); double *bases = c.bases ? c.bases + (int64_t)b0 * rs : nullptr;
     return c.x_f32 ? enqueue_decompose<float>(e, (const float *)c.x + (int64_t)b0 * c.x_stride, c.n, batch, c.x_stride, c.m, rows, bases, c.stream, fuse0, nan_input)
                    : enqueue_decompose<double>(e, (const double *)c.x + (int64_t)b0 * c.x_stride, c.n, batch, c.x_stride, c.m, rows, bases, c.stream, fuse0, nan_input);
@@ -1553,39 +1549,37 @@ int itd_set_batch_chunk(itd_engine *e, int32_t signals_per_chunk)
 }  // extern "C"
 
 namespace {
-// Trow = float: the rows32 host entries (no baselines, kept or returned).  select: the rows of (mask, residual) only, packed — all
-// their slots are copied back, those of rotations the decomposition did not reach with unspecified content; no baselines either
-template <typename Tin, typename Trow = double>
-int decompose_host(itd_engine *e, const Tin *x_host, int64_t n, int32_t M, Trow *rows_host, double *bases_host,
-                   int32_t *n_rows, int32_t *n_baselines, int32_t *stop_reason, int64_t *knot_counts,
-                   bool select = false, uint32_t mask = 0, bool residual = false)
+// The body of the six host entries.  host: the caller's rows as a Rows (its pointer a host address): float32 rows and selections come
+// without baselines, kept or returned; all of a selection's slots are copied back, those of rotations the decomposition did not reach
+// with unspecified content
+template <typename Tin>
+int decompose_host(itd_engine *e, const Tin *x_host, int64_t n, int32_t M, Rows host, double *bases_host,
+                   int32_t *n_rows, int32_t *n_baselines, int32_t *stop_reason, int64_t *knot_counts)
 {
-    if (select && !selection_ok(M, mask, residual ? 1 : 0)) return ITD_ERR_INVALID_ARG;
-    if (!e || !x_host || !rows_host) return ITD_ERR_INVALID_ARG;
+    if (!e || !x_host || !host.p) return ITD_ERR_INVALID_ARG;
     if (n < 3 || n > e->max_n || M < 0 || M > ITD_MAX_ITERATION) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    const size_t R = select ? (size_t)Rows(nullptr, false, mask, residual).count(M) : (size_t)M + 2;
     int rc = grow(e, e->d_io_x, (size_t)n * sizeof(Tin));
     if (rc) return rc;
-    rc = grow(e, e->d_io_rows, R * (size_t)n * sizeof(Trow));
+    rc = grow(e, e->d_io_rows, (size_t)host.stride(M, n) * host.esz());
     if (rc) return rc;
-    const bool dev_bases = sizeof(Trow) == 8 && !select && (bases_host || e->host_keep_bases);
+    const bool dev_bases = !host.f32 && !host.sel && (bases_host || e->host_keep_bases);
     e->kept_nb = -1;
     if (dev_bases) {
-        rc = grow(e, e->d_io_bases, R * (size_t)n * sizeof(double));
+        rc = grow(e, e->d_io_bases, (size_t)host.stride(M, n) * sizeof(double));
         if (rc) return rc;
     }
     hipStream_t st = e->own_stream;
     HIP_TRY(e, hipMemcpyAsync(e->d_io_x, x_host, (size_t)n * sizeof(Tin), hipMemcpyHostToDevice, st));
-    Rows rows(reinterpret_cast<Trow *>(e->d_io_rows.get()));
-    if (select) rows = Rows(rows.p, rows.f32, mask, residual);
+    Rows rows = host;
+    rows.p = e->d_io_rows.get();
     rc = enqueue_any<Tin>(e, (const Tin *)e->d_io_x, n, 1, n, M, rows, dev_bases ? e->d_io_bases : nullptr, st);
     if (rc) return rc;
     int32_t nr = 0, nb = 0, why = 0, nanlv = -1;
     int64_t kc[ITD_MAX_ROWS + 1];
     rc = itd_get_summary(e, &nr, &nb, &why, kc, &nanlv);
     if (rc) return rc;
-    rc = copy_to_host(e, rows_host, e->d_io_rows, (select ? R : (size_t)nr) * n * sizeof(Trow), st);
+    rc = copy_to_host(e, host.p, e->d_io_rows, (size_t)(host.sel ? host.count(M) : nr) * n * host.esz(), st);
     if (rc) return rc;
     if (bases_host) {
         rc = copy_to_host(e, bases_host, e->d_io_bases, (size_t)nb * n * sizeof(double), st);
@@ -1840,50 +1834,44 @@ int itd_decompose_host_f64(itd_engine *e, const double *x_host, int64_t n, int32
                            double *baselines_host, int32_t *n_rows, int32_t *n_baselines, int32_t *stop_reason,
                            int64_t *knot_counts)
 {
-    return decompose_host<double>(e, x_host, n, max_iteration, rows_host, baselines_host, n_rows, n_baselines,
-                                  stop_reason, knot_counts);
-}
-
-int itd_decompose_rows32_host_f32(itd_engine *e, const float *x_host, int64_t n, int32_t max_iteration, float *rows_host,
-                                  int32_t *n_rows, int32_t *stop_reason, int64_t *knot_counts)
-{
-    return decompose_host<float, float>(e, x_host, n, max_iteration, rows_host, nullptr, n_rows, nullptr, stop_reason, knot_counts);
-}
-
-int itd_decompose_rows32_host_f64(itd_engine *e, const double *x_host, int64_t n, int32_t max_iteration, float *rows_host,
-                                  int32_t *n_rows, int32_t *stop_reason, int64_t *knot_counts)
-{
-    return decompose_host<double, float>(e, x_host, n, max_iteration, rows_host, nullptr, n_rows, nullptr, stop_reason, knot_counts);
-}
-
-int itd_decompose_select_host_f32(itd_engine *e, const float *x_host, int64_t n, int32_t max_iteration, uint32_t rotation_mask,
-                                  int32_t want_residual, void *rows_host, int32_t rows_f32, int32_t *n_rows, int32_t *stop_reason,
-                                  int64_t *knot_counts)
-{
-    if ((want_residual != 0 && want_residual != 1) || (rows_f32 != 0 && rows_f32 != 1)) return ITD_ERR_INVALID_ARG;
-    return rows_f32 ? decompose_host<float, float>(e, x_host, n, max_iteration, static_cast<float *>(rows_host), nullptr, n_rows, nullptr, stop_reason,
-                                                   knot_counts, true, rotation_mask, want_residual != 0)
-                    : decompose_host<float, double>(e, x_host, n, max_iteration, static_cast<double *>(rows_host), nullptr, n_rows, nullptr, stop_reason,
-                                                    knot_counts, true, rotation_mask, want_residual != 0);
-}
-
-int itd_decompose_select_host_f64(itd_engine *e, const double *x_host, int64_t n, int32_t max_iteration, uint32_t rotation_mask,
-                                  int32_t want_residual, void *rows_host, int32_t rows_f32, int32_t *n_rows, int32_t *stop_reason,
-                                  int64_t *knot_counts)
-{
-    if ((want_residual != 0 && want_residual != 1) || (rows_f32 != 0 && rows_f32 != 1)) return ITD_ERR_INVALID_ARG;
-    return rows_f32 ? decompose_host<double, float>(e, x_host, n, max_iteration, static_cast<float *>(rows_host), nullptr, n_rows, nullptr, stop_reason,
-                                                    knot_counts, true, rotation_mask, want_residual != 0)
-                    : decompose_host<double, double>(e, x_host, n, max_iteration, static_cast<double *>(rows_host), nullptr, n_rows, nullptr, stop_reason,
-                                                     knot_counts, true, rotation_mask, want_residual != 0);
+    return decompose_host(e, x_host, n, max_iteration, Rows(rows_host), baselines_host, n_rows, n_baselines, stop_reason, knot_counts);
 }
 
 int itd_decompose_host_f32(itd_engine *e, const float *x_host, int64_t n, int32_t max_iteration, double *rows_host,
                            double *baselines_host, int32_t *n_rows, int32_t *n_baselines, int32_t *stop_reason,
                            int64_t *knot_counts)
 {
-    return decompose_host<float>(e, x_host, n, max_iteration, rows_host, baselines_host, n_rows, n_baselines,
-                                 stop_reason, knot_counts);
+    return decompose_host(e, x_host, n, max_iteration, Rows(rows_host), baselines_host, n_rows, n_baselines, stop_reason, knot_counts);
+}
+
+int itd_decompose_rows32_host_f32(itd_engine *e, const float *x_host, int64_t n, int32_t max_iteration, float *rows_host,
+                                  int32_t *n_rows, int32_t *stop_reason, int64_t *knot_counts)
+{
+    return decompose_host(e, x_host, n, max_iteration, Rows(rows_host), nullptr, n_rows, nullptr, stop_reason, knot_counts);
+}
+
+int itd_decompose_rows32_host_f64(itd_engine *e, const double *x_host, int64_t n, int32_t max_iteration, float *rows_host,
+                                  int32_t *n_rows, int32_t *stop_reason, int64_t *knot_counts)
+{
+    return decompose_host(e, x_host, n, max_iteration, Rows(rows_host), nullptr, n_rows, nullptr, stop_reason, knot_counts);
+}
+
+int itd_decompose_select_host_f32(itd_engine *e, const float *x_host, int64_t n, int32_t max_iteration, uint32_t rotation_mask,
+                                  int32_t want_residual, void *rows_host, int32_t rows_f32, int32_t *n_rows, int32_t *stop_reason,
+                                  int64_t *knot_counts)
+{
+    if (!selection_ok(max_iteration, rotation_mask, want_residual, rows_f32)) return ITD_ERR_INVALID_ARG;
+    return decompose_host(e, x_host, n, max_iteration, Rows(rows_host, rows_f32 != 0, rotation_mask, want_residual != 0), nullptr, n_rows, nullptr,
+                          stop_reason, knot_counts);
+}
+
+int itd_decompose_select_host_f64(itd_engine *e, const double *x_host, int64_t n, int32_t max_iteration, uint32_t rotation_mask,
+                                  int32_t want_residual, void *rows_host, int32_t rows_f32, int32_t *n_rows, int32_t *stop_reason,
+                                  int64_t *knot_counts)
+{
+    if (!selection_ok(max_iteration, rotation_mask, want_residual, rows_f32)) return ITD_ERR_INVALID_ARG;
+    return decompose_host(e, x_host, n, max_iteration, Rows(rows_host, rows_f32 != 0, rotation_mask, want_residual != 0), nullptr, n_rows, nullptr,
+                          stop_reason, knot_counts);
 }
 
 int itd_baseline_extract_f64(itd_engine *e, const double *x_dev, int64_t n, double *rot_dev, double *base_dev,

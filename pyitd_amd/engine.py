@@ -89,6 +89,27 @@ def zero_absent_slots(rows, select, n_rows):
     return rows
 
 
+# the C entries of each delivery of a decomposition's rows: device float32 / float64 input, host float32 / float64 input
+_ENTRIES = {"full": ("itd_decompose_f32", "itd_decompose_f64", "itd_decompose_host_f32", "itd_decompose_host_f64"),
+            "rows32": ("itd_decompose_rows32_f32", "itd_decompose_rows32_f64", "itd_decompose_rows32_host_f32", "itd_decompose_rows32_host_f64"),
+            "select": ("itd_decompose_select_f32", "itd_decompose_select_f64", "itd_decompose_select_host_f32", "itd_decompose_select_host_f64")}
+
+
+def rows_mode(rows_dtype, select, max_iteration):
+    """(rows_dtype, select) of a decomposition resolved once, as the C entries take them: a dict of "entries", the four C entries
+    (_ENTRIES); "pre" / "post", their arguments in front of and right behind the rows' pointer; "dtype" and "S", the rows' element type
+    and their number per signal; "no_baselines", None where the entries take baselines, else what they deliver instead.  A bad
+    rows_dtype or select raises ValueError."""
+    rdt = rows_dtype_of(rows_dtype)
+    r32 = rdt == np.float32
+    if select is not None:
+        mask, want_res, S = selection_of(select, max_iteration)
+        return {"entries": _ENTRIES["select"], "pre": (mask, want_res), "post": (1 if r32 else 0,), "dtype": rdt, "S": S,
+                "no_baselines": "selected rows"}
+    return {"entries": _ENTRIES["rows32" if r32 else "full"], "pre": (), "post": (), "dtype": rdt, "S": max_iteration + 2,
+            "no_baselines": "float32 rows" if r32 else None}
+
+
 class Engine:
     """One engine = one GPU + one workspace sized for (max_n, max_batch).  Not thread-safe."""
 
@@ -151,23 +172,12 @@ class Engine:
         select: only these rows (selection_of): rows_ptr is [batch][S][n] of rows_dtype, the selected rotations in ascending order and
         the residual last; nothing else is stored anywhere.  The slot of a rotation above summary()'s n_rows - 2 holds unspecified
         values.  No baselines either."""
-        f32_in = np.dtype(dtype) == np.float32
-        if select is not None:
-            mask, want_res, _ = selection_of(select, max_iteration)
-            r32 = 1 if rows_dtype_of(rows_dtype) == np.float32 else 0
-            if baselines_ptr:
-                raise ValueError("baselines are not kept with selected rows")
-            f = self._L.itd_decompose_select_f32 if f32_in else self._L.itd_decompose_select_f64
-            self._check(f(self._h, x_ptr, n, batch, x_stride, max_iteration, mask, want_res, rows_ptr, r32, stream))
-            return
-        if rows_dtype_of(rows_dtype) == np.float32:
-            if baselines_ptr:
-                raise ValueError("baselines are not kept with float32 rows")
-            f = self._L.itd_decompose_rows32_f32 if f32_in else self._L.itd_decompose_rows32_f64
-            self._check(f(self._h, x_ptr, n, batch, x_stride, max_iteration, rows_ptr, stream))
-            return
-        f = self._L.itd_decompose_f32 if f32_in else self._L.itd_decompose_f64
-        self._check(f(self._h, x_ptr, n, batch, x_stride, max_iteration, rows_ptr, baselines_ptr, stream))
+        mode = rows_mode(rows_dtype, select, max_iteration)
+        if mode["no_baselines"] and baselines_ptr:
+            raise ValueError("baselines are not kept with " + mode["no_baselines"])
+        f = getattr(self._L, mode["entries"][0 if np.dtype(dtype) == np.float32 else 1])
+        bases = () if mode["no_baselines"] else (baselines_ptr,)
+        self._check(f(self._h, x_ptr, n, batch, x_stride, max_iteration, *mode["pre"], rows_ptr, *mode["post"], *bases, stream))
 
     def summary(self, batch):
         n_rows = np.zeros(batch, np.int32)
@@ -317,13 +327,12 @@ class Engine:
         select: only these rows (selection_of): the result's "rows" (and `out`) are [S, n], the selected rotations in ascending
         order and the residual last, with "n_rows" the full decomposition's count; the slots of rotations it did not reach
         (index > n_rows - 2) are zero.  No baselines in that mode either."""
-        rdt = rows_dtype_of(rows_dtype)
-        sel = selection_of(select, max_iteration) if select is not None else None
+        mode = rows_mode(rows_dtype, select, max_iteration)
+        rdt, R, full = mode["dtype"], mode["S"], mode["no_baselines"] is None
         x = np.ascontiguousarray(x)
         if x.dtype != np.float32:
             x = np.ascontiguousarray(x, dtype=np.float64)
         n = x.shape[0]
-        R = sel[2] if sel else max_iteration + 2
         if out is None:
             rows = np.empty((R, n), rdt)
         else:
@@ -331,30 +340,19 @@ class Engine:
                     and out.shape[1] == n and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]):
                 raise ValueError("out must be a writable C-contiguous %s array of shape (>= %d, %d)" % (rdt.name, R, n))
             rows = out
-        if sel:
-            n_rows, stop = ctypes.c_int32(0), ctypes.c_int32(0)
-            kc = np.zeros(MAX_ROWS + 1, np.int64)
-            f = self._L.itd_decompose_select_host_f32 if x.dtype == np.float32 else self._L.itd_decompose_select_host_f64
-            rc = self._check(f(self._h, _np_ptr(x), n, max_iteration, sel[0], sel[1], _np_ptr(rows), 1 if rdt == np.float32 else 0,
-                               ctypes.byref(n_rows), ctypes.byref(stop), _np_ptr(kc)), allow=(ITD_ERR_NONFINITE,))
-            return {"rows": zero_absent_slots(rows[:R], list(select), n_rows.value), "n_rows": n_rows.value, "stop": stop.value,
-                    "knot_counts": kc, "nonfinite": rc == ITD_ERR_NONFINITE}
-        if rdt == np.float32:
-            n_rows, stop = ctypes.c_int32(0), ctypes.c_int32(0)
-            kc = np.zeros(MAX_ROWS + 1, np.int64)
-            f = self._L.itd_decompose_rows32_host_f32 if x.dtype == np.float32 else self._L.itd_decompose_rows32_host_f64
-            rc = self._check(f(self._h, _np_ptr(x), n, max_iteration, _np_ptr(rows), ctypes.byref(n_rows), ctypes.byref(stop),
-                               _np_ptr(kc)), allow=(ITD_ERR_NONFINITE,))
-            return {"rows": rows[: n_rows.value], "stop": stop.value, "knot_counts": kc, "nonfinite": rc == ITD_ERR_NONFINITE}
-        lazy = want_baselines == "lazy"
-        self._check(self._L.itd_set_host_keep_baselines(self._h, 1 if lazy else 0))
-        bases = np.zeros((R, n), np.float64) if (want_baselines and not lazy) else None
+        lazy = full and want_baselines == "lazy"
+        if full:
+            self._check(self._L.itd_set_host_keep_baselines(self._h, 1 if lazy else 0))
+        bases = np.zeros((R, n), np.float64) if (full and want_baselines and not lazy) else None
         n_rows, n_b, stop = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
         kc = np.zeros(MAX_ROWS + 1, np.int64)
-        f = self._L.itd_decompose_host_f32 if x.dtype == np.float32 else self._L.itd_decompose_host_f64
-        rc = self._check(f(self._h, _np_ptr(x), n, max_iteration, _np_ptr(rows), _np_ptr(bases), ctypes.byref(n_rows),
-                           ctypes.byref(n_b), ctypes.byref(stop), _np_ptr(kc)), allow=(ITD_ERR_NONFINITE,))
+        f = getattr(self._L, mode["entries"][2 if x.dtype == np.float32 else 3])
+        rc = self._check(f(self._h, _np_ptr(x), n, max_iteration, *mode["pre"], _np_ptr(rows), *mode["post"],
+                           *((_np_ptr(bases), ctypes.byref(n_rows), ctypes.byref(n_b)) if full else (ctypes.byref(n_rows),)),
+                           ctypes.byref(stop), _np_ptr(kc)), allow=(ITD_ERR_NONFINITE,))
         out = {"rows": rows[: n_rows.value], "stop": stop.value, "knot_counts": kc, "nonfinite": rc == ITD_ERR_NONFINITE}
+        if select is not None:     # all S slots, and the full decomposition's count beside them
+            out.update(rows=zero_absent_slots(rows[:R], list(select), n_rows.value), n_rows=n_rows.value)
         if lazy:
             nb = n_b.value
             out["n_baselines"] = nb
@@ -364,7 +362,7 @@ class Engine:
                 self._check(self._L.itd_get_last_baselines_host(self._h, _np_ptr(b), n, nb))
                 return b
             out["fetch_baselines"] = fetch_baselines
-        elif want_baselines:
+        elif bases is not None:
             out["baselines"] = bases[: n_b.value]
         return out
 

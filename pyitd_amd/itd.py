@@ -274,6 +274,22 @@ def itd_batch(x, max_iteration: int = 11, keep_baselines: bool = False, device=N
     if max_iteration < 0 or max_iteration > _lib.MAX_ITERATION:
         raise ValueError("max_iteration must be in 0..20 (the reference's buffers hold 22 rows, ITD.py:384-385)")
     R = selection_of(select, max_iteration)[2] if select is not None else max_iteration + 2
+
+    def result(eng, B, fetch):
+        """The call's summary read (NaN input: ValueError) and the result dict around fetch(), the rows — and the baselines — as the
+        caller gets them, once the call has run."""
+        s = eng.summary(B)
+        if (s["nan_levels"] == -2).any():
+            raise ValueError("an input signal contains NaN")
+        rows, bases = fetch()
+        if select is not None:
+            zero_absent_slots(rows, select, s["n_rows"])
+        out = {"n_rows": s["n_rows"], "stop": s["stop"], "knot_counts": s["knot_counts"], "rows": rows}
+        if keep_baselines:
+            out["baselines"] = bases
+            out["n_baselines"] = s["n_baselines"]
+        return out
+
     if _is_torch(x):
         import torch
         if not x.is_cuda or x.dim() != 2:
@@ -292,17 +308,12 @@ def itd_batch(x, max_iteration: int = 11, keep_baselines: bool = False, device=N
         eng.decompose_dev(xt.data_ptr(), numpy.float32 if xt.dtype == torch.float32 else numpy.float64, n, B,
                           xt.stride(0), max_iteration, rows.data_ptr(), bases.data_ptr() if keep_baselines else None, None,
                           rows_dtype=rdt, select=select)
-        s = eng.summary(B)
-        if (s["nan_levels"] == -2).any():
-            raise ValueError("an input signal contains NaN")
-        if select is not None:
-            torch.cuda.synchronize(xt.device)
-            zero_absent_slots(rows, select, s["n_rows"])
-        out = {"n_rows": s["n_rows"], "stop": s["stop"], "knot_counts": s["knot_counts"], "rows": rows}
-        if keep_baselines:
-            out["baselines"] = bases
-            out["n_baselines"] = s["n_baselines"]
-        return out
+
+        def fetch():
+            if select is not None:
+                torch.cuda.synchronize(xt.device)
+            return rows, bases
+        return result(eng, B, fetch)
     from .engine import DeviceBuffer
     a = numpy.asarray(x)
     if a.ndim != 2:
@@ -322,17 +333,8 @@ def itd_batch(x, max_iteration: int = 11, keep_baselines: bool = False, device=N
         eng = _batch_engine_for(n, B, dev)
         eng.decompose_dev(d_x.ptr, a.dtype, n, B, n, max_iteration, d_rows.ptr, d_bases.ptr if keep_baselines else None, None,
                           rows_dtype=rdt, select=select)
-        s = eng.summary(B)
-        if (s["nan_levels"] == -2).any():
-            raise ValueError("an input signal contains NaN")
-        out = {"n_rows": s["n_rows"], "stop": s["stop"], "knot_counts": s["knot_counts"],
-               "rows": d_rows.download(numpy.empty((B, R, n), rdt))}
-        if keep_baselines:
-            out["baselines"] = d_bases.download(numpy.empty((B, R, n), numpy.float64))
-            out["n_baselines"] = s["n_baselines"]
-        if select is not None:
-            zero_absent_slots(out["rows"], select, s["n_rows"])
-        return out
+        return result(eng, B, lambda: (d_rows.download(numpy.empty((B, R, n), rdt)),
+                                       d_bases.download(numpy.empty((B, R, n), numpy.float64)) if keep_baselines else None))
     finally:
         d_x.free()
         d_rows.free()
