@@ -151,6 +151,8 @@ __global__ void k_widen_idx(const int32_t *__restrict__ src, int64_t *__restrict
 }
 static_assert(FormPolicy::kRangeTiles == kKcTiles && FormPolicy::kFailCapacity == kKfFailCapacity && FormPolicy::kFailWait == kKfFailWait,
               "itd_policy.hpp restates the fused levels' geometry and fail bits");
+static_assert(kSplineSmallMax == kNakSmallMax && kSplineParallelMinN <= kSplineSmallMax && kSplineParallelMaxBatch > 1,
+              "itd_policy.hpp restates what one workgroup of itd_nak.hpp holds; the automatic solver reaches the one-workgroup form");
 }  // namespace
 
 // A call's result rows: the caller's buffer and its element type (float64, or float32 for the itd_decompose_rows32_* entries).  The
@@ -1729,18 +1731,23 @@ void extract_level0(const KnotWs &w, const Tin *x, int64_t x_stride, int64_t n, 
 
 // totals[b] = {knot count, the signal held a NaN} of `batch` signals: synchronises, fills counts_out (optional).  A NaN: the
 // reference's detect_peaks would take its NaN branch and write +inf into the caller's array — rejected, like NaN input of a
-// decomposition, unless the caller follows that branch itself (nan_is_error = false)
-int fetch_totals(itd_engine *e, const int32_t *totals, int batch, int32_t *counts_out, hipStream_t st, bool nan_is_error = true)
+// decomposition, unless the caller follows that branch itself (nan_is_error = false).  read_totals: the same from totals that are on
+// the host already (a copy taken earlier on the stream, the mapped reply's words)
+int read_totals(const int32_t *tot, int batch, int32_t *counts_out, bool nan_is_error = true)
 {
-    std::vector<int32_t> tot((size_t)batch * 2);
-    HIP_TRY(e, hipMemcpyAsync(tot.data(), totals, tot.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(e, hipStreamSynchronize(st));
     bool nan_in = false;
     for (int b = 0; b < batch; ++b) {
         if (counts_out) counts_out[b] = tot[2 * (size_t)b];
         nan_in = nan_in || tot[2 * (size_t)b + 1] != 0;
     }
     return nan_in && nan_is_error ? ITD_ERR_NONFINITE : ITD_OK;
+}
+int fetch_totals(itd_engine *e, const int32_t *totals, int batch, int32_t *counts_out, hipStream_t st, bool nan_is_error = true)
+{
+    std::vector<int32_t> tot((size_t)batch * 2);
+    HIP_TRY(e, hipMemcpyAsync(tot.data(), totals, tot.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(e, hipStreamSynchronize(st));
+    return read_totals(tot.data(), batch, counts_out, nan_is_error);
 }
 // the knot total of the last one-signal scan (nothing is written where the copy fails)
 int fetch_total(itd_engine *e, const KnotWs &w, hipStream_t st, int64_t *m_host, bool nan_is_error = true)
@@ -2008,6 +2015,21 @@ int itd_knot_values_f64(itd_engine *e, const double *x_dev, int64_t n, const int
 // itd_fourier_decomposition.py:49-122 = itd.cpp:156-239.  Single-level operator; synchronous like the other helpers.
 // ---------------------------------------------------------------------------------------------
 namespace {
+// What the cubic kernels work on, carved from d_cub for `batch` signals with knot arrays of L entries: the jobs in front, then K, bf
+// and b, then `extra` more arrays of [batch][L] doubles for the caller, from A.b + batch * L on.  The knot lists (A.e, A.e_stride,
+// A.job_stride) are the caller's to fill in.
+int cubic_args(itd_engine *e, const double *x, int64_t x_stride, int64_t n, int batch, int64_t L, int extra, CubicArgs &A)
+{
+    const size_t jobs_b = (((size_t)batch * sizeof(CubicJob)) + 255) & ~(size_t)255, arr_n = (size_t)batch * (size_t)L;
+    const int rc = grow(e, e->d_cub, jobs_b + (3 + (size_t)extra) * arr_n * sizeof(double));
+    if (rc) return rc;
+    double *arr = (double *)((char *)e->d_cub + jobs_b);
+    A.x = x; A.x_stride = x_stride; A.n = n;
+    A.jobs = (const CubicJob *)e->d_cub;
+    A.K = arr; A.bf = arr + arr_n; A.b = arr + 2 * arr_n; A.a_stride = L;
+    return ITD_OK;
+}
+
 // The cubic operator over `batch` signals, asynchronous on st.  extrema = NULL: every signal's own knots (itd.cpp:159-169);
 // else the caller's list(s) of idx + 1 entries (e_stride = 0: one list for every signal, itd.cpp:40-44).  *jobs_out: the
 // per-signal jobs on the device (idx used, valid, status) for callers that synchronise afterwards; *knots_out: the detected
@@ -2016,16 +2038,10 @@ int cubic_batch(itd_engine *e, const double *x, int64_t n, int batch, int64_t x_
                 int64_t idx, double *baseline, int64_t b_stride, hipStream_t st, const CubicJob **jobs_out, int *n_jobs_out,
                 const int32_t **knots_out = nullptr)
 {
-    const int64_t L = (extrema ? idx : n) + 2;                        // entries per knot array
-    const size_t jobs_b = (((size_t)batch * sizeof(CubicJob)) + 255) & ~(size_t)255;
-    int rc = grow(e, e->d_cub, jobs_b + 3 * (size_t)batch * (size_t)L * sizeof(double));
+    CubicArgs A;
+    int rc = cubic_args(e, x, x_stride, n, batch, (extrema ? idx : n) + 2, 0, A);
     if (rc) return rc;
     CubicJob *jobs = (CubicJob *)e->d_cub;
-    double *arr = (double *)((char *)e->d_cub + jobs_b);
-    CubicArgs A;
-    A.x = x; A.x_stride = x_stride; A.n = n;
-    A.K = arr; A.bf = arr + (size_t)batch * L; A.b = arr + 2 * (size_t)batch * L; A.a_stride = L;
-    A.jobs = jobs;
     int n_jobs;
     int64_t max_count;
     if (!extrema) {
@@ -2256,33 +2272,26 @@ int itd_find_extrema_host_f64(itd_engine *e, const double *s_host, int64_t n, in
 // ---------------------------------------------------------------------------------------------
 }  // extern "C"
 namespace {
-// the knot scan's workspace and, behind it in the same arena, the fit's arrays
-struct SplineWs {
-    KnotWs k;
-    double *a, *c;
-    SplineMeta *meta;
-    int64_t lda;
-};
-
-// baseline (and optionally rotation) of `batch` contiguous-sample signals; all device pointers; asynchronous on st
+// baseline (and optionally rotation) of `batch` contiguous-sample signals; all device pointers; asynchronous on st; *totals_out = the
+// device array of {knot count, NaN flag} per signal.  The fit's arrays lie behind the knot scan's workspace in the same arena.
 int spline_enqueue(itd_engine *e, const double *x, int64_t n, int batch, int64_t x_stride, int min_extrema, double *base,
-                   int64_t base_stride, double *rot, int64_t rot_stride, hipStream_t st, SplineWs &w)
+                   int64_t base_stride, double *rot, int64_t rot_stride, hipStream_t st, const int32_t **totals_out)
 {
-    w.lda = n + 3;                                   // m <= n + ... data sites: knots <= n - 2, m <= n; 1-based arrays
+    const int64_t lda = n + 3;                       // m <= n + ... data sites: knots <= n - 2, m <= n; 1-based arrays
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t B = (size_t)batch, b_a = al(B * 4 * (size_t)w.lda * sizeof(double)), b_c = al(B * (size_t)w.lda * sizeof(double));
+    const size_t B = (size_t)batch, b_a = al(B * 4 * (size_t)lda * sizeof(double)), b_c = al(B * (size_t)lda * sizeof(double));
     char *p = nullptr;
-    int rc = knot_workspace(e, e->d_sp, n, batch, kWsLists | kWsOrdered, w.k, b_a + b_c + al(B * sizeof(SplineMeta)), &p);
-    if (!rc) rc = knot_scan<double>(e, w.k, x, x_stride, n, batch, (int)kKnots, kScanOrdered, st);
+    KnotWs k;
+    int rc = knot_workspace(e, e->d_sp, n, batch, kWsLists | kWsOrdered, k, b_a + b_c + al(B * sizeof(SplineMeta)), &p);
+    if (!rc) rc = knot_scan<double>(e, k, x, x_stride, n, batch, (int)kKnots, kScanOrdered, st);
     if (rc) return rc;
-    w.a = (double *)p;
-    w.c = (double *)(p + b_a);
-    w.meta = (SplineMeta *)(p + b_a + b_c);
-    const KnotWs &k = w.k;
-    k_spline_fit<<<(batch + 63) / 64, 64, 0, st>>>(x, x_stride, n, batch, k.kidx, k.kidx_stride, k.totals, min_extrema, w.a, w.c, w.lda, w.meta);
-    k_spline_eval<<<dim3((unsigned)((n + 255) / 256), batch), 256, 0, st>>>(x, x_stride, n, batch, k.kidx, k.kidx_stride, w.c, w.meta, base,
+    double *a = (double *)p, *c = (double *)(p + b_a);
+    SplineMeta *meta = (SplineMeta *)(p + b_a + b_c);
+    k_spline_fit<<<(batch + 63) / 64, 64, 0, st>>>(x, x_stride, n, batch, k.kidx, k.kidx_stride, k.totals, min_extrema, a, c, lda, meta);
+    k_spline_eval<<<dim3((unsigned)((n + 255) / 256), batch), 256, 0, st>>>(x, x_stride, n, batch, k.kidx, k.kidx_stride, c, meta, base,
                                                                             base_stride, rot, rot_stride);
     HIP_TRY(e, hipGetLastError());
+    *totals_out = k.totals;
     return ITD_OK;
 }
 
@@ -2295,18 +2304,13 @@ int nak_enqueue(itd_engine *e, const double *x, int64_t n, int batch, int64_t x_
     int rc = knot_workspace(e, e->d_dw, n, batch, kWsDetect, w);
     if (!rc) rc = knot_scan<double>(e, w, x, x_stride, n, batch, (int)kKnots, kScanOrdered, st);     // kidx[b] = [0, knots, n-1]
     if (rc) return rc;
-    const int64_t L = n + 2;
-    const size_t jobs_b = (((size_t)batch * sizeof(CubicJob)) + 255) & ~(size_t)255;
-    rc = grow(e, e->d_cub, jobs_b + 6 * (size_t)batch * (size_t)L * sizeof(double));
+    CubicArgs A;
+    rc = cubic_args(e, x, x_stride, n, batch, n + 2, 3, A);
     if (rc) return rc;
     CubicJob *jobs = (CubicJob *)e->d_cub;
-    double *arr = (double *)((char *)e->d_cub + jobs_b);
-    CubicArgs A;
-    A.x = x; A.x_stride = x_stride; A.n = n;
-    A.e = w.kidx; A.e_stride = w.kidx_stride;
-    A.jobs = jobs; A.job_stride = 1;
-    A.K = arr; A.bf = arr + (size_t)batch * L; A.b = arr + 2 * (size_t)batch * L; A.a_stride = L;
-    double *cp = arr + 3 * (size_t)batch * L, *sub = arr + 4 * (size_t)batch * L, *rhs = arr + 5 * (size_t)batch * L;
+    A.e = w.kidx; A.e_stride = w.kidx_stride; A.job_stride = 1;
+    const size_t arr_n = (size_t)batch * (size_t)A.a_stride;
+    double *cp = A.b + arr_n, *sub = cp + arr_n, *rhs = sub + arr_n;     // the sweeps' three arrays behind the cubic ones
     k_nak_jobs<<<(batch + 255) / 256, 256, 0, st>>>(jobs, batch, w.totals, min_extrema);
     k_nak_values<<<dim3((unsigned)((n + 255) / 256), batch), 256, 0, st>>>(A);
     k_nak_rows<<<dim3((unsigned)((n + 255) / 256), batch), 256, 0, st>>>(A, sub, rhs);
@@ -2319,73 +2323,113 @@ int nak_enqueue(itd_engine *e, const double *x, int64_t n, int batch, int64_t x_
     return ITD_OK;
 }
 
-// the engine's 256 bytes of mapped pinned host memory (h_small / its device address d_small); false: not available (the callers
-// then copy through their own buffers as before)
-constexpr int kSmallWords = 32;           // 8-byte words of mapped host memory an operator's scalars come back in
-bool small_results(itd_engine *e)
-{
-    if (e->h_small) return e->d_small != nullptr;
-    if (e->h_small.alloc(kSmallWords * 8, nullptr, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (hipHostGetDevicePointer(&e->d_small, e->h_small, 0) != hipSuccess) { (void)hipGetLastError(); e->d_small = nullptr; return false; }
-    memset(e->h_small, 0, kSmallWords * 8);
-    return true;
-}
-
-// Wait for the launch that fills the first `nwords` mapped words: every word carries the call's number in its high half (small_put) —
-// whatever order the stores reach the host in, a result is taken only when all of its words are this call's.  The host polls: a few
-// microseconds behind the kernel's end instead of the ~25 us hipStreamSynchronize takes to come back from an interrupt on a busy host.
-// Falls back to the synchronisation if the words do not turn up within poll_ms (a long kernel, a fault).
-int32_t small_next(itd_engine *e) { e->small_seq = e->small_seq == INT32_MAX ? 1 : e->small_seq + 1; return e->small_seq; }
-int small_wait(itd_engine *e, int32_t seq, int nwords, hipStream_t st, int poll_ms = 2)
-{
-    volatile unsigned long long *w = (volatile unsigned long long *)e->h_small;
-    auto all_here = [&]() {
-        for (int i = 0; i < nwords; ++i) if ((uint32_t)(w[i] >> 32) != (uint32_t)seq) return false;
-        return true;
-    };
-    const auto t0 = std::chrono::steady_clock::now();
-    bool synced = false;
-    for (int spin = 0; !all_here(); ++spin) {
-        if ((spin & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(synced ? 2000 : poll_ms)) {
-            if (synced) { snprintf(e->err, sizeof(e->err), "the launch's result words did not arrive"); return ITD_ERR_HIP; }
-            HIP_TRY(e, hipStreamSynchronize(st));
-            synced = true;
+// The scalars an operator hands back, in the engine's 256 bytes of mapped pinned host memory (h_small / its device address d_small)
+// that the launch fills itself: 8-byte words, the value in the low half and the call's number in the high half (small_put), each
+// written whole.  Made for a call that wants its scalars this way: takes the call's number, or is false where the memory cannot be
+// mapped — the caller then copies through its own buffers.
+constexpr int kSmallWords = 32;
+struct SmallReply {
+    itd_engine *e;
+    int32_t seq = 0;          // 0: no reply (not wanted, not mapped); the kernel gets (words(), seq)
+    explicit SmallReply(itd_engine *eng, bool wanted = true) : e(eng)
+    {
+        if (!wanted) return;
+        if (!e->h_small) {
+            if (e->h_small.alloc(kSmallWords * 8, nullptr, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { (void)hipGetLastError(); return; }
+            if (hipHostGetDevicePointer(&e->d_small, e->h_small, 0) != hipSuccess) { (void)hipGetLastError(); e->d_small = nullptr; return; }
+            memset(e->h_small, 0, kSmallWords * 8);
         }
+        if (e->d_small) seq = e->small_seq = e->small_seq == INT32_MAX ? 1 : e->small_seq + 1;
     }
-    std::atomic_thread_fence(std::memory_order_acquire);
+    explicit operator bool() const { return seq != 0; }
+    unsigned long long *words() const { return seq ? (unsigned long long *)e->d_small : nullptr; }
+    // Wait for the launch that fills the first `nwords` words: whatever order the stores reach the host in, a result is taken only
+    // when all of its words are this call's.  The host polls: a few microseconds behind the kernel's end instead of the ~25 us
+    // hipStreamSynchronize takes to come back from an interrupt on a busy host.  Falls back to the synchronisation if the words do
+    // not turn up within 2 ms (a long kernel, a fault).
+    int wait(int nwords, hipStream_t st) const
+    {
+        volatile unsigned long long *w = (volatile unsigned long long *)e->h_small;
+        auto all_here = [&]() {
+            for (int i = 0; i < nwords; ++i) if ((uint32_t)(w[i] >> 32) != (uint32_t)seq) return false;
+            return true;
+        };
+        const auto t0 = std::chrono::steady_clock::now();
+        bool synced = false;
+        for (int spin = 0; !all_here(); ++spin) {
+            if ((spin & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(synced ? 2000 : 2)) {
+                if (synced) { snprintf(e->err, sizeof(e->err), "the launch's result words did not arrive"); return ITD_ERR_HIP; }
+                HIP_TRY(e, hipStreamSynchronize(st));
+                synced = true;
+            }
+        }
+        std::atomic_thread_fence(std::memory_order_acquire);
+        return ITD_OK;
+    }
+    // the value at word i: 32 bits in one word, 64 bits in two (low half first)
+    uint32_t u32(int i) const { return (uint32_t)((const volatile unsigned long long *)e->h_small)[i]; }
+    uint64_t u64(int i) const { return (uint64_t)u32(i) | ((uint64_t)u32(i + 1) << 32); }
+};
+
+// What the one-workgroup solver works on (k_nak_small, k_meitd_small, k_meitd_batch), per signal: the knot indices, then six arrays
+// of L = n + 2 doubles (K, dpg, M, cpg, subg, rhsg), each part 256-byte aligned.  The sweeps' four arrays live in dynamic LDS where
+// they fit (more than 64 KB of it has to be asked for).
+struct NakSmallWs {
+    int32_t *idx;                    // signal 0's block starts here; signal g's: sig_bytes further each
+    double *arr;
+    int64_t L;
+    size_t idx_bytes, sig_bytes;
+    bool in_lds;
+    size_t lds;                      // the launch's dynamic LDS
+    double *a(int k) const { return arr + k * L; }
+};
+// `count` signals' blocks at `offset` bytes of a grow-only arena, `tail` bytes for the caller behind the last one.  lds_floor: dynamic LDS the
+// kernel takes whatever the sweeps need (MEITD's entropy pass takes turns with them in the same bytes)
+int nak_small_ws(itd_engine *e, Buf<void> &arena, size_t offset, int64_t n, int count, size_t tail, size_t lds_floor, NakSmallWs &w)
+{
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    w.L = n + 2;
+    w.idx_bytes = al((size_t)w.L * sizeof(int32_t));
+    w.sig_bytes = w.idx_bytes + al(6 * (size_t)w.L * sizeof(double));
+    const size_t sweeps = 4 * (size_t)w.L * sizeof(double);
+    w.in_lds = sweeps <= kNakSmallLdsMax;
+    w.lds = std::max(w.in_lds ? sweeps : (size_t)0, lds_floor);
+    const int rc = grow(e, arena, offset + (size_t)count * w.sig_bytes + tail);
+    if (rc) return rc;
+    w.idx = (int32_t *)((char *)arena + offset);
+    w.arr = (double *)((char *)arena + offset + w.idx_bytes);
     return ITD_OK;
 }
-inline uint32_t small_get(const itd_engine *e, int i) { return (uint32_t)((const volatile unsigned long long *)e->h_small)[i]; }
+// launches the instance of a one-workgroup kernel that matches the workspace, granted its LDS
+template <typename... P, typename... A>
+int nak_small_launch(itd_engine *e, const NakSmallWs &w, void (*in_lds)(P...), void (*in_memory)(P...), unsigned grid, hipStream_t st, A... args)
+{
+    void (*const fn)(P...) = w.in_lds ? in_lds : in_memory;
+    const size_t grant = w.in_lds ? kNakSmallLdsMax : w.lds;      // (arrays in memory: the floor alone, if any)
+    if (grant) HIP_TRY(e, allow_lds(e, reinterpret_cast<const void *>(fn), grant));
+    fn<<<grid, kNakSmallThreads, w.lds, st>>>(args...);
+    HIP_TRY(e, hipGetLastError());
+    return ITD_OK;
+}
 
 // ONE signal of at most kNakSmallMax samples through the parallel-in-knots form: one launch, one workgroup (itd_nak.hpp: k_nak_small),
-// one 16-byte copy back — knots, NaN flag, validity, and (want_bcount) the knot count of the produced baseline.  Synchronous.
+// four words back — knots, NaN flag, validity, and (baseline_knots_host) the knot count of the produced baseline.  Synchronous.
 int nak_small(itd_engine *e, const double *x, int64_t n, int min_extrema, double *base, double *rot, hipStream_t st,
               int32_t *knots_host, int32_t *baseline_knots_host)
 {
-    const int64_t L = n + 2;
-    const size_t idx_b = (((size_t)L * sizeof(int32_t)) + 255) & ~(size_t)255, out_b = 256;
-    int rc = grow(e, e->d_cub, out_b + idx_b + 6 * (size_t)L * sizeof(double));
+    NakSmallWs w;
+    int rc = nak_small_ws(e, e->d_cub, 256, n, 1, 0, 0, w);     // (in front: the kernel's four words where nothing is mapped)
     if (rc) return rc;
-    const bool mapped = small_results(e);
     int32_t *out = (int32_t *)e->d_cub;
-    int32_t *idx = (int32_t *)((char *)e->d_cub + out_b);
-    double *arr = (double *)((char *)e->d_cub + out_b + idx_b);
-    const int32_t seq = mapped ? small_next(e) : 0;
-    unsigned long long *words = mapped ? (unsigned long long *)e->d_small : nullptr;
-    const size_t lds = 4 * (size_t)L * sizeof(double);
-    if (lds <= kNakSmallLdsMax) {                          // the sweeps' arrays in LDS (more than 64 KB of dynamic LDS has to be asked for)
-        HIP_TRY(e, allow_lds(e, reinterpret_cast<const void *>(&k_nak_small<true>), kNakSmallLdsMax));
-        k_nak_small<true><<<1, kNakSmallThreads, lds, st>>>(x, (int)n, min_extrema, idx, arr, arr + L, arr + 2 * L, arr + 3 * L, arr + 4 * L, arr + 5 * L,
-                                                             base, rot, baseline_knots_host ? 1 : 0, out, words, seq);
-    } else
-        k_nak_small<false><<<1, kNakSmallThreads, 0, st>>>(x, (int)n, min_extrema, idx, arr, arr + L, arr + 2 * L, arr + 3 * L, arr + 4 * L, arr + 5 * L,
-                                                            base, rot, baseline_knots_host ? 1 : 0, out, words, seq);
+    const SmallReply reply(e);
+    rc = nak_small_launch(e, w, k_nak_small<true>, k_nak_small<false>, 1, st, x, (int)n, min_extrema, w.idx, w.a(0), w.a(1), w.a(2), w.a(3),
+                          w.a(4), w.a(5), base, rot, baseline_knots_host ? 1 : 0, out, reply.words(), reply.seq);
+    if (rc) return rc;
     int32_t h[4] = {0, 0, 0, 0};
-    HIP_TRY(e, hipGetLastError());
-    if (mapped) {
-        const int rc2 = small_wait(e, seq, 4, st);
-        if (rc2) return rc2;
-        for (int q = 0; q < 4; ++q) h[q] = (int32_t)small_get(e, q);
+    if (reply) {
+        rc = reply.wait(4, st);
+        if (rc) return rc;
+        for (int q = 0; q < 4; ++q) h[q] = (int32_t)reply.u32(q);
     } else {
         HIP_TRY(e, hipMemcpyAsync(h, out, sizeof(h), hipMemcpyDeviceToHost, st));
         HIP_TRY(e, hipStreamSynchronize(st));
@@ -2395,6 +2439,35 @@ int nak_small(itd_engine *e, const double *x, int64_t n, int min_extrema, double
     return h[1] ? ITD_ERR_NONFINITE : ITD_OK;
 }
 
+// The extraction behind every entry below: device pointers, `batch` contiguous-sample signals; st NULL = the engine's own stream.
+// The form is the policy's (itd_policy.hpp: spline_form).  baseline_knots_host: also the knot count of every PRODUCED baseline — what
+// MEITD's loops ask for right after an extraction (MEITD.py:362-363, :497-505) — in the same synchronisation.  Synchronous; a NaN in
+// a signal is ITD_ERR_NONFINITE, a NaN in a produced baseline is not an error of its own.
+int spline_extract(itd_engine *e, const double *x, int64_t n, int32_t batch, int64_t x_stride, int32_t min_extrema, double *base,
+                   int64_t base_stride, double *rot, int64_t rot_stride, int32_t *knots_host, int32_t *baseline_knots_host, hipStream_t st)
+{
+    if (!e || !x || !base) return ITD_ERR_INVALID_ARG;
+    if (n < 3 || n >= (int64_t)INT32_MAX - 8 || batch < 1 || batch > kMaxGridY || min_extrema < 0) return ITD_ERR_INVALID_ARG;
+    if (batch > 1 && (x_stride < n || base_stride < n || (rot && rot_stride < n))) return ITD_ERR_INVALID_ARG;
+    DevGuard g(e->device);
+    st = stream_of(e, st);
+    const SplineForm form = spline_form(e->spline_solver, n, batch);
+    if (form == SplineForm::Small) return nak_small(e, x, n, min_extrema, base, rot, st, knots_host, baseline_knots_host);
+    const int32_t *totals = nullptr;
+    int rc = (form == SplineForm::Parallel ? nak_enqueue : spline_enqueue)(e, x, n, batch, x_stride, min_extrema, base, base_stride, rot,
+                                                                           rot_stride, st, &totals);
+    if (rc) return rc;
+    if (!baseline_knots_host) return fetch_totals(e, totals, batch, knots_host, st);
+    // (the extraction's totals are read before the counting launches reuse the detection workspace)
+    std::vector<int32_t> tot((size_t)batch * 2);
+    HIP_TRY(e, hipMemcpyAsync(tot.data(), totals, tot.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    KnotWs dw;
+    rc = knot_workspace(e, e->d_dw, n, batch, kWsDetect, dw);
+    if (!rc) rc = knot_scan<double>(e, dw, base, base_stride, n, batch, (int)kKnots, kScanTotals, st);
+    if (!rc) rc = fetch_totals(e, dw.totals, batch, baseline_knots_host, st, false);   // (one synchronisation for both)
+    return rc ? rc : read_totals(tot.data(), batch, knots_host);                        // (the NaN flags that count are the extraction's)
+}
+
 }  // namespace
 extern "C" {
 
@@ -2402,24 +2475,17 @@ int itd_baseline_extract_spline_f64(itd_engine *e, const double *x_dev, int64_t 
                                     int32_t min_extrema, double *baseline_dev, int64_t baseline_stride, double *rot_dev,
                                     int64_t rot_stride, int32_t *knots_host, void *stream)
 {
-    if (!e || !x_dev || !baseline_dev) return ITD_ERR_INVALID_ARG;
-    if (n < 3 || n >= (int64_t)INT32_MAX - 8 || batch < 1 || batch > 65535 /* grid.y of its launches */ || min_extrema < 0) return ITD_ERR_INVALID_ARG;
-    if (batch > 1 && (x_stride < n || baseline_stride < n || (rot_dev && rot_stride < n))) return ITD_ERR_INVALID_ARG;
-    DevGuard g(e->device);
-    hipStream_t st = stream_of(e, stream);
-    // few long signals: parallel in the knots; many short rows: one thread per signal, FITPACK's own sweep (bit-level)
-    const bool par = e->spline_solver == ITD_SPLINE_PARALLEL || (e->spline_solver == ITD_SPLINE_AUTO && batch < 256 && n >= 1024);
-    if (par && batch == 1 && n <= kNakSmallMax) return nak_small(e, x_dev, n, min_extrema, baseline_dev, rot_dev, st, knots_host, nullptr);
-    const int32_t *totals = nullptr;
-    SplineWs w;
-    int rc;
-    if (par) rc = nak_enqueue(e, x_dev, n, batch, x_stride, min_extrema, baseline_dev, baseline_stride, rot_dev, rot_stride, st, &totals);
-    else {
-        rc = spline_enqueue(e, x_dev, n, batch, x_stride, min_extrema, baseline_dev, baseline_stride, rot_dev, rot_stride, st, w);
-        totals = w.k.totals;
-    }
-    if (rc) return rc;
-    return fetch_totals(e, totals, batch, knots_host, st);
+    return spline_extract(e, x_dev, n, batch, x_stride, min_extrema, baseline_dev, baseline_stride, rot_dev, rot_stride, knots_host, nullptr,
+                          (hipStream_t)stream);
+}
+
+// the same plus the knot count of every PRODUCED baseline, one synchronisation for both
+int itd_baseline_extract_spline2_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t batch, int64_t x_stride,
+                                     int32_t min_extrema, double *baseline_dev, int64_t baseline_stride, double *rot_dev,
+                                     int64_t rot_stride, int32_t *knots_host, int32_t *baseline_knots_host, void *stream)
+{
+    return spline_extract(e, x_dev, n, batch, x_stride, min_extrema, baseline_dev, baseline_stride, rot_dev, rot_stride, knots_host,
+                          baseline_knots_host, (hipStream_t)stream);
 }
 
 int itd_set_spline_solver(itd_engine *e, int32_t solver)
@@ -2435,9 +2501,8 @@ int itd_baseline_extract_spline_host_f64(itd_engine *e, const double *x_host, in
     return itd_baseline_extract_spline_host2_f64(e, x_host, n, batch, min_extrema, baseline_host, rot_host, knots_host, nullptr);
 }
 
-// the same, plus (optionally) the knot count of every PRODUCED baseline — what MEITD's loops ask for right after an
-// extraction (MEITD.py:362-363, :497-505: `count = matlab_detect_peaks(baseline).size + ...`): one more launch on the data
-// already on the device instead of another upload / list download
+// host arrays in and out: upload, the extraction (with the produced baselines' knot counts if asked for: counted on the data already
+// on the device instead of another upload / list download), download
 int itd_baseline_extract_spline_host2_f64(itd_engine *e, const double *x_host, int64_t n, int32_t batch, int32_t min_extrema,
                                           double *baseline_host, double *rot_host, int32_t *knots_host, int32_t *baseline_knots_host)
 {
@@ -2450,19 +2515,10 @@ int itd_baseline_extract_spline_host2_f64(itd_engine *e, const double *x_host, i
     if (rc) return rc;
     double *d_x = e->d_sp2, *d_b = d_x + cnt, *d_r = d_b + cnt;
     HIP_TRY(e, hipMemcpyAsync(d_x, x_host, cnt * sizeof(double), hipMemcpyHostToDevice, st));
-    rc = itd_baseline_extract_spline_f64(e, d_x, n, batch, n, min_extrema, d_b, n, rot_host ? d_r : nullptr, n, knots_host, st);
+    rc = spline_extract(e, d_x, n, batch, n, min_extrema, d_b, n, rot_host ? d_r : nullptr, n, knots_host, baseline_knots_host, st);
     if (rc) return rc;
-    KnotWs w;
-    if (baseline_knots_host) {
-        if (batch > kMaxGridY) return ITD_ERR_INVALID_ARG;
-        rc = knot_workspace(e, e->d_dw, n, batch, kWsDetect, w);
-        if (!rc) rc = knot_scan<double>(e, w, d_b, n, n, batch, (int)kKnots, kScanTotals, st);   // counts only
-        if (rc) return rc;
-    }
     HIP_TRY(e, hipMemcpyAsync(baseline_host, d_b, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
     if (rot_host) HIP_TRY(e, hipMemcpyAsync(rot_host, d_r, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
-    // (the call's one synchronisation; a NaN in a baseline is not an error of its own)
-    if (baseline_knots_host) return fetch_totals(e, w.totals, batch, baseline_knots_host, st, false);
     HIP_TRY(e, hipStreamSynchronize(st));
     return ITD_OK;
 }
@@ -2498,16 +2554,17 @@ int itd_count_knots_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t b
     int rc = knot_workspace(e, e->d_dw, n, batch, kWsDetect, w);
     if (!rc) rc = knot_scan<double>(e, w, x_dev, x_stride, n, batch, mode, kScanTotals, st);
     if (rc) return rc;
-    if (2 * batch > kSmallWords || !small_results(e)) return fetch_totals(e, w.totals, batch, counts_host, st);
-    // a few counts: the GPU copies them into the mapped words itself
-    const int32_t seq = small_next(e);
-    k_copy_words<<<1, 64, 0, st>>>(w.totals, (unsigned long long *)e->d_small, 2 * batch, seq);
-    HIP_TRY(e, hipGetLastError());
-    rc = small_wait(e, seq, 2 * batch, st);
-    if (rc) return rc;
-    bool nan_in = false;
-    for (int b = 0; b < batch; ++b) { counts_host[b] = (int32_t)small_get(e, 2 * b); nan_in = nan_in || small_get(e, 2 * b + 1); }
-    return nan_in ? ITD_ERR_NONFINITE : ITD_OK;
+    const SmallReply reply(e, 2 * batch <= kSmallWords);
+    if (reply) {                  // a few counts: the GPU copies them into the mapped words itself
+        k_copy_words<<<1, 64, 0, st>>>(w.totals, reply.words(), 2 * batch, reply.seq);
+        HIP_TRY(e, hipGetLastError());
+        rc = reply.wait(2 * batch, st);
+        if (rc) return rc;
+        int32_t tot[kSmallWords];
+        for (int i = 0; i < 2 * batch; ++i) tot[i] = (int32_t)reply.u32(i);
+        return read_totals(tot, batch, counts_host);
+    } else
+        return fetch_totals(e, w.totals, batch, counts_host, st);
 }
 
 // the weighted sums and window counts of the six order-3 permutation patterns of x (itd_wpe.hpp; MEITD.py:79-128), and —
@@ -2532,29 +2589,28 @@ int itd_wpe3_f64(itd_engine *e, const double *x_dev, int64_t n, double *bin_weig
     double *out_s = reinterpret_cast<double *>(e->d_wpe + out_off);
     long long *out_c = reinterpret_cast<long long *>(out_s + 6);
     int *out_k = reinterpret_cast<int *>(out_c + 6);
-    // (one segment — MEITD's signals —: the sums land in the engine's mapped host words, no copy behind the launch)
-    const bool mapped = nseg == 1 && small_results(e);
-    // (the knot count of x rides along: a window's middle sample is a knot or not — MEITD.py:346-351, :373-378 ask for both)
-    const int32_t seq = mapped ? small_next(e) : 0;
-    k_wpe3<<<(unsigned)nseg, kWpeThreads, 0, st>>>(x_dev, nw, seg_len, part_s, part_c, knots_host ? part_k : nullptr,
-                                                   mapped ? (unsigned long long *)e->d_small : nullptr, seq);
+    // (one segment — MEITD's signals —: the sums land in the engine's mapped host words, no copy behind the launch.  The knot count
+    // of x rides along: a window's middle sample is a knot or not — MEITD.py:346-351, :373-378 ask for both)
+    const SmallReply reply(e, nseg == 1);
+    k_wpe3<<<(unsigned)nseg, kWpeThreads, 0, st>>>(x_dev, nw, seg_len, part_s, part_c, knots_host ? part_k : nullptr, reply.words(), reply.seq);
     if (nseg > 1) k_wpe3_combine<<<1, 64, 0, st>>>(part_s, part_c, (int)nseg, out_s, out_c, knots_host ? part_k : nullptr, out_k);
     HIP_TRY(e, hipGetLastError());
     struct { double s[6]; long long c[6]; int k[2]; } res;
     res.k[0] = res.k[1] = 0;
-    const size_t res_b = 6 * (sizeof(double) + sizeof(long long)) + (knots_host ? 2 * sizeof(int) : 0);
-    if (nseg > 1) HIP_TRY(e, hipMemcpyAsync(&res, out_s, res_b, hipMemcpyDeviceToHost, st));
-    else if (!mapped) HIP_TRY(e, hipMemcpyAsync(&res, part_s, res_b, hipMemcpyDeviceToHost, st));
-    if (mapped) {
-        const int rc2 = small_wait(e, seq, 20, st);
-        if (rc2) return rc2;
+    if (reply) {                  // words 0..11: the six sums, 12..17: the six window counts, 18: the knots, 19: the NaN flag
+        rc = reply.wait(20, st);
+        if (rc) return rc;
         for (int b = 0; b < 6; ++b) {
-            const unsigned long long bits = (unsigned long long)small_get(e, 2 * b) | ((unsigned long long)small_get(e, 2 * b + 1) << 32);
+            const uint64_t bits = reply.u64(2 * b);
             memcpy(&res.s[b], &bits, sizeof(double));
-            res.c[b] = (long long)small_get(e, 12 + b);
+            res.c[b] = (long long)reply.u32(12 + b);
         }
-        res.k[0] = (int)small_get(e, 18); res.k[1] = (int)small_get(e, 19);
-    } else HIP_TRY(e, hipStreamSynchronize(st));
+        res.k[0] = (int)reply.u32(18); res.k[1] = (int)reply.u32(19);
+    } else {
+        const size_t res_b = 6 * (sizeof(double) + sizeof(long long)) + (knots_host ? 2 * sizeof(int) : 0);
+        HIP_TRY(e, hipMemcpyAsync(&res, nseg > 1 ? out_s : part_s, res_b, hipMemcpyDeviceToHost, st));
+        HIP_TRY(e, hipStreamSynchronize(st));
+    }
     for (int b = 0; b < 6; ++b) { bin_weights_host[b] = res.s[b]; bin_windows_host[b] = (int64_t)res.c[b]; }
     if (knots_host) *knots_host = res.k[0];
     return knots_host && res.k[1] ? ITD_ERR_NONFINITE : ITD_OK;
@@ -2564,30 +2620,19 @@ int itd_wpe3_f64(itd_engine *e, const double *x_dev, int64_t n, double *bin_weig
 int itd_meitd_small_f64(itd_engine *e, double *rows_dev, int64_t n, double wpemax, int32_t *result_host, void *probe_log_host,
                         int32_t log_cap, void *stream)
 {
-    if (!e || !rows_dev || !result_host || n < 3 || n > kNakSmallMax || log_cap < 0 || (log_cap > 0 && !probe_log_host)) return ITD_ERR_INVALID_ARG;
+    if (!e || !rows_dev || !result_host || log_cap < 0 || (log_cap > 0 && !probe_log_host)) return ITD_ERR_INVALID_ARG;
     // (only where the host-driven loop's extractions take the same operator: the parallel-in-knots form of one signal)
-    if (!(e->spline_solver == ITD_SPLINE_PARALLEL || (e->spline_solver == ITD_SPLINE_AUTO && n >= 1024))) return ITD_ERR_INVALID_ARG;
+    if (!meitd_one_launch(e->spline_solver, n)) return ITD_ERR_INVALID_ARG;     // (bounds n too: 3 .. kNakSmallMax, so (int)n below is safe)
     DevGuard g(e->device);
     hipStream_t st = stream_of(e, stream);
-    const int64_t L = n + 2;
-    const size_t idx_b = (((size_t)L * sizeof(int32_t)) + 255) & ~(size_t)255, out_b = 256;
-    const size_t arr_b = 6 * (size_t)L * sizeof(double);
-    int rc = grow(e, e->d_cub, out_b + idx_b + arr_b + kMeitdLogCap * sizeof(MeitdProbe));
+    NakSmallWs w;               // (the two operators take turns in the same LDS; in front of the workspace: the result, behind it: the log)
+    int rc = nak_small_ws(e, e->d_cub, 256, n, 1, kMeitdLogCap * sizeof(MeitdProbe), kMeitdWpeLds, w);
     if (rc) return rc;
-    int32_t *idx = (int32_t *)((char *)e->d_cub + out_b);
-    double *arr = (double *)((char *)e->d_cub + out_b + idx_b);
-    MeitdProbe *dlog = (MeitdProbe *)((char *)e->d_cub + out_b + idx_b + arr_b);
-    MeitdOut *dout = (MeitdOut *)e->d_cub;                 // (the first 256 bytes of the workspace)
-    const size_t nak_lds = 4 * (size_t)L * sizeof(double);
-    const bool in_lds = nak_lds <= kNakSmallLdsMax;
-    const size_t lds = in_lds && nak_lds > kMeitdWpeLds ? nak_lds : kMeitdWpeLds;   // the two operators take turns in the same bytes
-    HIP_TRY(e, allow_lds(e, in_lds ? reinterpret_cast<const void *>(&k_meitd_small<true>) : reinterpret_cast<const void *>(&k_meitd_small<false>),
-                         in_lds ? kNakSmallLdsMax : kMeitdWpeLds));
-    if (in_lds)
-        k_meitd_small<true><<<1, kNakSmallThreads, lds, st>>>(rows_dev, (int)n, wpemax, idx, arr, arr + L, arr + 2 * L, arr + 3 * L, arr + 4 * L, arr + 5 * L, dlog, dout);
-    else
-        k_meitd_small<false><<<1, kNakSmallThreads, lds, st>>>(rows_dev, (int)n, wpemax, idx, arr, arr + L, arr + 2 * L, arr + 3 * L, arr + 4 * L, arr + 5 * L, dlog, dout);
-    HIP_TRY(e, hipGetLastError());
+    MeitdOut *dout = (MeitdOut *)e->d_cub;
+    MeitdProbe *dlog = (MeitdProbe *)((char *)w.idx + w.sig_bytes);
+    rc = nak_small_launch(e, w, k_meitd_small<true>, k_meitd_small<false>, 1, st, rows_dev, (int)n, wpemax, w.idx, w.a(0), w.a(1), w.a(2), w.a(3),
+                          w.a(4), w.a(5), dlog, dout);
+    if (rc) return rc;
     // (a whole loop: milliseconds — the header and the log are plain copies behind it)
     MeitdOut ho;
     HIP_TRY(e, hipMemcpyAsync(&ho, dout, sizeof(ho), hipMemcpyDeviceToHost, st));
@@ -2606,37 +2651,30 @@ int itd_meitd_batch_f64(itd_engine *e, double *rows_dev, int64_t n, int32_t batc
                         int32_t *result_host, void *probe_logs_host, int32_t log_cap, double *xitd_sums_host, int64_t *xitd_windows_host,
                         void *stream)
 {
-    if (!e || !rows_dev || !result_host || n < 3 || n > kNakSmallMax || batch < 1 || log_cap < 0 || (log_cap > 0 && !probe_logs_host))
-        return ITD_ERR_INVALID_ARG;
-    if (rows_stride < (int64_t)(kMeitdWork + 2 * kMeitdKept) * n || (!xitd_sums_host) != (!xitd_windows_host)) return ITD_ERR_INVALID_ARG;
+    if (!e || !rows_dev || !result_host || batch < 1 || log_cap < 0 || (log_cap > 0 && !probe_logs_host)) return ITD_ERR_INVALID_ARG;
     // (the same rule as itd_meitd_small_f64: where the host-driven loop's extractions take the parallel-in-knots form)
-    if (!(e->spline_solver == ITD_SPLINE_PARALLEL || (e->spline_solver == ITD_SPLINE_AUTO && n >= 1024))) return ITD_ERR_INVALID_ARG;
+    if (!meitd_one_launch(e->spline_solver, n)) return ITD_ERR_INVALID_ARG;     // (bounds n too: 3 .. kNakSmallMax, so (int)n below is safe)
+    if (rows_stride < (int64_t)(kMeitdWork + 2 * kMeitdKept) * n || (!xitd_sums_host) != (!xitd_windows_host)) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
     hipStream_t st = stream_of(e, stream);
-    const int64_t L = n + 2;
     const int grid_max = batch < kMaxGridY ? batch : kMaxGridY;
     const bool xitd = xitd_sums_host != nullptr;
-    const size_t idx_b = (((size_t)L * sizeof(int32_t)) + 255) & ~(size_t)255;
-    const size_t sig_b = idx_b + ((6 * (size_t)L * sizeof(double) + 255) & ~(size_t)255);
     const size_t out_b = (((size_t)grid_max * sizeof(MeitdOut)) + 255) & ~(size_t)255;
     const size_t log_b = (size_t)grid_max * kMeitdLogCap * sizeof(MeitdProbe);
     const size_t xs_b = xitd ? (size_t)grid_max * kMeitdKept * 6 * (sizeof(double) + sizeof(long long)) : 0;
     const size_t x_b = x_host ? (((size_t)grid_max * (size_t)n * sizeof(double)) + 255) & ~(size_t)255 : 0;
-    // (the logs are packed, as far as the longest reaches, behind everything else before they go to the host: log_b more)
-    int rc = grow(e, e->d_mb, out_b + log_b + xs_b + (size_t)grid_max * sig_b + x_b + log_b);
+    // results, logs, XITD's sums, the signals' solver workspaces, the staged signals; the logs are packed, as far as the longest
+    // reaches, behind everything else before they go to the host: log_b more
+    NakSmallWs w;
+    int rc = nak_small_ws(e, e->d_mb, out_b + log_b + xs_b, n, grid_max, x_b + log_b, kMeitdWpeLds, w);
     if (rc) return rc;
     MeitdOut *dout = (MeitdOut *)e->d_mb;
     MeitdProbe *dlog = (MeitdProbe *)((char *)e->d_mb + out_b);
     double *dxw = xitd ? (double *)((char *)e->d_mb + out_b + log_b) : nullptr;
     long long *dxc = xitd ? (long long *)(dxw + (size_t)grid_max * kMeitdKept * 6) : nullptr;
-    char *ws = (char *)e->d_mb + out_b + log_b + xs_b;
-    double *dx = x_host ? (double *)(ws + (size_t)grid_max * sig_b) : nullptr;
-    MeitdProbe *dpack = (MeitdProbe *)(ws + (size_t)grid_max * sig_b + x_b);
-    const size_t nak_lds = 4 * (size_t)L * sizeof(double);
-    const bool in_lds = nak_lds <= kNakSmallLdsMax;
-    const size_t lds = in_lds && nak_lds > kMeitdWpeLds ? nak_lds : kMeitdWpeLds;   // (as itd_meitd_small_f64)
-    HIP_TRY(e, allow_lds(e, in_lds ? reinterpret_cast<const void *>(&k_meitd_batch<true>) : reinterpret_cast<const void *>(&k_meitd_batch<false>),
-                         in_lds ? kNakSmallLdsMax : kMeitdWpeLds));
+    char *tail = (char *)w.idx + (size_t)grid_max * w.sig_bytes;
+    double *dx = x_host ? (double *)tail : nullptr;
+    MeitdProbe *dpack = (MeitdProbe *)(tail + x_b);
     const int32_t cap = log_cap < kMeitdLogCap ? log_cap : kMeitdLogCap;
     std::vector<MeitdOut> ho((size_t)grid_max);
     std::vector<MeitdProbe> hlog;
@@ -2645,11 +2683,9 @@ int itd_meitd_batch_f64(itd_engine *e, double *rows_dev, int64_t n, int32_t batc
         double *rows = rows_dev + (size_t)b0 * (size_t)rows_stride;
         // (the signals as one contiguous copy; each workgroup moves its own into row 5 of its block)
         if (x_host) HIP_TRY(e, hipMemcpyAsync(dx, x_host + (size_t)b0 * (size_t)n, (size_t)G * (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-        if (in_lds)
-            k_meitd_batch<true><<<(unsigned)G, kNakSmallThreads, lds, st>>>(dx, rows, rows_stride, (int)n, wpemax, ws, (int64_t)sig_b, (int64_t)idx_b, L, dlog, dout, dxw, dxc);
-        else
-            k_meitd_batch<false><<<(unsigned)G, kNakSmallThreads, lds, st>>>(dx, rows, rows_stride, (int)n, wpemax, ws, (int64_t)sig_b, (int64_t)idx_b, L, dlog, dout, dxw, dxc);
-        HIP_TRY(e, hipGetLastError());
+        rc = nak_small_launch(e, w, k_meitd_batch<true>, k_meitd_batch<false>, (unsigned)G, st, dx, rows, rows_stride, (int)n, wpemax, (char *)w.idx,
+                              (int64_t)w.sig_bytes, (int64_t)w.idx_bytes, w.L, dlog, dout, dxw, dxc);
+        if (rc) return rc;
         HIP_TRY(e, hipMemcpyAsync(ho.data(), dout, (size_t)G * sizeof(MeitdOut), hipMemcpyDeviceToHost, st));
         HIP_TRY(e, hipStreamSynchronize(st));
         int32_t most = 0;
@@ -2750,47 +2786,6 @@ int itd_wpe_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t order, do
     return ITD_OK;
 }
 
-// itd_baseline_extract_spline_f64 plus the knot count of every PRODUCED baseline, one synchronisation for both
-// (MEITD.py:362-363, :497-505)
-int itd_baseline_extract_spline2_f64(itd_engine *e, const double *x_dev, int64_t n, int32_t batch, int64_t x_stride,
-                                     int32_t min_extrema, double *baseline_dev, int64_t baseline_stride, double *rot_dev,
-                                     int64_t rot_stride, int32_t *knots_host, int32_t *baseline_knots_host, void *stream)
-{
-    if (!e || !x_dev || !baseline_dev) return ITD_ERR_INVALID_ARG;
-    if (n < 3 || n >= (int64_t)INT32_MAX - 8 || batch < 1 || batch > 65535 || min_extrema < 0) return ITD_ERR_INVALID_ARG;
-    if (batch > 1 && (x_stride < n || baseline_stride < n || (rot_dev && rot_stride < n))) return ITD_ERR_INVALID_ARG;
-    DevGuard g(e->device);
-    hipStream_t st = stream_of(e, stream);
-    const bool par = e->spline_solver == ITD_SPLINE_PARALLEL || (e->spline_solver == ITD_SPLINE_AUTO && batch < 256 && n >= 1024);
-    if (par && batch == 1 && n <= kNakSmallMax) return nak_small(e, x_dev, n, min_extrema, baseline_dev, rot_dev, st, knots_host, baseline_knots_host);
-    const int32_t *totals = nullptr;
-    SplineWs w;
-    int rc;
-    if (par) rc = nak_enqueue(e, x_dev, n, batch, x_stride, min_extrema, baseline_dev, baseline_stride, rot_dev, rot_stride, st, &totals);
-    else {
-        rc = spline_enqueue(e, x_dev, n, batch, x_stride, min_extrema, baseline_dev, baseline_stride, rot_dev, rot_stride, st, w);
-        totals = w.k.totals;
-    }
-    if (rc) return rc;
-    if (!baseline_knots_host) return fetch_totals(e, totals, batch, knots_host, st);
-    // (the extraction's totals are read before the counting launches reuse the detection workspace)
-    std::vector<int32_t> tot((size_t)batch * 2);
-    HIP_TRY(e, hipMemcpyAsync(tot.data(), totals, tot.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    KnotWs dw;
-    rc = knot_workspace(e, e->d_dw, n, batch, kWsDetect, dw);
-    if (!rc) rc = knot_scan<double>(e, dw, baseline_dev, baseline_stride, n, batch, (int)kKnots, kScanTotals, st);
-    if (rc) return rc;
-    // (one synchronisation for both; the NaN flags that count are the extraction's)
-    rc = fetch_totals(e, dw.totals, batch, baseline_knots_host, st, false);
-    if (rc) return rc;
-    bool nan_in = false;
-    for (int b = 0; b < batch; ++b) {
-        if (knots_host) knots_host[b] = tot[2 * (size_t)b];
-        nan_in = nan_in || tot[2 * (size_t)b + 1] != 0;
-    }
-    return nan_in ? ITD_ERR_NONFINITE : ITD_OK;
-}
-
 int itd_subtract_f64(itd_engine *e, const double *a_dev, const double *b_dev, double *out_dev, int64_t count, void *stream)
 {
     if (!e || !a_dev || !b_dev || !out_dev || count < 0) return ITD_ERR_INVALID_ARG;
@@ -2829,7 +2824,6 @@ int itd_crossways_f64(itd_engine *e, const double *img_dev, int32_t planes, int3
     int rc = grow(e, e->d_sp2, 3 * cnt * sizeof(double));
     if (rc) return rc;
     double *A = e->d_sp2, *Bq = A + cnt, *C = Bq + cnt;       // scratch planes
-    SplineWs w;
     auto tr = [&](const double *in, int r, int c, double *out) {
         k_transpose<<<dim3((c + 31) / 32, (r + 31) / 32, planes), 256, 0, st>>>(in, r, c, out);
     };
@@ -2839,9 +2833,10 @@ int itd_crossways_f64(itd_engine *e, const double *img_dev, int32_t planes, int3
     auto ext = [&](const double *in, int64_t sigs, int len, double *out) {
         for (int64_t s0 = 0; s0 < sigs; s0 += kMaxGridY) {
             const int nb = (int)std::min<int64_t>(kMaxGridY, sigs - s0);
-            const int rc2 = spline_enqueue(e, in + s0 * len, len, nb, len, min_extrema, out + s0 * len, len, nullptr, 0, st, w);
+            const int32_t *totals = nullptr;
+            const int rc2 = spline_enqueue(e, in + s0 * len, len, nb, len, min_extrema, out + s0 * len, len, nullptr, 0, st, &totals);
             if (rc2) return rc2;
-            k_or_nan_flags<<<(nb + 255) / 256, 256, 0, st>>>(w.k.totals, nb, e->d_flag);
+            k_or_nan_flags<<<(nb + 255) / 256, 256, 0, st>>>(totals, nb, e->d_flag);
         }
         return (int)ITD_OK;
     };

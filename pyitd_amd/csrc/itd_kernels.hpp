@@ -639,7 +639,7 @@ __device__ int far_nonempty(const int32_t *__restrict__ cnts, const int32_t *__r
 }
 
 // ---- scalars for a polling host: one 32-bit value and its call's number in ONE 8-byte store to host-mapped memory -------------------
-// A few operators hand a handful of scalars back to a host that polls for them (itd_engine.hip: small_wait) instead of synchronising
+// A few operators hand a handful of scalars back to a host that polls for them (itd_engine.hip: SmallReply) instead of synchronising
 // the stream.  Data words followed by a fence and a flag word are NOT enough on this path: stores of one wavefront to host memory can
 // arrive out of order (a 5000-call fuzz of MEITD's host-driven loop saw the flag in front of the data about once per 100 000
 // launches — a stale NaN flag or knot count, i.e. a wrong branch).  So every word validates itself: value in the low half, the call's

@@ -1,5 +1,6 @@
 // itd_policy.hpp — which form a decomposition takes and what the engine learns when a form falls short (DESIGN.md sections 10, 11,
-// 13).  Plain C++17: itd_engine.hip holds one FormPolicy, tests/test_policy_host.py drives one on the host.
+// 13), and which form a spline extraction takes (section 9).  Plain C++17: itd_engine.hip holds one FormPolicy,
+// tests/test_policy_host.py drives one on the host.
 #pragma once
 
 #include <algorithm>
@@ -144,3 +145,19 @@ struct FormPolicy {
     }
     void levels_off() { if (fuse_probe) fuse_off_span = doubled(fuse_off_span); fuse_off_left = fuse_off_span; fuse_probe = false; }
 };
+
+// ---- which form a spline extraction takes: nothing is learned, so plain functions of the call's shape ----
+// Few long signals: parallel in the knots; many short rows: one thread per signal, FITPACK's own sweep (bit-level).  One signal that
+// one workgroup can hold: the parallel form as one launch.
+constexpr int64_t kSplineParallelMinN = 1024;      // automatic: parallel in the knots from this many samples ...
+constexpr int32_t kSplineParallelMaxBatch = 256;   // ... for fewer signals than this
+constexpr int64_t kSplineSmallMax = 8192;          // samples one workgroup holds (itd_nak.hpp's kNakSmallMax)
+enum class SplineForm { Serial, Parallel, Small };
+inline SplineForm spline_form(int32_t solver, int64_t n, int32_t batch)
+{
+    const bool par = solver == ITD_SPLINE_PARALLEL || (solver == ITD_SPLINE_AUTO && batch < kSplineParallelMaxBatch && n >= kSplineParallelMinN);
+    if (!par) return SplineForm::Serial;
+    return batch == 1 && n <= kSplineSmallMax ? SplineForm::Small : SplineForm::Parallel;
+}
+// MEITD's selection loop as one launch: where every extraction of the host-driven loop on this signal would take the small form
+inline bool meitd_one_launch(int32_t solver, int64_t n) { return n >= 3 && spline_form(solver, n, 1) == SplineForm::Small; }

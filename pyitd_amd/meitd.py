@@ -71,7 +71,7 @@ class _Work:
         self.free_rows = [self.row(i) for i in range(6)]
         self.high0, self.low0 = self.row(6), self.row(6 + _ROWS_KEPT)
         # the whole loop as one launch: where an extraction of this signal is the one-workgroup parallel-in-knots operator anyway
-        self.one_launch = 3 <= n <= _ONE_LAUNCH_MAX and (solver == "parallel" or (solver == "auto" and n >= 1024))
+        self.one_launch = _one_launch(n, solver)
         self.last = {}
 
     def row(self, i):
@@ -222,6 +222,13 @@ def determine_if_first_is_proper_rotation(x, WPEMAX, device=0, solver="auto"):
 
 
 _ONE_LAUNCH_MAX = 8192      # itd_meitd_small_f64: one workgroup holds the signal's run
+
+
+def _one_launch(n, solver):
+    """Whether MEITD's selection loop on a signal of n samples runs as one launch: where every extraction of the host-driven loop
+    would be the one-workgroup parallel-in-knots operator anyway (csrc/itd_policy.hpp: meitd_one_launch, which the engine's entries
+    apply; tests/test_policy_host.py holds the two equal)."""
+    return 3 <= n <= _ONE_LAUNCH_MAX and (solver == "parallel" or (solver == "auto" and n >= 1024))
 
 
 def _proper_rows(log, WPEMAX):
@@ -436,7 +443,7 @@ def _batch(data, WPEMAX, device, solver, chunk, xitd):
 
     stats = last_batch = {"signals": B, "launches": 0, "chunks": 0, "status": {}, "handed_back": 0, "looped": 0}
     with _lock:
-        if not (3 <= n <= _ONE_LAUNCH_MAX and (solver == "parallel" or (solver == "auto" and n >= 1024))):
+        if not _one_launch(n, solver):
             stats["looped"] = B                    # no one-launch form for this length / solver: the single-signal path, one by one
             return [single(x) for x in arr]
         per = (6 + 2 * _ROWS_KEPT) * n             # elements of one signal's rows

@@ -1,5 +1,6 @@
 // Host build of pyitd_amd/csrc/itd_policy.hpp for tests/test_policy_host.py: the engine's choice of form and what it learns when a
-// form falls short, driven call by call without a GPU.  Test infrastructure: nothing in pyitd_amd/ uses this.
+// form falls short, driven call by call without a GPU, and the spline operators' form.  Test infrastructure: nothing in pyitd_amd/
+// uses this.
 #include <string.h>
 #include "../../pyitd_amd/csrc/itd_policy.hpp"
 
@@ -58,4 +59,12 @@ void policy_device_repaired(void *p, int fixed, int why, int batch, int L0)
 {
     static_cast<FormPolicy *>(p)->device_repaired(fixed, why, FormPolicy::many(fixed, batch), L0);
 }
+
+// the form a spline extraction takes (0: serial, 1: parallel in the knots, 2: one workgroup) and whether MEITD's loop is one launch
+int policy_spline_form(int solver, int64_t n, int batch)
+{
+    const SplineForm f = spline_form(solver, n, batch);
+    return f == SplineForm::Serial ? 0 : f == SplineForm::Parallel ? 1 : 2;
+}
+int policy_meitd_one_launch(int solver, int64_t n) { return meitd_one_launch(solver, n); }
 }

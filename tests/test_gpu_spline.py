@@ -518,6 +518,32 @@ def test_one_short_signal_in_one_launch_equals_the_launch_sequence(P, n):
         eng.spline_extract_host(x[None, :], 0)
 
 
+@pytest.mark.parametrize("form, n, batch", [("small", 1024, 1), ("parallel", 8193, 1), ("serial", 64, 2)])
+def test_host_and_device_entries_share_one_extraction(P, form, n, batch):
+    """The host form and the device form of the extraction are one body (itd_engine.hip: spline_extract) at the smallest shape
+    that selects each of its three forms under the automatic solver: baseline, rotation and both knot counts equal bit for bit,
+    and the baselines' counts equal a separate counting call on the returned baselines.  The signals: the fast end of the golden
+    chirp."""
+    from pyitd_amd.engine import DeviceBuffer
+    from pyitd_amd.spline import _eng
+    x = np.load(os.path.join(GOLDEN, "chirp65536_f32_m3.npz"))["x"].astype(np.float64)
+    x = np.ascontiguousarray(x[len(x) - batch * n:].reshape(batch, n))
+    eng = _eng(n, 0)
+    base_h, rot_h, knots_h, bk_h = eng.spline_extract_host(x, 0, want_rotation=True, want_baseline_knots=True)
+    assert min(knots_h) >= 4, "the signals have a spline to fit"
+    assert np.array_equal(bk_h, eng.count_knots_host(base_h))
+    buf = DeviceBuffer(3 * n * 8)
+    px, pb, pr = (buf.ptr + i * n * 8 for i in range(3))
+    got = np.empty((2, n))
+    for b in range(batch):
+        eng.copy(px, x[b].ctypes.data, x[b].nbytes, 1, wait=True)
+        assert eng.spline_extract_dev(px, n, pb, pr, 0, want_baseline_knots=True) == (int(knots_h[b]), int(bk_h[b])), (form, b)
+        eng.copy(got.ctypes.data, pb, got.nbytes, 0, wait=True)
+        assert np.array_equal(got[0].view(np.uint64), base_h[b].view(np.uint64)), "%s: baseline %d" % (form, b)
+        assert np.array_equal(got[1].view(np.uint64), rot_h[b].view(np.uint64)), "%s: rotation %d" % (form, b)
+    buf.free()
+
+
 def test_meitd_solver_argument_and_release(P):
     """MEITD(..., solver=): "serial" runs every extraction through FITPACK's own sweep (bit-level against scipy), "auto" / "parallel"
     through the parallel-in-knots form — on the golden signal both select the reference's components; release() frees the rows the

@@ -18,6 +18,9 @@ FUSE_AUTO, FUSE_OFF, FUSE_ONLY = 0, 1, 2
 VERIFY, CAPACITY, WAIT = 1, 2, 16
 # what the summary does after a refusal
 FAIL, REPAIR_SIGNALS, REPEAT_CALL = 0, 1, 2
+SPLINE_AUTO, SPLINE_SERIAL, SPLINE_PARALLEL = 0, 1, 2
+# the form of a spline extraction (tests/c_client/policy_host.cpp: policy_spline_form)
+SERIAL, PARALLEL, SMALL = 0, 1, 2
 
 
 @pytest.fixture(scope="module")
@@ -36,6 +39,7 @@ def lib(tmp_path_factory):
         "policy_workspace_unavailable": (I, [P]), "policy_resident_failed": (I, [P]), "policy_level0_fell_short": (I, [P]),
         "policy_fused_levels_delivered": (None, [P, I, I]), "policy_fused_levels_refused": (I, [P, I, I, I, I, I, I, I]),
         "policy_device_repaired": (None, [P, I, I, I, I]),
+        "policy_spline_form": (I, [I, I64, I]), "policy_meitd_one_launch": (I, [I, I64]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -267,3 +271,52 @@ def test_each_setter_clears_what_belongs_to_it(pol):
     assert pol.fuse_cap_auto == 0 and pol.fuse_cap_calls == 0 and pol.fuse_cap_span == 16
     # the counters stay
     assert pol.resident_repeats == 1 and pol.fuse_repeats >= 4
+
+
+def test_the_spline_form_at_every_edge_of_its_table(lib):
+    """spline_form(solver, n, batch).  The rule: parallel in the knots when the solver is set to it, or automatically for fewer than
+    256 signals of at least 1024 samples; then one signal of at most 8192 samples takes the one-workgroup form.  Every value below
+    is written out from that rule."""
+    batches = (1, 2, 255, 256)
+    expect = {
+        (SPLINE_AUTO, 1023): (SERIAL, SERIAL, SERIAL, SERIAL),
+        (SPLINE_AUTO, 1024): (SMALL, PARALLEL, PARALLEL, SERIAL),
+        (SPLINE_AUTO, 8192): (SMALL, PARALLEL, PARALLEL, SERIAL),
+        (SPLINE_AUTO, 8193): (PARALLEL, PARALLEL, PARALLEL, SERIAL),
+        (SPLINE_SERIAL, 1023): (SERIAL, SERIAL, SERIAL, SERIAL),
+        (SPLINE_SERIAL, 1024): (SERIAL, SERIAL, SERIAL, SERIAL),
+        (SPLINE_SERIAL, 8192): (SERIAL, SERIAL, SERIAL, SERIAL),
+        (SPLINE_SERIAL, 8193): (SERIAL, SERIAL, SERIAL, SERIAL),
+        (SPLINE_PARALLEL, 1023): (SMALL, PARALLEL, PARALLEL, PARALLEL),
+        (SPLINE_PARALLEL, 1024): (SMALL, PARALLEL, PARALLEL, PARALLEL),
+        (SPLINE_PARALLEL, 8192): (SMALL, PARALLEL, PARALLEL, PARALLEL),
+        (SPLINE_PARALLEL, 8193): (PARALLEL, PARALLEL, PARALLEL, PARALLEL),
+    }
+    for (solver, n), forms in expect.items():
+        got = tuple(lib.policy_spline_form(solver, n, b) for b in batches)
+        assert got == forms, (solver, n, got)
+
+
+ONE_LAUNCH_N = (2, 3, 1023, 1024, 8192, 8193)
+ONE_LAUNCH = {
+    SPLINE_AUTO: (False, False, False, True, True, False),
+    SPLINE_SERIAL: (False, False, False, False, False, False),
+    SPLINE_PARALLEL: (False, True, True, True, True, False),
+}
+
+
+def test_meitd_is_one_launch_where_its_extractions_take_the_one_workgroup_form(lib):
+    """meitd_one_launch(solver, n): at least 3 samples, at most 8192, and the parallel-in-knots form of ONE signal (set, or
+    automatic from 1024 samples) — written out from that rule."""
+    for solver, expect in ONE_LAUNCH.items():
+        got = tuple(bool(lib.policy_meitd_one_launch(solver, n)) for n in ONE_LAUNCH_N)
+        assert got == expect, (solver, got)
+
+
+def test_the_python_driver_s_one_launch_rule_is_the_engine_s(lib):
+    """pyitd_amd/meitd.py decides by its own restatement whether to call the one-launch entries; the entries refuse a call the
+    engine's rule does not cover, so the two must agree."""
+    from pyitd_amd import meitd
+    for name, solver in (("auto", SPLINE_AUTO), ("serial", SPLINE_SERIAL), ("parallel", SPLINE_PARALLEL)):
+        for n, expect in zip(ONE_LAUNCH_N, ONE_LAUNCH[solver]):
+            assert bool(meitd._one_launch(n, name)) == bool(lib.policy_meitd_one_launch(solver, n)) == expect, (name, n)
