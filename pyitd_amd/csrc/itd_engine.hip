@@ -1742,20 +1742,28 @@ int read_totals(const int32_t *tot, int batch, int32_t *counts_out, bool nan_is_
     }
     return nan_in && nan_is_error ? ITD_ERR_NONFINITE : ITD_OK;
 }
+int copy_totals(itd_engine *e, const int32_t *totals, int batch, int32_t *tot_host, hipStream_t st)
+{
+    HIP_TRY(e, hipMemcpyAsync(tot_host, totals, (size_t)batch * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(e, hipStreamSynchronize(st));
+    return ITD_OK;
+}
 int fetch_totals(itd_engine *e, const int32_t *totals, int batch, int32_t *counts_out, hipStream_t st, bool nan_is_error = true)
 {
     std::vector<int32_t> tot((size_t)batch * 2);
-    HIP_TRY(e, hipMemcpyAsync(tot.data(), totals, tot.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(e, hipStreamSynchronize(st));
-    return read_totals(tot.data(), batch, counts_out, nan_is_error);
+    const int rc = copy_totals(e, totals, batch, tot.data(), st);
+    return rc ? rc : read_totals(tot.data(), batch, counts_out, nan_is_error);
 }
-// the knot total of the last one-signal scan (nothing is written where the copy fails)
-int fetch_total(itd_engine *e, const KnotWs &w, hipStream_t st, int64_t *m_host, bool nan_is_error = true)
+// the knot total of the last one-signal scan and whether the signal holds a NaN, both from one copy (nothing is written where the
+// copy fails)
+int fetch_total(itd_engine *e, const KnotWs &w, hipStream_t st, int64_t *m_host, bool nan_is_error = true, bool *has_nan = nullptr)
 {
-    int32_t m32 = 0;
-    const int rc = fetch_totals(e, w.totals, 1, &m32, st, nan_is_error);
-    if (rc == ITD_OK || rc == ITD_ERR_NONFINITE) *m_host = m32;
-    return rc;
+    int32_t tot[2] = {0, 0};
+    const int rc = copy_totals(e, w.totals, 1, tot, st);
+    if (rc) return rc;
+    *m_host = tot[0];
+    if (has_nan) *has_nan = tot[1] != 0;
+    return read_totals(tot, 1, nullptr, nan_is_error);
 }
 
 // the three knot sets of the reference's own detect functions follow its NaN branch when the signal holds a NaN
@@ -1764,45 +1772,60 @@ inline bool nan_follows(const itd_engine *e, int mode)
     return e->nan_input_mode == ITD_NAN_INPUT_FOLLOW && (mode == (int)kKnots || mode == (int)kValleys || mode == (int)kPeaks);
 }
 
+// One signal's knots by predicate `mode` in the engine's fixed buffers, with the level-0 extraction behind the scan if rot / base
+// are given.  m = NULL: nothing is read back: one pass under the plain rules, asynchronous.  Else the total is read (*m, written
+// like fetch_total's), and a signal that holds a NaN is refused (ITD_ERR_NONFINITE) unless the mode follows the reference's NaN
+// branch: then it is scanned again the way the reference runs it (ITD.py:46-51, 64-68; numba_accelerated_itd.py:28-49) and the
+// total read again.  An extraction's second pass reads the mutated float64 copy that branch leaves behind (ITD.py:87-88), staged
+// in d_cub: *mutated = that copy, or NULL where the signal's own values are its knot values.  knots_out (device, optional): the
+// ordered list, synchronised
+template <typename Tin>
+int scan_one(itd_engine *e, const Tin *x, int64_t n, int mode, double *rot, double *base, int64_t *m, int32_t *knots_out,
+             hipStream_t st, const double **mutated = nullptr)
+{
+    const KnotWs w = helper_ws(e, n);
+    double *xm = nullptr;
+    bool has_nan = false;
+    auto pass = [&](bool follow) -> int {
+        const int rc = knot_scan<Tin>(e, w, x, n, n, 1, mode, m ? kScanOrdered : kScanOnly, st, -1, follow, xm);
+        if (rc) return rc;
+        if (rot) {   // (the scan has taken the ordered list: k_extract rewrites the per-tile lists)
+            if (xm) extract_level0<double>(w, xm, n, n, 1, rot, n, base, n, st);
+            else extract_level0<Tin>(w, x, n, n, 1, rot, n, base, n, st);
+            HIP_TRY(e, hipGetLastError());
+        }
+        return m ? fetch_total(e, w, st, m, !follow && !nan_follows(e, mode), &has_nan) : (int)ITD_OK;
+    };
+    int rc = pass(false);
+    if (rc || !m) return rc;
+    if (has_nan) {
+        if (rot) {
+            rc = grow(e, e->d_cub, (size_t)n * sizeof(double));
+            if (rc) return rc;
+            xm = (double *)e->d_cub;
+        }
+        rc = pass(true);
+        if (rc) return rc;
+    }
+    if (mutated) *mutated = xm;
+    if (knots_out && *m > 0) {
+        HIP_TRY(e, hipMemcpyAsync(knots_out, w.kidx + 1, sizeof(int32_t) * (size_t)*m, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(e, hipStreamSynchronize(st));
+    }
+    return ITD_OK;
+}
+
 template <typename Tin>
 int extract_dev(itd_engine *e, const Tin *x, int64_t n, double *rot, double *base, int32_t *knots, int64_t *m_host,
-                hipStream_t st, bool want_sync, bool *took_nan_path = nullptr)
+                hipStream_t st, bool want_sync, const double **mutated = nullptr)
 {
     if (!e || !x || !rot || !base) return ITD_ERR_INVALID_ARG;
     if (n < 3 || n > e->max_n) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    const KnotWs w = helper_ws(e, n);
-    const KnotAfter after = m_host || knots || want_sync ? kScanOrdered : kScanOnly;
-    int rc = knot_scan<Tin>(e, w, x, n, n, 1, (int)kKnots, after, st);   // the ordered list must be taken before
-    if (rc) return rc;                                                    // k_extract rewrites the per-tile lists
-    extract_level0<Tin>(w, x, n, n, 1, rot, n, base, n, st);
-    HIP_TRY(e, hipGetLastError());
-    if (after == kScanOrdered) {
-        int64_t m = 0;
-        rc = fetch_total(e, w, st, &m, !nan_follows(e, (int)kKnots));
-        if (rc) return rc;
-        int32_t has_nan = 0;
-        HIP_TRY(e, hipMemcpy(&has_nan, w.totals + 1, sizeof(int32_t), hipMemcpyDeviceToHost));
-        if (took_nan_path) *took_nan_path = has_nan != 0;
-        if (has_nan) {
-            // NaN in the signal: again, the way the reference runs it (ITD.py:87-88 over :46-51, 64-68): the mutated float64 copy
-            // goes into a staging buffer, the record-driven extraction reads that
-            rc = grow(e, e->d_cub, (size_t)n * sizeof(double));
-            if (rc) return rc;
-            double *xm = (double *)e->d_cub;
-            rc = knot_scan<Tin>(e, w, x, n, n, 1, (int)kKnots, after, st, -1, true, xm);
-            if (rc) return rc;
-            extract_level0<double>(w, xm, n, n, 1, rot, n, base, n, st);
-            HIP_TRY(e, hipGetLastError());
-            rc = fetch_total(e, w, st, &m, false);
-            if (rc) return rc;
-        }
-        if (m_host) *m_host = m;
-        if (knots && m > 0) {
-            HIP_TRY(e, hipMemcpyAsync(knots, w.kidx + 1, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(e, hipStreamSynchronize(st));
-        }
-    }
+    int64_t m = 0;
+    const int rc = scan_one<Tin>(e, x, n, (int)kKnots, rot, base, m_host || knots || want_sync ? &m : nullptr, knots, st, mutated);
+    if (rc) return rc;
+    if (m_host) *m_host = m;
     return ITD_OK;
 }
 
@@ -1812,27 +1835,67 @@ int detect_dev(itd_engine *e, const Tin *x, int64_t n, int32_t mode, int32_t *id
     if (!e || !x || !count) return ITD_ERR_INVALID_ARG;
     if (n < 3 || n > e->max_n || mode < 0 || mode > 4) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
-    const KnotWs w = helper_ws(e, n);
-    int rc = knot_scan<Tin>(e, w, x, n, n, 1, mode, kScanOrdered, st);
-    if (rc) return rc;
-    rc = fetch_total(e, w, st, count, !nan_follows(e, mode));
-    if (rc) return rc;
-    if (nan_follows(e, mode)) {
-        int32_t has_nan = 0;
-        HIP_TRY(e, hipMemcpy(&has_nan, w.totals + 1, sizeof(int32_t), hipMemcpyDeviceToHost));
-        if (has_nan) {   // the reference's NaN branch (ITD.py:46-51, 64-68; numba_accelerated_itd.py:28-49)
-            rc = knot_scan<Tin>(e, w, x, n, n, 1, mode, kScanOrdered, st, -1, true);
-            if (rc) return rc;
-            rc = fetch_total(e, w, st, count, false);
-            if (rc) return rc;
-        }
-    }
-    if (idx && *count > 0) {
-        HIP_TRY(e, hipMemcpyAsync(idx, w.kidx + 1, sizeof(int32_t) * (size_t)*count, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(e, hipStreamSynchronize(st));
-    }
-    return ITD_OK;
+    return scan_one<Tin>(e, x, n, mode, nullptr, nullptr, count, idx, st);
 }
+
+// What a host form of the single-level helpers stages through, on the engine's own stream: the caller's signal in d_io_x, its results
+// in regions of d_io_rows handed out in the order they are asked for (every element 8 bytes wide).  Once a copy from or into the
+// caller's memory has been enqueued, no return hands that memory back before the stream has drained: the destructor sees to it on
+// every path that has not said so itself (sync(); settled() behind a device form that has synchronised)
+struct HostStage {
+    itd_engine *e;
+    hipStream_t st;
+    DevGuard g;
+    int rc = ITD_OK;          // the first thing that went wrong while staging: no copy is enqueued behind it
+    double *x = nullptr;      // d_io_x
+    char *next = nullptr;     // d_io_rows: what has not been handed out ...
+    size_t left = 0;          // ... of so many elements
+    bool pending = false;     // a copy from or into the caller's memory may be in flight
+
+    explicit HostStage(itd_engine *e_) : e(e_), st(e_->own_stream), g(e_->device) {}
+    HostStage(const HostStage &) = delete;
+    ~HostStage() { if (pending) (void)hipStreamSynchronize(st); }
+
+    // the length of a signal that goes through the engine's fixed one-signal buffers
+    int check_n(int64_t n) { return rc = n < 3 || n > e->max_n ? (int)ITD_ERR_INVALID_ARG : rc; }
+    int reserve(size_t in_elems, size_t out_elems)
+    {
+        if (!rc) rc = grow(e, e->d_io_x, in_elems * sizeof(double));
+        if (!rc) rc = grow(e, e->d_io_rows, out_elems * sizeof(double));
+        if (!rc) { x = (double *)e->d_io_x; next = (char *)e->d_io_rows.get(); left = out_elems; }
+        return rc;
+    }
+    template <typename U> U *take(int64_t count)
+    {
+        static_assert(sizeof(U) == sizeof(double), "d_io_rows is carved in 8-byte elements");
+        if (count < 0 || (size_t)count > left) { rc = ITD_ERR_INVALID_ARG; return nullptr; }   // more than the entry reserved
+        U *p = (U *)next;
+        next += (size_t)count * sizeof(U); left -= (size_t)count;
+        return p;
+    }
+    template <typename U> int copy(U *dst, const U *src, int64_t count, hipMemcpyKind kind)
+    {
+        if (rc) return rc;
+        pending = true;
+        HIP_TRY(e, hipMemcpyAsync(dst, src, (size_t)count * sizeof(U), kind, st));
+        return ITD_OK;
+    }
+    template <typename U> int upload(U *dst_dev, const U *src_host, int64_t count) { return copy(dst_dev, src_host, count, hipMemcpyHostToDevice); }
+    template <typename U> int download(U *dst_host, const U *src_dev, int64_t count) { return copy(dst_host, src_dev, count, hipMemcpyDeviceToHost); }
+    // a device knot list (int32) widened into `region` and brought home as the int64 the host forms deliver
+    int knots_home(int64_t *dst_host, const int32_t *kidx, int64_t count, int64_t *region)
+    {
+        k_widen_idx<<<(unsigned)((count + 255) / 256), 256, 0, st>>>(kidx, region, count);
+        return download(dst_host, region, count);
+    }
+    int sync()
+    {
+        HIP_TRY(e, hipStreamSynchronize(st));
+        pending = false;
+        return ITD_OK;
+    }
+    void settled() { pending = false; }
+};
 }  // namespace
 
 extern "C" {
@@ -1899,34 +1962,25 @@ int itd_baseline_extract_host_f64(itd_engine *e, const double *x_host, int64_t n
                                   int64_t *knots_host, int64_t *m_host, double *bk_host)
 {
     if (!e || !x_host || !rot_host || !base_host) return ITD_ERR_INVALID_ARG;
-    if (n < 3 || n > e->max_n) return ITD_ERR_INVALID_ARG;
-    DevGuard g(e->device);
-    int rc = grow(e, e->d_io_x, (size_t)n * sizeof(double));
+    HostStage S(e);
+    if (S.check_n(n) || S.reserve(n, 4 * n + 2)) return S.rc;
+    double *d_rot = S.take<double>(n), *d_base = S.take<double>(n), *d_bk = S.take<double>(n + 2);
+    int64_t *d_k64 = S.take<int64_t>(n);
+    int rc = S.upload(S.x, x_host, n);
     if (rc) return rc;
-    // rows staging: [rot | base | bk(n+2) | knots64(n)]
-    rc = grow(e, e->d_io_rows, (size_t)(4 * n + 4) * sizeof(double));
-    if (rc) return rc;
-    hipStream_t st = e->own_stream;
-    double *d_rot = e->d_io_rows, *d_base = d_rot + n, *d_bk = d_base + n;
-    int64_t *d_k64 = (int64_t *)(d_bk + n + 2);
-    HIP_TRY(e, hipMemcpyAsync(e->d_io_x, x_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
     int64_t m = 0;
-    bool nan_path = false;
-    rc = extract_dev<double>(e, (const double *)e->d_io_x, n, d_rot, d_base, nullptr, &m, st, true, &nan_path);
-    if (rc) return rc;
-    HIP_TRY(e, hipMemcpyAsync(rot_host, d_rot, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(e, hipMemcpyAsync(base_host, d_base, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (knots_host && m > 0) {
-        k_widen_idx<<<(unsigned)((m + 255) / 256), 256, 0, st>>>(helper_ws(e, n).kidx + 1, d_k64, m);
-        HIP_TRY(e, hipMemcpyAsync(knots_host, d_k64, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    }
-    if (bk_host) {
+    const double *mutated = nullptr;
+    rc = extract_dev<double>(e, S.x, n, d_rot, d_base, nullptr, &m, S.st, true, &mutated);
+    if (!rc) rc = S.download(rot_host, d_rot, n);
+    if (!rc) rc = S.download(base_host, d_base, n);
+    if (!rc && knots_host && m > 0) rc = S.knots_home(knots_host, helper_ws(e, n).kidx + 1, m, d_k64);
+    if (!rc && bk_host) {
         // (a signal that holds NaNs: the knot values of the mutated copy, as the reference computes them after detect_peaks' write)
-        const double *xk = nan_path ? (const double *)e->d_cub : (const double *)e->d_io_x;
-        k_knot_values<double><<<(unsigned)((m + 2 + 255) / 256), 256, 0, st>>>(xk, n, helper_ws(e, n).kidx, (int)m, d_bk);
-        HIP_TRY(e, hipMemcpyAsync(bk_host, d_bk, (size_t)(m + 2) * sizeof(double), hipMemcpyDeviceToHost, st));
+        k_knot_values<double><<<(unsigned)((m + 2 + 255) / 256), 256, 0, S.st>>>(mutated ? mutated : S.x, n, helper_ws(e, n).kidx, (int)m, d_bk);
+        rc = S.download(bk_host, d_bk, m + 2);
     }
-    HIP_TRY(e, hipStreamSynchronize(st));
+    if (!rc) rc = S.sync();
+    if (rc) return rc;
     if (m_host) *m_host = m;
     return ITD_OK;
 }
@@ -1948,23 +2002,20 @@ int itd_detect_f32(itd_engine *e, const float *x_dev, int64_t n, int32_t mode, i
 int itd_detect_host_f64(itd_engine *e, const double *x_host, int64_t n, int32_t mode, int64_t *idx_host,
                         int64_t *count_host)
 {
-    if (!e || !x_host || !count_host) return ITD_ERR_INVALID_ARG;
-    if (n < 3 || n > e->max_n) return ITD_ERR_INVALID_ARG;
-    DevGuard g(e->device);
-    int rc = grow(e, e->d_io_x, (size_t)n * sizeof(double));
+    if (!e || !x_host || !count_host || mode < 0 || mode > 4) return ITD_ERR_INVALID_ARG;
+    HostStage S(e);
+    if (S.check_n(n) || S.reserve(n, n)) return S.rc;
+    int64_t *d_k64 = S.take<int64_t>(n);
+    int rc = S.upload(S.x, x_host, n);
     if (rc) return rc;
-    rc = grow(e, e->d_io_rows, (size_t)n * sizeof(int64_t));
-    if (rc) return rc;
-    hipStream_t st = e->own_stream;
-    HIP_TRY(e, hipMemcpyAsync(e->d_io_x, x_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
     int64_t m = 0;
-    rc = detect_dev<double>(e, (const double *)e->d_io_x, n, mode, nullptr, &m, st);
+    rc = detect_dev<double>(e, S.x, n, mode, nullptr, &m, S.st);
     if (rc) return rc;
+    S.settled();      // (detect_dev has read its total)
     if (idx_host && m > 0) {
-        int64_t *d_k64 = (int64_t *)e->d_io_rows;
-        k_widen_idx<<<(unsigned)((m + 255) / 256), 256, 0, st>>>(helper_ws(e, n).kidx + 1, d_k64, m);
-        HIP_TRY(e, hipMemcpyAsync(idx_host, d_k64, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(e, hipStreamSynchronize(st));
+        rc = S.knots_home(idx_host, helper_ws(e, n).kidx + 1, m, d_k64);
+        if (!rc) rc = S.sync();
+        if (rc) return rc;
     }
     *count_host = m;
     return ITD_OK;
@@ -1978,21 +2029,18 @@ int itd_knot_values_host_f64(itd_engine *e, const double *x_host, int64_t n, con
     for (int64_t k = 0; k < m + 2; ++k)
         if (extrema_host[k] < 0 || extrema_host[k] >= n) return ITD_ERR_INVALID_ARG;
     if (m == 0) return ITD_OK;
-    DevGuard g(e->device);
-    int rc = grow(e, e->d_io_x, (size_t)n * sizeof(double));
-    if (rc) return rc;
-    rc = grow(e, e->d_io_rows, (size_t)(m + 2) * sizeof(double));
-    if (rc) return rc;
-    hipStream_t st = e->own_stream;
-    std::vector<int32_t> e32((size_t)m + 2);
+    std::vector<int32_t> e32((size_t)m + 2);      // (ahead of the stage: it is uploaded from)
     for (int64_t k = 0; k < m + 2; ++k) e32[(size_t)k] = (int32_t)extrema_host[k];
-    HIP_TRY(e, hipMemcpyAsync(e->d_io_x, x_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(e, hipMemcpyAsync(e->d_kidx, e32.data(), (size_t)(m + 2) * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    k_knot_values<double><<<(unsigned)((m + 2 + 255) / 256), 256, 0, st>>>((const double *)e->d_io_x, n, e->d_kidx, (int)m, e->d_io_rows);
+    HostStage S(e);
+    if (S.reserve(n, m + 2)) return S.rc;
+    double *d_bk = S.take<double>(m + 2);
+    int rc = S.upload(S.x, x_host, n);
+    if (!rc) rc = S.upload(e->d_kidx.get(), (const int32_t *)e32.data(), m + 2);
+    if (rc) return rc;
+    k_knot_values<double><<<(unsigned)((m + 2 + 255) / 256), 256, 0, S.st>>>(S.x, n, e->d_kidx, (int)m, d_bk);
     // interior values only: bk[0] and bk[m+1] are the caller's (numba_accelerated_itd.py:171)
-    HIP_TRY(e, hipMemcpyAsync(bk_host + 1, e->d_io_rows + 1, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(e, hipStreamSynchronize(st));
-    return ITD_OK;
+    rc = S.download(bk_host + 1, d_bk + 1, m);
+    return rc ? rc : S.sync();
 }
 
 int itd_knot_values_f64(itd_engine *e, const double *x_dev, int64_t n, const int32_t *extrema_dev, int64_t m, double *bk_dev,
@@ -2107,18 +2155,41 @@ int cubic_dev(itd_engine *e, const double *x, int64_t n, const int32_t *extrema,
 }
 
 // the caller's knot list (host, int64, `count` entries) for the kernels: range-checked on the host copy first (narrowing to int32
-// must not wrap), uploaded into `scratch`, narrowed into d_cub_e
-int stage_extrema(itd_engine *e, const int64_t *extrema_host, int64_t count, int64_t n, int64_t *scratch, hipStream_t st,
-                  const int32_t **dev_out)
+// must not wrap; nothing has been enqueued where that fails), uploaded into `scratch`, narrowed into d_cub_e
+int stage_extrema(HostStage &S, const int64_t *extrema_host, int64_t count, int64_t n, int64_t *scratch, const int32_t **dev_out)
 {
     for (int64_t k = 0; k < count; ++k)
         if (extrema_host[k] < 0 || extrema_host[k] >= n) return ITD_ERR_INVALID_ARG;
-    const int rc = grow(e, e->d_cub_e, (size_t)count * sizeof(int32_t));
+    int rc = grow(S.e, S.e->d_cub_e, (size_t)count * sizeof(int32_t));
+    if (!rc) rc = S.upload(scratch, extrema_host, count);
     if (rc) return rc;
-    HIP_TRY(e, hipMemcpyAsync(scratch, extrema_host, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    k_narrow_idx<<<(unsigned)((count + 255) / 256), 256, 0, st>>>(scratch, e->d_cub_e, count);
-    *dev_out = e->d_cub_e;
+    k_narrow_idx<<<(unsigned)((count + 255) / 256), 256, 0, S.st>>>(scratch, S.e->d_cub_e, count);
+    *dev_out = S.e->d_cub_e;
     return ITD_OK;
+}
+
+// The host form of the natural-cubic operator and of its I/Q form: `comps` values per sample, body(x, list, baseline, &idx, st,
+// &knots) the device form (knots: where it leaves the knots it detected, asked for when the caller hands in no list)
+template <typename Body>
+int cubic_host(itd_engine *e, const double *x_host, int comps, int64_t n, const int64_t *extrema_host, int64_t idx,
+               double *baseline_host, int64_t *idx_out, int64_t *extrema_out_host, Body body)
+{
+    if (!e || !x_host || !baseline_host || (extrema_host && (idx < 2 || idx > n - 1))) return ITD_ERR_INVALID_ARG;
+    HostStage S(e);
+    if (S.check_n(n) || S.reserve((size_t)comps * n, 2 * n)) return S.rc;
+    double *d_base = S.take<double>(n);
+    int64_t *d_e64 = S.take<int64_t>(n);          // the caller's list on its way in, or the detected knots on their way out
+    const int32_t *ek = nullptr, *knots_dev = nullptr;
+    int rc = extrema_host ? stage_extrema(S, extrema_host, idx + 1, n, d_e64, &ek) : (int)ITD_OK;
+    if (!rc) rc = S.upload(S.x, x_host, comps * n);
+    if (rc) return rc;
+    int64_t got = 0;
+    rc = body(S.x, ek, d_base, &got, S.st, extrema_host ? nullptr : &knots_dev);
+    if (rc) return rc;
+    if (idx_out) *idx_out = got;
+    if (got >= 2) rc = S.download(baseline_host, d_base, n);     // itd.cpp:85-87: fewer than 2 knots, the caller's buffer is left alone
+    if (!rc && extrema_out_host && !extrema_host && got > 0) rc = S.knots_home(extrema_out_host, knots_dev, got, d_e64);
+    return rc ? rc : S.sync();
 }
 }  // namespace
 
@@ -2147,34 +2218,10 @@ int itd_baseline_extract_cubic_f32(itd_engine *e, const float *x_dev, int64_t n,
 int itd_baseline_extract_cubic_host_f64(itd_engine *e, const double *x_host, int64_t n, const int64_t *extrema_host,
                                         int64_t idx, double *baseline_host, int64_t *idx_out, int64_t *extrema_out_host)
 {
-    if (!e || !x_host || !baseline_host) return ITD_ERR_INVALID_ARG;
-    if (n < 3 || n > e->max_n) return ITD_ERR_INVALID_ARG;
-    DevGuard g(e->device);
-    hipStream_t st = e->own_stream;
-    int rc = grow(e, e->d_io_x, (size_t)n * sizeof(double));
-    if (rc) return rc;
-    rc = grow(e, e->d_io_rows, (size_t)n * sizeof(double) * 2);   // baseline | widened knots
-    if (rc) return rc;
-    HIP_TRY(e, hipMemcpyAsync(e->d_io_x, x_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-    const int32_t *ek = nullptr;
-    if (extrema_host) {
-        if (idx < 2 || idx > n - 1) return ITD_ERR_INVALID_ARG;
-        rc = stage_extrema(e, extrema_host, idx + 1, n, (int64_t *)(e->d_io_rows + n), st, &ek);
-        if (rc) return rc;
-    }
-    int64_t got = 0;
-    const int32_t *knots_dev = nullptr;
-    rc = cubic_dev(e, (const double *)e->d_io_x, n, ek, idx, e->d_io_rows, &got, st, extrema_host ? nullptr : &knots_dev);
-    if (rc) return rc;
-    if (idx_out) *idx_out = got;
-    if (got >= 2) HIP_TRY(e, hipMemcpyAsync(baseline_host, e->d_io_rows, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (extrema_out_host && !extrema_host && got > 0) {
-        int64_t *d_e64 = (int64_t *)(e->d_io_rows + n);
-        k_widen_idx<<<(unsigned)((got + 255) / 256), 256, 0, st>>>(knots_dev, d_e64, got);
-        HIP_TRY(e, hipMemcpyAsync(extrema_out_host, d_e64, (size_t)got * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(e, hipStreamSynchronize(st));
-    return ITD_OK;
+    return cubic_host(e, x_host, 1, n, extrema_host, idx, baseline_host, idx_out, extrema_out_host,
+                      [=](const double *x, const int32_t *ek, double *base, int64_t *got, hipStream_t st, const int32_t **knots) {
+                          return cubic_dev(e, x, n, ek, idx, base, got, st, knots);
+                      });
 }
 
 // The common-baseline form on complex (I/Q) data, itd.cpp:58-154 (itd_detect_fast.hpp: k_detect_fast_iq): knots where both
@@ -2211,57 +2258,31 @@ int itd_baseline_extract_iq_f64(itd_engine *e, const double *iq_dev, int64_t n, 
 int itd_baseline_extract_iq_host_f64(itd_engine *e, const double *iq_host, int64_t n, const int64_t *extrema_host, int64_t idx,
                                      double *baseline_host, int64_t *idx_out, int64_t *extrema_out_host)
 {
-    if (!e || !iq_host || !baseline_host) return ITD_ERR_INVALID_ARG;
-    if (n < 3 || n > e->max_n) return ITD_ERR_INVALID_ARG;
-    DevGuard g(e->device);
-    hipStream_t st = e->own_stream;
-    int rc = grow(e, e->d_io_x, (size_t)n * sizeof(double) * 2);
-    if (rc) return rc;
-    rc = grow(e, e->d_io_rows, (size_t)n * sizeof(double) * 2);   // baseline | widened knots
-    if (rc) return rc;
-    HIP_TRY(e, hipMemcpyAsync(e->d_io_x, iq_host, (size_t)n * sizeof(double) * 2, hipMemcpyHostToDevice, st));
-    const int32_t *ek = nullptr;
-    int64_t *d_e64 = (int64_t *)(e->d_io_rows + n);
-    if (extrema_host) {
-        if (idx < 2 || idx > n - 1) return ITD_ERR_INVALID_ARG;
-        rc = stage_extrema(e, extrema_host, idx + 1, n, d_e64, st, &ek);
-        if (rc) return rc;
-    }
-    int64_t got = extrema_host ? idx : 0;
-    rc = itd_baseline_extract_iq_f64(e, (const double *)e->d_io_x, n, ek, idx, e->d_io_rows, extrema_host ? nullptr : &got, st);
-    if (rc) return rc;
-    if (idx_out) *idx_out = got;
-    if (got >= 2) HIP_TRY(e, hipMemcpyAsync(baseline_host, e->d_io_rows, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (extrema_out_host && !extrema_host && got > 0) {
-        k_widen_idx<<<(unsigned)((got + 255) / 256), 256, 0, st>>>(helper_ws(e, n).kidx + 1, d_e64, got);
-        HIP_TRY(e, hipMemcpyAsync(extrema_out_host, d_e64, (size_t)got * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(e, hipStreamSynchronize(st));
-    return ITD_OK;
+    return cubic_host(e, iq_host, 2, n, extrema_host, idx, baseline_host, idx_out, extrema_out_host,
+                      [=](const double *iq, const int32_t *ek, double *base, int64_t *got, hipStream_t st, const int32_t **knots) {
+                          if (knots) *knots = helper_ws(e, n).kidx + 1;      // (its scan runs in the engine's fixed buffers)
+                          return itd_baseline_extract_iq_f64(e, iq, n, ek, idx, base, got, st);
+                      });
 }
 
 int itd_find_extrema_host_f64(itd_engine *e, const double *s_host, int64_t n, int64_t *extrema_host, int64_t *idx_out)
 {
     if (!e || !s_host || !extrema_host || !idx_out) return ITD_ERR_INVALID_ARG;
-    if (n < 3 || n > e->max_n) return ITD_ERR_INVALID_ARG;
-    DevGuard g(e->device);
-    hipStream_t st = e->own_stream;
-    int rc = grow(e, e->d_io_x, (size_t)n * sizeof(double));
+    HostStage S(e);
+    if (S.check_n(n) || S.reserve(n, n + 2)) return S.rc;
+    int64_t *d_e64 = S.take<int64_t>(n + 2);
+    int rc = S.upload(S.x, s_host, n);
     if (rc) return rc;
-    rc = grow(e, e->d_io_rows, (size_t)(n + 2) * sizeof(int64_t));
-    if (rc) return rc;
-    HIP_TRY(e, hipMemcpyAsync(e->d_io_x, s_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
     int64_t m = 0;
-    rc = cubic_detect(e, (const double *)e->d_io_x, n, (int)kZeroCross, &m, st);
+    rc = cubic_detect(e, S.x, n, (int)kZeroCross, &m, S.st);
     if (rc) return rc;
     // d_kidx = [0, crossings (m of them), extrapolated tail]: idx = m + 2 entries, the rest of the caller's array is zero
     const int64_t idx = m + 2;
     if (idx > n) return ITD_ERR_INVALID_ARG;   // the reference's own array would overflow (every interior sample a crossing)
-    int64_t *d_e64 = (int64_t *)e->d_io_rows;
-    k_widen_idx<<<(unsigned)((idx + 255) / 256), 256, 0, st>>>(helper_ws(e, n).kidx, d_e64, idx);
     memset(extrema_host, 0, (size_t)n * sizeof(int64_t));
-    HIP_TRY(e, hipMemcpyAsync(extrema_host, d_e64, (size_t)idx * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(e, hipStreamSynchronize(st));
+    rc = S.knots_home(extrema_host, helper_ws(e, n).kidx, idx, d_e64);
+    if (!rc) rc = S.sync();
+    if (rc) return rc;
     *idx_out = idx;
     return ITD_OK;
 }
@@ -2528,17 +2549,18 @@ int itd_baseline_extract_spline_host2_f64(itd_engine *e, const double *x_host, i
 int itd_count_knots_host_f64(itd_engine *e, const double *x_host, int64_t n, int32_t batch, int32_t mode, int32_t *counts_host)
 {
     if (!e || !x_host || !counts_host || n < 3 || batch < 1 || batch > kMaxGridY || mode < 0 || mode > 4) return ITD_ERR_INVALID_ARG;
-    DevGuard g(e->device);
-    hipStream_t st = e->own_stream;
     const size_t cnt = (size_t)n * (size_t)batch;
-    int rc = grow(e, e->d_io_x, cnt * sizeof(double));
+    HostStage S(e);
+    if (S.reserve(cnt, 0)) return S.rc;
+    int rc = S.upload(S.x, x_host, (int64_t)cnt);
     if (rc) return rc;
-    HIP_TRY(e, hipMemcpyAsync(e->d_io_x, x_host, cnt * sizeof(double), hipMemcpyHostToDevice, st));
     KnotWs w;
     rc = knot_workspace(e, e->d_dw, n, batch, kWsDetect, w);
-    if (!rc) rc = knot_scan<double>(e, w, (const double *)e->d_io_x, n, n, batch, mode, kScanTotals, st);
+    if (!rc) rc = knot_scan<double>(e, w, S.x, n, n, batch, mode, kScanTotals, S.st);
     if (rc) return rc;
-    return fetch_totals(e, w.totals, batch, counts_host, st);     // counted under the plain rules: see itd_detect_* for detect_peaks' NaN branch
+    rc = fetch_totals(e, w.totals, batch, counts_host, S.st);     // counted under the plain rules: see itd_detect_* for detect_peaks' NaN branch
+    if (rc != ITD_ERR_HIP) S.settled();                            // (the totals' copy has synchronised)
+    return rc;
 }
 
 // ---- MEITD's operators on device-resident signals (MEITD.py:344-534 keeps one signal and its rotations / baselines in a loop:
@@ -2862,18 +2884,15 @@ int itd_crossways_host_f64(itd_engine *e, const double *img_host, int32_t planes
                            double *out_host)
 {
     if (!e || !img_host || !out_host || planes < 1 || rows < 3 || cols < 3) return ITD_ERR_INVALID_ARG;
-    DevGuard g(e->device);
-    hipStream_t st = e->own_stream;
-    const size_t cnt = (size_t)planes * rows * cols;
-    int rc = grow(e, e->d_io_rows, 2 * cnt * sizeof(double));
+    const int64_t cnt = (int64_t)planes * rows * cols;
+    HostStage S(e);
+    if (S.reserve(0, 2 * (size_t)cnt)) return S.rc;        // both sides in d_io_rows
+    double *d_in = S.take<double>(cnt), *d_out = S.take<double>(cnt);
+    int rc = S.upload(d_in, img_host, cnt);
     if (rc) return rc;
-    double *d_in = e->d_io_rows, *d_out = d_in + cnt;
-    HIP_TRY(e, hipMemcpyAsync(d_in, img_host, cnt * sizeof(double), hipMemcpyHostToDevice, st));
-    rc = itd_crossways_f64(e, d_in, planes, rows, cols, min_extrema, d_out, st);
-    if (rc) return rc;
-    HIP_TRY(e, hipMemcpyAsync(out_host, d_out, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(e, hipStreamSynchronize(st));
-    return ITD_OK;
+    rc = itd_crossways_f64(e, d_in, planes, rows, cols, min_extrema, d_out, S.st);
+    if (!rc) rc = S.download(out_host, d_out, cnt);
+    return rc ? rc : S.sync();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2907,22 +2926,16 @@ int itd_instantaneous_host_f64(itd_engine *e, const double *rot_host, int64_t n,
                                double *freq_host)
 {
     if (!e || !rot_host) return ITD_ERR_INVALID_ARG;
-    if (n < 3 || n > e->max_n) return ITD_ERR_INVALID_ARG;
-    DevGuard g(e->device);
-    hipStream_t st = e->own_stream;
-    int rc = grow(e, e->d_io_x, (size_t)n * sizeof(double));
+    HostStage S(e);
+    if (S.check_n(n) || S.reserve(n, 3 * n)) return S.rc;
+    double *d_a = S.take<double>(n), *d_p = S.take<double>(n), *d_f = S.take<double>(n);
+    int rc = S.upload(S.x, rot_host, n);
     if (rc) return rc;
-    rc = grow(e, e->d_io_rows, 3 * (size_t)n * sizeof(double));
-    if (rc) return rc;
-    HIP_TRY(e, hipMemcpyAsync(e->d_io_x, rot_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-    double *d_a = e->d_io_rows, *d_p = d_a + n, *d_f = d_p + n;
-    rc = itd_instantaneous_f64(e, (const double *)e->d_io_x, n, d_a, d_p, d_f, st);
-    if (rc) return rc;
-    if (amp_host) HIP_TRY(e, hipMemcpyAsync(amp_host, d_a, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (phase_host) HIP_TRY(e, hipMemcpyAsync(phase_host, d_p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (freq_host) HIP_TRY(e, hipMemcpyAsync(freq_host, d_f, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(e, hipStreamSynchronize(st));
-    return ITD_OK;
+    rc = itd_instantaneous_f64(e, S.x, n, d_a, d_p, d_f, S.st);
+    if (!rc && amp_host) rc = S.download(amp_host, d_a, n);
+    if (!rc && phase_host) rc = S.download(phase_host, d_p, n);
+    if (!rc && freq_host) rc = S.download(freq_host, d_f, n);
+    return rc ? rc : S.sync();
 }
 
 int itd_set_kernel_timing(itd_engine *e, int max_decompositions)

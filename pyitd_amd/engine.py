@@ -410,43 +410,33 @@ class Engine:
         self._check(self._L.itd_find_extrema_host_f64(self._h, _np_ptr(s), n, _np_ptr(ext), ctypes.byref(idx)))
         return ext, int(idx.value)
 
-    def cubic_extract_host(self, x, extrema=None, idx=0):
-        """itd_baseline_extract_fast (itd_fourier_decomposition.py:49-122).  extrema=None: the knots are detected with
-        itd.cpp's predicate (itd.cpp:161-168).  Returns (baseline or None when fewer than 2 knots, knots int64, idx)."""
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        n = x.shape[0]
+    def _cubic_host(self, fn, arr, n, extrema, idx, what):
+        """The host forms of the natural-cubic operator: fn the ABI entry, arr its float64 input (n samples, one or two values each)."""
         base = np.empty(n)
         got = ctypes.c_int64(0)
         if extrema is None:
             kn = np.zeros(n, np.int64)
-            self._check(self._L.itd_baseline_extract_cubic_host_f64(self._h, _np_ptr(x), n, None, 0, _np_ptr(base),
-                                                                    ctypes.byref(got), _np_ptr(kn)))
+            self._check(fn(self._h, _np_ptr(arr), n, None, 0, _np_ptr(base), ctypes.byref(got), _np_ptr(kn)))
             return (base if got.value >= 2 else None), kn, int(got.value)
         e = np.ascontiguousarray(extrema, dtype=np.int64)
         if e.shape[0] < idx + 1:
-            raise ValueError("extrema_input needs idx+1 entries")
-        self._check(self._L.itd_baseline_extract_cubic_host_f64(self._h, _np_ptr(x), n, _np_ptr(e), int(idx), _np_ptr(base),
-                                                                ctypes.byref(got), None))
+            raise ValueError("%s needs idx+1 entries" % what)
+        self._check(fn(self._h, _np_ptr(arr), n, _np_ptr(e), int(idx), _np_ptr(base), ctypes.byref(got), None))
         return base, e, int(idx)
+
+    def cubic_extract_host(self, x, extrema=None, idx=0):
+        """itd_baseline_extract_fast (itd_fourier_decomposition.py:49-122).  extrema=None: the knots are detected with
+        itd.cpp's predicate (itd.cpp:161-168).  Returns (baseline or None when fewer than 2 knots, knots int64, idx)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        return self._cubic_host(self._L.itd_baseline_extract_cubic_host_f64, x, x.shape[0], extrema, idx, "extrema_input")
 
     def iq_extract_host(self, z, extrema=None, idx=0):
         """itd_baseline_extract_iq (itd.cpp:58-154): ONE real natural-cubic baseline for complex data — knots where both components
         have an extremum (extrema=None) or the caller's, the operator on the components' mean.  Returns (baseline or None when fewer
         than 2 knots, knots int64, idx)."""
         z = np.ascontiguousarray(z, dtype=np.complex128)
-        n = z.shape[0]
-        iq = z.view(np.float64)                       # interleaved (re, im)
-        base = np.empty(n)
-        got = ctypes.c_int64(0)
-        if extrema is None:
-            kn = np.zeros(n, np.int64)
-            self._check(self._L.itd_baseline_extract_iq_host_f64(self._h, _np_ptr(iq), n, None, 0, _np_ptr(base), ctypes.byref(got), _np_ptr(kn)))
-            return (base if got.value >= 2 else None), kn, int(got.value)
-        e = np.ascontiguousarray(extrema, dtype=np.int64)
-        if e.shape[0] < idx + 1:
-            raise ValueError("extrema needs idx+1 entries")
-        self._check(self._L.itd_baseline_extract_iq_host_f64(self._h, _np_ptr(iq), n, _np_ptr(e), int(idx), _np_ptr(base), ctypes.byref(got), None))
-        return base, e, int(idx)
+        # interleaved (re, im)
+        return self._cubic_host(self._L.itd_baseline_extract_iq_host_f64, z.view(np.float64), z.shape[0], extrema, idx, "extrema")
 
     # ---- batched single-level operators on device buffers (asynchronous; include/pyitd_hip.h: *_batch_f64) ---------------
     def extract_batch_dev(self, x_ptr, n, batch, x_stride, rot_ptr, rot_stride, base_ptr, base_stride, info_ptr=None, stream=None):

@@ -366,7 +366,17 @@ def test_nan_input_of_the_device_entries(nan_eng, n):
     if n > 5:
         x32[[0, 700 % n, n - 1]] = np.nan
     x = x32.astype(np.float64)
-    rot, base, kn, _ = cpu_oracle.itd_baseline_extract(x, want_knots=True)        # the reference's NaN branch
+    rot, base, kn, bk = cpu_oracle.itd_baseline_extract(x, want_knots=True)       # the reference's NaN branch
+    # the host form: the knot values too (those of the mutated copy: the branch's infinities are among them)
+    assert not np.all(np.isfinite(bk))
+    keep = x.copy()
+    h_rot, h_base, h_kn, h_bk = eng.baseline_extract_host(x, want_knots=True)
+    _bits(h_rot, rot, "host form, NaN branch rotation")
+    _bits(h_base, base, "host form, NaN branch baseline")
+    assert h_kn.dtype == np.int64 and np.array_equal(h_kn, kn)
+    assert h_bk.shape == (len(kn) + 2,)
+    _bits(h_bk, bk, "host form, NaN branch knot values")
+    _bits(x, keep, "the host form leaves the caller's array alone")
     for fn, xx in ((L.itd_baseline_extract_f64, x), (L.itd_baseline_extract_f32, x32)):
         for want_knots, want_m in ((True, True), (False, True), (True, False)):
             g = _extract(eng, fn, xx, want_knots, want_m)
@@ -452,6 +462,41 @@ def test_rejected_arguments(nan_eng):
         assert np.all(d.get(k) == SENT), "a refused call wrote %s" % k
     assert np.all(d.get("kn") == ISENT)
     d.free()
+
+
+def test_rejected_knot_lists_of_the_cubic_host_forms():
+    """A caller's list with idx outside [2, n - 1] or an entry outside [0, n): refused before anything is enqueued, the caller's
+    baseline buffer untouched, and the next valid call on the same engine gives what a fresh engine gives."""
+    import pyitd_amd
+    n = 16
+    x = signal32("thirds", n, seed=2).astype(np.float64)
+    z = (x + 1j * signal32("thirds", n, seed=3)).view(np.float64)
+    good = np.array([0, 3, 6, 9, 12, 15], np.int64)
+    forms = (("itd_baseline_extract_cubic_host_f64", x), ("itd_baseline_extract_iq_host_f64", z))
+
+    def call(e, name, arr, lst, idx):
+        base = np.full(n + PAD, SENT)
+        got = _i64(-5)
+        rc = getattr(e._L, name)(e._h, arr.ctypes.data, n, lst.ctypes.data, idx, base.ctypes.data, ctypes.byref(got), None)
+        return rc, base
+
+    fresh = pyitd_amd.Engine(1 << 10, 1, 0)
+    want = [call(fresh, name, arr, good, 5) for name, arr in forms]
+    fresh.close()
+    e = pyitd_amd.Engine(1 << 10, 1, 0)
+    long_list = np.arange(n + 1, dtype=np.int64) % n
+    for (name, arr), (want_rc, want_base) in zip(forms, want):
+        assert want_rc == OK and np.all(want_base[:n] != SENT) and np.all(want_base[n:] == SENT)
+        bad = [(good, 1), (long_list, n)]
+        bad += [(np.array(lst, np.int64), 5) for lst in ([0, 3, 6, 9, n, 15], [0, 3, -1, 9, 12, 15], [0, 3, 6, 9, 12, n])]
+        for lst, idx in bad:
+            rc, base = call(e, name, arr, lst, idx)
+            assert rc == INVALID, (name, lst, idx)
+            assert np.all(base == SENT), "a refused call wrote the baseline (%s, idx %d)" % (name, idx)
+            rc, base = call(e, name, arr, good, 5)
+            assert rc == OK
+            _bits(base, want_base, "%s after a refused call" % name)
+    e.close()
 
 
 def test_engine_device(eng):
