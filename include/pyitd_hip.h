@@ -558,14 +558,25 @@ int itd_instantaneous_host_f64(itd_engine *e, const double *rot_host, int64_t n,
  * The reference applies its single-level functions row by row (siftED2D.ipynb cell 1: itd_baseline_extract over the rows of an
  * image under numba.prange) and along channels (itd.cpp:40-44).  Signal b starts at x_dev + b * x_stride.  These calls work in
  * workspaces of their own (grown on demand: the first call of a size allocates — so capture a call only after one of its size has
- * run), apart from the decomposition's.
+ * run), apart from the decomposition's.  Growing frees the old block and allocates a larger one: a captured call keeps the
+ * addresses of the block it was captured in, so its graph is valid only while no larger call of its kind (the extraction has one
+ * workspace; the batched detection, knot counts and cubic batch share another) follows on the engine — after one, capture again.
+ * A later smaller call works in the front of the grown block and is no such call.
  *
  * itd_baseline_extract_batch_f64: itd_baseline_extract (ITD.py:79-121) of every signal: rot_dev / base_dev [batch] rows of n.
  *   info_dev (optional) [batch]: the signal's interior knot count; -1 - count if the signal holds a NaN — its rows then follow
  *   the plain rules, not detect_peaks' NaN branch (ITD.py:46-51): run that signal through itd_baseline_extract_* .
+ *   The plain rules of the extraction: the knots are the samples flagged by dx[i] > 0 & dx[i-1] <= 0 or dx[i] < 0 & dx[i-1] >= 0
+ *   as IEEE comparisons (one with a NaN is false: a NaN sample and both its neighbours are never knots), nothing is overwritten
+ *   with +inf, and the arithmetic of ITD.py:100-117 runs on those knots as written, NaNs propagating (oracle/numpy_itd.py:
+ *   baseline_extract(plain_nan=True) is the statement the tests compare with).  Any batch >= 1: above 65535 signals in chunks.
  * itd_detect_batch_f64: the knots of every signal by predicate `mode` (ITD_DETECT_*): idx_dev (optional) [batch] lists at
  *   idx_stride >= n - 2 (the knots alone, ascending); info_dev (optional) as above.  idx_dev == NULL: counts only (no list is
- *   built).  batch <= 65535.
+ *   built).  batch <= 65535.  The plain rules of the detection: every mode's predicate as IEEE comparisons on the samples as they
+ *   are — for ITD_DETECT_KNOTS, _VALLEYS and _PEAKS the flags above and their two halves, for the other two modes the loops of
+ *   itd.cpp:161-168 and itd_fourier_decomposition.py:17-31, which have no NaN rule to leave out.  Of a signal's list slot the entries
+ *   [0, count) are written with its knots; what the entries [count, n - 2) hold afterwards is unspecified (they may be written),
+ *   and nothing at or beyond entry n - 2 of a slot is touched.
  * itd_baseline_extract_cubic_batch_f64: itd_baseline_extract_fast (itd_fourier_decomposition.py:49-122) of every signal.
  *   extrema_dev: idx + 1 knots as in itd_baseline_extract_cubic_f64 — ONE list for every signal (extrema_stride = 0: "retain the
  *   extrema and reuse them ... along multiple channels", itd.cpp:40-44) or one per signal (extrema_stride >= idx + 1);

@@ -13,26 +13,54 @@ to the golden vectors):
 
 NaN handling: the reference's detect_peaks NaN branch (ITD.py:46-51, 64-68) is NOT restated here; inputs whose baselines
 go NaN are outside this leg's domain (the C oracle covers them) and raise.
+
+The plain rules (baseline_extract(x, plain_nan=True), valley_flags / peak_flags / knot_flags on any input): what the expressions
+above give when nothing treats a NaN specially — a comparison with a NaN is false, so a NaN sample and both its neighbours are
+never knots, nothing is overwritten with +inf, and the arithmetic of ITD.py:100-117 runs as written.  This is what the batched
+device entries (itd_baseline_extract_batch_f64, itd_detect_batch_f64) promise for a signal that holds a NaN.
 """
 import numpy as np
 
 MAX_ROWS = 22
 
 
-def knot_flags(x):
-    """bool[n]: interior knots of x = detect_peaks(x) U detect_peaks(-x) (ITD.py:59, 87-98; first/last never, :70-73)."""
-    dx = x[1:] - x[:-1]
+def _half_flags(x, peaks):
+    with np.errstate(invalid="ignore"):                         # (inf - inf in a row of extreme values: the comparison is false)
+        dx = x[1:] - x[:-1]
     f = np.zeros(x.shape[0], dtype=bool)
     vil, vix = dx[1:], dx[:-1]
-    f[1:-1] = ((vil > 0) & (vix <= 0)) | ((vil < 0) & (vix >= 0))
+    f[1:-1] = ((vil < 0) & (vix >= 0)) if peaks else ((vil > 0) & (vix <= 0))
     return f
 
 
-def baseline_extract(x):
-    """(rotation, baseline, m) of one extraction (ITD.py:79-121)."""
-    n = x.shape[0]
+def valley_flags(x):
+    """bool[n]: detect_peaks(x) under the plain rules (ITD.py:44-59): dx[i] > 0 & dx[i-1] <= 0; first/last never (:70-73)."""
+    return _half_flags(x, False)
+
+
+def peak_flags(x):
+    """bool[n]: the same on -dx (matlab_detect_peaks, numba_accelerated_itd.py:28-29; detect_peaks(-x), ITD.py:88)."""
+    return _half_flags(x, True)
+
+
+def knot_flags(x):
+    """bool[n]: interior knots of x = detect_peaks(x) U detect_peaks(-x) (ITD.py:59, 87-98; first/last never, :70-73)."""
+    return valley_flags(x) | peak_flags(x)
+
+
+def baseline_extract(x, plain_nan=False):
+    """(rotation, baseline, m) of one extraction (ITD.py:79-121).  plain_nan: NaN input is not refused, the same expressions run
+    under the plain rules (see the header), and the flagged indices are returned too: (rotation, baseline, m, knots)."""
+    if plain_nan:
+        with np.errstate(all="ignore"):
+            return _baseline_extract(x) + (np.flatnonzero(knot_flags(x)).astype(np.int64),)
     if np.isnan(x).any():
         raise ValueError("numpy restatement: NaN input (the reference's NaN branch is restated by the C oracle only)")
+    return _baseline_extract(x)
+
+
+def _baseline_extract(x):
+    n = x.shape[0]
     f = knot_flags(x)
     e = np.concatenate(([0], np.flatnonzero(f), [n - 1])).astype(np.int64)
     m = e.shape[0] - 2

@@ -9,6 +9,8 @@ their own (sentinel-filled, with pads behind every output), on the caller's stre
   itd_baseline_extract_spline_f64     strided batches under both solvers, row by row bit for bit against the host form
   itd_crossways_f64                   against oracle.spline_oracle.crossways
   itd_engine_device
+  itd_baseline_extract_batch_f64      here only with batch = 1 beside the single-signal entry's plain-rule form; held to references
+  itd_detect_batch_f64                (the C oracle, and oracle.numpy_itd's plain rules for NaN rows) in test_gpu_batch_ops.py
 Every _f32 entry gives exactly what its _f64 twin gives on the widened signal.  NaN input follows pyitd_hip.h's rules, and
 arguments that are refused on the host are refused.
 """

@@ -1,13 +1,38 @@
 """The batched single-level operators (pyitd_amd.batch: itd_baseline_extract_batch, count_knots_batch, detect_knots_batch,
 itd_baseline_extract_fast_channels) against the CPU oracle on random batches (1 .. 3000 rows of 3 .. 5000 samples, NaNs, plateaus, knot-free
-rows): rows bit for bit, counts and lists exact, the cubic channels to 1e-9.  usage: python tools/batch_ops_fuzz.py [cases] [seed]"""
+rows): rows bit for bit, counts and lists exact, the cubic channels to 1e-9.  Each case also calls the device entries directly at
+drawn strides and a drawn mode, compared the way tests/test_gpu_batch_ops.py compares (tests/batch_cases.py: sentinels in the stride
+gaps, NaN rows under the plain rules).  usage: python tools/batch_ops_fuzz.py [cases] [seed]"""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-from helpers import fuzz_signal, assert_bits_equal
+import batch_cases as bc
+from helpers import DevArrays, fuzz_signal, assert_bits_equal
 from oracle import cpu_oracle as O
 from pyitd_amd.batch import count_knots_batch, detect_knots_batch, itd_baseline_extract_batch, itd_baseline_extract_fast_channels
+from pyitd_amd.itd import _engine_for
+
+
+def strided(x, rng, what):
+    """the device entries on the first rows of x at drawn strides (odd ones flip the rows' alignment) and a drawn mode"""
+    x = x[:64]
+    B, n = x.shape
+    eng = _engine_for(n)
+    xs, rs, bs = (n + int(rng.choice([0, 1, 2, 3, 37])) for _ in range(3))
+    ks = n - 2 + int(rng.choice([0, 1, 7]))
+    mode, lists = int(rng.integers(0, 5)), bool(rng.integers(0, 2))
+    what += " strides %d %d %d %d mode %d lists %d" % (xs, rs, bs, ks, mode, lists)
+    d = DevArrays(eng, x=bc.layout(x, xs), rot=bc.blank(B, n, rs), base=bc.blank(B, n, bs), info=np.full(B + bc.PAD, bc.ISENT, np.int32),
+                  idx=bc.blank(B, n - 2, ks, bc.ISENT, dtype=np.int32), kinfo=np.full(B + bc.PAD, bc.ISENT, np.int32))
+    try:
+        eng.extract_batch_dev(d.ptr("x"), n, B, xs, d.ptr("rot"), rs, d.ptr("base"), bs, d.ptr("info"))
+        eng.detect_batch_dev(d.ptr("x"), n, B, xs, mode, d.ptr("idx") if lists else None, ks, d.ptr("kinfo"))
+        bc.check_extract({k: d.get(k) for k in ("x", "rot", "base", "info")}, x, bc.extract_reference(x), (xs, rs, bs), what)
+        bc.check_detect(dict(idx=d.get("idx") if lists else None, info=d.get("kinfo")), bc.detect_reference(x, mode), n, ks, what)
+    finally:
+        d.free()
+
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
@@ -33,6 +58,7 @@ for case in range(cases):
                 assert_bits_equal(base[b], bs, what + " row %d baseline" % b)
                 assert_bits_equal(rot[b], r, what + " row %d rotation" % b)
                 assert counts[b] == len(kn), what + " row %d count" % b
+            strided(x, rng, what)
             sub = x[:min(B, 64)]
             if not np.isnan(sub).any():
                 cnt = count_knots_batch(sub)
