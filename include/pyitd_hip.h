@@ -651,8 +651,14 @@ int itd_fourier_modes_f64(itd_engine *e, double *modes_dst, int64_t count, int32
  *                      bit-identical to the whole-signal operator's rows.
  * Ring, knot detection, knot selection and the operator all run on the device: a device-form push / flush enqueues its
  * launches on `stream` and returns (no host synchronisation; `*emitted` is known from the block count alone); the host forms
- * copy through pinned staging and synchronise once per call.  A NaN in a window makes the host forms return
- * ITD_ERR_NONFINITE (the block is emitted under plain comparison rules); the device forms record it for itd_stream_status. */
+ * copy through pinned staging and synchronise once per call.
+ * A NaN.  ITD_STREAM_LINEAR: the block is emitted under plain comparison rules.  ITD_STREAM_CUBIC: nothing is built on a window
+ * that holds a NaN — every block that takes its knots from such a window (the channel's own; channel 0's under shared_knots) is
+ * emitted unchanged, rotation 0.  Under shared_knots a channel other than 0 that holds a NaN while channel 0's window is finite
+ * gets a spline on channel 0's knots through its NaN: its samples of that block are unspecified (the NaN spreads through the
+ * sweeps), the other channels are not touched by it.  Either kind: a NaN in ANY channel's pushed block is recorded when the
+ * block is stored — the device forms leave it for itd_stream_status, the host forms return ITD_ERR_NONFINITE (outputs filled in)
+ * from the first emitting call on, until itd_stream_reset. */
 typedef struct itd_stream itd_stream;   /* opaque; not thread-safe */
 #define ITD_STREAM_CUBIC 0
 #define ITD_STREAM_LINEAR 1
@@ -672,7 +678,7 @@ int itd_stream_flush_f64(itd_stream *s, double *baseline_dev, int64_t baseline_s
 /* host forms: contiguous [channels][block] arrays; rot_host optional */
 int itd_stream_push_host_f64(itd_stream *s, const double *block_host, double *baseline_host, double *rot_host, int32_t *emitted);
 int itd_stream_flush_host_f64(itd_stream *s, double *baseline_host, double *rot_host, int32_t *emitted);
-/* synchronises the device; *status = 0, or 2 if some window since create / reset held a NaN */
+/* synchronises the device; *status = 0, or 2 if some block of some channel pushed since create / reset held a NaN */
 int itd_stream_status(itd_stream *s, int32_t *status);
 
 /* ---- the levels stream: the full multi-level ITD block by block -----------------------------------------------------------

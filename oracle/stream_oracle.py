@@ -33,7 +33,8 @@ Cubic operator (kind "cubic", itd_baseline_extract_fast with externally chosen k
               margin extrema either side of the emitted part (:34 is margin = 1), and two more behind it: the operator never
               computes the value of its second-to-last knot (K[idx-1] = 0, itd_fourier_decomposition.py:61: range(1, idx-1)),
               so that knot is kept outside the emitted part
-    fewer than 4 selected knots: the block is emitted unchanged (itd.cpp:170-172 "break early")
+    fewer than 4 selected knots: the block is emitted unchanged (itd.cpp:170-172 "break early"); so is every block whose
+              knot-giving window (its own; channel 0's under shared_knots) holds a NaN
     baseline = itd_baseline_extract_fast(window, sel, len(sel) - 1)[emitted part] — the operator pins the first and the last
               knot value to the data there (:83 = itd.cpp:35)
 
@@ -68,33 +69,42 @@ def select_knots(knots, lo, hi, margin):
     return knots[max(a - margin, 0): min(b + margin + 2, m)]
 
 
-def cubic_window(extract_fast, extrema_cpp, W, lo, hi, margin, knots=None):
-    """Baseline of W[lo:hi].  `knots`: retained extrema of another channel's window (itd.cpp:40-44), else W's own."""
-    if knots is None:
-        e, m = extrema_cpp(W)
-        knots = np.asarray(e[:m], dtype=np.int64)
-    sel = select_knots(knots, lo, hi, margin)
-    if len(sel) < 4:
-        return np.array(W[lo:hi], dtype=np.float64)
-    base = extract_fast(W, np.ascontiguousarray(sel, dtype=np.int64), len(sel) - 1)
-    return np.asarray(base)[lo:hi].copy()
+MIN_KNOTS = 4           # fewer selected knots: the block is emitted unchanged (itd.cpp:170-172)
+
+
+def window_knots(extrema_cpp, W):
+    """The knots a window gives: itd.cpp:161-168's predicate over it; none where the window holds a NaN — nothing is built on such
+    a window, so every block that takes its knots from it is emitted unchanged (the predicate has no NaN rule to follow)."""
+    if np.isnan(W).any():
+        return np.zeros(0, dtype=np.int64)
+    e, m = extrema_cpp(W)
+    return np.asarray(e[:m], dtype=np.int64)
+
+
+def selections(extrema_cpp, x2, L, margin, shared_knots=False):
+    """(channel, block, window W, lo, hi, the knot-giving window's knots, the selected knots) of every channel and block of
+    x2[C, n_blocks * L].  `shared_knots`: the retained extrema of channel 0's window serve every channel (itd.cpp:40-44)."""
+    C, n = x2.shape
+    assert n % L == 0 and n >= L
+    for j, (w0, wl, lo, hi) in enumerate(windows(n // L, L)):
+        knots = None
+        for c in range(C):
+            W = np.ascontiguousarray(x2[c, w0:w0 + wl])
+            if c == 0 or not shared_knots:
+                knots = window_knots(extrema_cpp, W)
+            yield c, j, W, lo, hi, knots, select_knots(knots, lo, hi, margin)
 
 
 def blockwise_cubic(extract_fast, extrema_cpp, x, L, margin, shared_knots=False):
     """x[C, n_blocks * L] (or one channel [n]) -> baseline of the same shape, block by block."""
     x2 = np.atleast_2d(np.asarray(x, dtype=np.float64))
-    C, n = x2.shape
-    assert n % L == 0 and n >= L
     out = np.empty_like(x2)
-    for j, (w0, wl, lo, hi) in enumerate(windows(n // L, L)):
-        knots = None
-        for c in range(C):
-            W = np.ascontiguousarray(x2[c, w0:w0 + wl])
-            if shared_knots and c == 0:
-                e, m = extrema_cpp(W)
-                knots = np.asarray(e[:m], dtype=np.int64)
-            out[c, j * L:(j + 1) * L] = cubic_window(extract_fast, extrema_cpp, W, lo, hi, margin,
-                                                     knots if shared_knots else None)
+    for c, j, W, lo, hi, _, sel in selections(extrema_cpp, x2, L, margin, shared_knots):
+        if len(sel) < MIN_KNOTS:
+            out[c, j * L:(j + 1) * L] = W[lo:hi]
+        else:
+            base = extract_fast(W, np.ascontiguousarray(sel, dtype=np.int64), len(sel) - 1)
+            out[c, j * L:(j + 1) * L] = np.asarray(base)[lo:hi]
     return out if np.ndim(x) == 2 else out[0]
 
 

@@ -25,7 +25,8 @@
 //                   loop, :107-111, is "number of knots e[1..idx-1] at or before the sample"), then the spline formula
 //                   (:113-120) with t*t*t where the reference has numpy's float64 ** 3 (libm pow; numba multiplies).
 // The association of the sweeps differs from the reference's serial loops, so float parity is a tolerance, not bit equality
-// (tests: 1e-9 of the signal's scale, measured ~4e-16); knot indices are exact.
+// (tests: 1e-9 of the signal's scale, measured ~4e-16; against exact splines four times the serial fp64 loops' error + 64 eps S:
+// tests/test_gpu_spline_exact.py, and tests/test_gpu_stream_exact.py for the block-wise stream's sub-lists); knot indices are exact.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -125,7 +125,7 @@ int stream_push(itd_stream *s, const double *blk, int64_t in_stride, double *bas
                 int64_t rot_stride, int32_t *emitted, hipStream_t st)
 {
     const int64_t L = s->L;
-    k_stream_store<<<dim3((unsigned)((L + 255) / 256), s->C), 256, 0, st>>>(blk, in_stride, s->ring, 5 * L, L, (int)(s->pushed % 3));
+    k_stream_store<<<dim3((unsigned)((L + 255) / 256), s->C), 256, 0, st>>>(blk, in_stride, s->ring, 5 * L, L, (int)(s->pushed % 3), s->d_status);
     ++s->pushed;
     if (emitted) *emitted = s->pushed >= 2 ? 1 : 0;
     if (s->pushed < 2) { HIP_TRY(s->eng, hipGetLastError()); return ITD_OK; }
@@ -352,7 +352,7 @@ int levels_step_seq(itd_stream *s, const LevelsArgs &a, hipStream_t st)
     const int64_t L = s->L, ring_stride = (int64_t)(s->M + 1) * 5 * L;
     const int C = s->C;
     if (a.in)
-        k_stream_store<<<dim3((unsigned)((L + 255) / 256), C), 256, 0, st>>>(a.in, a.in_stride, s->ring, ring_stride, L, (int)(a.t % 3));
+        k_stream_store<<<dim3((unsigned)((L + 255) / 256), C), 256, 0, st>>>(a.in, a.in_stride, s->ring, ring_stride, L, (int)(a.t % 3), nullptr);
     LevelsRoute r;
     r.a = a;
     r.rw = s->scr;

@@ -17,14 +17,17 @@
 
 namespace itd {
 
-// one incoming block of every channel into its slot (and the slot's mirror)
+// one incoming block of every channel into its slot (and the slot's mirror).  status (optional): |= 2 when a stored sample is a
+// NaN — the one place that sees every sample of EVERY channel: under shared knots only channel 0's window is scanned for knots,
+// so a NaN in another channel would otherwise go unreported.  (The levels stream keeps its own NaN rule and passes nullptr.)
 __global__ void k_stream_store(const double *__restrict__ blk, int64_t in_stride, double *__restrict__ ring, int64_t ring_stride,
-                               int64_t L, int slot)
+                               int64_t L, int slot, int32_t *__restrict__ status)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= L) return;
     const int c = blockIdx.y;
     const double v = blk[(int64_t)c * in_stride + i];
+    if (status && v != v) atomicOr(status, 2);
     double *r = ring + (int64_t)c * ring_stride;
     r[(int64_t)slot * L + i] = v;
     if (slot < 2) r[(int64_t)(slot + 3) * L + i] = v;

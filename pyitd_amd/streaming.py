@@ -17,6 +17,10 @@ and DESIGN.md section 7; the GPU tests hold these classes to an independent CPU 
 kind "cubic": itd_baseline_extract_fast (itd_fourier_decomposition.py:49-122) on the extrema from `margin` in front of the
 emitted block to margin + 2 behind it (the recipe's literal choice is margin 1); blocks with fewer than 4 such extrema are
 returned unchanged (itd.cpp:170-172).  `shared_knots`: channel 0's extrema serve every channel (itd.cpp:40-44).
+A NaN: a block whose knot-giving window (the channel's own; channel 0's under `shared_knots`) holds one is returned unchanged
+with rotation 0 — nothing is built on such a window; a channel that holds a NaN while channel 0's window is finite gets a
+spline through the NaN (unspecified samples).  A NaN in ANY channel sets status() to 2 until reset(), and push / flush raise
+ITDError (ITD_ERR_NONFINITE) from the first emitting call on.
 kind "linear": itd_baseline_extract on the window — away from a couple of knots at the window's ends bit-identical to the
 whole-signal operator, so a stream whose blocks hold a few knots each reproduces the whole-signal rows exactly.
 """
@@ -76,7 +80,7 @@ class Stream:
         self._check(self._L.itd_stream_reset(self._h))
 
     def status(self):
-        """Synchronises the device; 0, or 2 if some window since the last reset held a NaN."""
+        """Synchronises the device; 0, or 2 if some block of some channel pushed since the last reset held a NaN."""
         v = ctypes.c_int32(0)
         self._check(self._L.itd_stream_status(self._h, ctypes.byref(v)))
         return v.value

@@ -4,7 +4,9 @@
   * the pinned CPU oracle (oracle/stream_oracle.py over oracle/cpu_oracle.py) on seeded signals,
   * the whole-signal operator (tier-1: the stream IS the whole-signal result wherever blocks hold a few knots).
 Tier-1 (piecewise-affine, ITD.py:79-121): bit-exact.  Cubic (itd_fourier_decomposition.py:49-122): 1e-9 of the signal's scale
-(t**3 by multiplication vs libm pow, the sweeps as scans), knot selection decisions exact."""
+(t**3 by multiplication vs libm pow, the sweeps as scans), knot selection decisions exact.  The cubic stream, its knot selection and
+its NaN windows are held to exact splines, at a bound of a few ulps and on layouts aimed at every decision, in
+tests/test_gpu_stream_exact.py."""
 import os
 
 import numpy as np
