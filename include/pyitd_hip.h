@@ -590,6 +590,22 @@ int itd_baseline_extract_cubic_batch_f64(itd_engine *e, const double *x_dev, int
                                          const int32_t *extrema_dev, int64_t extrema_stride, int64_t idx, double *baseline_dev,
                                          int64_t baseline_stride, int32_t *info_dev, void *stream);
 
+/* ---- instantaneous amplitude / phase / frequency of many rows: asynchronous on `stream`, no host synchronisation, no host read,
+ * graph-capturable.  The definitions and the arithmetic of itd_instantaneous_f64 (on a row without a NaN the results are bit for bit
+ * that call's), for float64 or float32 rows — a float32 sample is widened exactly — as they come from itd_decompose_* and
+ * itd_decompose_rows32_*.  Row r starts at rows_dev + r * row_stride; its outputs at r * out_stride ELEMENTS of the output type
+ * behind amp_dev / phase_dev / freq_dev: float64 (out_f32 = 0) or float32 (out_f32 = 1: each element the float64 one rounded once
+ * at its store, as itd_decompose_rows32_* rounds).  Any output may be NULL, not all three.  3 <= n < 2^31 - 65537 as for the other
+ * batched entries; rows >= 1, above 65535 rows in chunks; both strides >= n when rows > 1; the outputs must not overlap the input.
+ * info_dev (optional) [rows]: the row's zero-crossing count; -1 - count if the row holds a NaN — its outputs are then
+ * unspecified, but nothing outside its n elements of each output is written.  Nothing outside the first n samples of a row is read.
+ * The workspace (40 bytes per 512 samples of min(rows, 65535) rows) is the engine's, grown on demand: the capture rule of the batched
+ * single-level operators above holds — capture a call only after one of its size has run, capture again after a larger one. */
+int itd_instantaneous_batch_f64(itd_engine *e, const double *rows_dev, int64_t n, int32_t rows, int64_t row_stride, void *amp_dev,
+                                void *phase_dev, void *freq_dev, int64_t out_stride, int32_t out_f32, int32_t *info_dev, void *stream);
+int itd_instantaneous_batch_f32(itd_engine *e, const float *rows_dev, int64_t n, int32_t rows, int64_t row_stride, void *amp_dev,
+                                void *phase_dev, void *freq_dev, int64_t out_stride, int32_t out_f32, int32_t *info_dev, void *stream);
+
 /* ---- the ITD-Fourier cascade (itd_fourier_decomposition.py:131-303) and its FFT ---------------------------------------------
  * itd_debug_fft_f64 (tests): `batch` transforms of n complex float64 points (interleaved re, im; transform b at 2 b n doubles) from
  *   in_dev into out_dev (may be in_dev): inverse 0 = numpy.fft.fft, 1 = numpy.fft.ifft (scaled by 1 / n).  n <= 8192: one

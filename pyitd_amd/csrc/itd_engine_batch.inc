@@ -5,6 +5,7 @@
 //       itd_detect_batch_f64                  ITD.py:33-76 / :87-98 / numba_accelerated_itd.py:17-59 / itd.cpp:161-168
 //       itd_baseline_extract_cubic_batch_f64  itd_fourier_decomposition.py:49-122 with one retained knot list for every
 //                                             channel (itd.cpp:40-44) or one list / the detected knots per signal
+//       itd_instantaneous_batch_f64 / _f32    amplitude, phase and frequency of every row (itd_tfe_batch.hpp)
 //   * block-wise operation (itd.cpp:31-38), itd_stream_*: a device-resident mirrored ring per channel (itd_stream.hpp), the
 //     window's knots, their selection and the operator all on the device — a push enqueues launches and returns; the host form
 //     synchronises once per push for its copies.  The recipe: include/pyitd_hip.h, DESIGN.md section 7.
@@ -50,6 +51,48 @@ int extract_batch(itd_engine *e, const double *x, int64_t n, int32_t batch, int6
         if (rc) return rc;
         extract_level0<double>(w, xc, x_stride, n, nb, rot + (int64_t)b0 * rot_stride, rot_stride, base + (int64_t)b0 * base_stride, base_stride, st);
         if (info || status) k_info_from_states<<<(nb + 255) / 256, 256, 0, st>>>(w.state, nb, info ? info + b0 : nullptr, status);
+    }
+    HIP_TRY(e, hipGetLastError());
+    return ITD_OK;
+}
+
+// instantaneous amplitude / phase / frequency of every row (itd_tfe_batch.hpp): records, carry, apply per chunk of rows — three
+// launches behind one another on `st`, nothing read on the host
+template <typename Tin, typename Tout>
+void inst_chunk(const Tin *x, int64_t x_stride, int64_t n, int64_t tiles, int nb, InstRec *rec, double *Ahead, double *Atail,
+                void *amp, void *phase, void *freq, int64_t out_stride, int32_t *info, hipStream_t st)
+{
+    const dim3 grid((unsigned)tiles, (unsigned)nb);
+    k_inst_records<Tin><<<grid, kWave, 0, st>>>(x, x_stride, n, tiles, rec);
+    if (tiles <= kInstCarrySmall) k_inst_carry<64><<<nb, 64, 0, st>>>(rec, tiles, Ahead, Atail, info);
+    else k_inst_carry<kInstCarryThreads><<<nb, kInstCarryThreads, 0, st>>>(rec, tiles, Ahead, Atail, info);
+    k_inst_apply<Tin, Tout><<<grid, kWave, 0, st>>>(x, x_stride, n, tiles, Ahead, Atail, (Tout *)amp, (Tout *)phase, (Tout *)freq, out_stride);
+}
+
+template <typename Tin>
+int inst_batch(itd_engine *e, const Tin *x, int64_t n, int32_t rows, int64_t x_stride, void *amp, void *phase, void *freq,
+               int64_t out_stride, int32_t out_f32, int32_t *info, void *stream)
+{
+    if (!e || !x || (!amp && !phase && !freq)) return ITD_ERR_INVALID_ARG;
+    if (n < 3 || n >= (int64_t)INT32_MAX - 65536 || rows < 1 || (out_f32 != 0 && out_f32 != 1)) return ITD_ERR_INVALID_ARG;
+    if (rows > 1 && (x_stride < n || out_stride < n)) return ITD_ERR_INVALID_ARG;
+    DevGuard g(e->device);
+    hipStream_t st = stream_of(e, stream);
+    const int64_t tiles = (n + kTfeTile - 1) / kTfeTile;
+    const int chunk = std::min<int32_t>(rows, kMaxGridY);
+    const size_t per = (size_t)chunk * (size_t)tiles;
+    const int rc = grow(e, e->d_ib, per * (sizeof(InstRec) + 2 * sizeof(double)));
+    if (rc) return rc;
+    InstRec *rec = (InstRec *)e->d_ib;
+    double *Ahead = (double *)(rec + per), *Atail = Ahead + per;
+    const size_t osz = out_f32 ? sizeof(float) : sizeof(double);
+    for (int b0 = 0; b0 < rows; b0 += chunk) {
+        const int nb = std::min(chunk, rows - b0);
+        const Tin *xc = x + (int64_t)b0 * x_stride;
+        const size_t off = (size_t)b0 * (size_t)out_stride * osz;
+        void *a = amp ? (char *)amp + off : nullptr, *p = phase ? (char *)phase + off : nullptr, *f = freq ? (char *)freq + off : nullptr;
+        if (out_f32) inst_chunk<Tin, float>(xc, x_stride, n, tiles, nb, rec, Ahead, Atail, a, p, f, out_stride, info ? info + b0 : nullptr, st);
+        else inst_chunk<Tin, double>(xc, x_stride, n, tiles, nb, rec, Ahead, Atail, a, p, f, out_stride, info ? info + b0 : nullptr, st);
     }
     HIP_TRY(e, hipGetLastError());
     return ITD_OK;
@@ -192,6 +235,17 @@ int itd_baseline_extract_cubic_batch_f64(itd_engine *e, const double *x_dev, int
     if (info_dev) k_info_from_jobs<<<(batch + 255) / 256, 256, 0, st>>>(jobs, n_jobs == batch ? 1 : 0, batch, info_dev);
     HIP_TRY(e, hipGetLastError());
     return ITD_OK;
+}
+
+int itd_instantaneous_batch_f64(itd_engine *e, const double *rows_dev, int64_t n, int32_t rows, int64_t row_stride, void *amp_dev,
+                                void *phase_dev, void *freq_dev, int64_t out_stride, int32_t out_f32, int32_t *info_dev, void *stream)
+{
+    return inst_batch<double>(e, rows_dev, n, rows, row_stride, amp_dev, phase_dev, freq_dev, out_stride, out_f32, info_dev, stream);
+}
+int itd_instantaneous_batch_f32(itd_engine *e, const float *rows_dev, int64_t n, int32_t rows, int64_t row_stride, void *amp_dev,
+                                void *phase_dev, void *freq_dev, int64_t out_stride, int32_t out_f32, int32_t *info_dev, void *stream)
+{
+    return inst_batch<float>(e, rows_dev, n, rows, row_stride, amp_dev, phase_dev, freq_dev, out_stride, out_f32, info_dev, stream);
 }
 
 int itd_stream_create(itd_stream **out, int device_id, int64_t block, int32_t channels, int32_t kind, int32_t margin, int32_t shared_knots)

@@ -454,6 +454,15 @@ class Engine:
         self._check(self._L.itd_baseline_extract_cubic_batch_f64(self._h, x_ptr, n, batch, x_stride, extrema_ptr, extrema_stride,
                                                                  idx, base_ptr, base_stride, info_ptr, stream))
 
+    def instantaneous_batch_dev(self, rows_ptr, dtype, n, rows, row_stride, amp_ptr, phase_ptr, freq_ptr, out_stride, out_f32=False,
+                                info_ptr=None, stream=None):
+        """Instantaneous amplitude / phase / frequency of every row (float32 or float64 by `dtype`) into the outputs that are not
+        None, float32 when out_f32; info int32[rows]: zero-crossing count, -1 - count if the row holds a NaN.  Pointers in, nothing
+        copied, nothing awaited."""
+        fn = self._L.itd_instantaneous_batch_f32 if np.dtype(dtype) == np.float32 else self._L.itd_instantaneous_batch_f64
+        self._check(fn(self._h, rows_ptr, n, rows, row_stride, amp_ptr, phase_ptr, freq_ptr, out_stride, 1 if out_f32 else 0,
+                       info_ptr, stream))
+
     # ---- the FITPACK flavour of the baseline and its 2-D consumers (itd_baseline_extract_spline_*, itd_crossways_*) --------
     def spline_extract_host(self, x, min_extrema=10, want_rotation=False, want_baseline_knots=False):
         """x[B, n] float64 -> (baseline[B, n], rotation[B, n] or None, knots[B]) (numba_accelerated_itd.py:182-211);
