@@ -606,6 +606,45 @@ int itd_instantaneous_batch_f64(itd_engine *e, const double *rows_dev, int64_t n
 int itd_instantaneous_batch_f32(itd_engine *e, const float *rows_dev, int64_t n, int32_t rows, int64_t row_stride, void *amp_dev,
                                 void *phase_dev, void *freq_dev, int64_t out_stride, int32_t out_f32, int32_t *info_dev, void *stream);
 
+/* ---- single-wave analysis of many rows (README.md:18-21, 47-53: "feature-based filtering" on the half waves): asynchronous on
+ * `stream`, no host synchronisation, no host read, graph-capturable.  A row's crossing indices c_0 < ... < c_{m-1} are those of
+ * itd_instantaneous_* (1 <= i <= n - 2 with a strict sign change x[i] -> x[i+1]); half wave k (0 <= k <= m) holds the samples
+ * start_k .. end_k with start_0 = 0, start_k = c_{k-1} + 1, end_k = c_k, end_m = n - 1; length_k = end_k - start_k + 1;
+ * A_k = max |x| over it (what itd_instantaneous_batch_* delivers per sample); peak_k = the smallest index of the half wave with
+ * |x| == A_k; value_k = x[peak_k], the signed extremum.  All decisions are exact on the sample as float64 (a float32 sample is
+ * widened exactly).  count = m + 1 <= n - 1.  Rows, strides, n, chunking and info_dev as for itd_instantaneous_batch_*: row r at
+ * rows_dev + r * row_stride; 3 <= n < 2^31 - 65537; rows >= 1, above 65535 rows in chunks; row_stride >= n when rows > 1;
+ * info_dev (optional) [rows]: the row's zero-crossing count, -1 - count if the row holds a NaN — its table entries and its
+ * filtered row are then unspecified, but nothing outside that row's own slots is written.  Nothing outside the first n samples of
+ * a row is read.
+ * itd_waves_batch_f64 / _f32: the table.  Row r's entries sit at r * wave_stride elements behind start_dev / length_dev / peak_dev
+ *   (int32) and value_dev (double, also for float32 rows: the widened sample); wave_stride >= cap when rows > 1.  The first
+ *   min(count, cap) entries of a slot are written, in the half waves' order; nothing at or beyond entry cap of a slot is touched, and
+ *   the entries from count on are left as they were.  count_dev (optional) [rows]: always the true count, so count > cap shows an
+ *   overflow.  Any table pointer may be NULL; if all four are, cap and wave_stride are ignored and the call only counts (no table
+ *   pass runs); count_dev or at least one table must be given.  cap >= 1 with a table.
+ * itd_wave_filter_batch_f64 / _f32: out[j] = x[j] if the half wave k of sample j has amp_lo <= A_k && A_k <= amp_hi &&
+ *   len_lo <= (double)length_k && (double)length_k <= len_hi as IEEE comparisons (a NaN bound keeps nothing), else +0.0.  The four
+ *   float64 bounds (amp_lo, amp_hi, len_lo, len_hi) of row r are read from bounds_dev + r * bounds_stride: bounds_stride = 0 is
+ *   one set for every row, bounds_stride >= 4 one set per row (as extrema_stride of the cubic batch); they are device memory, read
+ *   when the call runs — a captured call filters with whatever they hold at its replay.  Row r's output at r * out_stride ELEMENTS
+ *   of the output type behind out_dev: float64 (out_f32 = 0) or float32 (out_f32 = 1: the kept sample rounded once at its store);
+ *   out_stride >= n when rows > 1; out_dev must not overlap the input.  Bounds (0, +inf, 0, +inf) make a float64 output a
+ *   bit-exact copy of the row.
+ * The workspace (80 bytes per 512 samples of min(rows, 65535) rows: a 40-byte tile record, a 24-byte forward and a 16-byte
+ * backward carry) is the engine's own, apart from the instantaneous step's, grown on demand: the capture rule of the batched
+ * single-level operators above holds — capture a call only after one of its size has run, capture again after a larger one. */
+int itd_waves_batch_f64(itd_engine *e, const double *rows_dev, int64_t n, int32_t rows, int64_t row_stride, int32_t *start_dev,
+                        int32_t *length_dev, int32_t *peak_dev, double *value_dev, int64_t wave_stride, int32_t cap, int32_t *count_dev,
+                        int32_t *info_dev, void *stream);
+int itd_waves_batch_f32(itd_engine *e, const float *rows_dev, int64_t n, int32_t rows, int64_t row_stride, int32_t *start_dev,
+                        int32_t *length_dev, int32_t *peak_dev, double *value_dev, int64_t wave_stride, int32_t cap, int32_t *count_dev,
+                        int32_t *info_dev, void *stream);
+int itd_wave_filter_batch_f64(itd_engine *e, const double *rows_dev, int64_t n, int32_t rows, int64_t row_stride, const double *bounds_dev,
+                              int64_t bounds_stride, void *out_dev, int64_t out_stride, int32_t out_f32, int32_t *info_dev, void *stream);
+int itd_wave_filter_batch_f32(itd_engine *e, const float *rows_dev, int64_t n, int32_t rows, int64_t row_stride, const double *bounds_dev,
+                              int64_t bounds_stride, void *out_dev, int64_t out_stride, int32_t out_f32, int32_t *info_dev, void *stream);
+
 /* ---- the ITD-Fourier cascade (itd_fourier_decomposition.py:131-303) and its FFT ---------------------------------------------
  * itd_debug_fft_f64 (tests): `batch` transforms of n complex float64 points (interleaved re, im; transform b at 2 b n doubles) from
  *   in_dev into out_dev (may be in_dev): inverse 0 = numpy.fft.fft, 1 = numpy.fft.ifft (scaled by 1 / n).  n <= 8192: one

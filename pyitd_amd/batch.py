@@ -1,11 +1,14 @@
 """Row-wise / channel-wise forms of the single-level operators (numpy in -> numpy out) over the asynchronous batched entry
 points of the C ABI (itd_baseline_extract_batch_f64, itd_detect_batch_f64, itd_baseline_extract_cubic_batch_f64), and the
-instantaneous amplitude / phase / frequency of many rows (itd_instantaneous_batch_*; numpy or torch CUDA tensors).
+instantaneous amplitude / phase / frequency of many rows (itd_instantaneous_batch_*; numpy or torch CUDA tensors) and their
+single-wave analysis: the table of half waves and the feature filter (itd_waves_batch_*, itd_wave_filter_batch_*).
 
 The reference applies its operators row by row under numba.prange (siftED2D.ipynb cell 1) and re-uses retained extrema along
 channels (itd.cpp:40-44); here a whole batch is one launch sequence and no knot count crosses PCIe in between.  Device
 memory comes from the C ABI's own allocator (engine.DeviceBuffer): no torch needed.
 """
+from collections import namedtuple
+
 import numpy
 
 from ._lib import ITDError
@@ -209,4 +212,185 @@ def instantaneous_batch(rows, device=0, out_dtype=None, want=_INSTANTANEOUS):
         return tuple(bufs[w].download(numpy.empty((R, n), odt)).reshape(shape) for w in want)
     finally:
         for b in list(bufs.values()) + [d_x, d_info]:
+            b.free()
+
+
+# ---- single-wave analysis: the table of half waves and the feature filter (itd_waves_batch_*, itd_wave_filter_batch_*) -------
+Waves = namedtuple("Waves", "count start length peak value")
+
+
+def _accept_rows(rows, what):
+    """instantaneous_batch's acceptance of rows[..., n]: (torch?, the array or tensor, input dtype, shape, n, row count)."""
+    torch_in = _is_torch(rows)
+    a = rows if torch_in else numpy.asarray(rows)
+    idt = numpy.dtype(_np_dtype(a.dtype))
+    if idt not in (numpy.dtype(numpy.float32), numpy.dtype(numpy.float64)):
+        raise ValueError("rows must be float32 or float64, got %s" % (a.dtype,))
+    shape = tuple(a.shape)
+    if len(shape) < 2:
+        raise ValueError("expected rows[..., n] with at least one leading axis, got shape %s" % (shape,))
+    if shape[-1] < 3:
+        raise ValueError("%s needs at least 3 samples" % what)
+    R = int(numpy.prod(shape[:-1], dtype=numpy.int64))
+    if R < 1:
+        raise ValueError("no rows in an array of shape %s" % (shape,))
+    return torch_in, a, idt, shape, shape[-1], R
+
+
+def _tensor_stride(a, shape):
+    if not a.is_cuda:
+        raise ValueError("expected a CUDA tensor")
+    stride = _row_stride(shape, tuple(a.stride()))
+    if stride is None:
+        raise ValueError("the leading axes of a tensor with strides %s do not collapse to one row stride" % (tuple(a.stride()),))
+    return stride
+
+
+def _refuse_nan(info):
+    bad = numpy.flatnonzero(info < 0)
+    if bad.size:
+        raise ITDError(ITD_ERR_NONFINITE, "NaN in rows %s%s" % (bad[:16].tolist(), " ..." if bad.size > 16 else ""))
+
+
+def _refuse_overflow(count, cap):
+    over = numpy.flatnonzero(count > cap)
+    if over.size:
+        raise ValueError("cap = %d is less than the half waves of rows %s%s (up to %d)"
+                         % (cap, over[:16].tolist(), " ..." if over.size > 16 else "", int(count.max())))
+
+
+def single_waves(rows, cap=None, device=0):
+    """The half waves of every row of rows[..., n] — the runs of samples between strict sign changes, the waves the
+    instantaneous amplitude is the maximum of — as a table: Waves(count[...], start[..., cap], length[..., cap], peak[..., cap],
+    value[..., cap]).  Half wave k of a row begins at sample start, lasts length samples, attains its largest magnitude first at
+    sample peak and has value = rows[..., peak] there (the signed extremum: its sign is the half wave's polarity).  Entries at or
+    beyond a row's count are -1 (start, length, peak; int32) and nan (value; float64).
+
+    rows: float64 or float32, a numpy array or a torch CUDA tensor (used in place; its leading axes must collapse to one row
+    stride, its last axis must be dense; tensors come back on its device).  cap: the tables' last axis; None counts first and takes
+    the largest count; an explicit cap makes one call and raises ValueError naming the rows with more half waves.  Raises
+    ITDError (non-finite) naming the rows that hold a NaN."""
+    if cap is not None:
+        if int(cap) != cap or int(cap) < 1:
+            raise ValueError("cap must be a positive integer or None, got %r" % (cap,))
+        cap = int(cap)
+    torch_in, a, idt, shape, n, R = _accept_rows(rows, "single-wave analysis")
+    lead = shape[:-1]
+    if torch_in:
+        import torch
+        stride = _tensor_stride(a, shape)
+        dev = a.device.index
+        count = torch.empty(R, dtype=torch.int32, device=a.device)
+        info = torch.empty(R, dtype=torch.int32, device=a.device)
+        eng = _engine_for(3, dev)
+        torch.cuda.synchronize(a.device)    # the engine runs on its own stream
+        if cap is None:
+            eng.waves_batch_dev(a.data_ptr(), idt, n, R, stride, None, None, None, None, 0, 0, count.data_ptr(), info.data_ptr())
+            torch.cuda.synchronize(a.device)
+            _refuse_nan(info.cpu().numpy())
+            cap = int(count.max())
+        ints = [torch.full((R, cap), -1, dtype=torch.int32, device=a.device) for _ in range(3)]
+        value = torch.full((R, cap), float("nan"), dtype=torch.float64, device=a.device)
+        torch.cuda.synchronize(a.device)
+        eng.waves_batch_dev(a.data_ptr(), idt, n, R, stride, *[t.data_ptr() for t in ints], value.data_ptr(), cap, cap,
+                            count.data_ptr(), info.data_ptr())
+        torch.cuda.synchronize(a.device)
+        _refuse_nan(info.cpu().numpy())
+        _refuse_overflow(count.cpu().numpy(), cap)
+        return Waves(count.reshape(lead), *[t.reshape(lead + (cap,)) for t in ints], value.reshape(lead + (cap,)))
+    a = numpy.ascontiguousarray(a).reshape(R, n)
+    dev = int(device)
+    bufs = [DeviceBuffer(a.nbytes, dev), DeviceBuffer(4 * R, dev), DeviceBuffer(4 * R, dev)]
+    d_x, d_count, d_info = bufs
+    try:
+        d_x.upload(a)
+        eng = _engine_for(3, dev)
+        if cap is None:
+            eng.waves_batch_dev(d_x.ptr, idt, n, R, n, None, None, None, None, 0, 0, d_count.ptr, d_info.ptr)
+            _refuse_nan(d_info.download(numpy.empty(R, numpy.int32)))       # itd_dev_copy synchronises
+            cap = int(d_count.download(numpy.empty(R, numpy.int32)).max())
+        fill_i, fill_v = numpy.full((R, cap), -1, numpy.int32), numpy.full((R, cap), numpy.nan)
+        tabs = [DeviceBuffer(fill_i.nbytes, dev) for _ in range(3)] + [DeviceBuffer(fill_v.nbytes, dev)]
+        bufs += tabs
+        for b, f in zip(tabs, (fill_i, fill_i, fill_i, fill_v)):
+            b.upload(f)
+        eng.waves_batch_dev(d_x.ptr, idt, n, R, n, *[b.ptr for b in tabs], cap, cap, d_count.ptr, d_info.ptr)
+        _refuse_nan(d_info.download(numpy.empty(R, numpy.int32)))
+        count = d_count.download(numpy.empty(R, numpy.int32))
+        _refuse_overflow(count, cap)
+        outs = [b.download(numpy.empty_like(f)).reshape(lead + (cap,)) for b, f in zip(tabs, (fill_i, fill_i, fill_i, fill_v))]
+        return Waves(count.reshape(lead), *outs)
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def _wave_bounds(amplitude, length, lead):
+    """The filter's bounds as float64 [4] (one set for every row) or [R, 4]; refuses NaN bounds and lo > hi."""
+    cols = []
+    for name, pair in (("amplitude", amplitude), ("length", length)):
+        try:
+            lo, hi = pair
+        except (TypeError, ValueError):
+            raise ValueError("%s: a pair (lo, hi), got %r" % (name, pair))
+        lo, hi = numpy.asarray(lo, dtype=numpy.float64), numpy.asarray(hi, dtype=numpy.float64)
+        if numpy.isnan(lo).any() or numpy.isnan(hi).any():
+            raise ValueError("%s: a NaN bound" % name)
+        try:
+            both = numpy.broadcast_arrays(lo, hi)
+        except ValueError:
+            raise ValueError("%s: lo %s and hi %s do not broadcast" % (name, lo.shape, hi.shape))
+        if (both[0] > both[1]).any():
+            raise ValueError("%s: lo > hi" % name)
+        cols += [lo, hi]
+    if all(c.ndim == 0 for c in cols):
+        return numpy.array([float(c) for c in cols])
+    try:
+        cols = [numpy.broadcast_to(c, lead) for c in cols]
+    except ValueError:
+        raise ValueError("the bounds (shapes %s) do not broadcast to the leading axes %s of rows" % ([c.shape for c in cols], lead))
+    return numpy.ascontiguousarray(numpy.stack([c.reshape(-1) for c in cols], axis=1))
+
+
+def wave_filter(rows, amplitude=(0.0, numpy.inf), length=(0.0, numpy.inf), out_dtype=None, device=0):
+    """Feature-based filtering on single waves: every row of rows[..., n] with the samples of the half waves (single_waves) whose
+    amplitude A = |value| or whose length lies outside the closed intervals amplitude = (lo, hi), length = (lo, hi) set to +0.0,
+    all others copied.  Each bound is a scalar or an array that broadcasts to the leading axes of rows: every row — every level of
+    a decomposition, with its own time-scale — may have its own.  The default bounds copy the rows bit for bit.
+
+    rows as for single_waves; out_dtype: None / float64, or float32 (numpy or torch): each kept sample rounded once on the GPU.
+    Returns an array (tensor for a tensor) shaped like rows.  Raises ITDError (non-finite) naming the rows that hold a NaN."""
+    odt = numpy.dtype(numpy.float64 if out_dtype is None else _np_dtype(out_dtype))
+    if odt not in (numpy.dtype(numpy.float32), numpy.dtype(numpy.float64)):
+        raise ValueError("out_dtype must be float32 or float64")
+    torch_in, a, idt, shape, n, R = _accept_rows(rows, "the wave filter")
+    bounds = _wave_bounds(amplitude, length, shape[:-1])
+    bstride = 0 if bounds.ndim == 1 else 4
+    if torch_in:
+        import torch
+        stride = _tensor_stride(a, shape)
+        dev = a.device.index
+        out = torch.empty(shape, dtype=torch.float32 if odt == numpy.float32 else torch.float64, device=a.device)
+        info = torch.empty(R, dtype=torch.int32, device=a.device)
+        d_b = torch.from_numpy(bounds).to(a.device)
+        eng = _engine_for(3, dev)
+        torch.cuda.synchronize(a.device)    # the engine runs on its own stream
+        eng.wave_filter_batch_dev(a.data_ptr(), idt, n, R, stride, d_b.data_ptr(), bstride, out.data_ptr(), n, odt == numpy.float32,
+                                  info.data_ptr())
+        torch.cuda.synchronize(a.device)
+        _refuse_nan(info.cpu().numpy())
+        return out
+    a = numpy.ascontiguousarray(a).reshape(R, n)
+    dev = int(device)
+    bufs = [DeviceBuffer(a.nbytes, dev), DeviceBuffer(bounds.nbytes, dev), DeviceBuffer(R * n * odt.itemsize, dev), DeviceBuffer(4 * R, dev)]
+    d_x, d_b, d_out, d_info = bufs
+    try:
+        d_x.upload(a)
+        d_b.upload(bounds)
+        eng = _engine_for(3, dev)
+        eng.wave_filter_batch_dev(d_x.ptr, idt, n, R, n, d_b.ptr, bstride, d_out.ptr, n, odt == numpy.float32, d_info.ptr)
+        _refuse_nan(d_info.download(numpy.empty(R, numpy.int32)))           # itd_dev_copy synchronises
+        return d_out.download(numpy.empty((R, n), odt)).reshape(shape)
+    finally:
+        for b in bufs:
             b.free()

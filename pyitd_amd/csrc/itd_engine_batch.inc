@@ -6,6 +6,8 @@
 //       itd_baseline_extract_cubic_batch_f64  itd_fourier_decomposition.py:49-122 with one retained knot list for every
 //                                             channel (itd.cpp:40-44) or one list / the detected knots per signal
 //       itd_instantaneous_batch_f64 / _f32    amplitude, phase and frequency of every row (itd_tfe_batch.hpp)
+//       itd_waves_batch_f64 / _f32            the table of every row's half waves (itd_waves.hpp)
+//       itd_wave_filter_batch_f64 / _f32      every row filtered by its half waves' amplitude and length (itd_waves.hpp)
 //   * block-wise operation (itd.cpp:31-38), itd_stream_*: a device-resident mirrored ring per channel (itd_stream.hpp), the
 //     window's knots, their selection and the operator all on the device — a push enqueues launches and returns; the host form
 //     synchronises once per push for its copies.  The recipe: include/pyitd_hip.h, DESIGN.md section 7.
@@ -93,6 +95,93 @@ int inst_batch(itd_engine *e, const Tin *x, int64_t n, int32_t rows, int64_t x_s
         void *a = amp ? (char *)amp + off : nullptr, *p = phase ? (char *)phase + off : nullptr, *f = freq ? (char *)freq + off : nullptr;
         if (out_f32) inst_chunk<Tin, float>(xc, x_stride, n, tiles, nb, rec, Ahead, Atail, a, p, f, out_stride, info ? info + b0 : nullptr, st);
         else inst_chunk<Tin, double>(xc, x_stride, n, tiles, nb, rec, Ahead, Atail, a, p, f, out_stride, info ? info + b0 : nullptr, st);
+    }
+    HIP_TRY(e, hipGetLastError());
+    return ITD_OK;
+}
+
+// single-wave analysis (itd_waves.hpp): records and carry per chunk of rows, then the table and / or the filter — launches behind
+// one another on `st`, nothing read on the host.  The workspace is the engine's d_wv (not d_ib: a captured instantaneous call stays
+// valid): per tile a WaveRec, a WaveFwd and a WaveBwd.
+struct WaveWs {
+    WaveRec *rec;
+    WaveFwd *fwd;
+    WaveBwd *bwd;
+    int64_t tiles;
+    int chunk;
+};
+int wave_workspace(itd_engine *e, int64_t n, int32_t rows, WaveWs &w)
+{
+    w.tiles = (n + kTfeTile - 1) / kTfeTile;
+    w.chunk = std::min<int32_t>(rows, kMaxGridY);
+    const size_t per = (size_t)w.chunk * (size_t)w.tiles;
+    const int rc = grow(e, e->d_wv, per * (sizeof(WaveRec) + sizeof(WaveFwd) + sizeof(WaveBwd)));
+    if (rc) return rc;
+    w.rec = (WaveRec *)e->d_wv;
+    w.fwd = (WaveFwd *)(w.rec + per);
+    w.bwd = (WaveBwd *)(w.fwd + per);
+    return ITD_OK;
+}
+template <typename Tin>
+void wave_scan(const WaveWs &w, const Tin *x, int64_t x_stride, int64_t n, int nb, int32_t *count, int32_t *info, hipStream_t st)
+{
+    k_wave_records<Tin><<<dim3((unsigned)w.tiles, (unsigned)nb), kWave, 0, st>>>(x, x_stride, n, w.tiles, w.rec);
+    if (w.tiles <= kInstCarrySmall) k_wave_carry<64><<<nb, 64, 0, st>>>(w.rec, w.tiles, n, w.fwd, w.bwd, count, info);
+    else k_wave_carry<kInstCarryThreads><<<nb, kInstCarryThreads, 0, st>>>(w.rec, w.tiles, n, w.fwd, w.bwd, count, info);
+}
+
+template <typename Tin>
+int waves_batch(itd_engine *e, const Tin *x, int64_t n, int32_t rows, int64_t x_stride, int32_t *start, int32_t *length, int32_t *peak,
+                double *value, int64_t wave_stride, int32_t cap, int32_t *count, int32_t *info, void *stream)
+{
+    const bool table = start || length || peak || value;
+    if (!e || !x || (!table && !count)) return ITD_ERR_INVALID_ARG;
+    if (n < 3 || n >= (int64_t)INT32_MAX - 65536 || rows < 1) return ITD_ERR_INVALID_ARG;
+    if (rows > 1 && x_stride < n) return ITD_ERR_INVALID_ARG;
+    if (table && (cap < 1 || (rows > 1 && wave_stride < cap))) return ITD_ERR_INVALID_ARG;
+    DevGuard g(e->device);
+    hipStream_t st = stream_of(e, stream);
+    WaveWs w;
+    const int rc = wave_workspace(e, n, rows, w);
+    if (rc) return rc;
+    for (int b0 = 0; b0 < rows; b0 += w.chunk) {
+        const int nb = std::min(w.chunk, rows - b0);
+        const Tin *xc = x + (int64_t)b0 * x_stride;
+        const int64_t off = (int64_t)b0 * wave_stride;
+        wave_scan<Tin>(w, xc, x_stride, n, nb, count ? count + b0 : nullptr, info ? info + b0 : nullptr, st);
+        if (table)
+            k_wave_table<Tin><<<dim3((unsigned)w.tiles, (unsigned)nb), kWave, 0, st>>>(xc, x_stride, n, w.tiles, w.fwd, w.bwd,
+                                                                                      start ? start + off : nullptr, length ? length + off : nullptr,
+                                                                                      peak ? peak + off : nullptr, value ? value + off : nullptr,
+                                                                                      wave_stride, cap);
+    }
+    HIP_TRY(e, hipGetLastError());
+    return ITD_OK;
+}
+
+template <typename Tin>
+int wave_filter_batch(itd_engine *e, const Tin *x, int64_t n, int32_t rows, int64_t x_stride, const double *bounds, int64_t bounds_stride,
+                      void *out, int64_t out_stride, int32_t out_f32, int32_t *info, void *stream)
+{
+    if (!e || !x || !bounds || !out) return ITD_ERR_INVALID_ARG;
+    if (n < 3 || n >= (int64_t)INT32_MAX - 65536 || rows < 1 || (out_f32 != 0 && out_f32 != 1)) return ITD_ERR_INVALID_ARG;
+    if (rows > 1 && (x_stride < n || out_stride < n)) return ITD_ERR_INVALID_ARG;
+    if (bounds_stride != 0 && bounds_stride < 4) return ITD_ERR_INVALID_ARG;
+    DevGuard g(e->device);
+    hipStream_t st = stream_of(e, stream);
+    WaveWs w;
+    const int rc = wave_workspace(e, n, rows, w);
+    if (rc) return rc;
+    const size_t osz = out_f32 ? sizeof(float) : sizeof(double);
+    for (int b0 = 0; b0 < rows; b0 += w.chunk) {
+        const int nb = std::min(w.chunk, rows - b0);
+        const Tin *xc = x + (int64_t)b0 * x_stride;
+        const double *bc = bounds + (int64_t)b0 * bounds_stride;
+        void *oc = (char *)out + (size_t)b0 * (size_t)out_stride * osz;
+        const dim3 grid((unsigned)w.tiles, (unsigned)nb);
+        wave_scan<Tin>(w, xc, x_stride, n, nb, nullptr, info ? info + b0 : nullptr, st);
+        if (out_f32) k_wave_filter<Tin, float><<<grid, kWave, 0, st>>>(xc, x_stride, n, w.tiles, w.fwd, w.bwd, bc, bounds_stride, (float *)oc, out_stride);
+        else k_wave_filter<Tin, double><<<grid, kWave, 0, st>>>(xc, x_stride, n, w.tiles, w.fwd, w.bwd, bc, bounds_stride, (double *)oc, out_stride);
     }
     HIP_TRY(e, hipGetLastError());
     return ITD_OK;
@@ -246,6 +335,31 @@ int itd_instantaneous_batch_f32(itd_engine *e, const float *rows_dev, int64_t n,
                                 void *phase_dev, void *freq_dev, int64_t out_stride, int32_t out_f32, int32_t *info_dev, void *stream)
 {
     return inst_batch<float>(e, rows_dev, n, rows, row_stride, amp_dev, phase_dev, freq_dev, out_stride, out_f32, info_dev, stream);
+}
+
+int itd_waves_batch_f64(itd_engine *e, const double *rows_dev, int64_t n, int32_t rows, int64_t row_stride, int32_t *start_dev,
+                        int32_t *length_dev, int32_t *peak_dev, double *value_dev, int64_t wave_stride, int32_t cap, int32_t *count_dev,
+                        int32_t *info_dev, void *stream)
+{
+    return waves_batch<double>(e, rows_dev, n, rows, row_stride, start_dev, length_dev, peak_dev, value_dev, wave_stride, cap, count_dev,
+                               info_dev, stream);
+}
+int itd_waves_batch_f32(itd_engine *e, const float *rows_dev, int64_t n, int32_t rows, int64_t row_stride, int32_t *start_dev,
+                        int32_t *length_dev, int32_t *peak_dev, double *value_dev, int64_t wave_stride, int32_t cap, int32_t *count_dev,
+                        int32_t *info_dev, void *stream)
+{
+    return waves_batch<float>(e, rows_dev, n, rows, row_stride, start_dev, length_dev, peak_dev, value_dev, wave_stride, cap, count_dev,
+                              info_dev, stream);
+}
+int itd_wave_filter_batch_f64(itd_engine *e, const double *rows_dev, int64_t n, int32_t rows, int64_t row_stride, const double *bounds_dev,
+                              int64_t bounds_stride, void *out_dev, int64_t out_stride, int32_t out_f32, int32_t *info_dev, void *stream)
+{
+    return wave_filter_batch<double>(e, rows_dev, n, rows, row_stride, bounds_dev, bounds_stride, out_dev, out_stride, out_f32, info_dev, stream);
+}
+int itd_wave_filter_batch_f32(itd_engine *e, const float *rows_dev, int64_t n, int32_t rows, int64_t row_stride, const double *bounds_dev,
+                              int64_t bounds_stride, void *out_dev, int64_t out_stride, int32_t out_f32, int32_t *info_dev, void *stream)
+{
+    return wave_filter_batch<float>(e, rows_dev, n, rows, row_stride, bounds_dev, bounds_stride, out_dev, out_stride, out_f32, info_dev, stream);
 }
 
 int itd_stream_create(itd_stream **out, int device_id, int64_t block, int32_t channels, int32_t kind, int32_t margin, int32_t shared_knots)

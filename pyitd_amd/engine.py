@@ -463,6 +463,23 @@ class Engine:
         self._check(fn(self._h, rows_ptr, n, rows, row_stride, amp_ptr, phase_ptr, freq_ptr, out_stride, 1 if out_f32 else 0,
                        info_ptr, stream))
 
+    def waves_batch_dev(self, rows_ptr, dtype, n, rows, row_stride, start_ptr, length_ptr, peak_ptr, value_ptr, wave_stride, cap,
+                        count_ptr=None, info_ptr=None, stream=None):
+        """The half waves of every row (float32 or float64 by `dtype`): start / length / peak int32 and value float64 at
+        wave_stride entries per row, the first min(count, cap) of each written; count int32[rows] the true count; info as for
+        instantaneous_batch_dev.  All four table pointers None: counts only.  Pointers in, nothing copied, nothing awaited."""
+        fn = self._L.itd_waves_batch_f32 if np.dtype(dtype) == np.float32 else self._L.itd_waves_batch_f64
+        self._check(fn(self._h, rows_ptr, n, rows, row_stride, start_ptr, length_ptr, peak_ptr, value_ptr, wave_stride, cap, count_ptr,
+                       info_ptr, stream))
+
+    def wave_filter_batch_dev(self, rows_ptr, dtype, n, rows, row_stride, bounds_ptr, bounds_stride, out_ptr, out_stride, out_f32=False,
+                              info_ptr=None, stream=None):
+        """Every row with the samples of the half waves outside the float64 bounds (amp_lo, amp_hi, len_lo, len_hi) zeroed;
+        bounds_stride 0: one set for every row, >= 4: one per row.  Pointers in, nothing copied, nothing awaited."""
+        fn = self._L.itd_wave_filter_batch_f32 if np.dtype(dtype) == np.float32 else self._L.itd_wave_filter_batch_f64
+        self._check(fn(self._h, rows_ptr, n, rows, row_stride, bounds_ptr, bounds_stride, out_ptr, out_stride, 1 if out_f32 else 0,
+                       info_ptr, stream))
+
     # ---- the FITPACK flavour of the baseline and its 2-D consumers (itd_baseline_extract_spline_*, itd_crossways_*) --------
     def spline_extract_host(self, x, min_extrema=10, want_rotation=False, want_baseline_knots=False):
         """x[B, n] float64 -> (baseline[B, n], rotation[B, n] or None, knots[B]) (numba_accelerated_itd.py:182-211);
