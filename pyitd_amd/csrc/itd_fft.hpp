@@ -2,9 +2,10 @@
 //
 // Tier 1 (k_fft_lds): one workgroup per transform of n <= 8192 points, the whole transform in LDS (16 B per point: 128 KiB at
 // 8192, within the 160 KiB of a CU).  Stockham auto-sort stages over the factors of n: radices 8 / 4 / 2 / 3 / 5 / 7 as unrolled
-// butterflies held in registers, any other prime p as a generic O(p)-per-output stage.  A stage reads all of its inputs into
-// registers, synchronises and writes its outputs back over them: one LDS buffer, not two.
-// Twiddles come from the exact index (j * k) mod n in int64 and sincospi of the reduced ratio — never from an accumulated angle.
+// butterflies held in registers (butterfly<R>), any other prime p as a generic O(p)-per-output stage with a compensated sum.
+// A stage reads all of its inputs into registers, synchronises and writes its outputs back over them: one LDS buffer, not two.
+// Twiddles come from the exact index (j * k) mod n in int64, folded into the first octant, and sincospi of that ratio — never
+// from an accumulated angle.
 // Inputs may be real or complex, outputs complex or their real part, both strided; a workgroup may multiply its input by
 // W_m^{(x * i) mod m} first (x = blockIdx.x), the twiddle step of the four-step form.
 //
@@ -50,21 +51,86 @@ __device__ inline int next_radix(int m)
 
 __device__ inline double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __device__ inline double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
+__device__ inline double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
 
-// exp(-+ 2 pi i e / m): e reduced mod m exactly, then to (-m/2, m/2], one rounding in the ratio
+// exp(-+ 2 pi i e / m): e reduced mod m exactly, then the angle folded into the first octant in integers (t / 8m of a turn,
+// t <= m), so the one rounding in the ratio moves the angle by at most 2^-54 * pi / 4 and the quarter turns come out exact
+// (the ratio over (-1, 1] cost the radix-5 / 7 factors an ulp, which a constant row showed as 60 units in its empty outputs)
 __device__ inline double2 twiddle(int64_t e, int64_t m, int inverse)
 {
     e %= m;
     if (e < 0) e += m;
-    if (2 * e > m) e -= m;
+    int64_t t = 8 * e;
+    const bool neg_s = t > 4 * m;
+    if (neg_s) t = 8 * m - t;
+    const bool neg_c = t > 2 * m;
+    if (neg_c) t = 4 * m - t;
+    const bool swap = t > m;
+    if (swap) t = 2 * m - t;
     double s, c;
-    sincospi((double)(2 * e) / (double)m, &s, &c);
+    sincospi((double)t / (double)(4 * m), &s, &c);
+    if (swap) { const double x = s; s = c; c = x; }
+    if (neg_c) c = -c;
+    if (neg_s) s = -s;
     return make_double2(c, inverse ? s : -s);
 }
 
 __device__ inline int64_t side_off(const Side &s, int64_t t)
 {
     return (t / s.per) * s.ss + (t % s.per) * s.bs + (int64_t)blockIdx.x * s.xs;
+}
+
+// a * W_4 = a * (-+ i)
+__device__ inline double2 crot(double2 a, int inverse) { return inverse ? make_double2(-a.y, a.x) : make_double2(a.y, -a.x); }
+
+// the 4-point transform of a0 .. a3 by sums and differences alone
+__device__ inline void dft4(double2 a0, double2 a1, double2 a2, double2 a3, int inverse, double2 *X)
+{
+    const double2 t0 = cadd(a0, a2), t1 = csub(a0, a2), t2 = cadd(a1, a3), t3 = crot(csub(a1, a3), inverse);
+    X[0] = cadd(t0, t2); X[1] = cadd(t1, t3); X[2] = csub(t0, t2); X[3] = csub(t1, t3);
+}
+
+// out_k = sum_r v_r W_R^{r k}, wR[k] = W_R^k.  Equal inputs must cancel as well as they can (a constant or a pure tone puts a whole
+// row into one output; what the other outputs keep of it is their error):
+//   R = 8: the 4-point transforms of the even and of the odd inputs joined by W_8^k: sums and differences first, equal inputs cancel
+//          exactly (the plain 8-term sum left an ulp of the inputs in every output)
+//   odd R: the inputs r and R - r share a cosine and a sine; cos(2 pi / 3) is -1/2 exactly, so radix 3 cancels exactly too
+//   R = 2, 4: the plain sum (its factors are 0 and +-1: exact)
+template <int R>
+__device__ inline void butterfly(const double2 *v, const double2 *wR, int inverse, double2 *out)
+{
+    if constexpr (R == 8) {
+        double2 E[4], O[4];
+        dft4(v[0], v[2], v[4], v[6], inverse, E);
+        dft4(v[1], v[3], v[5], v[7], inverse, O);
+        O[1] = cmul(O[1], wR[1]); O[2] = crot(O[2], inverse); O[3] = cmul(O[3], wR[3]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { out[k] = cadd(E[k], O[k]); out[k + 4] = csub(E[k], O[k]); }
+    } else if constexpr (R % 2 == 1) {
+        constexpr int H = (R - 1) / 2;
+        double2 p[H], m[H];
+#pragma unroll
+        for (int r = 1; r <= H; ++r) { p[r - 1] = cadd(v[r], v[R - r]); m[r - 1] = csub(v[r], v[R - r]); }
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            double2 acc = v[0];
+#pragma unroll
+            for (int r = 1; r <= H; ++r) {
+                const double2 w = wR[(r * k) % R];
+                const double c = (R == 3 && k) ? -0.5 : w.x;
+                acc = cadd(acc, make_double2(p[r - 1].x * c - m[r - 1].y * w.y, p[r - 1].y * c + m[r - 1].x * w.y));
+            }
+            out[k] = acc;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            double2 acc = v[0];
+#pragma unroll
+            for (int r = 1; r < R; ++r) acc = cadd(acc, cmul(v[r], wR[(r * k) % R]));
+            out[k] = acc;
+        }
+    }
 }
 
 // one Stockham stage of radix R (2..8) over n points in LDS: butterfly j reads j + r n/R, writes (j / Ns) Ns R + j % Ns + k Ns
@@ -89,13 +155,7 @@ __device__ inline void stage_small(double2 *sb, int n, int Ns, int inverse)
                 v[r] = sb[j + r * nR];
                 if (r && jm) v[r] = cmul(v[r], twiddle((int64_t)r * jm * span, n, inverse));
             }
-#pragma unroll
-            for (int k = 0; k < R; ++k) {
-                double2 acc = v[0];
-#pragma unroll
-                for (int r = 1; r < R; ++r) acc = cadd(acc, cmul(v[r], wR[(r * k) % R]));
-                reg[q][k] = acc;
-            }
+            butterfly<R>(v, wR, inverse, reg[q]);
         }
     }
     __syncthreads();
@@ -111,7 +171,7 @@ __device__ inline void stage_small(double2 *sb, int n, int Ns, int inverse)
     __syncthreads();
 }
 
-// a stage of any radix R: every output as its own O(R) sum
+// a stage of any radix R: every output as its own O(R) sum (Kahan's)
 __device__ inline void stage_generic(double2 *sb, int n, int Ns, int R, int inverse)
 {
     const int nR = n / R, tid = threadIdx.x, nt = blockDim.x;
@@ -123,8 +183,15 @@ __device__ inline void stage_generic(double2 *sb, int n, int Ns, int R, int inve
         if (o < n) {
             const int j = o % nR, k = o / nR;
             const int64_t step = (int64_t)(j % Ns + k * Ns) * span;
-            double2 acc = sb[j];
-            for (int r = 1; r < R; ++r) acc = cadd(acc, cmul(sb[j + r * nR], twiddle(r * step, n, inverse)));
+            // a compensated sum: R terms of one phase (a tone, a constant) round the same way at every step, and the plain sum
+            // drifted by up to R / 2 ulps of the output (1e-13 of the peak at R = 8191)
+            double2 acc = sb[j], lost = make_double2(0.0, 0.0);
+            for (int r = 1; r < R; ++r) {
+                const double2 y = csub(cmul(sb[j + r * nR], twiddle(r * step, n, inverse)), lost);
+                const double2 t = cadd(acc, y);
+                lost = csub(csub(t, acc), y);
+                acc = t;
+            }
             reg[q] = acc;
         }
     }
