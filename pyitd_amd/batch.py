@@ -7,6 +7,7 @@ The reference applies its operators row by row under numba.prange (siftED2D.ipyn
 channels (itd.cpp:40-44); here a whole batch is one launch sequence and no knot count crosses PCIe in between.  Device
 memory comes from the C ABI's own allocator (engine.DeviceBuffer): no torch needed.
 """
+import contextlib
 from collections import namedtuple
 
 import numpy
@@ -146,81 +147,8 @@ def _row_stride(shape, strides):
     return lead[-1][1] if lead[-1][1] >= shape[-1] else None
 
 
-def instantaneous_batch(rows, device=0, out_dtype=None, want=_INSTANTANEOUS):
-    """Instantaneous amplitude, phase and frequency (pyitd_amd.instantaneous) of every row of rows[..., n] in one asynchronous
-    call: the rows of a batched decomposition as itd_batch delivers them, float64 or float32 (widened exactly on the GPU).
-
-    rows: a numpy array (staged through hipMalloc'd buffers; torch is not needed) or a torch CUDA tensor (used in place; its
-    leading axes must collapse to one row stride, its last axis must be dense).  want: which of "amplitude", "phase", "frequency"
-    to compute, in the order they are returned (a tuple of arrays with the input's shape; tensors on the input's device for a
-    tensor).  out_dtype: None / float64, or float32 (numpy or torch): each element the float64 one rounded once on the GPU.
-    Raises ITDError (non-finite) naming the rows that hold a NaN."""
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in _INSTANTANEOUS for w in want) or len(set(want)) != len(want):
-        raise ValueError("want: a non-empty selection of %s without repeats, got %r" % (_INSTANTANEOUS, want))
-    odt = numpy.dtype(numpy.float64 if out_dtype is None else _np_dtype(out_dtype))
-    if odt not in (numpy.dtype(numpy.float32), numpy.dtype(numpy.float64)):
-        raise ValueError("out_dtype must be float32 or float64")
-    torch_in = _is_torch(rows)
-    a = rows if torch_in else numpy.asarray(rows)
-    idt = numpy.dtype(_np_dtype(a.dtype))
-    if idt not in (numpy.dtype(numpy.float32), numpy.dtype(numpy.float64)):
-        raise ValueError("rows must be float32 or float64, got %s" % (a.dtype,))
-    shape = tuple(a.shape)
-    if len(shape) < 2:
-        raise ValueError("expected rows[..., n] with at least one leading axis, got shape %s" % (shape,))
-    n = shape[-1]
-    if n < 3:
-        raise ValueError("the instantaneous step needs at least 3 samples")
-    R = int(numpy.prod(shape[:-1], dtype=numpy.int64))
-    if R < 1:
-        raise ValueError("no rows in an array of shape %s" % (shape,))
-
-    def refuse(info):
-        bad = numpy.flatnonzero(info < 0)
-        if bad.size:
-            raise ITDError(ITD_ERR_NONFINITE, "NaN in rows %s%s" % (bad[:16].tolist(), " ..." if bad.size > 16 else ""))
-
-    if torch_in:
-        import torch
-        if not a.is_cuda:
-            raise ValueError("expected a CUDA tensor")
-        stride = _row_stride(shape, tuple(a.stride()))
-        if stride is None:
-            raise ValueError("the leading axes of a tensor with strides %s do not collapse to one row stride" % (tuple(a.stride()),))
-        dev = a.device.index
-        tdt = torch.float32 if odt == numpy.float32 else torch.float64
-        outs = {w: torch.empty(shape, dtype=tdt, device=a.device) for w in want}
-        info = torch.empty(R, dtype=torch.int32, device=a.device)
-        eng = _engine_for(3, dev)
-        torch.cuda.synchronize(a.device)    # the engine runs on its own stream
-        eng.instantaneous_batch_dev(a.data_ptr(), idt, n, R, stride, *[outs[w].data_ptr() if w in outs else None for w in _INSTANTANEOUS],
-                                    n, odt == numpy.float32, info.data_ptr())
-        torch.cuda.synchronize(a.device)
-        refuse(info.cpu().numpy())
-        return tuple(outs[w] for w in want)
-    a = numpy.ascontiguousarray(a).reshape(R, n)
-    dev = int(device)
-    bufs = {w: DeviceBuffer(R * n * odt.itemsize, dev) for w in want}
-    d_x, d_info = DeviceBuffer(a.nbytes, dev), DeviceBuffer(4 * R, dev)
-    try:
-        d_x.upload(a)
-        eng = _engine_for(3, dev)
-        eng.instantaneous_batch_dev(d_x.ptr, idt, n, R, n, *[bufs[w].ptr if w in bufs else None for w in _INSTANTANEOUS],
-                                    n, odt == numpy.float32, d_info.ptr)
-        refuse(d_info.download(numpy.empty(R, numpy.int32)))       # itd_dev_copy synchronises
-        return tuple(bufs[w].download(numpy.empty((R, n), odt)).reshape(shape) for w in want)
-    finally:
-        for b in list(bufs.values()) + [d_x, d_info]:
-            b.free()
-
-
-# ---- single-wave analysis: the table of half waves and the feature filter (itd_waves_batch_*, itd_wave_filter_batch_*) -------
-Waves = namedtuple("Waves", "count start length peak value")
-
-
 def _accept_rows(rows, what):
-    """instantaneous_batch's acceptance of rows[..., n]: (torch?, the array or tensor, input dtype, shape, n, row count)."""
+    """The acceptance of rows[..., n]: (torch?, the array or tensor, input dtype, shape, n, row count)."""
     torch_in = _is_torch(rows)
     a = rows if torch_in else numpy.asarray(rows)
     idt = numpy.dtype(_np_dtype(a.dtype))
@@ -250,6 +178,74 @@ def _refuse_nan(info):
     bad = numpy.flatnonzero(info < 0)
     if bad.size:
         raise ITDError(ITD_ERR_NONFINITE, "NaN in rows %s%s" % (bad[:16].tolist(), " ..." if bad.size > 16 else ""))
+
+
+def _out_dtype(out_dtype):
+    odt = numpy.dtype(numpy.float64 if out_dtype is None else _np_dtype(out_dtype))
+    if odt not in (numpy.dtype(numpy.float32), numpy.dtype(numpy.float64)):
+        raise ValueError("out_dtype must be float32 or float64")
+    return odt
+
+
+class _Staged(contextlib.ExitStack):
+    """The device buffers of one numpy-staged call (hipMalloc through the C ABI), freed when the block is left."""
+
+    def __init__(self, device):
+        super().__init__()
+        self.dev = int(device)
+
+    def empty(self, nbytes):
+        b = DeviceBuffer(nbytes, self.dev)
+        self.callback(b.free)
+        return b
+
+    def upload(self, array):
+        b = self.empty(array.nbytes)
+        b.upload(array)
+        return b
+
+
+def instantaneous_batch(rows, device=0, out_dtype=None, want=_INSTANTANEOUS):
+    """Instantaneous amplitude, phase and frequency (pyitd_amd.instantaneous) of every row of rows[..., n] in one asynchronous
+    call: the rows of a batched decomposition as itd_batch delivers them, float64 or float32 (widened exactly on the GPU).
+
+    rows: a numpy array (staged through hipMalloc'd buffers; torch is not needed) or a torch CUDA tensor (used in place; its
+    leading axes must collapse to one row stride, its last axis must be dense).  want: which of "amplitude", "phase", "frequency"
+    to compute, in the order they are returned (a tuple of arrays with the input's shape; tensors on the input's device for a
+    tensor).  out_dtype: None / float64, or float32 (numpy or torch): each element the float64 one rounded once on the GPU.
+    Raises ITDError (non-finite) naming the rows that hold a NaN."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in _INSTANTANEOUS for w in want) or len(set(want)) != len(want):
+        raise ValueError("want: a non-empty selection of %s without repeats, got %r" % (_INSTANTANEOUS, want))
+    odt = _out_dtype(out_dtype)
+    torch_in, a, idt, shape, n, R = _accept_rows(rows, "the instantaneous step")
+    if torch_in:
+        import torch
+        stride = _tensor_stride(a, shape)
+        dev = a.device.index
+        tdt = torch.float32 if odt == numpy.float32 else torch.float64
+        outs = {w: torch.empty(shape, dtype=tdt, device=a.device) for w in want}
+        info = torch.empty(R, dtype=torch.int32, device=a.device)
+        eng = _engine_for(3, dev)
+        torch.cuda.synchronize(a.device)    # the engine runs on its own stream
+        eng.instantaneous_batch_dev(a.data_ptr(), idt, n, R, stride, *[outs[w].data_ptr() if w in outs else None for w in _INSTANTANEOUS],
+                                    n, odt == numpy.float32, info.data_ptr())
+        torch.cuda.synchronize(a.device)
+        _refuse_nan(info.cpu().numpy())
+        return tuple(outs[w] for w in want)
+    a = numpy.ascontiguousarray(a).reshape(R, n)
+    with _Staged(device) as S:
+        bufs = {w: S.empty(R * n * odt.itemsize) for w in want}
+        d_x, d_info = S.upload(a), S.empty(4 * R)
+        eng = _engine_for(3, S.dev)
+        eng.instantaneous_batch_dev(d_x.ptr, idt, n, R, n, *[bufs[w].ptr if w in bufs else None for w in _INSTANTANEOUS],
+                                    n, odt == numpy.float32, d_info.ptr)
+        _refuse_nan(d_info.download(numpy.empty(R, numpy.int32)))      # itd_dev_copy synchronises
+        return tuple(bufs[w].download(numpy.empty((R, n), odt)).reshape(shape) for w in want)
+
+
+# ---- single-wave analysis: the table of half waves and the feature filter (itd_waves_batch_*, itd_wave_filter_batch_*) -------
+Waves = namedtuple("Waves", "count start length peak value")
 
 
 def _refuse_overflow(count, cap):
@@ -299,30 +295,22 @@ def single_waves(rows, cap=None, device=0):
         _refuse_overflow(count.cpu().numpy(), cap)
         return Waves(count.reshape(lead), *[t.reshape(lead + (cap,)) for t in ints], value.reshape(lead + (cap,)))
     a = numpy.ascontiguousarray(a).reshape(R, n)
-    dev = int(device)
-    bufs = [DeviceBuffer(a.nbytes, dev), DeviceBuffer(4 * R, dev), DeviceBuffer(4 * R, dev)]
-    d_x, d_count, d_info = bufs
-    try:
-        d_x.upload(a)
-        eng = _engine_for(3, dev)
+    with _Staged(device) as S:
+        d_x, d_count, d_info = S.upload(a), S.empty(4 * R), S.empty(4 * R)
+        eng = _engine_for(3, S.dev)
         if cap is None:
             eng.waves_batch_dev(d_x.ptr, idt, n, R, n, None, None, None, None, 0, 0, d_count.ptr, d_info.ptr)
             _refuse_nan(d_info.download(numpy.empty(R, numpy.int32)))       # itd_dev_copy synchronises
             cap = int(d_count.download(numpy.empty(R, numpy.int32)).max())
         fill_i, fill_v = numpy.full((R, cap), -1, numpy.int32), numpy.full((R, cap), numpy.nan)
-        tabs = [DeviceBuffer(fill_i.nbytes, dev) for _ in range(3)] + [DeviceBuffer(fill_v.nbytes, dev)]
-        bufs += tabs
-        for b, f in zip(tabs, (fill_i, fill_i, fill_i, fill_v)):
-            b.upload(f)
+        fills = (fill_i, fill_i, fill_i, fill_v)
+        tabs = [S.upload(f) for f in fills]
         eng.waves_batch_dev(d_x.ptr, idt, n, R, n, *[b.ptr for b in tabs], cap, cap, d_count.ptr, d_info.ptr)
         _refuse_nan(d_info.download(numpy.empty(R, numpy.int32)))
         count = d_count.download(numpy.empty(R, numpy.int32))
         _refuse_overflow(count, cap)
-        outs = [b.download(numpy.empty_like(f)).reshape(lead + (cap,)) for b, f in zip(tabs, (fill_i, fill_i, fill_i, fill_v))]
+        outs = [b.download(numpy.empty_like(f)).reshape(lead + (cap,)) for b, f in zip(tabs, fills)]
         return Waves(count.reshape(lead), *outs)
-    finally:
-        for b in bufs:
-            b.free()
 
 
 def _wave_bounds(amplitude, length, lead):
@@ -360,9 +348,7 @@ def wave_filter(rows, amplitude=(0.0, numpy.inf), length=(0.0, numpy.inf), out_d
 
     rows as for single_waves; out_dtype: None / float64, or float32 (numpy or torch): each kept sample rounded once on the GPU.
     Returns an array (tensor for a tensor) shaped like rows.  Raises ITDError (non-finite) naming the rows that hold a NaN."""
-    odt = numpy.dtype(numpy.float64 if out_dtype is None else _np_dtype(out_dtype))
-    if odt not in (numpy.dtype(numpy.float32), numpy.dtype(numpy.float64)):
-        raise ValueError("out_dtype must be float32 or float64")
+    odt = _out_dtype(out_dtype)
     torch_in, a, idt, shape, n, R = _accept_rows(rows, "the wave filter")
     bounds = _wave_bounds(amplitude, length, shape[:-1])
     bstride = 0 if bounds.ndim == 1 else 4
@@ -381,16 +367,9 @@ def wave_filter(rows, amplitude=(0.0, numpy.inf), length=(0.0, numpy.inf), out_d
         _refuse_nan(info.cpu().numpy())
         return out
     a = numpy.ascontiguousarray(a).reshape(R, n)
-    dev = int(device)
-    bufs = [DeviceBuffer(a.nbytes, dev), DeviceBuffer(bounds.nbytes, dev), DeviceBuffer(R * n * odt.itemsize, dev), DeviceBuffer(4 * R, dev)]
-    d_x, d_b, d_out, d_info = bufs
-    try:
-        d_x.upload(a)
-        d_b.upload(bounds)
-        eng = _engine_for(3, dev)
+    with _Staged(device) as S:
+        d_x, d_b, d_out, d_info = S.upload(a), S.upload(bounds), S.empty(R * n * odt.itemsize), S.empty(4 * R)
+        eng = _engine_for(3, S.dev)
         eng.wave_filter_batch_dev(d_x.ptr, idt, n, R, n, d_b.ptr, bstride, d_out.ptr, n, odt == numpy.float32, d_info.ptr)
         _refuse_nan(d_info.download(numpy.empty(R, numpy.int32)))           # itd_dev_copy synchronises
         return d_out.download(numpy.empty((R, n), odt)).reshape(shape)
-    finally:
-        for b in bufs:
-            b.free()

@@ -58,76 +58,96 @@ int extract_batch(itd_engine *e, const double *x, int64_t n, int32_t batch, int6
     return ITD_OK;
 }
 
-// instantaneous amplitude / phase / frequency of every row (itd_tfe_batch.hpp): records, carry, apply per chunk of rows — three
-// launches behind one another on `st`, nothing read on the host
-template <typename Tin, typename Tout>
-void inst_chunk(const Tin *x, int64_t x_stride, int64_t n, int64_t tiles, int nb, InstRec *rec, double *Ahead, double *Atail,
-                void *amp, void *phase, void *freq, int64_t out_stride, int32_t *info, hipStream_t st)
+// ---- the half-wave tile pipeline (itd_halfwave.hpp): the instantaneous step (itd_tfe_batch.hpp) and the single-wave analysis
+//      (itd_waves.hpp).  Per chunk of rows a scan (records, carry) and a consumer, launches behind one another on the stream,
+//      nothing read on the host.
+
+// what every batched call of the family refuses (outs: the call has somewhere to write)
+bool tile_args_ok(const itd_engine *e, const void *x, int64_t n, int32_t rows, int64_t x_stride, bool outs)
 {
-    const dim3 grid((unsigned)tiles, (unsigned)nb);
-    k_inst_records<Tin><<<grid, kWave, 0, st>>>(x, x_stride, n, tiles, rec);
-    if (tiles <= kInstCarrySmall) k_inst_carry<64><<<nb, 64, 0, st>>>(rec, tiles, Ahead, Atail, info);
-    else k_inst_carry<kInstCarryThreads><<<nb, kInstCarryThreads, 0, st>>>(rec, tiles, Ahead, Atail, info);
-    k_inst_apply<Tin, Tout><<<grid, kWave, 0, st>>>(x, x_stride, n, tiles, Ahead, Atail, (Tout *)amp, (Tout *)phase, (Tout *)freq, out_stride);
+    return e && x && outs && n >= 3 && n < (int64_t)INT32_MAX - 65536 && rows >= 1 && (rows == 1 || x_stride >= n);
+}
+// ... and where it writes rows of float64 / float32 samples
+bool tile_out_ok(int64_t n, int32_t rows, int64_t out_stride, int32_t out_f32)
+{
+    return (out_f32 == 0 || out_f32 == 1) && (rows == 1 || out_stride >= n);
+}
+
+// The pipeline's workspace in one of the engine's grow-only buffers, for chunk = min(rows, 65535) rows (the launches' grid.y):
+// per tile a record and what the carry leaves for the tile's first (head) and last (tail) half wave.
+template <typename Rec, typename Head, typename Tail>
+struct TileWs {
+    Rec *rec;
+    Head *head;
+    Tail *tail;
+    int64_t tiles;
+    int chunk;
+};
+using InstWs = TileWs<InstRec, double, double>;         // Ahead, Atail; in d_ib
+using WaveWs = TileWs<WaveRec, WaveFwd, WaveBwd>;       // in d_wv (not d_ib: a captured instantaneous call stays valid)
+template <typename Rec, typename Head, typename Tail>
+int tile_workspace(itd_engine *e, Buf<void> &buf, int64_t n, int32_t rows, TileWs<Rec, Head, Tail> &w)
+{
+    w.tiles = (n + kTfeTile - 1) / kTfeTile;
+    w.chunk = std::min<int32_t>(rows, kMaxGridY);
+    const size_t per = (size_t)w.chunk * (size_t)w.tiles;
+    const int rc = grow(e, buf, per * (sizeof(Rec) + sizeof(Head) + sizeof(Tail)));
+    w.rec = (Rec *)(void *)buf;
+    w.head = (Head *)(w.rec + per);
+    w.tail = (Tail *)(w.head + per);
+    return rc;
+}
+
+// f(b0, nb) for every chunk of rows; then what the launches left behind
+template <typename F>
+int for_row_chunks(itd_engine *e, int32_t rows, int chunk, F f)
+{
+    for (int b0 = 0; b0 < rows; b0 += chunk) f(b0, std::min(chunk, rows - b0));
+    HIP_TRY(e, hipGetLastError());
+    return ITD_OK;
+}
+// an optional array, `off` elements on
+template <typename A>
+A *at(A *p, int64_t off) { return p ? p + off : nullptr; }
+// ... of float64 / float32 samples
+void *at(void *p, int64_t off, int32_t f32) { return p ? (char *)p + (size_t)off * (f32 ? sizeof(float) : sizeof(double)) : nullptr; }
+
+template <typename Tin, typename Tout>
+void inst_chunk(const InstWs &w, const Tin *x, int64_t x_stride, int64_t n, int nb, void *amp, void *phase, void *freq, int64_t out_stride,
+                int32_t *info, hipStream_t st)
+{
+    const dim3 grid((unsigned)w.tiles, (unsigned)nb);
+    k_inst_records<Tin><<<grid, kWave, 0, st>>>(x, x_stride, n, w.tiles, w.rec);
+    if (w.tiles <= kInstCarrySmall) k_inst_carry<64><<<nb, 64, 0, st>>>(w.rec, w.tiles, w.head, w.tail, info);
+    else k_inst_carry<kInstCarryThreads><<<nb, kInstCarryThreads, 0, st>>>(w.rec, w.tiles, w.head, w.tail, info);
+    k_inst_apply<Tin, Tout><<<grid, kWave, 0, st>>>(x, x_stride, n, w.tiles, w.head, w.tail, (Tout *)amp, (Tout *)phase, (Tout *)freq, out_stride);
 }
 
 template <typename Tin>
 int inst_batch(itd_engine *e, const Tin *x, int64_t n, int32_t rows, int64_t x_stride, void *amp, void *phase, void *freq,
                int64_t out_stride, int32_t out_f32, int32_t *info, void *stream)
 {
-    if (!e || !x || (!amp && !phase && !freq)) return ITD_ERR_INVALID_ARG;
-    if (n < 3 || n >= (int64_t)INT32_MAX - 65536 || rows < 1 || (out_f32 != 0 && out_f32 != 1)) return ITD_ERR_INVALID_ARG;
-    if (rows > 1 && (x_stride < n || out_stride < n)) return ITD_ERR_INVALID_ARG;
+    if (!tile_args_ok(e, x, n, rows, x_stride, amp || phase || freq) || !tile_out_ok(n, rows, out_stride, out_f32)) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
     hipStream_t st = stream_of(e, stream);
-    const int64_t tiles = (n + kTfeTile - 1) / kTfeTile;
-    const int chunk = std::min<int32_t>(rows, kMaxGridY);
-    const size_t per = (size_t)chunk * (size_t)tiles;
-    const int rc = grow(e, e->d_ib, per * (sizeof(InstRec) + 2 * sizeof(double)));
+    InstWs w;
+    const int rc = tile_workspace(e, e->d_ib, n, rows, w);
     if (rc) return rc;
-    InstRec *rec = (InstRec *)e->d_ib;
-    double *Ahead = (double *)(rec + per), *Atail = Ahead + per;
-    const size_t osz = out_f32 ? sizeof(float) : sizeof(double);
-    for (int b0 = 0; b0 < rows; b0 += chunk) {
-        const int nb = std::min(chunk, rows - b0);
+    return for_row_chunks(e, rows, w.chunk, [&](int b0, int nb) {
         const Tin *xc = x + (int64_t)b0 * x_stride;
-        const size_t off = (size_t)b0 * (size_t)out_stride * osz;
-        void *a = amp ? (char *)amp + off : nullptr, *p = phase ? (char *)phase + off : nullptr, *f = freq ? (char *)freq + off : nullptr;
-        if (out_f32) inst_chunk<Tin, float>(xc, x_stride, n, tiles, nb, rec, Ahead, Atail, a, p, f, out_stride, info ? info + b0 : nullptr, st);
-        else inst_chunk<Tin, double>(xc, x_stride, n, tiles, nb, rec, Ahead, Atail, a, p, f, out_stride, info ? info + b0 : nullptr, st);
-    }
-    HIP_TRY(e, hipGetLastError());
-    return ITD_OK;
+        const int64_t off = (int64_t)b0 * out_stride;
+        void *a = at(amp, off, out_f32), *p = at(phase, off, out_f32), *f = at(freq, off, out_f32);
+        if (out_f32) inst_chunk<Tin, float>(w, xc, x_stride, n, nb, a, p, f, out_stride, at(info, b0), st);
+        else inst_chunk<Tin, double>(w, xc, x_stride, n, nb, a, p, f, out_stride, at(info, b0), st);
+    });
 }
 
-// single-wave analysis (itd_waves.hpp): records and carry per chunk of rows, then the table and / or the filter — launches behind
-// one another on `st`, nothing read on the host.  The workspace is the engine's d_wv (not d_ib: a captured instantaneous call stays
-// valid): per tile a WaveRec, a WaveFwd and a WaveBwd.
-struct WaveWs {
-    WaveRec *rec;
-    WaveFwd *fwd;
-    WaveBwd *bwd;
-    int64_t tiles;
-    int chunk;
-};
-int wave_workspace(itd_engine *e, int64_t n, int32_t rows, WaveWs &w)
-{
-    w.tiles = (n + kTfeTile - 1) / kTfeTile;
-    w.chunk = std::min<int32_t>(rows, kMaxGridY);
-    const size_t per = (size_t)w.chunk * (size_t)w.tiles;
-    const int rc = grow(e, e->d_wv, per * (sizeof(WaveRec) + sizeof(WaveFwd) + sizeof(WaveBwd)));
-    if (rc) return rc;
-    w.rec = (WaveRec *)e->d_wv;
-    w.fwd = (WaveFwd *)(w.rec + per);
-    w.bwd = (WaveBwd *)(w.fwd + per);
-    return ITD_OK;
-}
 template <typename Tin>
 void wave_scan(const WaveWs &w, const Tin *x, int64_t x_stride, int64_t n, int nb, int32_t *count, int32_t *info, hipStream_t st)
 {
     k_wave_records<Tin><<<dim3((unsigned)w.tiles, (unsigned)nb), kWave, 0, st>>>(x, x_stride, n, w.tiles, w.rec);
-    if (w.tiles <= kInstCarrySmall) k_wave_carry<64><<<nb, 64, 0, st>>>(w.rec, w.tiles, n, w.fwd, w.bwd, count, info);
-    else k_wave_carry<kInstCarryThreads><<<nb, kInstCarryThreads, 0, st>>>(w.rec, w.tiles, n, w.fwd, w.bwd, count, info);
+    if (w.tiles <= kInstCarrySmall) k_wave_carry<64><<<nb, 64, 0, st>>>(w.rec, w.tiles, n, w.head, w.tail, count, info);
+    else k_wave_carry<kInstCarryThreads><<<nb, kInstCarryThreads, 0, st>>>(w.rec, w.tiles, n, w.head, w.tail, count, info);
 }
 
 template <typename Tin>
@@ -135,56 +155,44 @@ int waves_batch(itd_engine *e, const Tin *x, int64_t n, int32_t rows, int64_t x_
                 double *value, int64_t wave_stride, int32_t cap, int32_t *count, int32_t *info, void *stream)
 {
     const bool table = start || length || peak || value;
-    if (!e || !x || (!table && !count)) return ITD_ERR_INVALID_ARG;
-    if (n < 3 || n >= (int64_t)INT32_MAX - 65536 || rows < 1) return ITD_ERR_INVALID_ARG;
-    if (rows > 1 && x_stride < n) return ITD_ERR_INVALID_ARG;
+    if (!tile_args_ok(e, x, n, rows, x_stride, table || count)) return ITD_ERR_INVALID_ARG;
     if (table && (cap < 1 || (rows > 1 && wave_stride < cap))) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
     hipStream_t st = stream_of(e, stream);
     WaveWs w;
-    const int rc = wave_workspace(e, n, rows, w);
+    const int rc = tile_workspace(e, e->d_wv, n, rows, w);
     if (rc) return rc;
-    for (int b0 = 0; b0 < rows; b0 += w.chunk) {
-        const int nb = std::min(w.chunk, rows - b0);
+    return for_row_chunks(e, rows, w.chunk, [&](int b0, int nb) {
         const Tin *xc = x + (int64_t)b0 * x_stride;
         const int64_t off = (int64_t)b0 * wave_stride;
-        wave_scan<Tin>(w, xc, x_stride, n, nb, count ? count + b0 : nullptr, info ? info + b0 : nullptr, st);
+        wave_scan<Tin>(w, xc, x_stride, n, nb, at(count, b0), at(info, b0), st);
         if (table)
-            k_wave_table<Tin><<<dim3((unsigned)w.tiles, (unsigned)nb), kWave, 0, st>>>(xc, x_stride, n, w.tiles, w.fwd, w.bwd,
-                                                                                      start ? start + off : nullptr, length ? length + off : nullptr,
-                                                                                      peak ? peak + off : nullptr, value ? value + off : nullptr,
+            k_wave_table<Tin><<<dim3((unsigned)w.tiles, (unsigned)nb), kWave, 0, st>>>(xc, x_stride, n, w.tiles, w.head, w.tail, at(start, off),
+                                                                                      at(length, off), at(peak, off), at(value, off),
                                                                                       wave_stride, cap);
-    }
-    HIP_TRY(e, hipGetLastError());
-    return ITD_OK;
+    });
 }
 
 template <typename Tin>
 int wave_filter_batch(itd_engine *e, const Tin *x, int64_t n, int32_t rows, int64_t x_stride, const double *bounds, int64_t bounds_stride,
                       void *out, int64_t out_stride, int32_t out_f32, int32_t *info, void *stream)
 {
-    if (!e || !x || !bounds || !out) return ITD_ERR_INVALID_ARG;
-    if (n < 3 || n >= (int64_t)INT32_MAX - 65536 || rows < 1 || (out_f32 != 0 && out_f32 != 1)) return ITD_ERR_INVALID_ARG;
-    if (rows > 1 && (x_stride < n || out_stride < n)) return ITD_ERR_INVALID_ARG;
+    if (!tile_args_ok(e, x, n, rows, x_stride, bounds && out) || !tile_out_ok(n, rows, out_stride, out_f32)) return ITD_ERR_INVALID_ARG;
     if (bounds_stride != 0 && bounds_stride < 4) return ITD_ERR_INVALID_ARG;
     DevGuard g(e->device);
     hipStream_t st = stream_of(e, stream);
     WaveWs w;
-    const int rc = wave_workspace(e, n, rows, w);
+    const int rc = tile_workspace(e, e->d_wv, n, rows, w);
     if (rc) return rc;
-    const size_t osz = out_f32 ? sizeof(float) : sizeof(double);
-    for (int b0 = 0; b0 < rows; b0 += w.chunk) {
-        const int nb = std::min(w.chunk, rows - b0);
+    return for_row_chunks(e, rows, w.chunk, [&](int b0, int nb) {
         const Tin *xc = x + (int64_t)b0 * x_stride;
         const double *bc = bounds + (int64_t)b0 * bounds_stride;
-        void *oc = (char *)out + (size_t)b0 * (size_t)out_stride * osz;
+        void *oc = at(out, (int64_t)b0 * out_stride, out_f32);
         const dim3 grid((unsigned)w.tiles, (unsigned)nb);
-        wave_scan<Tin>(w, xc, x_stride, n, nb, nullptr, info ? info + b0 : nullptr, st);
-        if (out_f32) k_wave_filter<Tin, float><<<grid, kWave, 0, st>>>(xc, x_stride, n, w.tiles, w.fwd, w.bwd, bc, bounds_stride, (float *)oc, out_stride);
-        else k_wave_filter<Tin, double><<<grid, kWave, 0, st>>>(xc, x_stride, n, w.tiles, w.fwd, w.bwd, bc, bounds_stride, (double *)oc, out_stride);
-    }
-    HIP_TRY(e, hipGetLastError());
-    return ITD_OK;
+        wave_scan<Tin>(w, xc, x_stride, n, nb, nullptr, at(info, b0), st);
+        if (out_f32) k_wave_filter<Tin, float><<<grid, kWave, 0, st>>>(xc, x_stride, n, w.tiles, w.head, w.tail, bc, bounds_stride, (float *)oc, out_stride);
+        else k_wave_filter<Tin, double><<<grid, kWave, 0, st>>>(xc, x_stride, n, w.tiles, w.head, w.tail, bc, bounds_stride, (double *)oc, out_stride);
+    });
 }
 
 }  // namespace

@@ -23,18 +23,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "itd_halfwave.hpp"
+
 #pragma clang fp contract(off)
 
 namespace itd {
-
-constexpr int kTfeTile = 512;
-
-// crossing index i: a sign change between x[i] and x[i+1] (find_extrema's test, itd_fourier_decomposition.py:23-27), 1 <= i <= n-2
-// exactly as k_detect's kZeroCross mode flags it (first and last sample never flag) — the per-tile bases come from that scan
-__device__ __forceinline__ bool tfe_crossing(int64_t i, int64_t n, double x0, double xp)
-{
-    return i >= 1 && i <= n - 2 && (((x0 > 0.0) && (0.0 > xp)) || ((x0 < 0.0) && (0.0 < xp)));
-}
 
 __global__ __launch_bounds__(64) void k_tfe_amplitude(const double *__restrict__ x, int64_t n, const int32_t *__restrict__ tile_base,
                                                       unsigned long long *__restrict__ amp_bits /* m+1, zeroed */)
@@ -104,13 +97,6 @@ __global__ __launch_bounds__(64) void k_tfe_phase(const double *__restrict__ x, 
             hw += __popcll(cm[g]);
         }
         const double A_ext = __builtin_bit_cast(double, amp_bits[hw]);       // the half wave of sample s + 512
-        auto phase_in = [&](double xi, double slope, double Aa) {
-            if (!(Aa > 0.0)) return 0.0;                    // an all-zero half wave
-            const double r = xi / Aa;
-            const double as = asin(r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r));
-            if (xi >= 0.0) return slope >= 0.0 ? as : pi - as;
-            return slope < 0.0 ? pi - as : 2.0 * pi + as;
-        };
         double ph[G];
 #pragma unroll
         for (int g = 0; g < G; ++g) ph[g] = phase_in(xr[g], xn[g] - xr[g], A[g]);
@@ -130,14 +116,6 @@ __global__ __launch_bounds__(64) void k_tfe_phase(const double *__restrict__ x, 
         }
         return;
     }
-    // phase of sample i in half wave k (amplitude A): rising or falling from the forward difference (the backward one at the last sample)
-    auto phase_of = [&](int64_t i, double xi, double slope, double A) {
-        if (!(A > 0.0)) return 0.0;                     // an all-zero half wave
-        const double r = xi / A;
-        const double as = asin(r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r));
-        if (xi >= 0.0) return slope >= 0.0 ? as : pi - as;
-        return slope < 0.0 ? pi - as : 2.0 * pi + as;
-    };
     for (int g = 0; g < kTfeTile / 64; ++g) {
         const int64_t j0 = s + g * 64;
         if (j0 >= n) break;
@@ -152,7 +130,7 @@ __global__ __launch_bounds__(64) void k_tfe_phase(const double *__restrict__ x, 
         const double A = in ? __builtin_bit_cast(double, amp_bits[k]) : 0.0;
         const double xprev = (in && j >= 1 && j + 1 >= n) ? x[j - 1] : 0.0;        // only the signal's last sample needs it
         const double slope = (j + 1 < n) ? xn - xj : xj - xprev;
-        const double ph = in ? phase_of(j, xj, slope, A) : 0.0;
+        const double ph = in ? phase_in(xj, slope, A) : 0.0;
         if (in && amp_out) amp_out[j] = A;
         if (in && phase_out) phase_out[j] = ph;
         if (freq_out) {
@@ -163,7 +141,7 @@ __global__ __launch_bounds__(64) void k_tfe_phase(const double *__restrict__ x, 
                 const int64_t k1 = k + (cross ? 1 : 0);
                 const double A1 = __builtin_bit_cast(double, amp_bits[k1]);
                 const double slope1 = (j + 2 < n) ? xnn - xn : xn - xj;
-                ph_next = phase_of(j + 1, xn, slope1, A1);
+                ph_next = phase_in(xn, slope1, A1);
             }
             double f = 0.0;
             if (j + 1 < n) {
@@ -175,7 +153,7 @@ __global__ __launch_bounds__(64) void k_tfe_phase(const double *__restrict__ x, 
                 if (lane == 0) {                         // its predecessor sits in the previous step
                     const int64_t kp = k - (tfe_crossing(j - 1, n, xprev, xj) ? 1 : 0);
                     const double Ap = __builtin_bit_cast(double, amp_bits[kp]);
-                    dp = ph - phase_of(j - 1, xprev, xj - xprev, Ap);
+                    dp = ph - phase_in(xprev, xj - xprev, Ap);
                 }
                 if (dp < 0.0) dp += 2.0 * pi;
                 f = dp / (2.0 * pi);

@@ -1,10 +1,11 @@
 // itd_tfe_batch.hpp — instantaneous amplitude, phase and frequency of MANY rows in one asynchronous call (the batched form of
-// itd_tfe.hpp: the same definitions, the same expressions, bit-identical results on NaN-free rows).
+// itd_tfe.hpp: the same definitions, the same phase expression (phase_in), bit-identical results on NaN-free rows).
 //
 // The single-row operator numbers a row's half waves globally: an ordered compaction of the zero crossings (whose count the
-// host reads to size the amplitude table), a memset and one atomic max per (step, half wave).  Here nothing is numbered.  A half
-// wave either begins and ends inside one 512-sample tile — its amplitude is then a segmented maximum of that tile alone — or it
-// is the first or the last half wave of a tile, and those two amplitudes follow from three numbers per tile:
+// host reads to size the amplitude table), a memset and one atomic max per (step, half wave).  Here nothing is numbered: the
+// tile pipeline of itd_halfwave.hpp with the smallest records.  A half wave either begins and ends inside one 512-sample tile
+// — its amplitude is then a segmented maximum of that tile alone — or it is the first or the last half wave of a tile, and
+// those two amplitudes follow from three numbers per tile:
 //     c      crossings whose index lies in the tile
 //     head   max |x| of the tile's samples up to and including its first crossing index (the whole tile if c == 0)
 //     tail   max |x| of the samples behind its last crossing index (0 if there are none or c == 0; 0 is neutral for a maximum
@@ -19,16 +20,16 @@
 //     k_inst_records   reads the row, writes one record per tile
 //     k_inst_carry     the scan over a row's records, one workgroup per row; also the row's crossing total / NaN flag (info)
 //     k_inst_apply     reads the row again: flags and in-tile segmented maxima anew, the first / last half wave's amplitude from
-//                      Ahead / Atail, the amplitude of sample s + 512 (lane 63's successor) from Ahead[t+1]; phase and frequency
-//                      exactly as k_tfe_phase writes them; streamed stores, each element rounded once where the output is float32
-// No workgroup waits for another, no atomics on global memory, no count on the host.  Nothing outside the first n samples of a
-// row is read.  Traffic for float64 in and out: 8 + 8 B read and 24 B written per sample, and per tile 24 B of record and 16 B of
-// Ahead / Atail written and read once or twice (about 0.2 B per sample).
+//                      Ahead / Atail, the amplitude of sample s + 512 (lane 63's successor) from Ahead[t+1]; one arcsine per
+//                      sample, the neighbour's phase from the next lane; streamed stores, each element rounded once where the
+//                      output is float32
+// Traffic for float64 in and out: 8 + 8 B read and 24 B written per sample, and per tile 24 B of record and 16 B of Ahead / Atail
+// written and read once or twice (about 0.2 B per sample).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "itd_tfe.hpp"
+#include "itd_halfwave.hpp"
 
 #pragma clang fp contract(off)
 
@@ -41,50 +42,12 @@ struct InstRec {
 };
 static_assert(sizeof(InstRec) == 24, "InstRec layout");
 
-constexpr int kInstSteps = kTfeTile / 64;
-constexpr int kInstCarryThreads = 256;                                   // long rows (more than kInstCarrySmall records)
-constexpr int kInstCarryPer = 8;                                         // records per thread and pass
-constexpr int kInstCarryChunk = kInstCarryThreads * kInstCarryPer;       // K = 2048 records (2^20 samples) per pass
-constexpr int kInstCarrySmall = 64 * kInstCarryPer;                      // up to here one wavefront takes the row in one pass
-
-// |x| as an unsigned integer (non-negative doubles order like their bit patterns); a NaN does not count, as in k_tfe_amplitude
-__device__ __forceinline__ unsigned long long inst_mag(double x, bool in)
-{
-    const double a = __builtin_fabs(x);
-    return (in && a == a) ? __builtin_bit_cast(unsigned long long, a) : 0ull;
-}
 __device__ __forceinline__ unsigned long long inst_umax(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 __device__ __forceinline__ unsigned long long inst_wave_max(unsigned long long v)
 {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v = inst_umax(v, __shfl_xor(v, d));
     return v;
-}
-
-// The tile's samples (lane + 64 g, zero behind the row's end), every sample's successor, the crossing flags of the tile and
-// before[g] = the crossings of the tile in front of the lane's sample of step g.  ext0 = x[s + 512] or 0.  Returns c.
-template <typename Tin>
-__device__ __forceinline__ int inst_load_tile(const Tin *__restrict__ x, int64_t n, int64_t s, int lane, double ext0,
-                                              double (&xr)[kInstSteps], double (&xn)[kInstSteps],
-                                              unsigned long long (&cm)[kInstSteps], int (&before)[kInstSteps])
-{
-#pragma unroll
-    for (int g = 0; g < kInstSteps; ++g) {
-        const int64_t j = s + g * 64 + lane;
-        xr[g] = j < n ? (double)x[j] : 0.0;
-    }
-    int c = 0;
-#pragma unroll
-    for (int g = 0; g < kInstSteps; ++g) {
-        const int64_t j = s + g * 64 + lane;
-        const double nxt = __shfl_down(xr[g], 1);
-        const double first_next = g + 1 < kInstSteps ? __shfl(xr[g + 1 < kInstSteps ? g + 1 : g], 0) : ext0;
-        xn[g] = lane == 63 ? first_next : nxt;
-        cm[g] = __ballot(tfe_crossing(j, n, xr[g], xn[g]));       // (j <= n - 2: xn is a sample of the row)
-        before[g] = c + __popcll(cm[g] & ((1ull << lane) - 1ull));
-        c += __popcll(cm[g]);
-    }
-    return c;
 }
 
 template <typename Tin>
@@ -99,19 +62,8 @@ __global__ __launch_bounds__(64) void k_inst_records(const Tin *__restrict__ row
     unsigned long long cm[kInstSteps];
     int before[kInstSteps];
     const int c = inst_load_tile<Tin>(x, n, s, lane, ext0, xr, xn, cm, before);
-    // positions (in the tile) of the first and the last crossing index; none: the head is the whole tile, the tail empty
-    int fpos = kTfeTile - 1, lpos = kTfeTile - 1;
-    if (c > 0) {
-        bool found = false;
-#pragma unroll
-        for (int g = 0; g < kInstSteps; ++g) {
-            if (cm[g]) {
-                if (!found) fpos = g * 64 + __builtin_ctzll(cm[g]);
-                found = true;
-                lpos = g * 64 + 63 - __builtin_clzll(cm[g]);
-            }
-        }
-    }
+    int fpos, lpos;
+    tile_crossing_span(cm, fpos, lpos);
     unsigned long long hv = 0ull, tv = 0ull;
     bool nan = false;
 #pragma unroll
@@ -142,113 +94,65 @@ struct InstMap {
     int reset;
     unsigned long long m;
 };
-__device__ __forceinline__ InstMap inst_then(InstMap f, InstMap g)
-{
-    InstMap r;
-    r.reset = f.reset | g.reset;
-    r.m = g.reset ? g.m : inst_umax(f.m, g.m);
-    return r;
-}
-__device__ __forceinline__ unsigned long long inst_apply_map(InstMap f, unsigned long long s) { return f.reset ? f.m : inst_umax(s, f.m); }
 
-// One workgroup per row.  Position p counts the records in scan order: record p in the forward pass (which leaves max(in, head)
-// in Ahead), record tiles - 1 - p in the backward pass (which completes Ahead and writes Atail).  A pass takes NT * kInstCarryPer
-// positions at a time — every thread kInstCarryPer consecutive ones, an exclusive scan of the threads' maps across the workgroup —
-// and carries its running value from one such chunk to the next.
+// halfwave_carry's policy: the state is in[] / out[] of a position; the forward pass leaves max(in, head) in Ahead, the backward
+// pass completes Ahead and writes Atail.  The row's crossing total is a per-thread sum and one LDS atomic (sh: two words, zeroed
+// by the kernel in front of the scan).
+struct InstCarry {
+    using Rec = InstRec;
+    using Map = InstMap;
+    using State = unsigned long long;
+    const InstRec *rec;
+    double *Ahead, *Atail;
+    int32_t *info;          // the row's word (or NULL)
+    int *sh;
+    int cnt = 0, nan = 0;
+
+    static __device__ __forceinline__ Map ident() { return {0, 0ull}; }
+    static __device__ __forceinline__ Map then(Map f, Map g) { return {f.reset | g.reset, g.reset ? g.m : inst_umax(f.m, g.m)}; }
+    static __device__ __forceinline__ State apply(Map f, State s) { return f.reset ? f.m : inst_umax(s, f.m); }
+    static __device__ __forceinline__ Map up(Map v, int d) { return {__shfl_up(v.reset, d), __shfl_up(v.m, d)}; }
+    __device__ __forceinline__ Rec load(int64_t t) const { return rec[t]; }
+    // forward: a tile with crossings hands on its tail, one without joins its maximum (head); backward: the head either way
+    __device__ __forceinline__ Map map(int dir, const Rec &r)
+    {
+        if (dir == 0) { cnt += r.c; nan |= r.nan; }
+        return {r.c > 0 ? 1 : 0, __builtin_bit_cast(unsigned long long, (dir == 0 && r.c > 0) ? r.tail : r.head)};
+    }
+    __device__ __forceinline__ State start(int) const { return 0ull; }
+    __device__ __forceinline__ void emit(int dir, int64_t t, const Rec &r, State v) const
+    {
+        if (dir == 0) {
+            Ahead[t] = __builtin_bit_cast(double, inst_umax(v, __builtin_bit_cast(unsigned long long, r.head)));
+        } else {
+            if (r.c == 0) {
+                const unsigned long long a = __builtin_bit_cast(unsigned long long, Ahead[t]);
+                Ahead[t] = __builtin_bit_cast(double, inst_umax(a, v));
+            }
+            Atail[t] = __builtin_bit_cast(double, inst_umax(__builtin_bit_cast(unsigned long long, r.tail), v));
+        }
+    }
+    __device__ __forceinline__ void pass_end(int, State) const {}
+    __device__ __forceinline__ void report(int tid) const
+    {
+        if (!info) return;
+        if (cnt) atomicAdd(&sh[0], cnt);
+        if (nan) atomicOr(&sh[1], 1);
+        __syncthreads();
+        if (tid == 0) *info = sh[1] ? -1 - sh[0] : sh[0];
+    }
+};
+
+// One workgroup per row: halfwave_carry over the row's records; also the row's crossing total / NaN flag (info).
 template <int NT>
 __global__ __launch_bounds__(NT) void k_inst_carry(const InstRec *__restrict__ rec, int64_t tiles, double *__restrict__ Ahead,
                                                    double *__restrict__ Atail, int32_t *__restrict__ info)
 {
-    constexpr int NW = NT / 64, R = kInstCarryPer;
-    __shared__ InstMap wave_tot[NW];
-    __shared__ int sh_cnt, sh_nan;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ int sh[2];
+    if (threadIdx.x == 0) { sh[0] = 0; sh[1] = 0; }     // (the scan's barriers stand between this and report's atomics)
     const int64_t row = blockIdx.x;
-    rec += row * tiles;
-    Ahead += row * tiles;
-    Atail += row * tiles;
-    if (tid == 0) { sh_cnt = 0; sh_nan = 0; }
-    int cnt = 0, nan = 0;
-    for (int dir = 0; dir < 2; ++dir) {
-        unsigned long long run = 0ull;                  // in[] / out[] of the chunk's first position
-        for (int64_t base = 0; base < tiles; base += (int64_t)NT * R) {
-            InstRec r[R];
-            InstMap f[R];
-            InstMap mine = {0, 0ull};
-#pragma unroll
-            for (int k = 0; k < R; ++k) {
-                const int64_t p = base + (int64_t)tid * R + k;
-                const bool in = p < tiles;
-                const int64_t t = dir ? tiles - 1 - p : p;
-                if (in) r[k] = rec[t];
-                else { r[k].c = 0; r[k].nan = 0; r[k].head = 0.0; r[k].tail = 0.0; }
-                f[k].reset = r[k].c > 0 ? 1 : 0;
-                // forward: a tile with crossings hands on its tail, one without joins its maximum (head); backward: the head either way
-                f[k].m = __builtin_bit_cast(unsigned long long, (dir == 0 && r[k].c > 0) ? r[k].tail : r[k].head);
-                if (!in) { f[k].reset = 0; f[k].m = 0ull; }
-                mine = inst_then(mine, f[k]);
-                if (dir == 0) { cnt += r[k].c; nan |= r[k].nan; }
-            }
-            // inclusive scan of the threads' maps along the wavefront, the wavefronts' totals through LDS
-            InstMap inc = mine;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                InstMap o;
-                o.reset = __shfl_up(inc.reset, d);
-                o.m = __shfl_up(inc.m, d);
-                if (lane >= d) inc = inst_then(o, inc);
-            }
-            __syncthreads();                            // (the previous chunk's reads of wave_tot are done)
-            if (lane == 63) wave_tot[wave] = inc;
-            __syncthreads();
-            InstMap excl;
-            excl.reset = __shfl_up(inc.reset, 1);
-            excl.m = __shfl_up(inc.m, 1);
-            if (lane == 0) { excl.reset = 0; excl.m = 0ull; }
-            InstMap front = {0, 0ull}, all = {0, 0ull};
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                if (w < wave) front = inst_then(front, wave_tot[w]);
-                all = inst_then(all, wave_tot[w]);
-            }
-            unsigned long long v = inst_apply_map(inst_then(front, excl), run);   // in[] / out[] of the thread's first position
-#pragma unroll
-            for (int k = 0; k < R; ++k) {
-                const int64_t p = base + (int64_t)tid * R + k;
-                if (p < tiles) {
-                    const int64_t t = dir ? tiles - 1 - p : p;
-                    const unsigned long long head = __builtin_bit_cast(unsigned long long, r[k].head);
-                    if (dir == 0) {
-                        Ahead[t] = __builtin_bit_cast(double, inst_umax(v, head));
-                    } else {
-                        const unsigned long long tail = __builtin_bit_cast(unsigned long long, r[k].tail);
-                        if (r[k].c == 0) {
-                            const unsigned long long a = __builtin_bit_cast(unsigned long long, Ahead[t]);
-                            Ahead[t] = __builtin_bit_cast(double, inst_umax(a, v));
-                        }
-                        Atail[t] = __builtin_bit_cast(double, inst_umax(tail, v));
-                    }
-                }
-                v = inst_apply_map(f[k], v);
-            }
-            run = inst_apply_map(all, run);
-        }
-        // the backward pass reads the Ahead the forward pass wrote (other threads of this workgroup)
-        __threadfence_block();
-        __syncthreads();
-    }
-    if (info) {
-        if (cnt) atomicAdd(&sh_cnt, cnt);
-        if (nan) atomicOr(&sh_nan, 1);
-        __syncthreads();
-        if (tid == 0) info[row] = sh_nan ? -1 - sh_cnt : sh_cnt;
-    }
-}
-
-template <typename Tout>
-__device__ __forceinline__ void inst_store(Tout *__restrict__ out, int64_t j, double v)
-{
-    __builtin_nontemporal_store((Tout)v, &out[j]);
+    InstCarry pol = {rec + row * tiles, Ahead + row * tiles, Atail + row * tiles, info ? info + row : nullptr, sh};
+    halfwave_carry<NT>(pol, tiles);
 }
 
 template <typename Tin, typename Tout>
@@ -273,26 +177,8 @@ __global__ __launch_bounds__(64) void k_inst_apply(const Tin *__restrict__ rows,
     unsigned long long cm[kInstSteps];
     int before[kInstSteps];
     const int c = inst_load_tile<Tin>(x, n, s, lane, ext0, xr, xn, cm, before);
-    if (c >= 2) {
-        // half waves 1 .. c-1 begin and end inside the tile: their maxima by one LDS atomic per sample (a maximum does not depend
-        // on the order; lanes of one half wave meet on one word).  (A segmented scan over the lanes of every step — k_tfe_amplitude's,
-        // 18 dependent cross-lane moves per step — cost 0.24 ms of the call's 1.53 ms on 9 x 2^24 samples.)
-        for (int i = 1 + lane; i < c; i += 64) seg[i] = 0ull;
-        __syncthreads();
-#pragma unroll
-        for (int g = 0; g < kInstSteps; ++g) {
-            const int64_t j = s + g * 64 + lane;
-            if (before[g] > 0 && before[g] < c && j < n) atomicMax(&seg[before[g]], inst_mag(xr[g], true));
-        }
-        __syncthreads();
-    }
-    auto phase_in = [&](double xi, double slope, double Aa) {
-        if (!(Aa > 0.0)) return 0.0;                    // an all-zero half wave
-        const double r = xi / Aa;
-        const double as = asin(r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r));
-        if (xi >= 0.0) return slope >= 0.0 ? as : pi - as;
-        return slope < 0.0 ? pi - as : 2.0 * pi + as;
-    };
+    tile_segment_max<false>(seg, nullptr, lane, s, n, c, xr, before);
+    __syncthreads();
     // the row's last sample takes the backward difference, for its slope and for its frequency
     const bool last_tile = !has_ext;
     const int lp = (int)(n - 1 - s);                    // its position in this tile (last_tile)

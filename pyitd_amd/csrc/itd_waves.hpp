@@ -1,6 +1,6 @@
 // itd_waves.hpp — single-wave analysis of MANY rows in one asynchronous call: the table of a row's half waves (start, length, peak,
-// signed extremum) and the row filtered by its half waves' amplitude and length.  The structure is itd_tfe_batch.hpp's, extended
-// from "the maximum of a half wave" to "the maximum, where it first occurs, where the half wave begins and where it ends".
+// signed extremum) and the row filtered by its half waves' amplitude and length.  The tile pipeline of itd_halfwave.hpp with records
+// that hold, beyond "the maximum of a half wave" (itd_tfe_batch.hpp), where it first occurs, where the half wave begins and ends.
 //
 // A half wave is the run of samples between two crossing indices (tfe_crossing): half wave k holds start_k .. end_k with
 // start_0 = 0, start_k = c_{k-1} + 1, end_k = c_k, end_m = n - 1.  A_k = max |x| over it, peak_k the smallest index that attains
@@ -28,20 +28,17 @@
 //     k_wave_carry     the two scans, one workgroup per row; also the row's count and info                    24 + 16 B per tile
 //     k_wave_table     every tile writes the half waves that END in it (the row's last tile the row's last one) at prefix + rank
 //     k_wave_filter    reads the row again, stores keep ? x : +0.0 (streamed; rounded once where the output is float32)
-// No workgroup waits for another, no atomics on global memory, nothing read on the host, nothing outside the first n samples of
-// a row read.  Traffic of the filter for float64 in and out: 8 + 8 B read and 8 B written per sample, 80 B per tile written and
+// Traffic of the filter for float64 in and out: 8 + 8 B read and 8 B written per sample, 80 B per tile written and
 // read (0.3 B per sample).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "itd_tfe_batch.hpp"
+#include "itd_halfwave.hpp"
 
 #pragma clang fp contract(off)
 
 namespace itd {
-
-constexpr int32_t kWaveNone = INT32_MAX;        // the index of the identity: no sample
 
 struct WavePair {
     unsigned long long m;   // |x| as a bit pattern
@@ -94,18 +91,8 @@ __global__ __launch_bounds__(64) void k_wave_records(const Tin *__restrict__ row
     unsigned long long cm[kInstSteps];
     int before[kInstSteps];
     const int c = inst_load_tile<Tin>(x, n, s, lane, ext0, xr, xn, cm, before);
-    int fpos = kTfeTile - 1, lpos = kTfeTile - 1;
-    if (c > 0) {
-        bool found = false;
-#pragma unroll
-        for (int g = 0; g < kInstSteps; ++g) {
-            if (cm[g]) {
-                if (!found) fpos = g * 64 + __builtin_ctzll(cm[g]);
-                found = true;
-                lpos = g * 64 + 63 - __builtin_clzll(cm[g]);
-            }
-        }
-    }
+    int fpos, lpos;
+    tile_crossing_span(cm, fpos, lpos);
     WavePair hv = {0ull, kWaveNone}, tv = {0ull, kWaveNone};
     bool nan = false;
 #pragma unroll
@@ -146,136 +133,84 @@ struct WaveState {
     WavePair p;
     int32_t pos, cnt;
 };
-__device__ __forceinline__ WaveMap wave_then(WaveMap f, WaveMap g)
-{
-    WaveMap r;
-    r.reset = f.reset | g.reset;
-    r.p = g.reset ? g.p : wave_pick(f.p, g.p);
-    r.pos = g.reset ? g.pos : f.pos;
-    r.cnt = f.cnt + g.cnt;
-    return r;
-}
-__device__ __forceinline__ WaveState wave_apply_map(WaveMap f, WaveState s)
-{
-    WaveState r;
-    r.p = f.reset ? f.p : wave_pick(s.p, f.p);
-    r.pos = f.reset ? f.pos : s.pos;
-    r.cnt = s.cnt + f.cnt;
-    return r;
-}
-__device__ __forceinline__ WaveMap wave_map_up(WaveMap v, int d)
-{
-    WaveMap o;
-    o.reset = __shfl_up(v.reset, d);
-    o.p.m = __shfl_up(v.p.m, d);
-    o.p.i = __shfl_up(v.p.i, d);
-    o.pos = __shfl_up(v.pos, d);
-    o.cnt = __shfl_up(v.cnt, d);
-    return o;
-}
 
-// One workgroup per row, k_inst_carry's passes: position p is record p in the forward pass and record tiles - 1 - p in the
-// backward pass, NT * kInstCarryPer positions at a time, the running state carried from one such chunk to the next.
+// halfwave_carry's policy: the forward pass writes Fwd, the backward pass Bwd (neither reads the other's); the row's crossing
+// total rides in the map and is what the forward pass ends with.
+struct WaveCarry {
+    using Rec = WaveRec;
+    using Map = WaveMap;
+    using State = WaveState;
+    const WaveRec *rec;
+    WaveFwd *fwd;
+    WaveBwd *bwd;
+    int32_t n;
+    int32_t *count, *info;  // the row's words (or NULL)
+    int *sh_nan;            // one word, zeroed by the kernel in front of the scan
+    int nan = 0;
+    int32_t total = 0;      // the row's crossings (every thread holds it after the forward pass)
+
+    static __device__ __forceinline__ Map ident() { return {0, {0ull, kWaveNone}, 0, 0}; }
+    static __device__ __forceinline__ Map then(Map f, Map g)
+    {
+        return {f.reset | g.reset, g.reset ? g.p : wave_pick(f.p, g.p), g.reset ? g.pos : f.pos, f.cnt + g.cnt};
+    }
+    static __device__ __forceinline__ State apply(Map f, State s)
+    {
+        return {f.reset ? f.p : wave_pick(s.p, f.p), f.reset ? f.pos : s.pos, s.cnt + f.cnt};
+    }
+    static __device__ __forceinline__ Map up(Map v, int d)
+    {
+        return {__shfl_up(v.reset, d), {__shfl_up(v.p.m, d), __shfl_up(v.p.i, d)}, __shfl_up(v.pos, d), __shfl_up(v.cnt, d)};
+    }
+    __device__ __forceinline__ Rec load(int64_t t) const { return rec[t]; }
+    // forward: a tile with crossings hands on its tail and where it begins, one without joins its head; backward: the head
+    // either way, and with crossings where the half wave ends
+    __device__ __forceinline__ Map map(int dir, const Rec &r)
+    {
+        const bool cut = r.c > 0;
+        if (dir == 0) {
+            nan |= r.nan;
+            return {cut ? 1 : 0, {cut ? r.tm : r.hm, cut ? r.ti : r.hi}, cut ? r.last + 1 : 0, r.c};
+        }
+        return {cut ? 1 : 0, {r.hm, r.hi}, cut ? r.first : 0, 0};
+    }
+    __device__ __forceinline__ State start(int dir) const { return {{0ull, kWaveNone}, dir ? n - 1 : 0, 0}; }
+    __device__ __forceinline__ void emit(int dir, int64_t t, const Rec &r, State v) const
+    {
+        if (dir == 0) {
+            const WavePair a = wave_pick(v.p, WavePair{r.hm, r.hi});
+            fwd[t] = {a.m, a.i, v.pos, v.cnt, 0};
+        } else {
+            const WavePair a = wave_pick(WavePair{r.tm, r.ti}, v.p);
+            bwd[t] = {a.m, a.i, v.pos};
+        }
+    }
+    __device__ __forceinline__ void pass_end(int dir, State run)
+    {
+        if (dir == 0) total = run.cnt;
+    }
+    __device__ __forceinline__ void report(int tid) const
+    {
+        if (nan) atomicOr(sh_nan, 1);
+        __syncthreads();
+        if (tid == 0) {
+            if (count) *count = total + 1;
+            if (info) *info = *sh_nan ? -1 - total : total;
+        }
+    }
+};
+
+// One workgroup per row: halfwave_carry over the row's records; also the row's count and info.
 template <int NT>
 __global__ __launch_bounds__(NT) void k_wave_carry(const WaveRec *__restrict__ rec, int64_t tiles, int64_t n, WaveFwd *__restrict__ fwd,
                                                    WaveBwd *__restrict__ bwd, int32_t *__restrict__ count, int32_t *__restrict__ info)
 {
-    constexpr int NW = NT / 64, R = kInstCarryPer;
-    const WaveMap ident = {0, {0ull, kWaveNone}, 0, 0};
-    __shared__ WaveMap wave_tot[NW];
     __shared__ int sh_nan;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (threadIdx.x == 0) sh_nan = 0;                   // (the scan's barriers stand between this and report's atomic)
     const int64_t row = blockIdx.x;
-    rec += row * tiles;
-    fwd += row * tiles;
-    bwd += row * tiles;
-    if (tid == 0) sh_nan = 0;
-    int nan = 0;
-    int32_t total = 0;                                 // the row's crossings (every thread holds it after the forward pass)
-    for (int dir = 0; dir < 2; ++dir) {
-        WaveState run = {{0ull, kWaveNone}, dir ? (int32_t)(n - 1) : 0, 0};     // in[] / out[] of the chunk's first position
-        for (int64_t base = 0; base < tiles; base += (int64_t)NT * R) {
-            WaveRec r[R];
-            WaveMap f[R];
-            WaveMap mine = ident;
-#pragma unroll
-            for (int k = 0; k < R; ++k) {
-                const int64_t p = base + (int64_t)tid * R + k;
-                const bool in = p < tiles;
-                const int64_t t = dir ? tiles - 1 - p : p;
-                f[k] = ident;
-                if (in) {
-                    r[k] = rec[t];
-                    const bool cut = r[k].c > 0;
-                    f[k].reset = cut ? 1 : 0;
-                    // forward: a tile with crossings hands on its tail and where it begins, one without joins its head;
-                    // backward: the head either way, and with crossings where the half wave ends
-                    if (dir == 0) {
-                        f[k].p.m = cut ? r[k].tm : r[k].hm;
-                        f[k].p.i = cut ? r[k].ti : r[k].hi;
-                        f[k].pos = cut ? r[k].last + 1 : 0;
-                        f[k].cnt = r[k].c;
-                        nan |= r[k].nan;
-                    } else {
-                        f[k].p.m = r[k].hm;
-                        f[k].p.i = r[k].hi;
-                        f[k].pos = cut ? r[k].first : 0;
-                    }
-                } else {
-                    r[k].hm = r[k].tm = 0ull; r[k].c = r[k].nan = 0; r[k].hi = r[k].ti = kWaveNone; r[k].first = r[k].last = 0;
-                }
-                mine = wave_then(mine, f[k]);
-            }
-            // inclusive scan of the threads' maps along the wavefront, the wavefronts' totals through LDS
-            WaveMap inc = mine;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const WaveMap o = wave_map_up(inc, d);
-                if (lane >= d) inc = wave_then(o, inc);
-            }
-            __syncthreads();                            // (the previous chunk's reads of wave_tot are done)
-            if (lane == 63) wave_tot[wave] = inc;
-            __syncthreads();
-            WaveMap excl = wave_map_up(inc, 1);
-            if (lane == 0) excl = ident;
-            WaveMap front = ident, all = ident;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                if (w < wave) front = wave_then(front, wave_tot[w]);
-                all = wave_then(all, wave_tot[w]);
-            }
-            WaveState v = wave_apply_map(wave_then(front, excl), run);      // in[] / out[] of the thread's first position
-#pragma unroll
-            for (int k = 0; k < R; ++k) {
-                const int64_t p = base + (int64_t)tid * R + k;
-                if (p < tiles) {
-                    const int64_t t = dir ? tiles - 1 - p : p;
-                    if (dir == 0) {
-                        const WavePair h = {r[k].hm, r[k].hi};
-                        const WavePair a = wave_pick(v.p, h);
-                        WaveFwd o;
-                        o.m = a.m; o.i = a.i; o.start = v.pos; o.prefix = v.cnt; o.pad = 0;
-                        fwd[t] = o;
-                    } else {
-                        const WavePair tl = {r[k].tm, r[k].ti};
-                        const WavePair a = wave_pick(tl, v.p);
-                        WaveBwd o;
-                        o.m = a.m; o.i = a.i; o.end = v.pos;
-                        bwd[t] = o;
-                    }
-                }
-                v = wave_apply_map(f[k], v);
-            }
-            run = wave_apply_map(all, run);
-        }
-        if (dir == 0) total = run.cnt;
-    }
-    if (nan) atomicOr(&sh_nan, 1);
-    __syncthreads();
-    if (tid == 0) {
-        if (count) count[row] = total + 1;
-        if (info) info[row] = sh_nan ? -1 - total : total;
-    }
+    WaveCarry pol = {rec + row * tiles, fwd + row * tiles, bwd + row * tiles, (int32_t)n, count ? count + row : nullptr,
+                     info ? info + row : nullptr, &sh_nan};
+    halfwave_carry<NT>(pol, tiles);
 }
 
 // What the table and the filter need of a tile's half waves, by their number r = 0 .. c inside the tile, in LDS:
@@ -296,27 +231,7 @@ __device__ __forceinline__ void wave_tile_segments(WaveTileLds<kPeak> &L, int la
                                                    const unsigned long long (&cm)[kInstSteps], const int (&before)[kInstSteps],
                                                    const WaveFwd F, const WaveBwd B)
 {
-    if (c >= 2) {
-        for (int i = 1 + lane; i < c; i += 64) {
-            L.mag[i] = 0ull;
-            if (kPeak) L.peak[i] = kWaveNone;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int g = 0; g < kInstSteps; ++g) {
-            const int64_t j = s + g * 64 + lane;
-            if (before[g] > 0 && before[g] < c && j < n) atomicMax(&L.mag[before[g]], inst_mag(xr[g], true));
-        }
-        if (kPeak) {
-            __syncthreads();
-#pragma unroll
-            for (int g = 0; g < kInstSteps; ++g) {
-                const int64_t j = s + g * 64 + lane;
-                if (before[g] > 0 && before[g] < c && j < n && inst_mag(xr[g], true) == L.mag[before[g]])
-                    atomicMin(&L.peak[before[g]], (int32_t)j);
-            }
-        }
-    }
+    tile_segment_max<kPeak>(L.mag, L.peak, lane, s, n, c, xr, before);
     // a crossing index is the last sample of the half wave it belongs to
 #pragma unroll
     for (int g = 0; g < kInstSteps; ++g)

@@ -1,12 +1,13 @@
 """The batched instantaneous step (itd_instantaneous_batch_f64 / _f32, pyitd_amd.instantaneous_batch; itd_tfe_batch.hpp) against
 the single-row operator (bit for bit: the same expressions on the same operands) and, independently of it, against the exact
 results of oracle/exact_tfe.py with test_gpu_instantaneous_exact.py's bounds: amplitude bit for bit, phase within 4 ulp(2 pi) of
-the exact value, frequency within 8 ulp(2 pi) / 2 pi of it.
+the exact value, frequency within 8 ulp(2 pi) / 2 pi of it — at every length of that file's LENGTHS too.
 
 Where the kernels can go wrong: a half wave inside one 64-sample step, across steps of a tile, across tiles (the tile records and
 their scan along the row), across the scan's chunks — k_inst_carry takes K = 2048 records (2^20 samples) per pass on rows of more
 than 512 tiles, the forward pass counted from the row's first tile and the backward pass from its last; the row of
-(2 K + 1) * 512 + 5 samples below was written for that K — the row's last sample in a tile of its own, strides, output subsets,
+(2 K + 1) * 512 + 5 samples below was written for that K, the rows of 512, 513 and 514 tiles for the seam between
+k_inst_carry<64> and k_inst_carry<256> — the row's last sample in a tile of its own, strides, output subsets,
 float32 rows in and out, NaN rows, more rows than one launch's grid takes, a caller's stream and a captured graph.
 The file also passes with PYITD_POISON=1.
 """
@@ -85,6 +86,15 @@ def test_signal_families_against_the_exact_reference(P, n):
         check(rows[r], a[r], p[r], f[r], what="%s n=%d" % (fam, n))
 
 
+def test_every_length_near_the_step_and_tile_seams_against_the_exact_reference(P):
+    fams = ("seams", "quantised")
+    for n in LENGTHS:
+        rows = np.stack([family(fam, n) for fam in fams])
+        a, p, f = P.instantaneous_batch(rows)
+        for r, fam in enumerate(fams):
+            check(rows[r], a[r], p[r], f[r], what="%s n=%d" % (fam, n))
+
+
 # ---- 3. half waves across many tiles and across the carry's chunk seams ------------------------------------------------------
 def test_half_waves_of_many_tiles(P):
     n = 60000
@@ -132,6 +142,25 @@ def test_half_waves_across_the_carry_chunks(P):
     for r in range(2):
         assert a[r, 0] == 0.9375 and a[r, -1] == 0.96875
         _check_long(rows[r], a[r], p[r], f[r], "single crossing, row %d" % r)
+
+
+@pytest.mark.parametrize("tiles", (512, 513, 514))
+def test_one_row_across_the_carry_instantiations(P, tiles):
+    """Rows of (tiles - 1) * 512 + 5 samples with a single crossing and the two maxima at the row's second and last sample, as
+    above, through the single-row call and through the batched call of one row: 512 tiles is the longest such row that
+    k_inst_carry<64> takes (one pass of one wavefront, every thread's eight records in use), 513 and 514 tiles are the shortest
+    that go to k_inst_carry<256>."""
+    n = (tiles - 1) * 512 + 5
+    rng = np.random.default_rng(tiles)
+    x = with_crossings(n, [100 * 512 + 300], rng, mag=0.1 + 0.5 * rng.random(n))
+    x[1] = 0.9375
+    x[-1] = np.sign(x[-1]) * 0.96875
+    assert np.count_nonzero(et.structure(x)[0]) == 1
+    a, p, f = P.instantaneous(x)
+    assert a[0] == 0.9375 and a[-1] == 0.96875
+    _check_long(x, a, p, f, "single crossing, %d tiles" % tiles)
+    for got, want, what in zip(P.instantaneous_batch(x[None, :]), (a, p, f), NAMES):
+        _bits(got[0], want, "%d tiles, batched: %s" % (tiles, what))
 
 
 # ---- 4. strides and confinement ------------------------------------------------------------------------------------------
@@ -256,6 +285,39 @@ def test_on_a_callers_stream_and_in_a_graph(P, eng):
         for k, w in zip(NAMES, eager):
             _bits(d.get(k), w, "replayed: %s" % k)
         assert d.get("info").tolist() == [int(np.count_nonzero(et.structure(r)[0])) for r in y]
+    d.free()
+
+
+def test_a_captured_graph_survives_a_larger_single_row_call(P, eng):
+    """The batched call's workspace is its own: a single-row call of 8192 samples on the same engine, after the 2 x 1030 call was
+    captured, leaves the captured launches' addresses valid, and the replay equals the uncaptured call bit for bit."""
+    import torch
+    n, R, big = 1030, 2, 8192
+    rows = np.stack([family(f, n) for f in ("seams", "noise")])
+    sent = np.full((R, n), SENT)
+    d = DevArrays(eng, x=rows, a=sent, p=sent, f=sent, info=np.zeros(R, np.int32),
+                  y=family("noise", big), ya=np.zeros(big), yp=np.zeros(big), yf=np.zeros(big))
+    args = (d.ptr("x"), np.float64, n, R, n, d.ptr("a"), d.ptr("p"), d.ptr("f"), n, False, d.ptr("info"))
+    s = torch.cuda.Stream()
+    eng.instantaneous_batch_dev(*args, s.cuda_stream)           # (the warm-up of this size: the capture allocates nothing)
+    s.synchronize()
+    want = {k: d.get(k) for k in NAMES}
+    for r in range(R):
+        check(rows[r], want["a"][r], want["p"][r], want["f"][r], what="uncaptured row %d" % r)
+    g = torch.cuda.CUDAGraph()
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(g, stream=side):
+            eng.instantaneous_batch_dev(*args, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    rc = eng._L.itd_instantaneous_f64(eng._h, d.ptr("y"), big, d.ptr("ya"), d.ptr("yp"), d.ptr("yf"), None)
+    assert rc == 0, rc
+    for k in NAMES:
+        d.put(k, sent)
+    g.replay()
+    torch.cuda.synchronize()
+    for k in NAMES:
+        _bits(d.get(k), want[k], "replayed behind the single-row call: %s" % k)
     d.free()
 
 

@@ -109,6 +109,24 @@ def test_power_of_two_scaling(P, fam):
             _bits(f2, f, "%s 2^%d frequency" % (fam, k))
 
 
+def test_a_row_with_a_nan_is_refused_with_the_outputs_untouched(P):
+    """1030 samples are three tiles, the last of 6 samples; the NaN sits in the second.  itd_instantaneous_f64 answers
+    ITD_ERR_NONFINITE and has written nothing: every element of the three outputs keeps its sentinel."""
+    from pyitd_amd.engine import ITD_ERR_NONFINITE
+    from pyitd_amd.itd import _engine_for
+    n = 1030
+    x = family("noise", n)
+    x[700] = np.nan
+    eng = _engine_for(n)
+    sent = np.full(n + 13, SENT)
+    d = DevArrays(eng, x=x, a=sent, p=sent, f=sent)
+    rc = eng._L.itd_instantaneous_f64(eng._h, d.ptr("x"), n, d.ptr("a"), d.ptr("p"), d.ptr("f"), None)
+    assert rc == ITD_ERR_NONFINITE, rc
+    for k in ("a", "p", "f"):
+        assert np.all(d.get(k) == SENT), "%s is written" % k
+    d.free()
+
+
 def test_device_form_every_subset_of_outputs_on_a_callers_stream(P):
     """itd_instantaneous_f64 on device buffers: the input is filled by a copy queued on the caller's stream, the call runs on
     that stream, the results are read after that stream alone has been synchronised; every non-empty subset of outputs equals
