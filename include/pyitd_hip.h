@@ -606,6 +606,39 @@ int itd_instantaneous_batch_f64(itd_engine *e, const double *rows_dev, int64_t n
 int itd_instantaneous_batch_f32(itd_engine *e, const float *rows_dev, int64_t n, int32_t rows, int64_t row_stride, void *amp_dev,
                                 void *phase_dev, void *freq_dev, int64_t out_stride, int32_t out_f32, int32_t *info_dev, void *stream);
 
+/* ---- the time-frequency-energy spectrum of many rows: every row's energy binned over time and frequency:
+ * asynchronous on `stream`, no host synchronisation, no host read, graph-capturable.  For a row x[0..n) that holds no NaN, A[j] and
+ * f[j] are the instantaneous amplitude and frequency (cycles per sample) — the same bits itd_instantaneous_batch_* stores in
+ * float64 — and never leave the GPU's registers.
+ *   edges_dev [bins + 1] float64, finite and strictly increasing, 1 <= bins <= 512: device memory, read when the call runs — a
+ *     captured call bins with whatever they hold at its replay.  Their order cannot be checked without reading device memory:
+ *     unordered edges give unspecified bins (nothing outside the outputs is written).
+ *   hop: a positive multiple of 64; below 512 only 64, 128 or 256.  T = ceil(n / hop) time bins.
+ *   weight: 0 = count (w = 1.0), 1 = amplitude (w = A), 2 = energy (w = A * A, one float64 multiply).
+ * The frequency bin of sample j is the k with edges[k] <= f[j] && f[j] < edges[k+1] as IEEE comparisons; a sample with no such k
+ * (f below edges[0], at or above edges[bins], NaN) is OUTSIDE.  The order of every sum is part of the definition:
+ *   step sum   step s covers samples 64 s .. 64 s + 63, counted from the row's first sample.  v[l] = w[64 s + l] if that sample
+ *              exists and lies in bin k, else +0.0; the 64 values are reduced by the adjacent-pair tree (v0 + v1), (v2 + v3), ...,
+ *              then pairs of those, six levels.  All weights are non-negative, so the +0.0 entries change nothing.
+ *   cell       S[t, k] starts at +0.0; the step sums of the steps t * hop / 64 .. (t + 1) * hop / 64 - 1 that exist are added one
+ *              after the other, in increasing step order.
+ *   outside    outside[t] = the number of outside samples with j / hop == t.
+ * Row r's spectrum [T][bins] float64 (also for float32 rows) sits at spec_dev + r * spec_stride, spec_stride >= T * bins when
+ * rows > 1; outside_dev (optional) [rows][T] int32, dense.  Every cell and every entry is written, an empty cell as +0.0: the
+ * buffers need no clearing, and nothing else is written.  No atomics on global memory and no floating-point atomics: the result
+ * is the same bits from run to run and in any batch position.  Rows, n, row_stride, chunking and info_dev as for
+ * itd_instantaneous_batch_* (info: the zero-crossing count, -1 - count if the row holds a NaN — that row's spectrum is then not to
+ * be used).  ITD_ERR_INVALID_ARG before any launch for bins, hop or weight out of range, n < 3 or a stride too small.  The parallel
+ * grain is (row, time bin) — (row, 512 samples) where hop < 512: a caller who wants a marginal spectrum sums a spectrum of many
+ * time bins rather than asking for hop >= n.  The workspace (40 bytes per 512 samples of min(rows, 65535) rows) is the engine's
+ * own, apart from the instantaneous step's, grown on demand: the capture rule of the batched single-level operators above holds. */
+int itd_tfe_spectrum_f64(itd_engine *e, const double *rows_dev, int64_t n, int32_t rows, int64_t row_stride, const double *edges_dev,
+                         int32_t bins, int64_t hop, int32_t weight, double *spec_dev, int64_t spec_stride, int32_t *outside_dev,
+                         int32_t *info_dev, void *stream);
+int itd_tfe_spectrum_f32(itd_engine *e, const float *rows_dev, int64_t n, int32_t rows, int64_t row_stride, const double *edges_dev,
+                         int32_t bins, int64_t hop, int32_t weight, double *spec_dev, int64_t spec_stride, int32_t *outside_dev,
+                         int32_t *info_dev, void *stream);
+
 /* ---- single-wave analysis of many rows (README.md:18-21, 47-53: "feature-based filtering" on the half waves): asynchronous on
  * `stream`, no host synchronisation, no host read, graph-capturable.  A row's crossing indices c_0 < ... < c_{m-1} are those of
  * itd_instantaneous_* (1 <= i <= n - 2 with a strict sign change x[i] -> x[i+1]); half wave k (0 <= k <= m) holds the samples

@@ -81,6 +81,8 @@ ABI = {
     "itd_baseline_extract_cubic_batch_f64": (_INT, [_P, _P, _I64, _I32, _I64, _P, _I64, _I64, _P, _I64, _P, _P]),
     "itd_instantaneous_batch_f64": (_INT, [_P, _P, _I64, _I32, _I64, _P, _P, _P, _I64, _I32, _P, _P]),
     "itd_instantaneous_batch_f32": (_INT, [_P, _P, _I64, _I32, _I64, _P, _P, _P, _I64, _I32, _P, _P]),
+    "itd_tfe_spectrum_f64": (_INT, [_P, _P, _I64, _I32, _I64, _P, _I32, _I64, _I32, _P, _I64, _P, _P, _P]),
+    "itd_tfe_spectrum_f32": (_INT, [_P, _P, _I64, _I32, _I64, _P, _I32, _I64, _I32, _P, _I64, _P, _P, _P]),
     "itd_waves_batch_f64": (_INT, [_P, _P, _I64, _I32, _I64, _P, _P, _P, _P, _I64, _I32, _P, _P, _P]),
     "itd_waves_batch_f32": (_INT, [_P, _P, _I64, _I32, _I64, _P, _P, _P, _P, _I64, _I32, _P, _P, _P]),
     "itd_wave_filter_batch_f64": (_INT, [_P, _P, _I64, _I32, _I64, _P, _I64, _P, _I64, _I32, _P, _P]),

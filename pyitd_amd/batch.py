@@ -244,8 +244,72 @@ def instantaneous_batch(rows, device=0, out_dtype=None, want=_INSTANTANEOUS):
         return tuple(bufs[w].download(numpy.empty((R, n), odt)).reshape(shape) for w in want)
 
 
+# ---- the time-frequency-energy spectrum (itd_tfe_spectrum_*) ---------------------------------------------------------------
+Spectrum = namedtuple("Spectrum", "power outside")
+_WEIGHTS = ("count", "amplitude", "energy")
+MAX_BINS = 512
+
+
+def _spectrum_args(edges, hop, weight):
+    """The checked (edges float64 [F + 1], hop, weight code) of tfe_spectrum."""
+    if _is_torch(edges):
+        edges = edges.detach().cpu().numpy()
+    e = numpy.ascontiguousarray(edges, dtype=numpy.float64)
+    if e.ndim != 1 or not 2 <= e.size <= MAX_BINS + 1:
+        raise ValueError("edges: a 1-D array of 2 to %d entries, got shape %s" % (MAX_BINS + 1, e.shape))
+    if not numpy.isfinite(e).all() or not (e[1:] > e[:-1]).all():
+        raise ValueError("edges must be finite and strictly increasing")
+    if isinstance(hop, bool) or int(hop) != hop or hop < 64 or hop % 64 != 0 or (hop < 512 and hop not in (64, 128, 256)):
+        raise ValueError("hop: a positive multiple of 64 (below 512: 64, 128 or 256), got %r" % (hop,))
+    if weight not in _WEIGHTS:
+        raise ValueError("weight: one of %s, got %r" % (_WEIGHTS, weight))
+    return e, int(hop), _WEIGHTS.index(weight)
+
+
+def tfe_spectrum(rows, edges, hop, weight="energy", device=0):
+    """The time-frequency-energy spectrum of every row of rows[..., n] in one asynchronous call: the row's instantaneous amplitude A
+    and frequency f (instantaneous_batch; cycles per sample) binned over time — T = ceil(n / hop) bins of hop samples — and over
+    frequency — F = len(edges) - 1 bins, sample j in bin k where edges[k] <= f[j] < edges[k+1].  Returns
+    Spectrum(power[..., T, F] float64, outside[..., T] int32): power sums 1 ("count"), A ("amplitude") or A * A ("energy") over the
+    samples of a cell; outside counts the samples of a time bin whose frequency lies in no bin.  The order of every sum is fixed
+    (include/pyitd_hip.h): the result is the same bits from run to run and in any batch position, and A and f are never stored.
+
+    rows: float64 or float32, a numpy array or a torch CUDA tensor (used in place; its leading axes must collapse to one row stride,
+    its last axis must be dense; tensors come back on its device).  edges: 2 to 513 finite, strictly increasing values.  hop: a
+    positive multiple of 64, below 512 only 64, 128 or 256.  The parallel grain is (row, time bin): a caller who wants the
+    marginal spectrum sums a spectrum of many time bins rather than asking for hop >= n.  Raises ValueError for bad edges, hop or
+    weight, ITDError (non-finite) naming the rows that hold a NaN."""
+    e, hop, wcode = _spectrum_args(edges, hop, weight)
+    torch_in, a, idt, shape, n, R = _accept_rows(rows, "the spectrum")
+    F, T = e.size - 1, -(-n // hop)
+    lead = shape[:-1]
+    if torch_in:
+        import torch
+        stride = _tensor_stride(a, shape)
+        dev = a.device.index
+        power = torch.empty((R, T, F), dtype=torch.float64, device=a.device)
+        outside = torch.empty((R, T), dtype=torch.int32, device=a.device)
+        info = torch.empty(R, dtype=torch.int32, device=a.device)
+        d_e = torch.from_numpy(e).to(a.device)
+        eng = _engine_for(3, dev)
+        torch.cuda.synchronize(a.device)    # the engine runs on its own stream
+        eng.tfe_spectrum_dev(a.data_ptr(), idt, n, R, stride, d_e.data_ptr(), F, hop, wcode, power.data_ptr(), T * F, outside.data_ptr(),
+                             info.data_ptr())
+        torch.cuda.synchronize(a.device)
+        _refuse_nan(info.cpu().numpy())
+        return Spectrum(power.reshape(lead + (T, F)), outside.reshape(lead + (T,)))
+    a = numpy.ascontiguousarray(a).reshape(R, n)
+    with _Staged(device) as S:
+        d_x, d_e, d_p, d_o, d_info = S.upload(a), S.upload(e), S.empty(8 * R * T * F), S.empty(4 * R * T), S.empty(4 * R)
+        eng = _engine_for(3, S.dev)
+        eng.tfe_spectrum_dev(d_x.ptr, idt, n, R, n, d_e.ptr, F, hop, wcode, d_p.ptr, T * F, d_o.ptr, d_info.ptr)
+        _refuse_nan(d_info.download(numpy.empty(R, numpy.int32)))          # itd_dev_copy synchronises
+        return Spectrum(d_p.download(numpy.empty((R, T, F))).reshape(lead + (T, F)),
+                        d_o.download(numpy.empty((R, T), numpy.int32)).reshape(lead + (T,)))
+
+
 # ---- single-wave analysis: the table of half waves and the feature filter (itd_waves_batch_*, itd_wave_filter_batch_*) -------
-Waves = namedtuple("Waves", "count start length peak value")
+Waves =namedtuple("Waves", "count start length peak value")
 
 
 def _refuse_overflow(count, cap):

@@ -6,6 +6,7 @@
 //       itd_baseline_extract_cubic_batch_f64  itd_fourier_decomposition.py:49-122 with one retained knot list for every
 //                                             channel (itd.cpp:40-44) or one list / the detected knots per signal
 //       itd_instantaneous_batch_f64 / _f32    amplitude, phase and frequency of every row (itd_tfe_batch.hpp)
+//       itd_tfe_spectrum_f64 / _f32           every row's energy binned over time and frequency (itd_tfe_spectrum.hpp)
 //       itd_waves_batch_f64 / _f32            the table of every row's half waves (itd_waves.hpp)
 //       itd_wave_filter_batch_f64 / _f32      every row filtered by its half waves' amplitude and length (itd_waves.hpp)
 //   * block-wise operation (itd.cpp:31-38), itd_stream_*: a device-resident mirrored ring per channel (itd_stream.hpp), the
@@ -112,15 +113,22 @@ A *at(A *p, int64_t off) { return p ? p + off : nullptr; }
 // ... of float64 / float32 samples
 void *at(void *p, int64_t off, int32_t f32) { return p ? (char *)p + (size_t)off * (f32 ? sizeof(float) : sizeof(double)) : nullptr; }
 
+// records and carry of nb rows: Ahead / Atail of every tile, the rows' info words
+template <typename Tin>
+void inst_scan(const InstWs &w, const Tin *x, int64_t x_stride, int64_t n, int nb, int32_t *info, hipStream_t st)
+{
+    k_inst_records<Tin><<<dim3((unsigned)w.tiles, (unsigned)nb), kWave, 0, st>>>(x, x_stride, n, w.tiles, w.rec);
+    if (w.tiles <= kInstCarrySmall) k_inst_carry<64><<<nb, 64, 0, st>>>(w.rec, w.tiles, w.head, w.tail, info);
+    else k_inst_carry<kInstCarryThreads><<<nb, kInstCarryThreads, 0, st>>>(w.rec, w.tiles, w.head, w.tail, info);
+}
+
 template <typename Tin, typename Tout>
 void inst_chunk(const InstWs &w, const Tin *x, int64_t x_stride, int64_t n, int nb, void *amp, void *phase, void *freq, int64_t out_stride,
                 int32_t *info, hipStream_t st)
 {
-    const dim3 grid((unsigned)w.tiles, (unsigned)nb);
-    k_inst_records<Tin><<<grid, kWave, 0, st>>>(x, x_stride, n, w.tiles, w.rec);
-    if (w.tiles <= kInstCarrySmall) k_inst_carry<64><<<nb, 64, 0, st>>>(w.rec, w.tiles, w.head, w.tail, info);
-    else k_inst_carry<kInstCarryThreads><<<nb, kInstCarryThreads, 0, st>>>(w.rec, w.tiles, w.head, w.tail, info);
-    k_inst_apply<Tin, Tout><<<grid, kWave, 0, st>>>(x, x_stride, n, w.tiles, w.head, w.tail, (Tout *)amp, (Tout *)phase, (Tout *)freq, out_stride);
+    inst_scan<Tin>(w, x, x_stride, n, nb, info, st);
+    k_inst_apply<Tin, Tout><<<dim3((unsigned)w.tiles, (unsigned)nb), kWave, 0, st>>>(x, x_stride, n, w.tiles, w.head, w.tail, (Tout *)amp, (Tout *)phase,
+                                                                                     (Tout *)freq, out_stride);
 }
 
 template <typename Tin>
@@ -139,6 +147,32 @@ int inst_batch(itd_engine *e, const Tin *x, int64_t n, int32_t rows, int64_t x_s
         void *a = at(amp, off, out_f32), *p = at(phase, off, out_f32), *f = at(freq, off, out_f32);
         if (out_f32) inst_chunk<Tin, float>(w, xc, x_stride, n, nb, a, p, f, out_stride, at(info, b0), st);
         else inst_chunk<Tin, double>(w, xc, x_stride, n, nb, a, p, f, out_stride, at(info, b0), st);
+    });
+}
+
+// The time-frequency-energy spectrum (itd_tfe_spectrum.hpp): the instantaneous step's scan in a workspace of its own (d_ts: a
+// captured instantaneous call stays valid), then k_tfe_bin — one wavefront per (row, time bin), per (row, tile) where hop < 512.
+template <typename Tin>
+int tfe_spectrum(itd_engine *e, const Tin *x, int64_t n, int32_t rows, int64_t x_stride, const double *edges, int32_t bins, int64_t hop,
+                 int32_t weight, double *spec, int64_t spec_stride, int32_t *outside, int32_t *info, void *stream)
+{
+    if (!tile_args_ok(e, x, n, rows, x_stride, edges && spec)) return ITD_ERR_INVALID_ARG;
+    if (bins < 1 || bins > kTfeMaxBins || weight < 0 || weight > 2) return ITD_ERR_INVALID_ARG;
+    if (hop < 64 || hop % 64 != 0 || (hop < kTfeTile && hop != 64 && hop != 128 && hop != 256)) return ITD_ERR_INVALID_ARG;
+    const int64_t T = (n + hop - 1) / hop;
+    if (rows > 1 && spec_stride < T * bins) return ITD_ERR_INVALID_ARG;
+    DevGuard g(e->device);
+    hipStream_t st = stream_of(e, stream);
+    InstWs w;
+    const int rc = tile_workspace(e, e->d_ts, n, rows, w);
+    if (rc) return rc;
+    const size_t lds = (3 * (size_t)bins + 1) * sizeof(double);      // acc[bins], edges[bins + 1], msk[bins]
+    return for_row_chunks(e, rows, w.chunk, [&](int b0, int nb) {
+        const Tin *xc = x + (int64_t)b0 * x_stride;
+        inst_scan<Tin>(w, xc, x_stride, n, nb, at(info, b0), st);
+        const dim3 grid((unsigned)(hop >= kTfeTile ? T : w.tiles), (unsigned)nb);
+        k_tfe_bin<Tin><<<grid, kWave, lds, st>>>(xc, x_stride, n, w.tiles, w.head, w.tail, edges, bins, hop, weight, T,
+                                                 spec + (int64_t)b0 * spec_stride, spec_stride, at(outside, (int64_t)b0 * T));
     });
 }
 
@@ -343,6 +377,19 @@ int itd_instantaneous_batch_f32(itd_engine *e, const float *rows_dev, int64_t n,
                                 void *phase_dev, void *freq_dev, int64_t out_stride, int32_t out_f32, int32_t *info_dev, void *stream)
 {
     return inst_batch<float>(e, rows_dev, n, rows, row_stride, amp_dev, phase_dev, freq_dev, out_stride, out_f32, info_dev, stream);
+}
+
+int itd_tfe_spectrum_f64(itd_engine *e, const double *rows_dev, int64_t n, int32_t rows, int64_t row_stride, const double *edges_dev,
+                         int32_t bins, int64_t hop, int32_t weight, double *spec_dev, int64_t spec_stride, int32_t *outside_dev,
+                         int32_t *info_dev, void *stream)
+{
+    return tfe_spectrum<double>(e, rows_dev, n, rows, row_stride, edges_dev, bins, hop, weight, spec_dev, spec_stride, outside_dev, info_dev, stream);
+}
+int itd_tfe_spectrum_f32(itd_engine *e, const float *rows_dev, int64_t n, int32_t rows, int64_t row_stride, const double *edges_dev,
+                         int32_t bins, int64_t hop, int32_t weight, double *spec_dev, int64_t spec_stride, int32_t *outside_dev,
+                         int32_t *info_dev, void *stream)
+{
+    return tfe_spectrum<float>(e, rows_dev, n, rows, row_stride, edges_dev, bins, hop, weight, spec_dev, spec_stride, outside_dev, info_dev, stream);
 }
 
 int itd_waves_batch_f64(itd_engine *e, const double *rows_dev, int64_t n, int32_t rows, int64_t row_stride, int32_t *start_dev,

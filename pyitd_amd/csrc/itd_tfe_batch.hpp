@@ -155,19 +155,19 @@ __global__ __launch_bounds__(NT) void k_inst_carry(const InstRec *__restrict__ r
     halfwave_carry<NT>(pol, tiles);
 }
 
-template <typename Tin, typename Tout>
-__global__ __launch_bounds__(64) void k_inst_apply(const Tin *__restrict__ rows, int64_t row_stride, int64_t n, int64_t tiles,
-                                                   const double *__restrict__ Ahead, const double *__restrict__ Atail,
-                                                   Tout *__restrict__ amp_out, Tout *__restrict__ phase_out,
-                                                   Tout *__restrict__ freq_out, int64_t out_stride)
+// One tile's amplitudes, phases and frequencies, handed to a sink sample by sample: what k_inst_apply stores and what k_tfe_bin
+// (itd_tfe_spectrum.hpp) bins, from the same expressions.  Called by the tile's wavefront (one wavefront per workgroup); seg:
+// kTfeTile + 1 words of LDS; rt: the tile's index into Ahead / Atail (row * tiles + t).  The sink receives
+//     sample(g, j, in, A, ph)    the lane's sample j = s + 64 g + lane (in: j < n): amplitude and phase
+//     freq(g, j, write, f)       its frequency (asked for by want_f); write is false behind the row's end and for the lone sample
+//                                of a row's last tile, whose frequency comes from the tile before:
+//     last(A, f)                 sample n - 1 = s + 512, where that is the row's last: its amplitude and frequency (all lanes)
+template <typename Tin, typename Sink>
+__device__ __forceinline__ void inst_tile_eval(const Tin *__restrict__ x, int64_t n, int64_t s, int64_t rt, int lane,
+                                               const double *__restrict__ Ahead, const double *__restrict__ Atail,
+                                               unsigned long long *seg, bool want_f, Sink &sink)
 {
     const double pi = 3.14159265358979323846;
-    __shared__ unsigned long long seg[kTfeTile + 1];   // max |x| of the tile's half waves, by their number inside the tile
-    const int lane = threadIdx.x;
-    const int64_t t = blockIdx.x, s = t * kTfeTile;
-    const Tin *x = rows + (int64_t)blockIdx.y * row_stride;
-    const int64_t o = (int64_t)blockIdx.y * out_stride;
-    const int64_t rt = (int64_t)blockIdx.y * tiles + t;
     const bool has_ext = s + kTfeTile < n;              // sample s + 512 exists: the tile is not the row's last
     const double ext = (lane < 2 && s + kTfeTile + lane < n) ? (double)x[s + kTfeTile + lane] : 0.0;
     const double ext0 = __shfl(ext, 0), ext1 = __shfl(ext, 1);
@@ -210,9 +210,8 @@ __global__ __launch_bounds__(64) void k_inst_apply(const Tin *__restrict__ rows,
     for (int g = 0; g < kInstSteps; ++g) {
         const int64_t j = s + g * 64 + lane;
         const bool in = j < n;
-        if (in && amp_out) inst_store<Tout>(amp_out + o, j, A[g]);
-        if (in && phase_out) inst_store<Tout>(phase_out + o, j, ph[g]);
-        if (freq_out) {
+        sink.sample(g, j, in, A[g], ph[g]);
+        if (want_f) {
             const double nxt = __shfl_down(ph[g], 1);
             const double first_next = g + 1 < kInstSteps ? __shfl(ph[g + 1 < kInstSteps ? g + 1 : g], 0) : ph_ext;
             double dp = (lane == 63 ? first_next : nxt) - ph[g];
@@ -226,16 +225,52 @@ __global__ __launch_bounds__(64) void k_inst_apply(const Tin *__restrict__ rows,
                 }
             }
             if (dp < 0.0) dp += 2.0 * pi;               // the phase wraps once per wave
-            if (write) inst_store<Tout>(freq_out + o, j, dp / (2.0 * pi));
+            sink.freq(g, j, write, dp / (2.0 * pi));
         }
     }
-    if (freq_out && has_ext && s + kTfeTile == n - 1) {
+    if (want_f && has_ext && s + kTfeTile == n - 1) {
         // sample s + 512 is the row's last: its backward difference is this tile's last forward one
         const double p_last = __shfl(ph[kInstSteps - 1], 63);
         double dp = ph_ext - p_last;
         if (dp < 0.0) dp += 2.0 * pi;
-        if (lane == 0) inst_store<Tout>(freq_out + o, n - 1, dp / (2.0 * pi));
+        sink.last(A_ext, dp / (2.0 * pi));
     }
+}
+
+// k_inst_apply's sink: streamed stores of the outputs asked for
+template <typename Tout>
+struct InstStore {
+    Tout *amp_out, *phase_out, *freq_out;       // the row's outputs (or NULL)
+    int64_t n;
+    int lane;
+    __device__ __forceinline__ void sample(int, int64_t j, bool in, double A, double ph) const
+    {
+        if (in && amp_out) inst_store<Tout>(amp_out, j, A);
+        if (in && phase_out) inst_store<Tout>(phase_out, j, ph);
+    }
+    __device__ __forceinline__ void freq(int, int64_t j, bool write, double f) const
+    {
+        if (write) inst_store<Tout>(freq_out, j, f);
+    }
+    __device__ __forceinline__ void last(double, double f) const
+    {
+        if (lane == 0) inst_store<Tout>(freq_out, n - 1, f);
+    }
+};
+
+template <typename Tin, typename Tout>
+__global__ __launch_bounds__(64) void k_inst_apply(const Tin *__restrict__ rows, int64_t row_stride, int64_t n, int64_t tiles,
+                                                   const double *__restrict__ Ahead, const double *__restrict__ Atail,
+                                                   Tout *__restrict__ amp_out, Tout *__restrict__ phase_out,
+                                                   Tout *__restrict__ freq_out, int64_t out_stride)
+{
+    __shared__ unsigned long long seg[kTfeTile + 1];   // max |x| of the tile's half waves, by their number inside the tile
+    const int lane = threadIdx.x;
+    const int64_t t = blockIdx.x, s = t * kTfeTile;
+    const Tin *x = rows + (int64_t)blockIdx.y * row_stride;
+    const int64_t o = (int64_t)blockIdx.y * out_stride;
+    InstStore<Tout> sink = {amp_out ? amp_out + o : nullptr, phase_out ? phase_out + o : nullptr, freq_out ? freq_out + o : nullptr, n, lane};
+    inst_tile_eval<Tin>(x, n, s, (int64_t)blockIdx.y * tiles + t, lane, Ahead, Atail, seg, freq_out != nullptr, sink);
 }
 
 }  // namespace itd

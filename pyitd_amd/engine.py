@@ -463,6 +463,15 @@ class Engine:
         self._check(fn(self._h, rows_ptr, n, rows, row_stride, amp_ptr, phase_ptr, freq_ptr, out_stride, 1 if out_f32 else 0,
                        info_ptr, stream))
 
+    def tfe_spectrum_dev(self, rows_ptr, dtype, n, rows, row_stride, edges_ptr, bins, hop, weight, spec_ptr, spec_stride,
+                         outside_ptr=None, info_ptr=None, stream=None):
+        """The time-frequency-energy spectrum of every row (float32 or float64 by `dtype`): float64 [T, bins] per row at
+        spec_stride elements, T = ceil(n / hop); edges float64 [bins + 1] in device memory; weight 0 count, 1 amplitude, 2 energy;
+        outside int32 [rows, T] (optional); info as for instantaneous_batch_dev.  Pointers in, nothing copied, nothing awaited."""
+        fn = self._L.itd_tfe_spectrum_f32 if np.dtype(dtype) == np.float32 else self._L.itd_tfe_spectrum_f64
+        self._check(fn(self._h, rows_ptr, n, rows, row_stride, edges_ptr, bins, hop, weight, spec_ptr, spec_stride, outside_ptr,
+                       info_ptr, stream))
+
     def waves_batch_dev(self, rows_ptr, dtype, n, rows, row_stride, start_ptr, length_ptr, peak_ptr, value_ptr, wave_stride, cap,
                         count_ptr=None, info_ptr=None, stream=None):
         """The half waves of every row (float32 or float64 by `dtype`): start / length / peak int32 and value float64 at
