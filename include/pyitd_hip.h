@@ -678,6 +678,44 @@ int itd_wave_filter_batch_f64(itd_engine *e, const double *rows_dev, int64_t n, 
 int itd_wave_filter_batch_f32(itd_engine *e, const float *rows_dev, int64_t n, int32_t rows, int64_t row_stride, const double *bounds_dev,
                               int64_t bounds_stride, void *out_dev, int64_t out_stride, int32_t out_f32, int32_t *info_dev, void *stream);
 
+/* ---- the joint amplitude-length histogram of many rows' half waves: how a row's half waves are distributed
+ * over amplitude, length and time, without the table — what a caller looks at to choose itd_wave_filter_batch_*'s bounds.
+ * Asynchronous on `stream`, no host synchronisation, no host read, graph-capturable.  For a row x[0..n) that holds no NaN, its half
+ * waves k = 0 .. m have start_k, end_k, length_k, A_k and peak_k exactly as defined for itd_waves_batch_* above.  Given amplitude
+ * edges ae[0..abins], length edges le[0..lbins] (float64) and hop, every half wave has
+ *   amplitude bin   the i with ae[i] <= A_k && A_k < ae[i+1]
+ *   length bin      the j with le[j] <= (double)length_k && (double)length_k < le[j+1]
+ *   time bin        t = peak_k / hop (integer division); T = ceil(n / hop)
+ * as IEEE comparisons on float64, half-open bins as in itd_tfe_spectrum_*.  If both i and j exist, count[t][i][j] += 1 and
+ * samples[t][i][j] += length_k; otherwise outside[t] += 1.  All three outputs are int32 and cannot overflow (a row has at most
+ * n - 1 half waves and n samples).  sum(count) + sum(outside) = m + 1, and sum(samples) plus the lengths of the outside half waves
+ * is n.  Every cell and every entry is written by the call, an empty cell as 0: the buffers need no clearing, and nothing else is
+ * written.  Every update is an integer add (no floating-point atomics): the result is the same bits from run to run and in any
+ * batch position.
+ *   aedges_dev, ledges_dev: row r's edges at aedges_dev + r * aedges_stride (abins + 1 values) and ledges_dev + r * ledges_stride
+ *     (lbins + 1 values); a stride of 0 is one set for every row, otherwise aedges_stride >= abins + 1, ledges_stride >= lbins + 1
+ *     (as bounds_stride of the filter).  Strictly increasing, no NaN; -inf as a first and +inf as a last edge are allowed.  They
+ *     are device memory, read when the call runs — a captured call bins with whatever they hold at its replay.  Their order cannot
+ *     be checked without reading device memory: unordered edges give unspecified bins (nothing outside the outputs is written).
+ *   1 <= abins <= 64, 1 <= lbins <= 64, abins * lbins <= 1024.
+ *   hop: a positive multiple of 512 (a half wave whose peak lies in a 512-sample tile falls into one time bin); a multiple of 512
+ *     that is >= n gives T = 1.
+ *   count_dev, samples_dev: row r's [T][abins][lbins] int32 at r * hist_stride elements, hist_stride >= T * abins * lbins when
+ *     rows > 1; the gaps between the rows' slots are not written.  Either may be NULL, not both.  outside_dev (optional):
+ *     [rows][T] int32, dense.
+ * Rows, n, row_stride, chunking and info_dev as for itd_waves_batch_* (info: the zero-crossing count m, -1 - m if the row holds a
+ * NaN — that row's histogram is then unspecified, but nothing outside its own slots is written).  ITD_ERR_INVALID_ARG before any
+ * launch for bins, hop or a stride out of range, n < 3, missing edges or both histograms NULL.  The workspace is the single-wave
+ * analysis's (80 bytes per 512 samples of min(rows, 65535) rows); its capture rule holds. */
+int itd_wave_hist_batch_f64(itd_engine *e, const double *rows_dev, int64_t n, int32_t rows, int64_t row_stride, const double *aedges_dev,
+                            int64_t aedges_stride, int32_t abins, const double *ledges_dev, int64_t ledges_stride, int32_t lbins,
+                            int64_t hop, int32_t *count_dev, int32_t *samples_dev, int64_t hist_stride, int32_t *outside_dev,
+                            int32_t *info_dev, void *stream);
+int itd_wave_hist_batch_f32(itd_engine *e, const float *rows_dev, int64_t n, int32_t rows, int64_t row_stride, const double *aedges_dev,
+                            int64_t aedges_stride, int32_t abins, const double *ledges_dev, int64_t ledges_stride, int32_t lbins,
+                            int64_t hop, int32_t *count_dev, int32_t *samples_dev, int64_t hist_stride, int32_t *outside_dev,
+                            int32_t *info_dev, void *stream);
+
 /* ---- the ITD-Fourier cascade (itd_fourier_decomposition.py:131-303) and its FFT ---------------------------------------------
  * itd_debug_fft_f64 (tests): `batch` transforms of n complex float64 points (interleaved re, im; transform b at 2 b n doubles) from
  *   in_dev into out_dev (may be in_dev): inverse 0 = numpy.fft.fft, 1 = numpy.fft.ifft (scaled by 1 / n).  n <= 8192: one

@@ -87,6 +87,8 @@ ABI = {
     "itd_waves_batch_f32": (_INT, [_P, _P, _I64, _I32, _I64, _P, _P, _P, _P, _I64, _I32, _P, _P, _P]),
     "itd_wave_filter_batch_f64": (_INT, [_P, _P, _I64, _I32, _I64, _P, _I64, _P, _I64, _I32, _P, _P]),
     "itd_wave_filter_batch_f32": (_INT, [_P, _P, _I64, _I32, _I64, _P, _I64, _P, _I64, _I32, _P, _P]),
+    "itd_wave_hist_batch_f64": (_INT, [_P, _P, _I64, _I32, _I64, _P, _I64, _I32, _P, _I64, _I32, _I64, _P, _P, _I64, _P, _P, _P]),
+    "itd_wave_hist_batch_f32": (_INT, [_P, _P, _I64, _I32, _I64, _P, _I64, _I32, _P, _I64, _I32, _I64, _P, _P, _I64, _P, _P, _P]),
     "itd_debug_fft_f64": (_INT, [_P, _P, _P, _I64, _I32, _I32]),
     "itd_fourier_mode_any_f64": (_INT, [_P, _P, _I64, _I64, _I64, _P, _I64, _P, _P]),
     "itd_fourier_mode_valid_f64": (_INT, [_P, _P, _I64, _I64, _I64, _P, _I64, _P, _P]),

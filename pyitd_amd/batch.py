@@ -1,7 +1,8 @@
 """Row-wise / channel-wise forms of the single-level operators (numpy in -> numpy out) over the asynchronous batched entry
 points of the C ABI (itd_baseline_extract_batch_f64, itd_detect_batch_f64, itd_baseline_extract_cubic_batch_f64), and the
 instantaneous amplitude / phase / frequency of many rows (itd_instantaneous_batch_*; numpy or torch CUDA tensors) and their
-single-wave analysis: the table of half waves and the feature filter (itd_waves_batch_*, itd_wave_filter_batch_*).
+single-wave analysis: the table of half waves, the feature filter and the half waves' joint amplitude-length histogram
+(itd_waves_batch_*, itd_wave_filter_batch_*, itd_wave_hist_batch_*).
 
 The reference applies its operators row by row under numba.prange (siftED2D.ipynb cell 1) and re-uses retained extrema along
 channels (itd.cpp:40-44); here a whole batch is one launch sequence and no knot count crosses PCIe in between.  Device
@@ -437,3 +438,88 @@ def wave_filter(rows, amplitude=(0.0, numpy.inf), length=(0.0, numpy.inf), out_d
         eng.wave_filter_batch_dev(d_x.ptr, idt, n, R, n, d_b.ptr, bstride, d_out.ptr, n, odt == numpy.float32, d_info.ptr)
         _refuse_nan(d_info.download(numpy.empty(R, numpy.int32)))           # itd_dev_copy synchronises
         return d_out.download(numpy.empty((R, n), odt)).reshape(shape)
+
+
+# ---- the joint amplitude-length histogram of the half waves (itd_wave_hist_batch_*) ------------------------------------------
+WaveHistogram = namedtuple("WaveHistogram", "count samples outside")
+MAX_WAVE_BINS = 64          # per axis
+MAX_WAVE_CELLS = 1024       # amplitude bins * length bins
+_WAVE_TILE = 512
+
+
+def _hist_edges(edges, name, lead):
+    """One axis's edges as float64 [N + 1] (one set for every row) or [R, N + 1]; refuses NaN and edges that do not increase."""
+    if _is_torch(edges):
+        edges = edges.detach().cpu().numpy()
+    e = numpy.asarray(edges, dtype=numpy.float64)
+    if e.ndim < 1 or not 2 <= e.shape[-1] <= MAX_WAVE_BINS + 1:
+        raise ValueError("%s: 2 to %d edges along the last axis, got shape %s" % (name, MAX_WAVE_BINS + 1, e.shape))
+    if numpy.isnan(e).any():
+        raise ValueError("%s: a NaN edge" % name)
+    if not (e[..., 1:] > e[..., :-1]).all():
+        raise ValueError("%s must be strictly increasing" % name)
+    if e.ndim == 1:
+        return numpy.ascontiguousarray(e)
+    try:
+        e = numpy.broadcast_to(e, lead + e.shape[-1:])
+    except ValueError:
+        raise ValueError("%s (shape %s) do not broadcast to the leading axes %s of rows" % (name, e.shape, lead))
+    return numpy.ascontiguousarray(e).reshape(-1, e.shape[-1])
+
+
+def _hist_hop(hop, n):
+    if hop is None:
+        return -(-n // _WAVE_TILE) * _WAVE_TILE
+    if isinstance(hop, bool) or int(hop) != hop or hop < _WAVE_TILE or hop % _WAVE_TILE != 0:
+        raise ValueError("hop: None or a positive multiple of %d, got %r" % (_WAVE_TILE, hop))
+    return int(hop)
+
+
+def wave_histogram(rows, amplitude_edges, length_edges, hop=None, device=0):
+    """The joint amplitude-length histogram of the half waves (single_waves) of every row of rows[..., n] in one asynchronous call,
+    without their table: the picture from which wave_filter's bounds are chosen.  Half wave k falls into amplitude bin i where
+    amplitude_edges[i] <= A_k < amplitude_edges[i+1], length bin j where length_edges[j] <= length_k < length_edges[j+1] and time
+    bin t = peak_k // hop of T = ceil(n / hop).  Returns WaveHistogram(count[..., T, Na, Nl], samples[..., T, Na, Nl],
+    outside[..., T]), all int32: the half waves of a cell, the samples they hold, and the half waves of a time bin that lie in no
+    cell.  count.sum() + outside.sum() is the row's number of half waves.  Every update is an integer add: the same bits from run
+    to run and in any batch position.
+
+    rows as for single_waves.  Each edge argument is a 1-D array (one set for every row) or an array whose leading axes broadcast to
+    the leading axes of rows — every level of a decomposition, with its own time-scale, may have its own; 1 to 64 bins per axis, at
+    most 1024 cells, strictly increasing, -inf / +inf allowed at the ends.  hop: None (one time bin) or a positive multiple of 512.
+    Raises ValueError for bad edges or hop, ITDError (non-finite) naming the rows that hold a NaN."""
+    torch_in, a, idt, shape, n, R = _accept_rows(rows, "the wave histogram")
+    lead = shape[:-1]
+    ae, le = _hist_edges(amplitude_edges, "amplitude_edges", lead), _hist_edges(length_edges, "length_edges", lead)
+    Na, Nl = ae.shape[-1] - 1, le.shape[-1] - 1
+    if Na * Nl > MAX_WAVE_CELLS:
+        raise ValueError("%d x %d bins are more than %d cells" % (Na, Nl, MAX_WAVE_CELLS))
+    hop = _hist_hop(hop, n)
+    T = -(-n // hop)
+    astride, lstride = (0 if ae.ndim == 1 else Na + 1), (0 if le.ndim == 1 else Nl + 1)
+    slot = T * Na * Nl
+    if torch_in:
+        import torch
+        stride = _tensor_stride(a, shape)
+        dev = a.device.index
+        count, samples = (torch.empty((R, T, Na, Nl), dtype=torch.int32, device=a.device) for _ in range(2))
+        outside = torch.empty((R, T), dtype=torch.int32, device=a.device)
+        info = torch.empty(R, dtype=torch.int32, device=a.device)
+        d_a, d_l = torch.from_numpy(ae).to(a.device), torch.from_numpy(le).to(a.device)
+        eng = _engine_for(3, dev)
+        torch.cuda.synchronize(a.device)    # the engine runs on its own stream
+        eng.wave_hist_batch_dev(a.data_ptr(), idt, n, R, stride, d_a.data_ptr(), astride, Na, d_l.data_ptr(), lstride, Nl, hop,
+                                count.data_ptr(), samples.data_ptr(), slot, outside.data_ptr(), info.data_ptr())
+        torch.cuda.synchronize(a.device)
+        _refuse_nan(info.cpu().numpy())
+        return WaveHistogram(count.reshape(lead + (T, Na, Nl)), samples.reshape(lead + (T, Na, Nl)), outside.reshape(lead + (T,)))
+    a = numpy.ascontiguousarray(a).reshape(R, n)
+    with _Staged(device) as S:
+        d_x, d_a, d_l = S.upload(a), S.upload(ae), S.upload(le)
+        d_c, d_s, d_o, d_info = S.empty(4 * R * slot), S.empty(4 * R * slot), S.empty(4 * R * T), S.empty(4 * R)
+        eng = _engine_for(3, S.dev)
+        eng.wave_hist_batch_dev(d_x.ptr, idt, n, R, n, d_a.ptr, astride, Na, d_l.ptr, lstride, Nl, hop, d_c.ptr, d_s.ptr, slot, d_o.ptr,
+                                d_info.ptr)
+        _refuse_nan(d_info.download(numpy.empty(R, numpy.int32)))          # itd_dev_copy synchronises
+        return WaveHistogram(*[b.download(numpy.empty((R, T, Na, Nl), numpy.int32)).reshape(lead + (T, Na, Nl)) for b in (d_c, d_s)],
+                             d_o.download(numpy.empty((R, T), numpy.int32)).reshape(lead + (T,)))

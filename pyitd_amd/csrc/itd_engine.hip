@@ -32,6 +32,7 @@
 #include "itd_tfe_batch.hpp"
 #include "itd_tfe_spectrum.hpp"
 #include "itd_waves.hpp"
+#include "itd_wave_hist.hpp"
 #include "itd_spline.hpp"
 #include "itd_nak.hpp"
 #include "itd_wpe.hpp"
@@ -277,7 +278,7 @@ struct itd_engine {
     Buf<void> d_sp;                                       // spline flavour (batched): the scan's parts, fit arrays, metadata
     Buf<double> d_sp2;                                    // 2-D consumers: three planes of scratch
     Buf<void> d_ib;                                       // batched instantaneous step (itd_instantaneous_batch_*): tile records, Ahead / Atail
-    Buf<void> d_wv;                                       // single-wave analysis (itd_waves_batch_*, itd_wave_filter_batch_*): tile records, forward / backward carries
+    Buf<void> d_wv;                                       // single-wave analysis (itd_waves_batch_*, itd_wave_filter_batch_*, itd_wave_hist_batch_*): tile records, forward / backward carries
     Buf<void> d_ts;                                       // time-frequency-energy spectrum (itd_tfe_spectrum_*): tile records, Ahead / Atail
     Buf<void> d_mb;                                       // MEITD over a batch (itd_meitd_batch_f64): per-signal results, solver arrays, logs, XITD sums
     Buf<int64_t> d_rowtab;                                // itd_gather_rows_f64: the row table

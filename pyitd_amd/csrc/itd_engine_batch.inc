@@ -9,6 +9,7 @@
 //       itd_tfe_spectrum_f64 / _f32           every row's energy binned over time and frequency (itd_tfe_spectrum.hpp)
 //       itd_waves_batch_f64 / _f32            the table of every row's half waves (itd_waves.hpp)
 //       itd_wave_filter_batch_f64 / _f32      every row filtered by its half waves' amplitude and length (itd_waves.hpp)
+//       itd_wave_hist_batch_f64 / _f32        every row's half waves binned over amplitude, length and time (itd_wave_hist.hpp)
 //   * block-wise operation (itd.cpp:31-38), itd_stream_*: a device-resident mirrored ring per channel (itd_stream.hpp), the
 //     window's knots, their selection and the operator all on the device — a push enqueues launches and returns; the host form
 //     synchronises once per push for its copies.  The recipe: include/pyitd_hip.h, DESIGN.md section 7.
@@ -229,6 +230,38 @@ int wave_filter_batch(itd_engine *e, const Tin *x, int64_t n, int32_t rows, int6
     });
 }
 
+// The joint amplitude-length histogram of the rows' half waves (itd_wave_hist.hpp): the rows' slots zeroed, the single-wave scan in
+// its workspace (d_wv), then k_wave_hist in k_wave_table's place.
+template <typename Tin>
+int wave_hist_batch(itd_engine *e, const Tin *x, int64_t n, int32_t rows, int64_t x_stride, const double *aedges, int64_t aedges_stride,
+                    int32_t abins, const double *ledges, int64_t ledges_stride, int32_t lbins, int64_t hop, int32_t *count, int32_t *samples,
+                    int64_t hist_stride, int32_t *outside, int32_t *info, void *stream)
+{
+    if (!tile_args_ok(e, x, n, rows, x_stride, aedges && ledges && (count || samples))) return ITD_ERR_INVALID_ARG;
+    if (abins < 1 || abins > kWaveHistMaxBins || lbins < 1 || lbins > kWaveHistMaxBins || abins * lbins > kWaveHistMaxCells) return ITD_ERR_INVALID_ARG;
+    if (hop < kTfeTile || hop % kTfeTile != 0) return ITD_ERR_INVALID_ARG;
+    if ((aedges_stride != 0 && aedges_stride < abins + 1) || (ledges_stride != 0 && ledges_stride < lbins + 1)) return ITD_ERR_INVALID_ARG;
+    const int64_t T = (n + hop - 1) / hop, slot = T * abins * lbins;
+    if (rows > 1 && hist_stride < slot) return ITD_ERR_INVALID_ARG;
+    DevGuard g(e->device);
+    hipStream_t st = stream_of(e, stream);
+    WaveWs w;
+    const int rc = tile_workspace(e, e->d_wv, n, rows, w);
+    if (rc) return rc;
+    const size_t lds = wave_hist_lds(abins, lbins);
+    return for_row_chunks(e, rows, w.chunk, [&](int b0, int nb) {
+        const Tin *xc = x + (int64_t)b0 * x_stride;
+        int32_t *cc = at(count, (int64_t)b0 * hist_stride), *sc = at(samples, (int64_t)b0 * hist_stride), *oc = at(outside, (int64_t)b0 * T);
+        k_wave_hist_zero<<<dim3((unsigned)((slot + kWaveHistZeroThreads - 1) / kWaveHistZeroThreads), (unsigned)nb), kWaveHistZeroThreads, 0, st>>>(
+            cc, sc, hist_stride, slot, oc, T);
+        wave_scan<Tin>(w, xc, x_stride, n, nb, nullptr, at(info, b0), st);
+        k_wave_hist<Tin><<<dim3((unsigned)w.tiles, (unsigned)nb), kWave, lds, st>>>(xc, x_stride, n, w.tiles, w.head, w.tail,
+                                                                                   aedges + (int64_t)b0 * aedges_stride, aedges_stride, abins,
+                                                                                   ledges + (int64_t)b0 * ledges_stride, ledges_stride, lbins,
+                                                                                   hop, T, cc, sc, hist_stride, oc);
+    });
+}
+
 }  // namespace
 
 struct itd_stream {
@@ -415,6 +448,23 @@ int itd_wave_filter_batch_f32(itd_engine *e, const float *rows_dev, int64_t n, i
                               int64_t bounds_stride, void *out_dev, int64_t out_stride, int32_t out_f32, int32_t *info_dev, void *stream)
 {
     return wave_filter_batch<float>(e, rows_dev, n, rows, row_stride, bounds_dev, bounds_stride, out_dev, out_stride, out_f32, info_dev, stream);
+}
+
+int itd_wave_hist_batch_f64(itd_engine *e, const double *rows_dev, int64_t n, int32_t rows, int64_t row_stride, const double *aedges_dev,
+                            int64_t aedges_stride, int32_t abins, const double *ledges_dev, int64_t ledges_stride, int32_t lbins,
+                            int64_t hop, int32_t *count_dev, int32_t *samples_dev, int64_t hist_stride, int32_t *outside_dev,
+                            int32_t *info_dev, void *stream)
+{
+    return wave_hist_batch<double>(e, rows_dev, n, rows, row_stride, aedges_dev, aedges_stride, abins, ledges_dev, ledges_stride, lbins, hop,
+                                   count_dev, samples_dev, hist_stride, outside_dev, info_dev, stream);
+}
+int itd_wave_hist_batch_f32(itd_engine *e, const float *rows_dev, int64_t n, int32_t rows, int64_t row_stride, const double *aedges_dev,
+                            int64_t aedges_stride, int32_t abins, const double *ledges_dev, int64_t ledges_stride, int32_t lbins,
+                            int64_t hop, int32_t *count_dev, int32_t *samples_dev, int64_t hist_stride, int32_t *outside_dev,
+                            int32_t *info_dev, void *stream)
+{
+    return wave_hist_batch<float>(e, rows_dev, n, rows, row_stride, aedges_dev, aedges_stride, abins, ledges_dev, ledges_stride, lbins, hop,
+                                  count_dev, samples_dev, hist_stride, outside_dev, info_dev, stream);
 }
 
 int itd_stream_create(itd_stream **out, int device_id, int64_t block, int32_t channels, int32_t kind, int32_t margin, int32_t shared_knots)

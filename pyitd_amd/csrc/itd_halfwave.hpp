@@ -1,5 +1,5 @@
 // itd_halfwave.hpp — the half-wave tile pipeline that the instantaneous step (itd_tfe_batch.hpp) and the single-wave analysis
-// (itd_waves.hpp) are built on: what a half wave is, how a 512-sample tile is loaded and cut, and the scan that joins the tiles.
+// (itd_waves.hpp, itd_wave_hist.hpp) are built on: what a half wave is, how a 512-sample tile is loaded and cut, and the scan that joins the tiles.
 //
 // A proper rotation is cut into half waves at its zero crossings (Frei & Osorio 2007, single-wave analysis; README.md:13-21,
 // 41-55).  Crossing index i (tfe_crossing): a strict sign change between x[i] and x[i+1], 1 <= i <= n-2; a crossing index is the
@@ -11,8 +11,8 @@
 //     records   reads the row, writes one record per tile                       grid (tiles, rows), 64 threads
 //     carry     halfwave_carry over a row's records; the row's info word        grid rows, 64 or kInstCarryThreads threads
 //     consumer  reads the row again: the tile's own half waves anew, the first and last one from the carries
-// No workgroup waits for another, no atomics on global memory, no count on the host, nothing outside the first n samples of a
-// row read.  The operators differ in what a record, a carry and a consumer hold: a policy each.
+// No workgroup waits for another, no atomics on global memory (but the integer adds of itd_wave_hist.hpp's histogram), no count on
+// the host, nothing outside the first n samples of a row read.  The operators differ in what a record, a carry and a consumer hold: a policy each.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -489,6 +489,15 @@ class Engine:
         self._check(fn(self._h, rows_ptr, n, rows, row_stride, bounds_ptr, bounds_stride, out_ptr, out_stride, 1 if out_f32 else 0,
                        info_ptr, stream))
 
+    def wave_hist_batch_dev(self, rows_ptr, dtype, n, rows, row_stride, aedges_ptr, aedges_stride, abins, ledges_ptr, ledges_stride, lbins,
+                            hop, count_ptr, samples_ptr, hist_stride, outside_ptr=None, info_ptr=None, stream=None):
+        """Every row's half waves binned over time (T = ceil(n / hop), by the peak), amplitude and length: count and samples int32
+        [T, abins, lbins] per row at hist_stride elements (either may be None), outside int32 [rows, T] (optional); the float64
+        edges in device memory, a stride of 0: one set for every row.  Pointers in, nothing copied, nothing awaited."""
+        fn = self._L.itd_wave_hist_batch_f32 if np.dtype(dtype) == np.float32 else self._L.itd_wave_hist_batch_f64
+        self._check(fn(self._h, rows_ptr, n, rows, row_stride, aedges_ptr, aedges_stride, abins, ledges_ptr, ledges_stride, lbins, hop,
+                       count_ptr, samples_ptr, hist_stride, outside_ptr, info_ptr, stream))
+
     # ---- the FITPACK flavour of the baseline and its 2-D consumers (itd_baseline_extract_spline_*, itd_crossways_*) --------
     def spline_extract_host(self, x, min_extrema=10, want_rotation=False, want_baseline_knots=False):
         """x[B, n] float64 -> (baseline[B, n], rotation[B, n] or None, knots[B]) (numba_accelerated_itd.py:182-211);
