@@ -12,6 +12,7 @@ the same order).  Outputs are *data only* (inputs + expected outputs) written
 to tests/golden/*.npz; no reference source text is stored.
 
 Usage:  python oracle/gen_golden.py [--ref /root/reference] [--out tests/golden]
+        python oracle/gen_golden.py --meitd-branches      (tests/golden/meitd/ only; every other golden stays as it is)
 """
 import argparse
 import contextlib
@@ -292,6 +293,438 @@ def make_spline_cases(ref_dir, out_dir, radio):
     print("spline image48x64: crossways + ensemble low-pass (numpy.random.seed(20240))")
 
 
+# --------------------------------------------------------------------------
+# MEITD's selection loop, case by case chosen for the branches it takes (tests/golden/meitd/)
+# --------------------------------------------------------------------------
+MEITD_TRACED = ("MEITD", "retrieve_proper_rotation", "determine_if_first_is_proper_rotation")
+MEITD_WPEMAX = (0.3, 0.45, 0.6, 0.9, 2.0)
+MEITD_FAMILIES = ("two_tones_noise", "walk", "white_noise", "tone_1pct_noise", "slow_tone", "quantised_tone", "sine_product", "smoothed_walk")
+MEITD_FILE_MAX = 1 << 20           # bytes per fixture
+MEITD_DIR_MAX = 4 * 1000 * 1000    # bytes of the directory
+MEITD_SHORT_SEARCH = 5000          # short candidates tried before line 488 may be recorded as unreached
+_MEITD_M = None                    # the reference module (per process: the short search runs in a pool)
+
+
+def _load_meitd(ref_dir):
+    global _MEITD_M
+    if _MEITD_M is None:
+        _install_numba_shim()
+        sys.path.insert(0, ref_dir)
+        try:
+            import MEITD as M
+        finally:
+            sys.path.pop(0)
+        _MEITD_M = M
+    return _MEITD_M
+
+
+def meitd_family(kind, n, seed):
+    """a seeded signal of one of MEITD_FAMILIES"""
+    rng = np.random.default_rng([kind, n, seed])
+    t = np.arange(n) / 1000.0
+    if kind == 0:
+        return (np.sin(2 * np.pi * rng.uniform(1, 6) * t) * (1 + 0.5 * np.sin(2 * np.pi * rng.uniform(0.1, 1) * t))
+                + 0.3 * np.sin(2 * np.pi * rng.uniform(20, 60) * t + 1) + rng.uniform(0.02, 0.3) * rng.standard_normal(n))
+    if kind == 1:
+        return np.cumsum(rng.standard_normal(n)) * 0.3
+    if kind == 2:
+        return rng.standard_normal(n)
+    if kind == 3:
+        return np.sin(2 * np.pi * rng.uniform(2, 30) * t) + 0.01 * rng.standard_normal(n)
+    if kind == 4:
+        return np.sin(2 * np.pi * rng.uniform(3, 8) * 1000.0 / n * t + rng.uniform(0, 6))
+    if kind == 5:
+        return np.round(3 * np.sin(2 * np.pi * rng.uniform(2, 9) * t) + rng.standard_normal(n))
+    if kind == 6:
+        return np.sin(2 * np.pi * rng.uniform(1.5, 4) * 1000.0 / n * t) * np.sin(2 * np.pi * rng.uniform(5, 12) * 1000.0 / n * t)
+    return np.convolve(np.cumsum(rng.standard_normal(n)), np.ones(9) / 9, "same")
+
+
+def meitd_short_candidate(i):
+    """candidate i of the search for line 488: (x, WPEMAX), n <= 300"""
+    rng = np.random.default_rng([488, i])
+    n = int(rng.choice([100, 128, 200, 300]))
+    t = np.arange(n) / n
+    k = i % 6
+    if k == 0:
+        x = np.sin(2 * np.pi * rng.uniform(2, 5) * t) + rng.uniform(0.0, 0.05) * rng.standard_normal(n)
+    elif k == 1:
+        x = np.sin(2 * np.pi * rng.uniform(1.5, 4) * t) * np.sin(2 * np.pi * rng.uniform(5, 12) * t)
+    elif k == 2:
+        x = np.convolve(np.cumsum(rng.standard_normal(n)), np.ones(9) / 9, "same")
+    elif k == 3:
+        x = np.sin(2 * np.pi * rng.uniform(2, 4) * t) + 0.4 * np.sin(2 * np.pi * rng.uniform(6, 14) * t + rng.uniform(0, 6))
+    elif k == 4:      # a steep trend under a few waves and a ripple
+        x = rng.uniform(2, 20) * t + np.sin(2 * np.pi * rng.uniform(3, 6) * t) + rng.uniform(0.0, 0.3) * np.sin(2 * np.pi * rng.uniform(15, 40) * t)
+    else:
+        x = np.convolve(rng.standard_normal(n), np.ones(15) / 15, "same") + rng.uniform(0, 3) * t
+    return x, float(rng.choice(MEITD_WPEMAX))
+
+
+def meitd_long_candidate(i, n=1024):
+    """candidate i of the search for line 488 at a length the one-launch kernels take: (x, WPEMAX)"""
+    rng = np.random.default_rng([4881024, i])
+    t = np.arange(n) / n
+    k = i % 6
+    if k == 0:
+        x = np.sin(2 * np.pi * rng.uniform(2, 5) * t) + rng.uniform(0.0, 0.05) * rng.standard_normal(n)
+    elif k == 1:
+        x = np.sin(2 * np.pi * rng.uniform(1.5, 4) * t) * np.sin(2 * np.pi * rng.uniform(5, 12) * t)
+    elif k == 2:
+        x = np.convolve(np.cumsum(rng.standard_normal(n)), np.ones(65) / 65, "same")
+    elif k == 3:
+        x = np.sin(2 * np.pi * rng.uniform(2, 4) * t) + 0.4 * np.sin(2 * np.pi * rng.uniform(6, 14) * t + rng.uniform(0, 6))
+    elif k == 4:
+        x = rng.uniform(2, 20) * t + np.sin(2 * np.pi * rng.uniform(3, 6) * t) + rng.uniform(0.0, 0.3) * np.sin(2 * np.pi * rng.uniform(15, 40) * t)
+    else:
+        x = np.convolve(rng.standard_normal(n), np.ones(121) / 121, "same") + rng.uniform(0, 3) * t
+    return x, float(rng.choice(MEITD_WPEMAX))
+
+
+def meitd_traced(M, x, wpemax):
+    """the reference's MEITD(x, 40, wpemax) under a line tracer on MEITD_TRACED: (result or the exception's name, lines reached, the
+    entropies it drew)"""
+    lines, drawn = set(), []
+    orig = M.weighted_permutation_entropy
+
+    def wpe(*a, **k):
+        v = orig(*a, **k)
+        drawn.append(float(np.mean(v)))
+        return v
+
+    def local(frame, event, arg):
+        if event == "line":
+            lines.add(frame.f_lineno)
+        return local
+
+    def tracer(frame, event, arg):
+        if frame.f_code.co_filename == M.__file__ and frame.f_code.co_name in MEITD_TRACED:
+            lines.add(frame.f_lineno)         # (the line of the `def`, where the interpreter counts it as executable)
+            return local
+        return None
+
+    M.weighted_permutation_entropy = wpe
+    sys.settrace(tracer)
+    try:
+        with contextlib.redirect_stdout(io.StringIO()), np.errstate(all="ignore"):
+            r = M.MEITD(x.copy(), 40, wpemax)
+    except Exception as ex:       # noqa
+        r = type(ex).__name__
+    finally:
+        sys.settrace(None)
+        M.weighted_permutation_entropy = orig
+    return r, lines, drawn
+
+
+def _meitd_short_hits(args):
+    """pool worker: which of the short candidates [lo, hi) reach line 488"""
+    ref_dir, lo, hi, candidate = args
+    M = _load_meitd(ref_dir)
+    hits = []
+    for i in range(lo, hi):
+        x, w = candidate(i)
+        r, lines, _ = meitd_traced(M, x, w)
+        if 488 in lines and not isinstance(r, str):
+            hits.append(i)
+    return hits
+
+
+def _meitd_trace_candidate(args):
+    """pool worker: one family candidate under the tracer"""
+    ref_dir, kind, n, seed, w = args
+    return meitd_traced(_load_meitd(ref_dir), meitd_family(kind, n, seed), w)
+
+
+def _entropy_margin(drawn, wpemax):
+    """(a): the distance of the nearest drawn entropy from a threshold (NaN entropies fail every comparison alike: exempt)"""
+    d = np.array([v for v in drawn if np.isfinite(v)])
+    return float(min(np.abs(d - 0.2).min(), np.abs(d - wpemax).min())) if d.size else float("inf")
+
+
+def _port_run(x, wpemax, noise_seed=None):
+    """pyitd_amd.meitd.MEITD over oracle.meitd_oracle.CpuWork; noise_seed: every extracted baseline perturbed by 1e-13 max|x| of
+    standard normal noise (the rotation follows).  Returns (high, low, residual), the work."""
+    from oracle import meitd_oracle
+    from pyitd_amd import meitd
+    works = []
+    rng = np.random.default_rng(noise_seed)
+    peak = float(np.max(np.abs(x)))
+    eps = 1e-13 * peak
+
+    class Watched(meitd_oracle.CpuWork):
+        """CpuWork that knows which rows were COMPUTED (a baseline, a rotation, a difference: the device holds them to rounding
+        only) and, wherever extrema of such a row are taken, records its smallest |x[i + 1] - x[i]|: a tie there is a decision the
+        last bit makes (`ties`, in units of max|x|)."""
+
+        def __init__(self, n):
+            meitd_oracle.CpuWork.__init__(self, n)
+            self.computed, self.ties = set(), float("inf")
+
+        def _look(self, src):
+            if src in self.computed:
+                self.ties = min(self.ties, float(np.abs(np.diff(self.rows[src])).min()) / max(peak, 1e-300))
+
+        def upload(self, x, dst):
+            self.computed.discard(dst)
+            meitd_oracle.CpuWork.upload(self, x, dst)
+
+        def assign(self, dst, src):
+            (self.computed.add if src in self.computed else self.computed.discard)(dst)
+            meitd_oracle.CpuWork.assign(self, dst, src)
+
+        def zero(self, dst):
+            self.computed.discard(dst)
+            meitd_oracle.CpuWork.zero(self, dst)
+
+        def subtract(self, a, b, out):
+            self.computed.add(out)
+            meitd_oracle.CpuWork.subtract(self, a, b, out)
+
+        def count(self, src):
+            self._look(src)
+            return meitd_oracle.CpuWork.count(self, src)
+
+        def probe(self, src):
+            self._look(src)
+            return meitd_oracle.CpuWork.probe(self, src)
+
+        def extract(self, src, base, rot=None, want_baseline_count=False):
+            self._look(src)
+            r = meitd_oracle.CpuWork.extract(self, src, base, rot, want_baseline_count)
+            self.computed |= {base} | ({rot} if rot is not None else set())
+            if want_baseline_count:
+                self._look(base)
+            return r
+
+    class Noisy(Watched):
+        def extract(self, src, base, rot=None, want_baseline_count=False):
+            Watched.extract(self, src, base, rot, False)
+            xs = self.rows[src].copy()
+            self.rows[base] += eps * rng.standard_normal(self.n)
+            if rot is not None:
+                self.rows[rot] = xs - self.rows[base]
+            return int(meitd_oracle.cpu_oracle.knots(self.rows[base]).size) if want_baseline_count else None
+
+    def work_for(n, device=0, solver="auto"):
+        works.append((Watched if noise_seed is None else Noisy)(n))
+        return works[-1]
+
+    saved = meitd._work_for
+    meitd._work_for = work_for
+    try:
+        with np.errstate(all="ignore"):
+            r = meitd.MEITD(x.copy(), WPEMAX=wpemax)
+    finally:
+        meitd._work_for = saved
+    return r, works[-1]
+
+
+def _bits_equal(a, b):
+    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    return a.shape == b.shape and canon_bytes(a) == canon_bytes(b)
+
+
+def meitd_record(M, x, wpemax, traced=None):
+    """The fixture of one case, or (None, why) where the reference alone does not decide it with room to spare: (a) every entropy it
+    draws at least 1e-6 from 0.2 and from WPEMAX; (b) the port's loop over CpuWork with every extracted baseline perturbed by 1e-13
+    max|x| keeps the same numbers of rows, the same numbers of extractions, counts and probes (the GPU tests hold the kernels to
+    them), and every component within 1e-10 of the scale; every COMPUTED row whose extrema are taken has no two neighbouring samples
+    closer than 1e-12 max|x| (an exact tie in a baseline of a quantised signal survives no rounding, and random noise does not
+    tell: it breaks every tie); (c) XITD's rows at least 1e-9 apart in entropy."""
+    import scipy
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    n = x.size
+    r, lines, drawn = traced if traced is not None else meitd_traced(M, x, wpemax)
+    if isinstance(r, str):
+        return None, "the reference raises " + r
+    high, low, residual = (np.array(a) for a in r)
+    margin = _entropy_margin(drawn, wpemax)
+    if not margin >= 1e-6:
+        return None, "an entropy %.3g from a threshold" % margin
+    (ph, pl, pr), work = _port_run(x, wpemax)
+    if not (_bits_equal(ph, high) and _bits_equal(pl, low) and _bits_equal(pr, residual)):
+        raise AssertionError("the port over CpuWork differs from the reference: n %d WPEMAX %g" % (n, wpemax))
+    if not work.ties >= 1e-12:
+        return None, "extrema taken of a computed row with neighbouring samples %.3g of the scale apart" % work.ties
+    scale = max(1.0, float(np.max(np.abs(x))))
+    worst = 0.0
+    for seed in (1, 2):
+        (qh, ql, qr), noisy = _port_run(x, wpemax, noise_seed=seed)
+        if np.shape(qh) != np.shape(ph) or np.shape(ql) != np.shape(pl):
+            return None, "a perturbation of 1e-13 changes the number of rows"
+        if noisy.calls != work.calls:     # (a branch taken otherwise behind the same rows: an extrema count of a baseline with ties)
+            return None, "a perturbation of 1e-13 changes the operators called: %s, unperturbed %s" % (noisy.calls, work.calls)
+        worst = max([worst] + [float(np.max(np.abs(a - b))) / scale for a, b in zip((qh, ql, qr), (ph, pl, pr)) if np.size(a)])
+    if not worst <= 1e-10:
+        return None, "a perturbation of 1e-13 moves a component by %.3g" % worst
+    rec = {"x": x, "wpemax": np.float64(wpemax), "high": high, "low": low, "residual": residual,
+           "lines": np.array(sorted(lines), dtype=np.int64), "margin_entropy": np.float64(margin), "margin_perturbed": np.float64(worst),
+           "margin_ties": np.float64(work.ties),
+           "scipy_version": np.array(scipy.__version__),
+           "port_calls": np.array([work.calls[k] for k in ("extract", "count", "probe")], dtype=np.int64)}
+    with contextlib.redirect_stdout(io.StringIO()), np.errstate(all="ignore"):
+        dr, db, dp = M.determine_if_first_is_proper_rotation(x.copy(), wpemax)
+        rr, rp = M.retrieve_proper_rotation(x.copy(), wpemax)
+    rec["determine_proper"], rec["retrieve_proper"] = np.int64(dp), np.int64(rp)
+    if n <= 1024:
+        rec["determine_rotation"], rec["determine_baseline"], rec["retrieve_rotation"] = np.array(dr), np.array(db), np.array(rr)
+    if wpemax == 0.6:
+        with contextlib.redirect_stdout(io.StringIO()), np.errstate(all="ignore"):
+            xi = np.array(M.XITD(x.copy()))
+            rows = np.vstack((np.vstack((high, low)), residual))
+            ent = np.array([float(M.weighted_permutation_entropy(row, order=3, normalize=True)) for row in rows])
+        finite = np.sort(ent[np.isfinite(ent)])
+        gap = float(np.diff(finite).min()) if finite.size > 1 else float("inf")
+        if not gap >= 1e-9:
+            return None, "two rows' entropies %.3g apart" % gap
+        order = np.argsort(ent)
+        if not _bits_equal(rows[order], xi):
+            raise AssertionError("XITD's rows are not MEITD's in the order of their entropies: n %d" % n)
+        rec["xitd_order"], rec["xitd_rows"], rec["margin_xitd"] = order.astype(np.int64), np.int64(len(xi)), np.float64(gap)
+    return rec, ""
+
+
+def _npz_bytes(rec):
+    buf = io.BytesIO()
+    np.savez_compressed(buf, **rec)
+    return buf.getbuffer().nbytes
+
+
+def make_meitd_branch_cases(ref_dir, out_dir):
+    """tests/golden/meitd/: the reference's MEITD (MEITD.py:395-534) on a small set of signals that together take every branch of
+    its loop, of retrieve_proper_rotation (:344-368) and of determine_if_first_is_proper_rotation (:371-392), each decided by the
+    reference with room to spare (meitd_record).  Data only: signals, outputs, line NUMBERS, margins."""
+    import dis
+    import multiprocessing
+    M = _load_meitd(ref_dir)
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    os.makedirs(out_dir, exist_ok=True)
+    executable = sorted({l for name in MEITD_TRACED for _, l in dis.findlinestarts(getattr(M, name).__code__) if l})
+    cases = {}                           # name -> record
+
+    def keep(name, x, w, traced=None, must=True):
+        rec, why = meitd_record(M, x, w, traced)
+        if rec is None:
+            if must:
+                raise AssertionError("%s: %s" % (name, why))
+            print("meitd %-34s dropped: %s" % (name, why))
+            return False
+        assert _npz_bytes(rec) <= MEITD_FILE_MAX, name
+        rec["lines"] = np.array(sorted(set(rec["lines"].tolist()) & set(executable)), dtype=np.int64)
+        cases[name] = rec
+        print("meitd %-34s n %-5d WPEMAX %-4g high %-2d low %-2d lines %-3d margins %.2g %.2g  %d kB" % (
+            name, rec["x"].size, w, len(rec["high"]) if rec["high"].ndim == 2 else 0, len(rec["low"]) if rec["low"].ndim == 2 else 0,
+            len(rec["lines"]), rec["margin_entropy"], rec["margin_perturbed"], _npz_bytes(rec) // 1000), flush=True)
+        return True
+
+    def extrema(x):
+        return int(np.asarray(M.matlab_detect_peaks(x)).size + np.asarray(M.matlab_detect_peaks(-x)).size)
+
+    # (1) the fixed edge cases
+    for n in (1024, 200):
+        t = np.linspace(0.0, 1.0, n)
+        keep("edge_constant_%d" % n, np.full(n, 1.5), 0.6)
+        keep("edge_ramp_%d" % n, np.linspace(-1.0, 2.0, n), 0.6)
+        keep("edge_one_bump_%d" % n, np.exp(-np.linspace(-3, 3, n) ** 2), 0.6)
+    for k in (4, 5, 6):                  # k extrema of a slow sine: k half waves, the ends an eighth of a period from an extremum
+        x = np.sin(np.pi * k * np.linspace(0.0, 1.0, 1024) + 0.25 * np.pi) + 0.1 * np.linspace(0.0, 1.0, 1024)
+        assert extrema(x) == k, (k, extrema(x))
+        keep("edge_%d_extrema_1024" % k, x, 2.0 if k == 6 else 0.6)
+
+    # (2) line 488: a search over short signals, and over signals of 1024 samples for the kernels' own lengths
+    searched = {}
+    with multiprocessing.Pool(min(8, os.cpu_count() or 1)) as pool:
+        for what, candidate, most, step in (("short", meitd_short_candidate, MEITD_SHORT_SEARCH, 250), ("1024", meitd_long_candidate, 2000, 50)):
+            hit = None
+            for lo in range(0, most, step * 8):
+                parts = pool.map(_meitd_short_hits, [(ref_dir, a, min(a + step, most), candidate) for a in range(lo, min(lo + step * 8, most), step)])
+                for i in sorted(sum(parts, [])):
+                    x, w = candidate(i)
+                    if keep("line488_%s_c%d" % (what, i), x, w, must=False):
+                        hit = i
+                        break
+                if hit is not None:
+                    break
+            searched[what] = most if hit is None else hit + 1
+            print("meitd line 488, %s candidates: %s after %d" % (what, "reached by candidate %d" % hit if hit is not None else "not reached", searched[what]), flush=True)
+    searched = searched["short"]
+
+    # (3) seeded families at the lengths that select the kernels' forms, chosen greedily for what they add
+    key_lines = (433, 442, 446, 461, 500, 508, 513)
+    jobs = []
+    for n, seeds, kinds, wp in ((1024, (0, 1), range(8), MEITD_WPEMAX), (600, (0,), (0, 3, 6, 7), (0.6, 2.0)),
+                                (4800, (0,), (3, 4, 6, 7), (0.6, 2.0)), (5000, (0,), (3, 4, 6, 7), (0.6, 2.0)), (8192, (0,), (3, 4, 6, 7), (0.6, 2.0))):
+        jobs += [(ref_dir, kind, n, seed, w) for kind in kinds for seed in seeds for w in wp]
+    jobs += [(ref_dir, kind, 1024, seed, 0.6) for kind in range(8) for seed in (2, 3)]
+    with multiprocessing.Pool(min(8, os.cpu_count() or 1)) as pool:
+        traced = pool.map(_meitd_trace_candidate, jobs, chunksize=1)
+    pool_c = []
+    for (_, kind, n, seed, w), tr in zip(jobs, traced):
+        if isinstance(tr[0], str):
+            continue
+        rows = len(tr[0][0]) + len(tr[0][1]) if np.ndim(tr[0][0]) == 2 else 0
+        if (n >= 4800 and rows > 8) or not _entropy_margin(tr[2], w) >= 1e-6:
+            continue
+        items = set(tr[1]) | {("w", w, l) for l in key_lines if l in tr[1]} | {("family", kind), ("w", w)}
+        items |= {("must", l) for l in (461, 508) if l in tr[1] and w == 0.6}
+        if n >= 1024:
+            items |= {("must", "device", l) for l in tr[1]} | {("device", n, l) for l in key_lines if l in tr[1]}
+        pool_c.append(("%s_%d_s%d_w%s" % (MEITD_FAMILIES[kind], n, seed, ("%g" % w).replace(".", "p")), meitd_family(kind, n, seed), w, tr, items,
+                       (rows + 2) * n))
+    print("meitd: %d of %d traced candidates in the pool" % (len(pool_c), len(jobs)), flush=True)
+    have = set()
+    for rec in cases.values():
+        have |= set(rec["lines"].tolist())
+        if 1024 <= rec["x"].size <= 8192:
+            have |= {("must", "device", int(l)) for l in rec["lines"]}
+    for l in key_lines:
+        print("meitd line %d: reached by %s" % (l, ", ".join("%d candidates at %g" % (sum(1 for c in pool_c if ("w", w, l) in c[4]), w) for w in MEITD_WPEMAX)))
+
+    def worth(item):                 # what the set has to reach counts before what makes it varied
+        return 100.0 if isinstance(item, int) or item[0] == "must" else 1.0
+
+    for n, most in ((8192, 1), (5000, 1), (4800, 1), (600, 2), (1024, 10)):
+        kept = 0
+        while kept < most:
+            gain = [(sum(worth(it) for it in c[4] - have) / (1.0 + c[5] / 50000.0), -c[5], i) for i, c in enumerate(pool_c) if c[1].size == n]
+            if not gain or max(gain)[0] <= 0:
+                break
+            name, x, w, tr, items, _ = pool_c.pop(max(gain)[2])
+            if keep(name, x, w, traced=tr, must=False):
+                have |= items
+                kept += 1
+        assert kept, "no case of %d samples" % n
+
+    # (4) what the set reaches
+    def union(sel):
+        return sorted(set().union(*[set(cases[k]["lines"].tolist()) for k in cases if sel(cases[k])]))
+
+    reached = union(lambda r: True)
+    unreached = sorted(set(executable) - set(reached))
+    assert set(reached) <= set(executable), sorted(set(reached) - set(executable))
+    assert set(unreached) <= {488}, "lines not reached: %s" % unreached
+    assert not unreached or searched >= MEITD_SHORT_SEARCH
+    device = union(lambda r: 1024 <= r["x"].size <= 8192)
+    assert device == reached, "the one-launch lengths miss %s" % sorted(set(reached) - set(device))
+    at06 = union(lambda r: float(r["wpemax"]) == 0.6)
+    assert 461 in at06 and 508 in at06, "WPEMAX 0.6 misses the dig loop or line 461"
+    for f in os.listdir(out_dir):        # (the directory is this function's: a case of an earlier run that is no longer chosen goes)
+        if f.endswith(".npz"):
+            os.remove(os.path.join(out_dir, f))
+    total = 0
+    for name, rec in cases.items():
+        path = os.path.join(out_dir, name + ".npz")
+        np.savez_compressed(path, **rec)
+        total += os.path.getsize(path)
+    path = os.path.join(out_dir, "index.npz")
+    np.savez_compressed(path, names=np.array(sorted(cases)), executable_lines=np.array(executable, dtype=np.int64),
+                        unreached=np.array(unreached, dtype=np.int64), short_candidates_searched=np.int64(searched))
+    total += os.path.getsize(path)
+    assert total <= MEITD_DIR_MAX, total
+    print("meitd: %d cases, %d executable lines, %d reached, unreached %s; one-launch lengths reach %d; %.2f MB" % (
+        len(cases), len(executable), len(reached), unreached, len(device), total / 1e6))
+
+
 def make_stream_cases(cub, ns1, out_dir, radio):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from oracle import stream_oracle as so
@@ -357,8 +790,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(__file__), "..", "tests", "golden"))
+    ap.add_argument("--meitd-branches", action="store_true", help="only tests/golden/meitd/ (make_meitd_branch_cases); nothing else is rewritten")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
+    if args.meitd_branches:
+        make_meitd_branch_cases(args.ref, os.path.join(args.out, "meitd"))
+        return
     ref_mod, ns1, radio = load_reference(args.ref)
 
     def case(name, x, m, **kw):

@@ -2,7 +2,11 @@
 for the device rows pyitd_amd/meitd.py works on.  Only tests/ and tools' CPU legs use this module; the product path never does.
 
 Pinned by tests/golden/spline/meitd_*.npz: `wpe` there is the reference's own weighted_permutation_entropy(x, 3, True), and
-high / low / residual / xitd its own MEITD / XITD outputs (oracle/gen_golden.py)."""
+high / low / residual / xitd its own MEITD / XITD outputs (oracle/gen_golden.py) — three signals of 3000 samples at WPEMAX 0.6 —
+and by tests/golden/meitd/*.npz (gen_golden.py: make_meitd_branch_cases; tests/test_meitd_reference_cpu.py): the reference's MEITD,
+XITD order, retrieve_proper_rotation and determine_if_first_is_proper_rotation on cases that together take every branch of
+MEITD.py:344-534 — the dig loop, the three early exits, five thresholds — with pyitd_amd.meitd's loop over CpuWork equal to them bit
+for bit, operator counts (CpuWork.calls) included."""
 from math import factorial
 
 import numpy
