@@ -839,6 +839,50 @@ int itd_levels_stream_flush_f64(itd_stream *s, double *rows_dev, int64_t row_str
 int itd_levels_stream_push_host_f64(itd_stream *s, const double *block_host, double *rows_host, uint8_t *exact_host, int32_t *emitted);
 int itd_levels_stream_flush_host_f64(itd_stream *s, double *rows_host, uint8_t *exact_host, int32_t *emitted);
 
+/* ---- the wave-filter stream: the single-wave feature filter block by block, at a fixed latency -----
+ * itd_wave_filter_batch_* needs the whole row: a half wave's amplitude and length are known only once it has ended.  A wave-filter
+ * stream takes blocks of `rows` rows in lock step and gives the same blocks back filtered, a known number of blocks later.  With
+ * blocks of L samples and a horizon of H samples, row r after P pushes is x[0 .. P L).  Crossing indices, half waves, A_k and
+ * length_k are exactly those of itd_waves_batch_* above on the indices of the whole stream; the last half wave ends at the
+ * stream's last sample, known at the flush.  The output is
+ *   y[j] = x[j]  if the half wave k of sample j has length_k <= H && amp_lo <= A_k && A_k <= amp_hi &&
+ *                len_lo <= (double)length_k && (double)length_k <= len_hi   (IEEE comparisons on float64; a NaN bound keeps nothing)
+ *          +0.0  otherwise
+ * — itd_wave_filter_batch_f64 of the concatenated blocks with len_hi replaced by min(len_hi, H), bit for bit; with len_hi <= H
+ * the whole-row filter itself.  A HALF WAVE LONGER THAN THE HORIZON IS NEVER KEPT: that is the price of a bounded latency.
+ * Latency D = ceil(H / L) blocks (itd_wave_stream_latency; -1 if s is not a wave stream): push p (counted from 0) emits block
+ * p - D when p >= D; every flush emits the next block still held, so min(P, D) flushes emit, emitted = 0 once the stream is empty,
+ * and the stream then starts afresh.  A push between flushes is refused.  Block b is decided from the samples
+ * [b L - H, (b+1) L + H) that exist and from nothing else; a ring of 2 D + 1 blocks per row is the stream's whole state.
+ *   8 <= block <= 8192, 1 <= rows <= 65535, 1 <= horizon <= 2^22.  Everything is allocated at create: the rings
+ *   (rows (2 D + 1) block 8 bytes), one 16-byte record per block in them (rows (2 D + 1) 16 bytes: whether the block holds a crossing
+ *   index, its largest magnitude), the host forms' device and pinned staging (two blocks and four bounds per row, each twice) and,
+ *   as for the other streams, an engine of the stream's own (its launch stream and error text); ITD_ERR_NOMEM when it does not
+ *   fit.  ITD_ERR_INVALID_ARG before any HIP call for a NULL handle, a NULL pointer or a value out of range.  A call that fails
+ *   leaves the stream as it was: a flush whose launch fails has emitted nothing and has not begun the flush.
+ *   block_dev: row r's block at block_dev + r in_stride (in_stride >= block when rows > 1) — the dense [channels][M+1][block] rows of
+ *     itd_levels_stream_push_f64 go in as channels (M+1) rows with in_stride = block.
+ *   out_dev: row r's filtered block at out_dev + r out_stride; required whenever the call emits, written only then.
+ *   bounds_dev: (amp_lo, amp_hi, len_lo, len_hi) of row r at bounds_dev + r bounds_stride, bounds_stride 0 (one set for every row)
+ *     or >= 4; device memory, read when the launch runs, as for itd_wave_filter_batch_*; required whenever the call emits.  A block
+ *     is filtered with the bounds that hold when it is emitted: a caller who changes the bounds in mid-stream judges a half wave
+ *     that spans two emitted blocks under both sets.
+ * Device forms: one launch per call on `stream`, no host synchronisation, no host read; *emitted follows from the block count
+ * alone.  Host forms: contiguous [rows][block] in and out, bounds_host [rows][4]; pinned staging, one synchronisation per call.
+ * A NaN in any pushed block sets bit 2 of itd_stream_status until itd_stream_reset; that row's emitted samples are unspecified
+ * from then on, nothing outside the row's own slots is written.  itd_stream_destroy / reset / blocks / status / last_error apply
+ * (blocks: pushed and not yet emitted); the single-level and the levels push / flush entries refuse a wave stream. */
+#define ITD_STREAM_WAVES 3    /* a wave-filter stream (itd_wave_stream_create); not a kind itd_stream_create takes */
+int itd_wave_stream_create(itd_stream **out, int device_id, int64_t block, int32_t rows, int64_t horizon);
+int itd_wave_stream_latency(const itd_stream *s);
+int itd_wave_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_stride, const double *bounds_dev,
+                             int64_t bounds_stride, double *out_dev, int64_t out_stride, int32_t *emitted, void *stream);
+int itd_wave_stream_flush_f64(itd_stream *s, const double *bounds_dev, int64_t bounds_stride, double *out_dev,
+                              int64_t out_stride, int32_t *emitted, void *stream);
+int itd_wave_stream_push_host_f64(itd_stream *s, const double *block_host, const double *bounds_host, double *out_host,
+                                  int32_t *emitted);
+int itd_wave_stream_flush_host_f64(itd_stream *s, const double *bounds_host, double *out_host, int32_t *emitted);
+
 /* ---- introspection for benchmarks -------------------------------------------------------------
  * hipEvent pairs on the launch stream.  Extraction launches are dispatched with their own start/stop events
  * (hipExtLaunchKernel: the events take the dispatch's own begin/end timestamps, so they agree with rocprofv3's kernel durations); the

@@ -13,6 +13,8 @@
 //   * block-wise operation (itd.cpp:31-38), itd_stream_*: a device-resident mirrored ring per channel (itd_stream.hpp), the
 //     window's knots, their selection and the operator all on the device — a push enqueues launches and returns; the host form
 //     synchronises once per push for its copies.  The recipe: include/pyitd_hip.h, DESIGN.md section 7.
+//   * the wave-filter stream, itd_wave_stream_*: itd_wave_filter_batch_*'s filter block by block at a fixed latency, one launch per
+//     push (itd_wave_stream.hpp, DESIGN.md section 21).
 
 namespace {
 
@@ -285,6 +287,12 @@ struct itd_stream {
     Buf<uint8_t> d_exact; Pinned<uint8_t> h_exact;   // host form: [C]
     size_t lds = 0;
     const void *fn = nullptr;
+    // wave-filter stream (ITD_STREAM_WAVES, k_wave_stream in itd_wave_stream.hpp): C rows, ring = [C][2 D + 1][L]; t = the blocks
+    // pushed, P as above
+    int64_t H = 0, sent = 0;        // the horizon; the blocks emitted since create / reset / the last flush
+    int32_t D = 0;                  // the latency in blocks, ceil(H / L)
+    Buf<double> d_bnd; Pinned<double> h_bnd;         // host form: [C][4]
+    Buf<WaveBlockRec> rec;          // [C][2 D + 1]: what every block in the ring left behind when it arrived
 };
 
 namespace {
@@ -516,6 +524,7 @@ int itd_stream_reset(itd_stream *s)
     s->pushed = 0;
     s->t = 0;
     s->P = -1;
+    s->sent = 0;
     HIP_TRY(s->eng, hipMemsetAsync(s->d_status, 0, sizeof(int32_t), s->eng->own_stream));
     HIP_TRY(s->eng, hipStreamSynchronize(s->eng->own_stream));
     return ITD_OK;
@@ -524,6 +533,7 @@ int itd_stream_reset(itd_stream *s)
 int64_t itd_stream_blocks(const itd_stream *s)
 {
     if (!s) return -1;
+    if (s->kind == ITD_STREAM_WAVES) return (s->P < 0 ? s->t : s->P) - s->sent;
     if (s->kind != ITD_STREAM_LEVELS) return s->pushed;
     return (s->P < 0 ? s->t : s->P) - std::max<int64_t>(0, s->t - s->M - 1);   // pushed, less the blocks whose rows have left
 }
@@ -532,7 +542,7 @@ const char *itd_stream_last_error(const itd_stream *s) { return s && s->eng ? s-
 int itd_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_stride, double *baseline_dev, int64_t baseline_stride,
                         double *rot_dev, int64_t rot_stride, int32_t *emitted, void *stream)
 {
-    if (!s || !block_dev || s->kind == ITD_STREAM_LEVELS) return ITD_ERR_INVALID_ARG;
+    if (!s || !block_dev || s->kind >= ITD_STREAM_LEVELS) return ITD_ERR_INVALID_ARG;   // (a levels or a wave stream: its own entries)
     if (s->C > 1 && (in_stride < s->L || (baseline_dev && baseline_stride < s->L) || (rot_dev && rot_stride < s->L))) return ITD_ERR_INVALID_ARG;
     if (s->pushed >= 1 && !baseline_dev) return ITD_ERR_INVALID_ARG;      // this push emits a block
     DevGuard g(s->eng->device);
@@ -542,7 +552,7 @@ int itd_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_strid
 int itd_stream_flush_f64(itd_stream *s, double *baseline_dev, int64_t baseline_stride, double *rot_dev, int64_t rot_stride,
                          int32_t *emitted, void *stream)
 {
-    if (!s || s->kind == ITD_STREAM_LEVELS) return ITD_ERR_INVALID_ARG;
+    if (!s || s->kind >= ITD_STREAM_LEVELS) return ITD_ERR_INVALID_ARG;
     if (s->pushed >= 1 && !baseline_dev) return ITD_ERR_INVALID_ARG;
     if (s->C > 1 && ((baseline_dev && baseline_stride < s->L) || (rot_dev && rot_stride < s->L))) return ITD_ERR_INVALID_ARG;
     DevGuard g(s->eng->device);
@@ -564,7 +574,7 @@ namespace {
 // host form: pinned staging in and out, ONE synchronisation per call
 int stream_host(itd_stream *s, const double *block_host, double *baseline_host, double *rot_host, int32_t *emitted, bool flush)
 {
-    if (!s || (!flush && !block_host) || !baseline_host || s->kind == ITD_STREAM_LEVELS) return ITD_ERR_INVALID_ARG;
+    if (!s || (!flush && !block_host) || !baseline_host || s->kind >= ITD_STREAM_LEVELS) return ITD_ERR_INVALID_ARG;
     itd_engine *e = s->eng;
     DevGuard g(e->device);
     const size_t cnt = (size_t)s->C * (size_t)s->L;
@@ -872,5 +882,189 @@ int itd_levels_stream_push_host_f64(itd_stream *s, const double *block_host, dou
 int itd_levels_stream_flush_host_f64(itd_stream *s, double *rows_host, uint8_t *exact_host, int32_t *emitted)
 {
     return levels_host(s, nullptr, rows_host, exact_host, emitted, true);
+}
+}  // extern "C"
+
+// ---- the wave-filter stream: itd_wave_stream_* (include/pyitd_hip.h; the kernel, the locality rule and the ring:
+//      k_wave_stream in itd_wave_stream.hpp) --------------------------------------------------------------------------------
+namespace {
+
+// one step, ONE launch: the arriving block (blk, or nullptr on a flush step) into the ring, block b (b < 0: none) filtered and out
+int wave_step(itd_stream *s, const double *blk, int64_t in_stride, const double *bounds, int64_t bounds_stride, double *out,
+              int64_t out_stride, int64_t b, hipStream_t st)
+{
+    const int64_t L = s->L, D = s->D, R = 2 * D + 1;
+    WaveStreamArgs a = {};
+    a.in = blk; a.in_stride = in_stride;
+    a.ring = s->ring;
+    a.rec = s->rec;
+    a.arr = s->t * L;
+    a.bounds = bounds; a.bounds_stride = bounds_stride;
+    a.out = out; a.out_stride = out_stride;
+    a.status = s->d_status;
+    a.L = (int32_t)L; a.D = (int32_t)D; a.H = (int32_t)s->H;
+    a.store_slot = blk ? (int32_t)(s->t % R) : 0;
+    a.emit = b >= 0 ? 1 : 0;
+    if (b >= 0) {
+        const int64_t exists = (s->P < 0 ? s->t + 1 : s->P) * L;          // (a push: the arriving block included)
+        const int64_t lo = std::max<int64_t>(b * L - s->H, 0), hi = std::min<int64_t>((b + 1) * L + s->H, exists);
+        a.base = (b - D) * L;
+        a.slot0 = (int32_t)((((b - D) % R) + R) % R);
+        a.rd_lo = (int32_t)(lo - a.base);
+        a.rd_hi = (int32_t)(hi - a.base);
+        a.at_start = lo == 0 ? 1 : 0;
+        a.at_end = s->P >= 0 && hi == exists ? 1 : 0;
+    }
+    void *args[] = {&a};
+    HIP_TRY(s->eng, hipLaunchKernel(s->fn, dim3((unsigned)s->C), dim3((unsigned)s->threads), args, s->lds, st));
+    HIP_TRY(s->eng, hipGetLastError());
+    return ITD_OK;
+}
+
+int wave_push(itd_stream *s, const double *blk, int64_t in_stride, const double *bounds, int64_t bounds_stride, double *out,
+              int64_t out_stride, int32_t *emitted, hipStream_t st)
+{
+    const bool emits = s->t >= s->D;
+    const int rc = wave_step(s, blk, in_stride, bounds, bounds_stride, out, out_stride, emits ? s->t - s->D : -1, st);
+    if (rc) return rc;
+    ++s->t;
+    if (emits) ++s->sent;
+    if (emitted) *emitted = emits ? 1 : 0;
+    return ITD_OK;
+}
+
+// one block per call: the next block still held
+int wave_flush(itd_stream *s, const double *bounds, int64_t bounds_stride, double *out, int64_t out_stride, int32_t *emitted,
+               hipStream_t st)
+{
+    if (emitted) *emitted = 0;
+    if (s->P < 0 && s->t == 0) return ITD_OK;      // empty: nothing to run
+    const bool begins = s->P < 0;                  // the first flush step: the stream's length is fixed from here on
+    if (begins) s->P = s->t;
+    const int rc = wave_step(s, nullptr, 0, bounds, bounds_stride, out, out_stride, s->sent, st);
+    if (rc) {                                      // nothing was emitted: the stream is as it was, pushes are still taken
+        if (begins) s->P = -1;
+        return rc;
+    }
+    if (emitted) *emitted = 1;
+    if (++s->sent == s->P) { s->t = 0; s->P = -1; s->sent = 0; }          // the last block: the stream starts afresh
+    return ITD_OK;
+}
+
+bool wave_io_ok(const itd_stream *s, bool emits, const double *bounds, int64_t bounds_stride, const double *out, int64_t out_stride)
+{
+    if (bounds_stride != 0 && bounds_stride < 4) return false;
+    if (emits && (!bounds || !out)) return false;
+    return s->C == 1 || !out || out_stride >= s->L;
+}
+
+}  // namespace
+
+extern "C" {
+
+int itd_wave_stream_create(itd_stream **out, int device_id, int64_t block, int32_t rows, int64_t horizon)
+{
+    if (!out) return ITD_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (block < 8 || block > kWaveStreamMaxBlock || rows < 1 || rows > kMaxGridY) return ITD_ERR_INVALID_ARG;
+    if (horizon < 1 || horizon > kWaveStreamMaxHorizon) return ITD_ERR_INVALID_ARG;
+    static_assert(kWaveStreamMaxBlock == kResidentMax, "the stream's largest block is the resident limit");
+    itd_stream *s = new (std::nothrow) itd_stream();
+    if (!s) return ITD_ERR_NOMEM;
+    int rc = itd_engine_create(&s->eng, device_id, 3 * block, 1);
+    if (rc) { delete s; return rc; }
+    s->L = block; s->C = rows; s->kind = ITD_STREAM_WAVES; s->H = horizon;
+    s->D = (int32_t)((horizon + block - 1) / block);
+    s->threads = block <= 256 * kWaveStreamSpt ? 256 : 1024;
+    s->fn = s->threads == 256 ? reinterpret_cast<const void *>(&k_wave_stream<256>) : reinterpret_cast<const void *>(&k_wave_stream<1024>);
+    s->lds = wave_stream_lds((int)block);
+    DevGuard g(device_id);
+    const size_t C = (size_t)rows, L = (size_t)block, R = 2 * (size_t)s->D + 1;
+    // the grant is the kernel function's, not this stream's: the most its instance ever asks for, so that a later stream with a
+    // shorter block does not lower it under a live one
+    hipError_t hrc = allow_lds(s->eng, s->fn, wave_stream_lds(s->threads == 256 ? 256 * kWaveStreamSpt : kWaveStreamMaxBlock));
+    if (hrc == hipSuccess) hrc = s->ring.alloc(C * R * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->rec.alloc(C * R * sizeof(WaveBlockRec));
+    if (hrc == hipSuccess) hrc = s->d_status.alloc(64);
+    if (hrc == hipSuccess) hrc = hipMemset(s->d_status, 0, 64);
+    // the host form's staging: [rows][L] in and out, [rows][4] bounds
+    if (hrc == hipSuccess) hrc = s->d_in.alloc(C * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->d_out.alloc(C * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->d_bnd.alloc(C * 4 * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->h_in.alloc(C * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->h_out.alloc(C * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->h_bnd.alloc(C * 4 * sizeof(double));
+    if (hrc == hipSuccess) hrc = hipDeviceSynchronize();     // (the fill ran on the null stream)
+    if (hrc != hipSuccess) {
+        const bool oom = hrc == hipErrorOutOfMemory;
+        (void)hipGetLastError();
+        itd_stream_destroy(s);
+        return oom ? ITD_ERR_NOMEM : ITD_ERR_HIP;
+    }
+    *out = s;
+    return ITD_OK;
+}
+
+int itd_wave_stream_latency(const itd_stream *s) { return s && s->kind == ITD_STREAM_WAVES ? s->D : -1; }
+
+int itd_wave_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_stride, const double *bounds_dev, int64_t bounds_stride,
+                             double *out_dev, int64_t out_stride, int32_t *emitted, void *stream)
+{
+    if (!s || !block_dev || s->kind != ITD_STREAM_WAVES) return ITD_ERR_INVALID_ARG;
+    if (s->P >= 0) return ITD_ERR_INVALID_ARG;                               // flushing: drain or reset first
+    if (s->C > 1 && in_stride < s->L) return ITD_ERR_INVALID_ARG;
+    if (!wave_io_ok(s, s->t >= s->D, bounds_dev, bounds_stride, out_dev, out_stride)) return ITD_ERR_INVALID_ARG;
+    DevGuard g(s->eng->device);
+    return wave_push(s, block_dev, in_stride, bounds_dev, bounds_stride, out_dev, out_stride, emitted, stream_of(s->eng, stream));
+}
+
+int itd_wave_stream_flush_f64(itd_stream *s, const double *bounds_dev, int64_t bounds_stride, double *out_dev, int64_t out_stride,
+                              int32_t *emitted, void *stream)
+{
+    if (!s || s->kind != ITD_STREAM_WAVES) return ITD_ERR_INVALID_ARG;
+    if (!wave_io_ok(s, itd_stream_blocks(s) > 0, bounds_dev, bounds_stride, out_dev, out_stride)) return ITD_ERR_INVALID_ARG;
+    DevGuard g(s->eng->device);
+    return wave_flush(s, bounds_dev, bounds_stride, out_dev, out_stride, emitted, stream_of(s->eng, stream));
+}
+
+}  // extern "C"
+
+namespace {
+// host form: pinned staging in and out, ONE synchronisation per call
+int wave_host(itd_stream *s, const double *block_host, const double *bounds_host, double *out_host, int32_t *emitted, bool flush)
+{
+    if (!s || s->kind != ITD_STREAM_WAVES || (!flush && !block_host) || !bounds_host || !out_host) return ITD_ERR_INVALID_ARG;
+    if (!flush && s->P >= 0) return ITD_ERR_INVALID_ARG;
+    itd_engine *e = s->eng;
+    DevGuard g(e->device);
+    const size_t cnt = (size_t)s->C * (size_t)s->L, bcnt = (size_t)s->C * 4;
+    hipStream_t st = e->own_stream;
+    int32_t em = 0;
+    int rc;
+    memcpy(s->h_bnd, bounds_host, bcnt * sizeof(double));
+    HIP_TRY(e, hipMemcpyAsync(s->d_bnd, s->h_bnd, bcnt * sizeof(double), hipMemcpyHostToDevice, st));
+    if (flush) rc = wave_flush(s, s->d_bnd, 4, s->d_out, s->L, &em, st);
+    else {
+        memcpy(s->h_in, block_host, cnt * sizeof(double));
+        HIP_TRY(e, hipMemcpyAsync(s->d_in, s->h_in, cnt * sizeof(double), hipMemcpyHostToDevice, st));
+        rc = wave_push(s, s->d_in, s->L, s->d_bnd, 4, s->d_out, s->L, &em, st);
+    }
+    if (rc) return rc;
+    if (em) HIP_TRY(e, hipMemcpyAsync(s->h_out, s->d_out, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(e, hipStreamSynchronize(st));
+    if (em) memcpy(out_host, s->h_out, cnt * sizeof(double));
+    if (emitted) *emitted = em;
+    return ITD_OK;
+}
+}  // namespace
+
+extern "C" {
+int itd_wave_stream_push_host_f64(itd_stream *s, const double *block_host, const double *bounds_host, double *out_host, int32_t *emitted)
+{
+    return wave_host(s, block_host, bounds_host, out_host, emitted, false);
+}
+int itd_wave_stream_flush_host_f64(itd_stream *s, const double *bounds_host, double *out_host, int32_t *emitted)
+{
+    return wave_host(s, nullptr, bounds_host, out_host, emitted, true);
 }
 }  // extern "C"

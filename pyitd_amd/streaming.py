@@ -23,6 +23,10 @@ spline through the NaN (unspecified samples).  A NaN in ANY channel sets status(
 ITDError (ITD_ERR_NONFINITE) from the first emitting call on.
 kind "linear": itd_baseline_extract on the window — away from a couple of knots at the window's ends bit-identical to the
 whole-signal operator, so a stream whose blocks hold a few knots each reproduces the whole-signal rows exactly.
+
+LevelsStream: the full multi-level decomposition block by block.  WaveFilterStream: the single-wave feature filter
+(pyitd_amd.wave_filter) block by block at a fixed latency — what takes a LevelsStream's rows and gives feature-filtered components,
+entirely on the device.
 """
 import ctypes
 
@@ -292,3 +296,144 @@ def blockwise_itd(x, block, levels, device=0):
     rows = numpy.concatenate([o[0] for o in outs], axis=2)
     exact = numpy.stack([o[1] for o in outs], axis=1)
     return (rows[0], exact[0]) if flat else (rows, exact)
+
+
+class WaveFilterStream:
+    """The single-wave feature filter block by block at a fixed latency (itd_wave_stream_* in include/pyitd_hip.h): blocks of
+    `rows` rows go in, the same blocks come out with the samples of the half waves outside the bounds set to +0.0 — bit for bit
+    pyitd_amd.wave_filter of the concatenated rows with the upper length bound capped at `horizon`.  A half wave longer than
+    `horizon` samples is never kept: that is the price of the bounded latency.  ONE launch per push on the GPU.
+
+        st = WaveFilterStream(1024, rows=9, horizon=2048)
+        st.latency                                      # D = ceil(horizon / block) = 2
+        for block in blocks:                            # block: [rows, 1024]
+            out = st.push(block, bounds)                # None for the first D pushes, then the filtered block p - D
+        while (out := st.flush(bounds)) is not None: ...
+
+    bounds: (amp_lo, amp_hi, len_lo, len_hi) as float64 [4] (one set for every row) or [rows, 4]; or amplitude=(lo, hi),
+    length=(lo, hi) as wave_filter takes them.  A block is filtered with the bounds given when it is emitted.  A NaN in a pushed block
+    sets status() bit 2 until reset(); that row's output is unspecified from then on.
+
+    Samples in, feature-filtered components out, entirely on the device — a LevelsStream's rows pushed by pointer:
+
+        lv = LevelsStream(1024, levels=4, channels=2)
+        wf = WaveFilterStream(1024, rows=2 * 5, horizon=2048)
+        # rows_d [2, 5, 1024], out_d [10, 1024], bounds_d [10, 4] float64 on the device, all on one stream `s`
+        if lv.push_dev(block_ptr, 1024, rows_ptr, 1024, 5 * 1024, None, s):
+            if wf.push_dev(rows_ptr, 1024, bounds_ptr, 4, out_ptr, 1024, s):
+                ...                                     # out_d holds the filtered rows of the block pushed levels + 1 + D steps ago
+    """
+
+    def __init__(self, block, rows=1, horizon=None, device=0):
+        horizon = block if horizon is None else horizon
+        if not 8 <= block <= 8192:
+            raise ValueError("block must be 8 .. 8192 samples")
+        if not 1 <= rows <= 65535:
+            raise ValueError("rows must be 1 .. 65535")
+        if not 1 <= horizon <= 2 ** 22:
+            raise ValueError("horizon must be 1 .. 2^22 samples")
+        self._L = _lib.load()
+        h = ctypes.c_void_p()
+        rc = self._L.itd_wave_stream_create(ctypes.byref(h), int(device), int(block), int(rows), int(horizon))
+        if rc:
+            raise ITDError(rc, "itd_wave_stream_create(block=%d, rows=%d, horizon=%d)" % (block, rows, horizon))
+        self._h = h
+        self.block, self.rows, self.horizon, self.device = int(block), int(rows), int(horizon), int(device)
+        self._flat = False          # the last push took a 1-D block: the blocks that leave are 1-D too
+
+    close = Stream.close
+    __del__ = Stream.__del__
+    _check = Stream._check
+    blocks_held = Stream.blocks_held
+    reset = Stream.reset
+    status = Stream.status
+
+    @property
+    def latency(self):
+        """D = ceil(horizon / block): push p emits block p - D."""
+        return self._L.itd_wave_stream_latency(self._h)
+
+    # ---- device buffers (raw pointers; asynchronous on `stream`) ----------------------------------------------------
+    def push_dev(self, block_ptr, in_stride, bounds_ptr, bounds_stride, out_ptr, out_stride, stream=None):
+        """Store one block of every row; True if a filtered block was written."""
+        em = ctypes.c_int32(0)
+        self._check(self._L.itd_wave_stream_push_f64(self._h, block_ptr, in_stride, bounds_ptr, bounds_stride, out_ptr, out_stride,
+                                                     ctypes.byref(em), stream))
+        return bool(em.value)
+
+    def flush_dev(self, bounds_ptr, bounds_stride, out_ptr, out_stride, stream=None):
+        em = ctypes.c_int32(0)
+        self._check(self._L.itd_wave_stream_flush_f64(self._h, bounds_ptr, bounds_stride, out_ptr, out_stride, ctypes.byref(em), stream))
+        return bool(em.value)
+
+    # ---- numpy in -> numpy out (one synchronisation per call) ----------------------------------------------------------
+    def _bounds(self, bounds, amplitude, length):
+        if bounds is None:
+            from .batch import _wave_bounds
+            inf = (0.0, numpy.inf)
+            bounds = _wave_bounds(inf if amplitude is None else amplitude, inf if length is None else length, (self.rows,))
+        elif amplitude is not None or length is not None:
+            raise ValueError("give bounds or amplitude= / length=, not both")
+        b = numpy.asarray(bounds, dtype=numpy.float64)
+        if b.shape == (4,):
+            b = numpy.broadcast_to(b, (self.rows, 4))
+        if b.shape != (self.rows, 4):
+            raise ValueError("bounds: [4] or [%d, 4], got %s" % (self.rows, b.shape))
+        return numpy.ascontiguousarray(b)
+
+    def push(self, samples, bounds=None, amplitude=None, length=None):
+        """samples [rows, block] (or [block] for one row).  None for the first `latency` pushes, then the filtered block pushed
+        `latency` pushes ago, shaped like the input."""
+        x = numpy.ascontiguousarray(samples, dtype=numpy.float64)
+        flat = x.ndim == 1
+        x2 = x.reshape(1, -1) if flat else x
+        if x2.shape != (self.rows, self.block):
+            raise ValueError("expected blocks of shape (%d, %d)" % (self.rows, self.block))
+        b = self._bounds(bounds, amplitude, length)
+        out = numpy.empty_like(x2)
+        em = ctypes.c_int32(0)
+        self._check(self._L.itd_wave_stream_push_host_f64(self._h, _np_ptr(x2), _np_ptr(b), _np_ptr(out), ctypes.byref(em)))
+        self._flat = flat
+        if not em.value:
+            return None
+        return out[0] if flat else out
+
+    def flush(self, bounds=None, amplitude=None, length=None):
+        """The next block still held (one per call), shaped like the blocks of the last push; None once the stream is empty."""
+        b = self._bounds(bounds, amplitude, length)
+        out = numpy.empty((self.rows, self.block))
+        em = ctypes.c_int32(0)
+        self._check(self._L.itd_wave_stream_flush_host_f64(self._h, _np_ptr(b), _np_ptr(out), ctypes.byref(em)))
+        if not em.value:
+            return None
+        return out[0] if self._flat else out
+
+
+def blockwise_wave_filter(rows, block, horizon, amplitude=(0.0, numpy.inf), length=(0.0, numpy.inf), device=0):
+    """Run rows[R, n_blocks * block] (or [n]) through a WaveFilterStream: what a caller with an unbounded source does block by
+    block.  Returns the filtered rows, shaped like the input: wave_filter(rows, amplitude, (length[0], min(length[1], horizon)))."""
+    x = numpy.asarray(rows, dtype=numpy.float64)
+    flat = x.ndim == 1
+    x2 = x.reshape(1, -1) if flat else x
+    if x2.ndim != 2:
+        raise ValueError("rows: [R, n] or [n]")
+    R, n = x2.shape
+    if n % block or n < block:
+        raise ValueError("the length must be a multiple of the block")
+    st = WaveFilterStream(block, R, horizon, device)
+    outs = []
+    try:
+        b = st._bounds(None, amplitude, length)
+        for k in range(n // block):
+            r = st.push(x2[:, k * block:(k + 1) * block], b)
+            if r is not None:
+                outs.append(r)
+        while True:
+            r = st.flush(b)
+            if r is None:
+                break
+            outs.append(r)
+    finally:
+        st.close()
+    y = numpy.concatenate(outs, axis=1)
+    return y[0] if flat else y

@@ -1,0 +1,121 @@
+"""Microseconds per push of the wave-filter stream (pyitd_amd.streaming.WaveFilterStream, device form), steady state, float64 rows on
+the device, L = 1024, rows in {9, 9 * 64}, H in {1024, 8192, 65536}, beside
+
+  * what a caller had before the stream for the same job: on every push a contiguous device copy of the (2 D + 1) L window
+    followed by itd_wave_filter_batch_f64 over it.  THIS COMPOSITION IS WRONG AT THE WINDOW'S EDGES (a half wave cut by the
+    window looks shorter and smaller than it is); it stands here for its cost only;
+  * LevelsStream.push_dev at L = 1024, 8 levels, rows / 9 channels: the stage whose rows the wave-filter stream consumes.
+
+The three forms run in one process, alternating, `--reps` times each; every figure is the median of the repetitions' means, with
+the spread (min .. max) behind it.  Rows: white noise, a random walk (long half waves: the searches run far) and a sine in noise,
+in turn.  usage: python tools/wave_stream_bench.py [--pushes 200] [--reps 3] > profiles/r20/wave_stream.txt"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from pyitd_amd import Engine, streaming  # noqa: E402
+
+L = 1024
+LEVELS = 8
+
+
+def rows_signal(rng, rows, n):
+    t = np.arange(n) / n
+    x = np.empty((rows, n))
+    for r in range(rows):
+        if r % 3 == 0:
+            x[r] = rng.standard_normal(n)
+        elif r % 3 == 1:
+            x[r] = np.cumsum(rng.standard_normal(n))
+        else:
+            x[r] = np.sin(2 * np.pi * rng.uniform(5, 500) * t) + 0.1 * rng.standard_normal(n)
+    return x
+
+
+def timed(step, pushes, warm, ts):
+    for k in range(warm):
+        step(k)
+    ts.synchronize()
+    t0 = time.perf_counter()
+    for k in range(pushes):
+        step(warm + k)
+    ts.synchronize()
+    return (time.perf_counter() - t0) / pushes * 1e6
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pushes", type=int, default=200)
+    ap.add_argument("--reps", type=int, default=3)
+    a = ap.parse_args()
+    rng = np.random.default_rng(0)
+    ts = torch.cuda.Stream()
+    s = ts.cuda_stream
+    print("# wave-filter stream, us per push (device form, steady state), L = %d, float64 rows on the device" % L)
+    print("# composition = device copy of the (2D+1) L window + itd_wave_filter_batch_f64: wrong at the window's edges, here for its cost only")
+    print("# levels = LevelsStream.push_dev, L = %d, %d levels, rows / 9 channels; median of %d repetitions of %d pushes (min .. max)"
+          % (L, LEVELS, a.reps, a.pushes))
+    print("# (the composition: %d pushes per repetition where its window exceeds 1224 blocks over all rows)" % max(20, a.pushes // 8))
+    for rows in (9, 9 * 64):
+        for H in (1024, 8192, 65536):
+            D = -(-H // L)
+            W = 2 * D + 1
+            nb = W + 8
+            n = nb * L
+            x = torch.from_numpy(rows_signal(rng, rows, n)).cuda()
+            bounds = torch.tensor([0.1, 10.0, 2.0, float(H)], dtype=torch.float64, device="cuda")
+            out = torch.empty(rows, L, dtype=torch.float64, device="cuda")
+            win = torch.empty(rows, W * L, dtype=torch.float64, device="cuda")
+            wout = torch.empty(rows, W * L, dtype=torch.float64, device="cuda")
+            C = rows // 9
+            xl = x[:C]
+            lrows = torch.empty(C, LEVELS + 1, L, dtype=torch.float64, device="cuda")
+            torch.cuda.synchronize()
+            eng = Engine(W * L, 1)
+            pushes = a.pushes if rows * W <= 9 * 17 * 8 else max(20, a.pushes // 8)       # (the composition moves the whole window)
+
+            def stream_form():
+                st = streaming.WaveFilterStream(L, rows, H)
+                us = timed(lambda k: st.push_dev(x[:, (k % nb) * L:].data_ptr(), n, bounds.data_ptr(), 0, out.data_ptr(), L, s),
+                           a.pushes, W + 8, ts)
+                st.close()
+                return us
+
+            def composition():
+                def step(k):
+                    with torch.cuda.stream(ts):
+                        win.copy_(x[:, (k % 8) * L:(k % 8 + W) * L])
+                    eng.wave_filter_batch_dev(win.data_ptr(), np.float64, W * L, rows, W * L, bounds.data_ptr(), 0, wout.data_ptr(),
+                                              W * L, False, None, s)
+                return timed(step, pushes, 5, ts)
+
+            def levels_form():
+                st = streaming.LevelsStream(L, LEVELS, C)
+                us = timed(lambda k: st.push_dev(xl[:, (k % nb) * L:].data_ptr(), n, lrows.data_ptr(), L, (LEVELS + 1) * L, None, s),
+                           a.pushes, LEVELS + 8, ts)
+                st.close()
+                return us
+
+            res = {"stream": [], "composition": [], "levels": []}
+            for _ in range(a.reps):
+                res["stream"].append(stream_form())
+                res["composition"].append(composition())
+                res["levels"].append(levels_form())
+            eng.close()
+
+            def fmt(v):
+                return "%9.1f (%.1f .. %.1f)" % (statistics.median(v), min(v), max(v))
+            print("rows=%4d H=%6d D=%3d  stream %s  composition %s  levels %s" % (rows, H, D, fmt(res["stream"]), fmt(res["composition"]),
+                                                                                 fmt(res["levels"])), flush=True)
+            del x, win, wout
+            torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
