@@ -883,6 +883,57 @@ int itd_wave_stream_push_host_f64(itd_stream *s, const double *block_host, const
                                   int32_t *emitted);
 int itd_wave_stream_flush_host_f64(itd_stream *s, const double *bounds_host, double *out_host, int32_t *emitted);
 
+/* ---- the spectrum stream: the time-frequency-energy spectrum block by block, at a fixed latency -----------
+ * itd_tfe_spectrum_* needs the whole row: a sample's amplitude is its half wave's largest |x|, known only when the half wave ends.
+ * A spectrum stream takes blocks of `rows` rows in lock step and gives finished time slices of their spectra, a known number of
+ * blocks later.  With blocks of L samples, a horizon of H samples and hop | L, row r after P pushes is x[0 .. P L).
+ *   A[j], f[j]   the instantaneous amplitude and frequency of the concatenated row: the same bits itd_instantaneous_batch_f64 gives for
+ *                it (the same expressions; the stream's last sample takes the backward difference, known at the flush).
+ *   overlong     sample j is overlong if its half wave has more than H samples, or sample j + 1 exists and ITS half wave has more
+ *                than H samples (f[j] needs A[j + 1]); the stream's last sample, which has no successor and whose backward difference
+ *                needs A of its predecessor, is overlong as well if that predecessor lies in another half wave of more than H
+ *                samples.  An overlong sample is outside, whatever its frequency would be.
+ *   emitted block b   C = L / hop cells: power[C][bins] (float64), outside[C], overlong[C] (int32) — exactly rows b C .. (b+1) C - 1 of
+ *                itd_tfe_spectrum_f64's definition above applied to the concatenated row with the overlong samples forced outside:
+ *                the same bins by the same comparisons, the same 64-sample step sums by the adjacent-pair tree, added into the cell
+ *                in increasing step order.  Every cell is written, an empty one as +0.0.  outside counts the overlong samples too,
+ *                overlong counts them alone.  Where no sample is overlong the slices are itd_tfe_spectrum_f64(concatenated rows,
+ *                edges, hop, weight) bit for bit.
+ * Latency D = ceil((H + 1) / L) blocks (itd_spectrum_stream_latency; -1 if s is not a spectrum stream) — one sample more than the
+ * wave-filter stream's reach: the last sample of block b needs A of sample (b+1) L, whose half wave, if it has at most H samples,
+ * ends at (b+1) L + H - 1 at the latest, and the crossing test reads one sample further.  Block b is decided from the samples
+ * [b L - H, (b+1) L + H] that exist and from nothing else.  Push p (counted from 0) emits block p - D when p >= D; every flush emits
+ * the next block still held, then emitted = 0 and the stream starts afresh.  A push between flushes is refused.
+ *   64 <= block <= 4096, hop a value itd_tfe_spectrum_* accepts (a positive multiple of 64; below 512 only 64, 128, 256) that
+ *   divides block, 1 <= rows <= 65535, 1 <= horizon <= 2^22, 1 <= bins <= 512, weight 0 (count), 1 (amplitude), 2 (energy).
+ *   Everything is allocated at create: the rings (rows (2 D + 1) block 8 bytes), one 16-byte record per block in them, the host forms'
+ *   staging and an engine of the stream's own; ITD_ERR_NOMEM when it does not fit.  ITD_ERR_INVALID_ARG before any HIP call for a
+ *   NULL handle, a NULL pointer or a value out of range.  A call that fails leaves the stream as it was.
+ *   block_dev: row r's block at block_dev + r in_stride (in_stride >= block when rows > 1).
+ *   edges_dev: edges[0 .. bins] of row r at edges_dev + r edges_stride; edges_stride 0 (one set for every row) or >= bins + 1; device
+ *     memory, read when the launch runs (finite and strictly increasing: the caller's duty); a caller may move them between pushes;
+ *     required whenever the call emits.
+ *   power_dev: row r's cells at power_dev + r power_stride (>= C bins when rows > 1); required whenever the call emits, written only then.
+ *   outside_dev, overlong_dev: optional; row r's counts at + r count_stride (>= C when rows > 1).
+ * Device forms: one launch per call on `stream`, no host synchronisation, no host read; *emitted follows from the block count alone.
+ * Host forms: contiguous [rows][block] in, [rows][C][bins] and [rows][C] out, edges_host with edges_stride as above; pinned staging,
+ * one synchronisation per call.  A NaN in any pushed block sets bit 2 of itd_stream_status until itd_stream_reset; that row is
+ * unspecified from then on, nothing outside the row's own slots is written.  itd_stream_destroy / reset / blocks / status /
+ * last_error apply; every other stream kind's push and flush entries refuse a spectrum stream, and these refuse theirs. */
+#define ITD_STREAM_SPECTRUM 4 /* a spectrum stream (itd_spectrum_stream_create); not a kind itd_stream_create takes */
+int itd_spectrum_stream_create(itd_stream **out, int device_id, int64_t block, int32_t rows, int64_t horizon, int64_t hop, int32_t bins,
+                               int32_t weight);
+int itd_spectrum_stream_latency(const itd_stream *s);
+int itd_spectrum_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_stride, const double *edges_dev, int64_t edges_stride,
+                                 double *power_dev, int64_t power_stride, int32_t *outside_dev, int32_t *overlong_dev,
+                                 int64_t count_stride, int32_t *emitted, void *stream);
+int itd_spectrum_stream_flush_f64(itd_stream *s, const double *edges_dev, int64_t edges_stride, double *power_dev, int64_t power_stride,
+                                  int32_t *outside_dev, int32_t *overlong_dev, int64_t count_stride, int32_t *emitted, void *stream);
+int itd_spectrum_stream_push_host_f64(itd_stream *s, const double *block_host, const double *edges_host, int64_t edges_stride,
+                                      double *power_host, int32_t *outside_host, int32_t *overlong_host, int32_t *emitted);
+int itd_spectrum_stream_flush_host_f64(itd_stream *s, const double *edges_host, int64_t edges_stride, double *power_host,
+                                       int32_t *outside_host, int32_t *overlong_host, int32_t *emitted);
+
 /* ---- introspection for benchmarks -------------------------------------------------------------
  * hipEvent pairs on the launch stream.  Extraction launches are dispatched with their own start/stop events
  * (hipExtLaunchKernel: the events take the dispatch's own begin/end timestamps, so they agree with rocprofv3's kernel durations); the

@@ -34,6 +34,7 @@
 #include "itd_waves.hpp"
 #include "itd_wave_hist.hpp"
 #include "itd_wave_stream.hpp"
+#include "itd_spectrum_stream.hpp"
 #include "itd_spline.hpp"
 #include "itd_nak.hpp"
 #include "itd_wpe.hpp"

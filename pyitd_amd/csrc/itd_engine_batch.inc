@@ -293,6 +293,11 @@ struct itd_stream {
     int32_t D = 0;                  // the latency in blocks, ceil(H / L)
     Buf<double> d_bnd; Pinned<double> h_bnd;         // host form: [C][4]
     Buf<WaveBlockRec> rec;          // [C][2 D + 1]: what every block in the ring left behind when it arrived
+    // spectrum stream (ITD_STREAM_SPECTRUM, k_spectrum_stream in itd_spectrum_stream.hpp): the wave stream's ring, records and counters
+    // with D = ceil((H + 1) / L); host form: d_out / h_out = power [C][L / hop][F], d_bnd / h_bnd = edges [C][F + 1]
+    int32_t F = 0, weight = 0;      // bins; 0 count, 1 amplitude, 2 energy
+    int64_t hop = 0;
+    Buf<int32_t> d_cnt; Pinned<int32_t> h_cnt;       // host form: outside and overlong, [2][C][L / hop]
 };
 
 namespace {
@@ -533,7 +538,7 @@ int itd_stream_reset(itd_stream *s)
 int64_t itd_stream_blocks(const itd_stream *s)
 {
     if (!s) return -1;
-    if (s->kind == ITD_STREAM_WAVES) return (s->P < 0 ? s->t : s->P) - s->sent;
+    if (s->kind == ITD_STREAM_WAVES || s->kind == ITD_STREAM_SPECTRUM) return (s->P < 0 ? s->t : s->P) - s->sent;
     if (s->kind != ITD_STREAM_LEVELS) return s->pushed;
     return (s->P < 0 ? s->t : s->P) - std::max<int64_t>(0, s->t - s->M - 1);   // pushed, less the blocks whose rows have left
 }
@@ -542,7 +547,7 @@ const char *itd_stream_last_error(const itd_stream *s) { return s && s->eng ? s-
 int itd_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_stride, double *baseline_dev, int64_t baseline_stride,
                         double *rot_dev, int64_t rot_stride, int32_t *emitted, void *stream)
 {
-    if (!s || !block_dev || s->kind >= ITD_STREAM_LEVELS) return ITD_ERR_INVALID_ARG;   // (a levels or a wave stream: its own entries)
+    if (!s || !block_dev || s->kind >= ITD_STREAM_LEVELS) return ITD_ERR_INVALID_ARG;   // (a levels, a wave or a spectrum stream: its own entries)
     if (s->C > 1 && (in_stride < s->L || (baseline_dev && baseline_stride < s->L) || (rot_dev && rot_stride < s->L))) return ITD_ERR_INVALID_ARG;
     if (s->pushed >= 1 && !baseline_dev) return ITD_ERR_INVALID_ARG;      // this push emits a block
     DevGuard g(s->eng->device);
@@ -1066,5 +1071,222 @@ int itd_wave_stream_push_host_f64(itd_stream *s, const double *block_host, const
 int itd_wave_stream_flush_host_f64(itd_stream *s, const double *bounds_host, double *out_host, int32_t *emitted)
 {
     return wave_host(s, nullptr, bounds_host, out_host, emitted, true);
+}
+}  // extern "C"
+
+// ---- the spectrum stream: itd_spectrum_stream_* (include/pyitd_hip.h; the kernel, the locality rule and the LDS budget:
+//      k_spectrum_stream in itd_spectrum_stream.hpp) ---------------------------------------------------------------------------
+namespace {
+
+// one step, ONE launch: the arriving block (blk, or nullptr on a flush step) into the ring, block b's cells (b < 0: none) out
+int spectrum_step(itd_stream *s, const double *blk, int64_t in_stride, const double *edges, int64_t edges_stride, double *power,
+                  int64_t power_stride, int32_t *outside, int32_t *overlong, int64_t count_stride, int64_t b, hipStream_t st)
+{
+    const int64_t L = s->L, D = s->D, R = 2 * D + 1;
+    SpectrumStreamArgs a = {};
+    a.in = blk; a.in_stride = in_stride;
+    a.ring = s->ring;
+    a.rec = s->rec;
+    a.arr = s->t * L;
+    a.edges = edges; a.edges_stride = edges_stride;
+    a.power = power; a.power_stride = power_stride;
+    a.outside = outside; a.overlong = overlong; a.count_stride = count_stride;
+    a.status = s->d_status;
+    a.L = (int32_t)L; a.D = (int32_t)D; a.H = (int32_t)s->H;
+    a.F = s->F; a.spc = (int32_t)(s->hop / 64); a.weight = s->weight;
+    a.store_slot = blk ? (int32_t)(s->t % R) : 0;
+    a.emit = b >= 0 ? 1 : 0;
+    if (b >= 0) {
+        const int64_t exists = (s->P < 0 ? s->t + 1 : s->P) * L;          // (a push: the arriving block included)
+        const int64_t lo = std::max<int64_t>(b * L - s->H, 0), hi = std::min<int64_t>((b + 1) * L + s->H + 1, exists);
+        a.base = (b - D) * L;
+        a.slot0 = (int32_t)((((b - D) % R) + R) % R);
+        a.rd_lo = (int32_t)(lo - a.base);
+        a.rd_hi = (int32_t)(hi - a.base);
+        a.at_start = lo == 0 ? 1 : 0;
+        a.at_end = s->P >= 0 && hi == exists ? 1 : 0;
+    }
+    void *args[] = {&a};
+    HIP_TRY(s->eng, hipLaunchKernel(s->fn, dim3((unsigned)s->C), dim3((unsigned)s->threads), args, s->lds, st));
+    HIP_TRY(s->eng, hipGetLastError());
+    return ITD_OK;
+}
+
+int spectrum_push(itd_stream *s, const double *blk, int64_t in_stride, const double *edges, int64_t edges_stride, double *power,
+                  int64_t power_stride, int32_t *outside, int32_t *overlong, int64_t count_stride, int32_t *emitted, hipStream_t st)
+{
+    const bool emits = s->t >= s->D;
+    const int rc = spectrum_step(s, blk, in_stride, edges, edges_stride, power, power_stride, outside, overlong, count_stride,
+                                 emits ? s->t - s->D : -1, st);
+    if (rc) return rc;
+    ++s->t;
+    if (emits) ++s->sent;
+    if (emitted) *emitted = emits ? 1 : 0;
+    return ITD_OK;
+}
+
+// one block per call: the next block still held
+int spectrum_flush(itd_stream *s, const double *edges, int64_t edges_stride, double *power, int64_t power_stride, int32_t *outside,
+                   int32_t *overlong, int64_t count_stride, int32_t *emitted, hipStream_t st)
+{
+    if (emitted) *emitted = 0;
+    if (s->P < 0 && s->t == 0) return ITD_OK;      // empty: nothing to run
+    const bool begins = s->P < 0;                  // the first flush step: the stream's length is fixed from here on
+    if (begins) s->P = s->t;
+    const int rc = spectrum_step(s, nullptr, 0, edges, edges_stride, power, power_stride, outside, overlong, count_stride, s->sent, st);
+    if (rc) {                                      // nothing was emitted: the stream is as it was, pushes are still taken
+        if (begins) s->P = -1;
+        return rc;
+    }
+    if (emitted) *emitted = 1;
+    if (++s->sent == s->P) { s->t = 0; s->P = -1; s->sent = 0; }          // the last block: the stream starts afresh
+    return ITD_OK;
+}
+
+bool spectrum_io_ok(const itd_stream *s, bool emits, const double *edges, int64_t edges_stride, const double *power, int64_t power_stride,
+                    const int32_t *outside, const int32_t *overlong, int64_t count_stride)
+{
+    const int64_t cells = s->L / s->hop;
+    if (edges_stride != 0 && edges_stride < s->F + 1) return false;
+    if (emits && (!edges || !power)) return false;
+    if (s->C == 1) return true;
+    if (power && power_stride < cells * s->F) return false;
+    return !(outside || overlong) || count_stride >= cells;
+}
+
+bool spectrum_hop_ok(int64_t hop) { return hop >= 64 && hop % 64 == 0 && (hop >= kTfeTile || hop == 64 || hop == 128 || hop == 256); }
+
+}  // namespace
+
+extern "C" {
+
+int itd_spectrum_stream_create(itd_stream **out, int device_id, int64_t block, int32_t rows, int64_t horizon, int64_t hop, int32_t bins,
+                               int32_t weight)
+{
+    if (!out) return ITD_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (block < kSpectrumStreamMinBlock || block > kSpectrumStreamMaxBlock || rows < 1 || rows > kMaxGridY) return ITD_ERR_INVALID_ARG;
+    if (horizon < 1 || horizon > kWaveStreamMaxHorizon) return ITD_ERR_INVALID_ARG;
+    if (!spectrum_hop_ok(hop) || block % hop != 0) return ITD_ERR_INVALID_ARG;
+    if (bins < 1 || bins > kTfeMaxBins || weight < 0 || weight > 2) return ITD_ERR_INVALID_ARG;
+    itd_stream *s = new (std::nothrow) itd_stream();
+    if (!s) return ITD_ERR_NOMEM;
+    int rc = itd_engine_create(&s->eng, device_id, 3 * block, 1);
+    if (rc) { delete s; return rc; }
+    s->L = block; s->C = rows; s->kind = ITD_STREAM_SPECTRUM; s->H = horizon;
+    s->hop = hop; s->F = bins; s->weight = weight;
+    s->D = (int32_t)((horizon + 1 + block - 1) / block);
+    s->threads = block <= 256 * kWaveStreamSpt ? 256 : 512;
+    s->fn = s->threads == 256 ? reinterpret_cast<const void *>(&k_spectrum_stream<256>) : reinterpret_cast<const void *>(&k_spectrum_stream<512>);
+    s->lds = spectrum_stream_lds((int)block, bins, s->threads);
+    DevGuard g(device_id);
+    const size_t C = (size_t)rows, L = (size_t)block, R = 2 * (size_t)s->D + 1, cells = (size_t)(block / hop), F = (size_t)bins;
+    // the grant is the kernel function's, not this stream's: the most its instance ever asks for (wave stream: the same rule)
+    hipError_t hrc = allow_lds(s->eng, s->fn, spectrum_stream_lds(s->threads == 256 ? 256 * kWaveStreamSpt : kSpectrumStreamMaxBlock,
+                                                                  kTfeMaxBins, s->threads));
+    if (hrc == hipSuccess) hrc = s->ring.alloc(C * R * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->rec.alloc(C * R * sizeof(WaveBlockRec));
+    if (hrc == hipSuccess) hrc = s->d_status.alloc(64);
+    if (hrc == hipSuccess) hrc = hipMemset(s->d_status, 0, 64);
+    // the host form's staging: [rows][L] in, [rows][cells][F] power and [2][rows][cells] counts out, [rows][F + 1] edges
+    if (hrc == hipSuccess) hrc = s->d_in.alloc(C * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->d_out.alloc(C * cells * F * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->d_bnd.alloc(C * (F + 1) * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->d_cnt.alloc(2 * C * cells * sizeof(int32_t));
+    if (hrc == hipSuccess) hrc = s->h_in.alloc(C * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->h_out.alloc(C * cells * F * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->h_bnd.alloc(C * (F + 1) * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->h_cnt.alloc(2 * C * cells * sizeof(int32_t));
+    if (hrc == hipSuccess) hrc = hipDeviceSynchronize();     // (the fill ran on the null stream)
+    if (hrc != hipSuccess) {
+        const bool oom = hrc == hipErrorOutOfMemory;
+        (void)hipGetLastError();
+        itd_stream_destroy(s);
+        return oom ? ITD_ERR_NOMEM : ITD_ERR_HIP;
+    }
+    *out = s;
+    return ITD_OK;
+}
+
+int itd_spectrum_stream_latency(const itd_stream *s) { return s && s->kind == ITD_STREAM_SPECTRUM ? s->D : -1; }
+
+int itd_spectrum_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_stride, const double *edges_dev, int64_t edges_stride,
+                                 double *power_dev, int64_t power_stride, int32_t *outside_dev, int32_t *overlong_dev, int64_t count_stride,
+                                 int32_t *emitted, void *stream)
+{
+    if (!s || !block_dev || s->kind != ITD_STREAM_SPECTRUM) return ITD_ERR_INVALID_ARG;
+    if (s->P >= 0) return ITD_ERR_INVALID_ARG;                               // flushing: drain or reset first
+    if (s->C > 1 && in_stride < s->L) return ITD_ERR_INVALID_ARG;
+    if (!spectrum_io_ok(s, s->t >= s->D, edges_dev, edges_stride, power_dev, power_stride, outside_dev, overlong_dev, count_stride))
+        return ITD_ERR_INVALID_ARG;
+    DevGuard g(s->eng->device);
+    return spectrum_push(s, block_dev, in_stride, edges_dev, edges_stride, power_dev, power_stride, outside_dev, overlong_dev, count_stride,
+                         emitted, stream_of(s->eng, stream));
+}
+
+int itd_spectrum_stream_flush_f64(itd_stream *s, const double *edges_dev, int64_t edges_stride, double *power_dev, int64_t power_stride,
+                                  int32_t *outside_dev, int32_t *overlong_dev, int64_t count_stride, int32_t *emitted, void *stream)
+{
+    if (!s || s->kind != ITD_STREAM_SPECTRUM) return ITD_ERR_INVALID_ARG;
+    if (!spectrum_io_ok(s, itd_stream_blocks(s) > 0, edges_dev, edges_stride, power_dev, power_stride, outside_dev, overlong_dev, count_stride))
+        return ITD_ERR_INVALID_ARG;
+    DevGuard g(s->eng->device);
+    return spectrum_flush(s, edges_dev, edges_stride, power_dev, power_stride, outside_dev, overlong_dev, count_stride, emitted,
+                          stream_of(s->eng, stream));
+}
+
+}  // extern "C"
+
+namespace {
+// host form: pinned staging in and out, ONE synchronisation per call
+int spectrum_host(itd_stream *s, const double *block_host, const double *edges_host, int64_t edges_stride, double *power_host,
+                  int32_t *outside_host, int32_t *overlong_host, int32_t *emitted, bool flush)
+{
+    if (!s || s->kind != ITD_STREAM_SPECTRUM || (!flush && !block_host) || !edges_host || !power_host) return ITD_ERR_INVALID_ARG;
+    if (edges_stride != 0 && edges_stride < s->F + 1) return ITD_ERR_INVALID_ARG;
+    if (!flush && s->P >= 0) return ITD_ERR_INVALID_ARG;
+    itd_engine *e = s->eng;
+    DevGuard g(e->device);
+    const size_t C = (size_t)s->C, cnt = C * (size_t)s->L, cells = (size_t)(s->L / s->hop), F1 = (size_t)s->F + 1;
+    const size_t pcnt = C * cells * (size_t)s->F, ccnt = C * cells;
+    hipStream_t st = e->own_stream;
+    int32_t em = 0;
+    int rc;
+    for (size_t r = 0; r < (edges_stride ? C : 1); ++r) memcpy(s->h_bnd + r * F1, edges_host + r * (size_t)edges_stride, F1 * sizeof(double));
+    HIP_TRY(e, hipMemcpyAsync(s->d_bnd, s->h_bnd, (edges_stride ? C : 1) * F1 * sizeof(double), hipMemcpyHostToDevice, st));
+    const int64_t es = edges_stride ? (int64_t)F1 : 0, ps = (int64_t)(cells * (size_t)s->F);
+    int32_t *d_outside = s->d_cnt, *d_overlong = s->d_cnt + ccnt;
+    if (flush) rc = spectrum_flush(s, s->d_bnd, es, s->d_out, ps, d_outside, d_overlong, (int64_t)cells, &em, st);
+    else {
+        memcpy(s->h_in, block_host, cnt * sizeof(double));
+        HIP_TRY(e, hipMemcpyAsync(s->d_in, s->h_in, cnt * sizeof(double), hipMemcpyHostToDevice, st));
+        rc = spectrum_push(s, s->d_in, s->L, s->d_bnd, es, s->d_out, ps, d_outside, d_overlong, (int64_t)cells, &em, st);
+    }
+    if (rc) return rc;
+    if (em) {
+        HIP_TRY(e, hipMemcpyAsync(s->h_out, s->d_out, pcnt * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(e, hipMemcpyAsync(s->h_cnt, s->d_cnt, 2 * ccnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(e, hipStreamSynchronize(st));
+    if (em) {
+        memcpy(power_host, s->h_out, pcnt * sizeof(double));
+        if (outside_host) memcpy(outside_host, s->h_cnt, ccnt * sizeof(int32_t));
+        if (overlong_host) memcpy(overlong_host, s->h_cnt + ccnt, ccnt * sizeof(int32_t));
+    }
+    if (emitted) *emitted = em;
+    return ITD_OK;
+}
+}  // namespace
+
+extern "C" {
+int itd_spectrum_stream_push_host_f64(itd_stream *s, const double *block_host, const double *edges_host, int64_t edges_stride,
+                                      double *power_host, int32_t *outside_host, int32_t *overlong_host, int32_t *emitted)
+{
+    return spectrum_host(s, block_host, edges_host, edges_stride, power_host, outside_host, overlong_host, emitted, false);
+}
+int itd_spectrum_stream_flush_host_f64(itd_stream *s, const double *edges_host, int64_t edges_stride, double *power_host,
+                                       int32_t *outside_host, int32_t *overlong_host, int32_t *emitted)
+{
+    return spectrum_host(s, nullptr, edges_host, edges_stride, power_host, outside_host, overlong_host, emitted, true);
 }
 }  // extern "C"

@@ -19,7 +19,8 @@
 // H <= D L, so the readable range lies in the blocks b - D .. b + D: a ring of R = 2 D + 1 blocks per row, block q in slot q % R.
 // Push p stores block p and (p >= D) emits block p - D; the flush steps emit the blocks still held.
 //
-// One launch per step, one workgroup per row (k_wave_stream):
+// One launch per step, one workgroup per row (k_wave_stream; steps 1 to 3 are device functions — WaveRing, wave_ring_store,
+// wave_ring_cut, wave_ring_search_left / _right — that k_spectrum_stream of itd_spectrum_stream.hpp calls too):
 //   1. the arriving block into the row's ring (a NaN in it: status = 2, a plain store); the launch itself reads the arriving block
 //      from the caller's pointer, so no fence stands between the store and the searches;
 //   2. the emitted block's samples in registers, their crossing flags as ballots and a prefix over them in LDS: every sample's
@@ -88,73 +89,40 @@ inline size_t wave_stream_lds(int L)
            groups * sizeof(int32_t) + 8 * sizeof(int32_t) + sizeof(unsigned long long);
 }
 
-template <int TH>
-__global__ __launch_bounds__(TH) void k_wave_stream(WaveStreamArgs a)
-{
-    constexpr int SPT = kWaveStreamSpt, U = kWaveStreamUnroll, W = TH / 64;
-    static_assert(TH % 64 == 0 && TH * SPT >= 64, "geometry");
-    extern __shared__ __attribute__((aligned(16))) unsigned char ws_lds[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int L = a.L, D = a.D, H = a.H, R = 2 * D + 1;
-    const int G = (L + 63) >> 6;                                          // 64-sample groups of the block
-    unsigned long long *mag = reinterpret_cast<unsigned long long *>(ws_lds);          // [L + 1]
-    unsigned long long *bal = mag + (L + 1);                                          // [G]
-    unsigned long long *amx = bal + G;                                                // [1] the arriving block's max |x|
-    int32_t *edge = reinterpret_cast<int32_t *>(amx + 1);                              // [L + 2], positions relative to the block
-    int32_t *pre = edge + (L + 2);                                                    // [G]
-    int32_t *ctl = pre + G;           // [0] c, [1] the left search's crossing, [2] the right search's, [3] the arriving block's flag
-    const int64_t row = blockIdx.x;
-    double *const ring = a.ring + row * (int64_t)R * L;
-    const double *const in = a.in ? a.in + row * a.in_stride : nullptr;
-    WaveBlockRec *const rec = a.rec + row * (int64_t)R;
+// ---- what the stream kernels share (k_wave_stream here, k_spectrum_stream in itd_spectrum_stream.hpp): one row's ring as a launch
+// sees it, the arriving block's record, and the two searches that pass whole blocks by their records ---------------------------------
 
-    // 1. the arriving block into its slot, its record behind it
-    if (in) {
-        if (tid == 0) { *amx = 0ull; ctl[3] = 0; }
-        __syncthreads();
-        double *dst = ring + (int64_t)a.store_slot * L;
-        bool nan = false, cross = false;
-        unsigned long long mx = 0ull;
-        for (int s = tid; s < L; s += TH) {
-            const double v = in[s];
-            nan |= v != v;
-            dst[s] = v;
-            mx = max(mx, inst_mag(v, true));
-            if (s + 1 < L) cross |= tfe_crossing(a.arr + s, a.arr + L, v, in[s + 1]);
-        }
-        if (nan) *a.status = 2;                                           // (every writer stores the same word)
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) mx = max(mx, (unsigned long long)__shfl_xor(mx, d));
-        if (lane == 0 && mx) atomicMax(amx, mx);
-        if (__any(cross) && lane == 0) ctl[3] = 1;
-        __syncthreads();
-        if (tid == 0) rec[a.store_slot] = {*amx, ctl[3], 0};
-    }
-    if (!a.emit) return;
+// One row's ring window: window position w (0 <= w < R L) is the sample base + w of the stream; window block k sits in ring slot
+// (slot0 + k) % R, but the arriving block (k = 2 D of a push), which is read from the caller's pointer.
+struct WaveRing {
+    const double *in;              // the arriving block of this row (nullptr on a flush step)
+    double *ring;                  // [R][L]
+    WaveBlockRec *rec;             // [R]
+    int64_t base, n_abs;           // the absolute index of window position 0; of the readable range's end (a crossing index's successor lies inside it)
+    int32_t L, D, R, slot0, rd_lo, rd_hi, lane;
 
-    // window position w (0 <= w < R L) -> the sample: the arriving block from the caller's pointer, any other from the ring
-    auto ld = [&](int w) -> double {
+    __device__ __forceinline__ double ld(int w) const
+    {
         const int k = (int)((unsigned)w / (unsigned)L), s = w - k * L;
         if (in && k == 2 * D) return in[s];
-        int slot = a.slot0 + k;
+        int slot = slot0 + k;
         if (slot >= R) slot -= R;
         return ring[(int64_t)slot * L + s];
-    };
-    const int b0 = D * L;                                                 // the emitted block's first window position
-    const int64_t n_abs = a.base + a.rd_hi;                               // a crossing index's successor lies inside the readable range
+    }
     // Window block k (never the arriving one) can be passed whole: no crossing index among its samples, its last one included
     // (whose successor, block k + 1's first sample, the caller has checked to be readable).  mx: its max |x|.
-    auto passable = [&](int k, unsigned long long &mx) -> bool {
-        int slot = a.slot0 + k;
+    __device__ __forceinline__ bool passable(int k, unsigned long long &mx) const
+    {
+        int slot = slot0 + k;
         if (slot >= R) slot -= R;
         const WaveBlockRec r = rec[slot];
         mx = r.mx;
         const int w = (k + 1) * L - 1;
-        return r.cross == 0 && !tfe_crossing(a.base + w, n_abs, ld(w), ld(w + 1));
-    };
+        return r.cross == 0 && !tfe_crossing(base + w, n_abs, ld(w), ld(w + 1));
+    }
     // the lanes' verdicts on 64 blocks in search order: how many can be passed before the first that cannot, their max |x| into m
-    auto pass_blocks = [&](bool ok, unsigned long long mx, unsigned long long &m) -> int {
+    __device__ __forceinline__ int pass_blocks(bool ok, unsigned long long mx, unsigned long long &m) const
+    {
         const unsigned long long no = ~__ballot(ok);
         const int f = no ? __builtin_ctzll(no) : 64;
         unsigned long long part = lane < f ? mx : 0ull;
@@ -162,26 +130,154 @@ __global__ __launch_bounds__(TH) void k_wave_stream(WaveStreamArgs a)
         for (int d = 32; d >= 1; d >>= 1) part = max(part, (unsigned long long)__shfl_xor(part, d));
         m = max(m, part);
         return f;
-    };
+    }
+};
 
-    // 2. the block: samples, flags, half-wave numbers, inner maxima
-    for (int i = tid; i <= L; i += TH) mag[i] = 0ull;
-    if (tid == 0) { ctl[1] = INT32_MIN; ctl[2] = INT32_MAX; }
-    const double *const blk = ring + (int64_t)((a.slot0 + D) % R) * L;    // (window block D: never the arriving one, D >= 1)
-    double xr[SPT];
-    bool cr[SPT];
+// the ring of row `row` under a launch's arguments (WaveStreamArgs, SpectrumStreamArgs: the same ring fields)
+template <typename Args>
+__device__ __forceinline__ WaveRing wave_ring_of(const Args &a, int64_t row, int lane)
+{
+    const int R = 2 * a.D + 1;
+    return {a.in ? a.in + row * a.in_stride : nullptr, a.ring + row * (int64_t)R * a.L, a.rec + row * (int64_t)R, a.base, a.base + a.rd_hi,
+            a.L, a.D, R, a.slot0, a.rd_lo, a.rd_hi, lane};
+}
+
+// The arriving block (absolute index of its first sample: arr) into its slot, its record behind it; a NaN in it: *status = 2, a plain
+// store.  amx (one word) and flag (one word): LDS.  Called by every thread of the row's workgroup; ends behind a barrier.
+template <int TH>
+__device__ __forceinline__ void wave_ring_store(const WaveRing &rg, int64_t arr, int store_slot, int32_t *status, unsigned long long *amx,
+                                                int32_t *flag, int tid)
+{
+    const int L = rg.L, lane = rg.lane;
+    const double *const in = rg.in;
+    if (tid == 0) { *amx = 0ull; *flag = 0; }
+    __syncthreads();
+    double *dst = rg.ring + (int64_t)store_slot * L;
+    bool nan = false, cross = false;
+    unsigned long long mx = 0ull;
+    for (int s = tid; s < L; s += TH) {
+        const double v = in[s];
+        nan |= v != v;
+        dst[s] = v;
+        mx = max(mx, inst_mag(v, true));
+        if (s + 1 < L) cross |= tfe_crossing(arr + s, arr + L, v, in[s + 1]);
+    }
+    if (nan) *status = 2;                                                 // (every writer stores the same word)
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) mx = max(mx, (unsigned long long)__shfl_xor(mx, d));
+    if (lane == 0 && mx) atomicMax(amx, mx);
+    if (__any(cross) && lane == 0) *flag = 1;
+    __syncthreads();
+    if (tid == 0) rg.rec[store_slot] = {*amx, *flag, 0};
+}
+
+// To the left of the emitted block (window block D): the last crossing index in [rd_lo, D L) — found, INT32_MIN if none — and max |x|
+// behind it (m).  Whole blocks are passed by their records first, every wavefront on its own (no barrier); then chunk by chunk, ending
+// at the first chunk that holds a crossing.  slot: a word of LDS that holds INT32_MIN.
+template <int TH, int U>
+__device__ __forceinline__ void wave_ring_search_left(const WaveRing &rg, int32_t *slot, int tid, unsigned long long &m, int &found)
+{
+    const int L = rg.L, lane = rg.lane;
+    m = 0ull;
+    found = INT32_MIN;
+    int k = rg.D - 1;
+    for (int f = 64; f == 64;) {
+        const int kk = k - lane;
+        unsigned long long mx = 0ull;
+        const bool ok = kk >= 0 && kk * L >= rg.rd_lo && rg.passable(kk, mx);
+        f = rg.pass_blocks(ok, mx, m);
+        k -= f;
+    }
+    for (int hi = (k + 1) * L; hi > rg.rd_lo && found == INT32_MIN; hi -= TH * U) {
+        double v[U];
+        int pos = INT32_MIN;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int w = hi - (u + 1) * TH + tid;
+            const bool on = w >= rg.rd_lo;
+            v[u] = on ? rg.ld(w) : 0.0;
+            double nx = __shfl_down(v[u], 1);
+            if (on && (lane == 63 || w + 1 >= hi - u * TH)) nx = rg.ld(w + 1);     // (w + 1 <= D L < rd_hi: it exists)
+            if (on && tfe_crossing(rg.base + w, rg.n_abs, v[u], nx)) pos = max(pos, w);
+        }
+        if (pos != INT32_MIN) atomicMax(slot, pos);
+        __syncthreads();
+        found = *slot;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int w = hi - (u + 1) * TH + tid;
+            if (w >= rg.rd_lo && w > found) m = max(m, inst_mag(v[u], true));
+        }
+        __syncthreads();                                                  // (nobody is a chunk ahead of a reader of *slot)
+    }
+}
+
+// To the right: the first crossing index in [(D + 1) L, rd_hi - 1) — found, INT32_MAX if none — and max |x| up to it (m).  slot: a
+// word of LDS that holds INT32_MAX.
+template <int TH, int U>
+__device__ __forceinline__ void wave_ring_search_right(const WaveRing &rg, int32_t *slot, int tid, unsigned long long &m, int &found)
+{
+    const int L = rg.L, lane = rg.lane;
+    m = 0ull;
+    found = INT32_MAX;
+    int k = rg.D + 1;
+    for (int f = 64; f == 64;) {
+        const int kk = k + lane;
+        unsigned long long mx = 0ull;
+        const bool ok = (kk + 1) * L < rg.rd_hi && rg.passable(kk, mx);     // (block kk + 1's first sample is readable)
+        f = rg.pass_blocks(ok, mx, m);
+        k += f;
+    }
+    for (int lo = k * L; lo < rg.rd_hi && found == INT32_MAX; lo += TH * U) {
+        double v[U];
+        int pos = INT32_MAX;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int w = lo + u * TH + tid;
+            const bool on = w < rg.rd_hi;
+            v[u] = on ? rg.ld(w) : 0.0;
+            double nx = __shfl_down(v[u], 1);
+            if (on && lane == 63) nx = w + 1 < rg.rd_hi ? rg.ld(w + 1) : 0.0;
+            if (on && tfe_crossing(rg.base + w, rg.n_abs, v[u], nx)) pos = min(pos, w);    // (w + 1 = rd_hi: refused by n_abs)
+        }
+        if (pos != INT32_MAX) atomicMin(slot, pos);
+        __syncthreads();
+        found = *slot;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int w = lo + u * TH + tid;
+            if (w < rg.rd_hi && w <= found) m = max(m, inst_mag(v[u], true));
+        }
+        __syncthreads();
+    }
+}
+
+// The emitted block (window block D, blk) cut at its crossings, called by every thread of the row's workgroup: the thread's samples
+// xr (s = (jj W + wave) 64 + lane, 0.0 behind the block), their successors' difference where asked for (slope), their crossing flags
+// cr and half-wave numbers seg = 0 .. c inside the block; in LDS edge[r + 1] = the r-th crossing's position, mag[r] = max |x| of the
+// block's part of half wave r (one LDS atomic per sample), bal / pre: the flags' ballots and their prefix, *cnt = c.  The caller's
+// searches complete mag[0], edge[0], mag[c] and edge[c + 1]; its barrier follows them.
+template <int TH, bool kSlope>
+__device__ __forceinline__ int wave_ring_cut(const WaveRing &rg, const double *blk, unsigned long long *mag, unsigned long long *bal,
+                                             int32_t *edge, int32_t *pre, int32_t *cnt, int tid, int wave, double (&xr)[kWaveStreamSpt],
+                                             double (&slope)[kWaveStreamSpt], bool (&cr)[kWaveStreamSpt], int (&seg)[kWaveStreamSpt])
+{
+    constexpr int SPT = kWaveStreamSpt, W = TH / 64;
+    const int L = rg.L, lane = rg.lane, G = (L + 63) >> 6, b0 = rg.D * L;
 #pragma unroll
     for (int jj = 0; jj < SPT; ++jj) {
         const int g = jj * W + wave, s = g * 64 + lane;                   // (g is the same for the whole wavefront)
         xr[jj] = 0.0;
         cr[jj] = false;
+        if (kSlope) slope[jj] = 0.0;
         if (g < G) {
             double xn = 0.0;
             if (s < L) {
                 xr[jj] = blk[s];
                 if (s + 1 < L) xn = blk[s + 1];
-                else if (b0 + L < a.rd_hi) xn = ld(b0 + L);
-                cr[jj] = tfe_crossing(a.base + b0 + s, n_abs, xr[jj], xn);
+                else if (b0 + L < rg.rd_hi) xn = rg.ld(b0 + L);
+                cr[jj] = tfe_crossing(rg.base + b0 + s, rg.n_abs, xr[jj], xn);
+                if (kSlope) slope[jj] = xn - xr[jj];
             }
             const unsigned long long m = __ballot(cr[jj]);
             if (lane == 0) bal[g] = m;
@@ -199,11 +295,10 @@ __global__ __launch_bounds__(TH) void k_wave_stream(WaveStreamArgs a)
         const int t0 = __shfl(i0, 63), t1 = __shfl(i1, 63);
         if (lane < G) pre[lane] = i0 - p0;
         if (lane + 64 < G) pre[lane + 64] = t0 + i1 - p1;
-        if (lane == 0) ctl[0] = t0 + t1;
+        if (lane == 0) *cnt = t0 + t1;
     }
     __syncthreads();
-    const int c = ctl[0];
-    int seg[SPT];
+    const int c = *cnt;
 #pragma unroll
     for (int jj = 0; jj < SPT; ++jj) {
         const int g = jj * W + wave, s = g * 64 + lane;
@@ -214,80 +309,55 @@ __global__ __launch_bounds__(TH) void k_wave_stream(WaveStreamArgs a)
             if (cr[jj]) edge[seg[jj] + 1] = s;                            // a crossing index is the last sample of its half wave
         }
     }
+    return c;
+}
+
+template <int TH>
+__global__ __launch_bounds__(TH) void k_wave_stream(WaveStreamArgs a)
+{
+    constexpr int SPT = kWaveStreamSpt, U = kWaveStreamUnroll, W = TH / 64;
+    static_assert(TH % 64 == 0 && TH * SPT >= 64, "geometry");
+    extern __shared__ __attribute__((aligned(16))) unsigned char ws_lds[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int L = a.L, D = a.D, H = a.H;
+    const int G = (L + 63) >> 6;                                          // 64-sample groups of the block
+    unsigned long long *mag = reinterpret_cast<unsigned long long *>(ws_lds);          // [L + 1]
+    unsigned long long *bal = mag + (L + 1);                                          // [G]
+    unsigned long long *amx = bal + G;                                                // [1] the arriving block's max |x|
+    int32_t *edge = reinterpret_cast<int32_t *>(amx + 1);                              // [L + 2], positions relative to the block
+    int32_t *pre = edge + (L + 2);                                                    // [G]
+    int32_t *ctl = pre + G;           // [0] c, [1] the left search's crossing, [2] the right search's, [3] the arriving block's flag
+    const int64_t row = blockIdx.x;
+    const WaveRing rg = wave_ring_of(a, row, lane);
+
+    // 1. the arriving block into its slot, its record behind it
+    if (rg.in) wave_ring_store<TH>(rg, a.arr, a.store_slot, a.status, amx, &ctl[3], tid);
+    if (!a.emit) return;
+    const int b0 = D * L;                                                 // the emitted block's first window position
+
+    // 2. the block: samples, flags, half-wave numbers, inner maxima
+    for (int i = tid; i <= L; i += TH) mag[i] = 0ull;
+    if (tid == 0) { ctl[1] = INT32_MIN; ctl[2] = INT32_MAX; }
+    const double *const blk = rg.ring + (int64_t)((a.slot0 + D) % rg.R) * L;    // (window block D: never the arriving one, D >= 1)
+    double xr[SPT], unused[SPT];
+    bool cr[SPT];
+    int seg[SPT];
+    const int c = wave_ring_cut<TH, false>(rg, blk, mag, bal, edge, pre, &ctl[0], tid, wave, xr, unused, cr, seg);
 
     // 3. the outer searches, chunk by chunk, each ending at the first chunk that holds a crossing
-    // left: the last crossing index in [rd_lo, b0) and max |x| behind it
     {
-        unsigned long long m = 0ull;
-        int found = INT32_MIN;
-        int k = D - 1;                                                    // (every wavefront steps over the blocks on its own: no barrier)
-        for (int f = 64; f == 64;) {
-            const int kk = k - lane;
-            unsigned long long mx = 0ull;
-            const bool ok = kk >= 0 && kk * L >= a.rd_lo && passable(kk, mx);
-            f = pass_blocks(ok, mx, m);
-            k -= f;
-        }
-        for (int hi = (k + 1) * L; hi > a.rd_lo && found == INT32_MIN; hi -= TH * U) {
-            double v[U];
-            int pos = INT32_MIN;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int w = hi - (u + 1) * TH + tid;
-                const bool on = w >= a.rd_lo;
-                v[u] = on ? ld(w) : 0.0;
-                double nx = __shfl_down(v[u], 1);
-                if (on && (lane == 63 || w + 1 >= hi - u * TH)) nx = ld(w + 1);     // (w + 1 <= b0 < rd_hi: it exists)
-                if (on && tfe_crossing(a.base + w, n_abs, v[u], nx)) pos = max(pos, w);
-            }
-            if (pos != INT32_MIN) atomicMax(&ctl[1], pos);
-            __syncthreads();
-            found = ctl[1];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int w = hi - (u + 1) * TH + tid;
-                if (w >= a.rd_lo && w > found) m = max(m, inst_mag(v[u], true));
-            }
-            __syncthreads();                                              // (nobody is a chunk ahead of a reader of ctl[1])
-        }
+        unsigned long long m;
+        int found;
+        wave_ring_search_left<TH, U>(rg, &ctl[1], tid, m, found);
         if (m) atomicMax(&mag[0], m);
         // half wave 0 begins behind the crossing; without one at the stream's start (if the range reaches it), else out of reach
         if (tid == 0) edge[0] = found != INT32_MIN ? found - b0 : (a.at_start ? a.rd_lo - 1 - b0 : -H - 2);
     }
-    // right: the first crossing index in [b0 + L, rd_hi - 1) and max |x| up to it
     {
-        unsigned long long m = 0ull;
-        int found = INT32_MAX;
-        int k = D + 1;
-        for (int f = 64; f == 64;) {
-            const int kk = k + lane;
-            unsigned long long mx = 0ull;
-            const bool ok = (kk + 1) * L < a.rd_hi && passable(kk, mx);     // (block kk + 1's first sample is readable)
-            f = pass_blocks(ok, mx, m);
-            k += f;
-        }
-        for (int lo = k * L; lo < a.rd_hi && found == INT32_MAX; lo += TH * U) {
-            double v[U];
-            int pos = INT32_MAX;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int w = lo + u * TH + tid;
-                const bool on = w < a.rd_hi;
-                v[u] = on ? ld(w) : 0.0;
-                double nx = __shfl_down(v[u], 1);
-                if (on && lane == 63) nx = w + 1 < a.rd_hi ? ld(w + 1) : 0.0;
-                if (on && tfe_crossing(a.base + w, n_abs, v[u], nx)) pos = min(pos, w);    // (w + 1 = rd_hi: refused by n_abs)
-            }
-            if (pos != INT32_MAX) atomicMin(&ctl[2], pos);
-            __syncthreads();
-            found = ctl[2];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int w = lo + u * TH + tid;
-                if (w < a.rd_hi && w <= found) m = max(m, inst_mag(v[u], true));
-            }
-            __syncthreads();
-        }
+        unsigned long long m;
+        int found;
+        wave_ring_search_right<TH, U>(rg, &ctl[2], tid, m, found);
         if (m) atomicMax(&mag[c], m);
         // half wave c ends at the crossing; without one at the flushed stream's last sample (if the range reaches it), else out of reach
         if (tid == 0) edge[c + 1] = found != INT32_MAX ? found - b0 : (a.at_end ? a.rd_hi - 1 - b0 : L + H + 2);

@@ -26,9 +26,11 @@ whole-signal operator, so a stream whose blocks hold a few knots each reproduces
 
 LevelsStream: the full multi-level decomposition block by block.  WaveFilterStream: the single-wave feature filter
 (pyitd_amd.wave_filter) block by block at a fixed latency — what takes a LevelsStream's rows and gives feature-filtered components,
-entirely on the device.
+entirely on the device.  SpectrumStream: the time-frequency-energy spectrum (pyitd_amd.tfe_spectrum) block by
+block at a fixed latency — finished time slices of a live decomposition's spectrum.
 """
 import ctypes
+from collections import namedtuple
 
 import numpy
 
@@ -437,3 +439,153 @@ def blockwise_wave_filter(rows, block, horizon, amplitude=(0.0, numpy.inf), leng
         st.close()
     y = numpy.concatenate(outs, axis=1)
     return y[0] if flat else y
+
+
+StreamSpectrum = namedtuple("StreamSpectrum", "power outside overlong")
+_WEIGHTS = ("count", "amplitude", "energy")
+
+
+def _legal_hop(hop):
+    return not isinstance(hop, bool) and int(hop) == hop and hop >= 64 and hop % 64 == 0 and (hop >= 512 or hop in (64, 128, 256))
+
+
+class SpectrumStream:
+    """The time-frequency-energy spectrum block by block at a fixed latency (itd_spectrum_stream_* in include/pyitd_hip.h): blocks
+    of `rows` rows go in, finished time slices of their spectra come out — the cells pyitd_amd.tfe_spectrum gives for the
+    concatenated rows, bit for bit, wherever no half wave is longer than `horizon` samples.  A sample whose half wave, or whose
+    successor's half wave, is longer than that is OVERLONG (the stream's last sample, which has no successor: its predecessor's):
+    it is counted outside (and in `overlong`) whatever its frequency would be — the price of the bounded latency.  ONE launch per
+    push on the GPU.
+
+        st = SpectrumStream(1024, rows=9, horizon=2048, edges=numpy.linspace(0.0, 0.5, 65), hop=256)
+        st.latency                                      # D = ceil((horizon + 1) / block) = 3
+        for block in blocks:                            # block: [rows, 1024]
+            out = st.push(block)                        # None for the first D pushes, then block p - D's cells:
+            ...                                         # out.power [rows, 4, 64], out.outside [rows, 4], out.overlong [rows, 4]
+        while (out := st.flush()) is not None: ...
+
+    block: a multiple of hop, 64 .. 4096; hop: what tfe_spectrum accepts (a multiple of 64; below 512 only 64, 128 or 256), by
+    default the block where that is a legal hop.  edges: float64 [F + 1] (one set for every row) or [rows, F + 1], finite and
+    strictly increasing, 1 <= F <= 512; push(samples, edges=...) replaces them from that push on.  weight: "count", "amplitude"
+    or "energy".  A NaN in a pushed block sets status() bit 2 until reset(); that row is unspecified from then on.
+
+    Samples in, a running waterfall of every component out, entirely on the device — a LevelsStream's rows pushed by pointer:
+
+        lv = LevelsStream(1024, levels=3, channels=2)
+        sp = SpectrumStream(1024, rows=2 * 4, horizon=2048, edges=edges, hop=256)
+        # rows_d [2, 4, 1024] float64, edges_d [65] float64, power_d [8, 4, 64] float64, out_d / ovl_d [8, 4] int32: on the device,
+        # everything on one stream `s`
+        if lv.push_dev(block_ptr, 1024, rows_ptr, 1024, 4 * 1024, None, s):
+            if sp.push_dev(rows_ptr, 1024, edges_ptr, 0, power_ptr, 4 * 64, out_ptr, ovl_ptr, 4, s):
+                ...                                     # power_d holds the cells of the block pushed levels + 1 + D steps ago
+    """
+
+    def __init__(self, block, rows=1, horizon=None, edges=None, hop=None, weight="energy", device=0):
+        horizon = block if horizon is None else horizon
+        if isinstance(block, bool) or int(block) != block or not 64 <= block <= 4096:
+            raise ValueError("block must be 64 .. 4096 samples")
+        if hop is None:
+            if not _legal_hop(block):
+                raise ValueError("hop must be given: a block of %d samples is no legal hop" % block)
+            hop = block
+        if not _legal_hop(hop) or block % hop:
+            raise ValueError("hop: a positive multiple of 64 (below 512: 64, 128 or 256) that divides the block, got %r" % (hop,))
+        if not 1 <= rows <= 65535:
+            raise ValueError("rows must be 1 .. 65535")
+        if not 1 <= horizon <= 2 ** 22:
+            raise ValueError("horizon must be 1 .. 2^22 samples")
+        if weight not in _WEIGHTS:
+            raise ValueError("weight: one of %s, got %r" % (_WEIGHTS, weight))
+        if edges is None:
+            raise ValueError("edges: float64 [F + 1] or [rows, F + 1]")
+        self.block, self.rows, self.horizon, self.hop, self.weight, self.device = int(block), int(rows), int(horizon), int(hop), weight, int(device)
+        self.cells = self.block // self.hop
+        self.bins = None
+        self._edges = self._check_edges(edges)
+        self.bins = self._edges.shape[-1] - 1
+        self._L = _lib.load()
+        h = ctypes.c_void_p()
+        rc = self._L.itd_spectrum_stream_create(ctypes.byref(h), self.device, self.block, self.rows, self.horizon, self.hop, self.bins,
+                                                _WEIGHTS.index(weight))
+        if rc:
+            raise ITDError(rc, "itd_spectrum_stream_create(block=%d, rows=%d, horizon=%d, hop=%d, bins=%d)"
+                           % (block, rows, horizon, hop, self.bins))
+        self._h = h
+        self._flat = False          # the last push took a 1-D block: the slices that leave have no row axis either
+
+    close = Stream.close
+    __del__ = Stream.__del__
+    _check = Stream._check
+    blocks_held = Stream.blocks_held
+    reset = Stream.reset
+    status = Stream.status
+
+    @property
+    def latency(self):
+        """D = ceil((horizon + 1) / block): push p emits block p - D."""
+        return self._L.itd_spectrum_stream_latency(self._h)
+
+    def _check_edges(self, edges):
+        e = numpy.ascontiguousarray(edges, dtype=numpy.float64)
+        if e.ndim not in (1, 2) or (e.ndim == 2 and e.shape[0] != self.rows) or not 2 <= e.shape[-1] <= 513:
+            raise ValueError("edges: [F + 1] or [%d, F + 1] with 1 <= F <= 512, got shape %s" % (self.rows, e.shape))
+        if self.bins is not None and e.shape[-1] != self.bins + 1:
+            raise ValueError("edges: the stream has %d bins, got %d edges" % (self.bins, e.shape[-1]))
+        if not numpy.isfinite(e).all() or not (e[..., 1:] > e[..., :-1]).all():
+            raise ValueError("edges must be finite and strictly increasing")
+        return e
+
+    # ---- device buffers (raw pointers; asynchronous on `stream`) ----------------------------------------------------
+    def push_dev(self, block_ptr, in_stride, edges_ptr, edges_stride, power_ptr, power_stride, outside_ptr=None, overlong_ptr=None,
+                 count_stride=0, stream=None):
+        """Store one block of every row; True if a block's cells were written."""
+        em = ctypes.c_int32(0)
+        self._check(self._L.itd_spectrum_stream_push_f64(self._h, block_ptr, in_stride, edges_ptr, edges_stride, power_ptr, power_stride,
+                                                         outside_ptr, overlong_ptr, count_stride, ctypes.byref(em), stream))
+        return bool(em.value)
+
+    def flush_dev(self, edges_ptr, edges_stride, power_ptr, power_stride, outside_ptr=None, overlong_ptr=None, count_stride=0,
+                  stream=None):
+        em = ctypes.c_int32(0)
+        self._check(self._L.itd_spectrum_stream_flush_f64(self._h, edges_ptr, edges_stride, power_ptr, power_stride, outside_ptr,
+                                                          overlong_ptr, count_stride, ctypes.byref(em), stream))
+        return bool(em.value)
+
+    # ---- numpy in -> numpy out (one synchronisation per call) ----------------------------------------------------------
+    def _outputs(self):
+        return (numpy.empty((self.rows, self.cells, self.bins)), numpy.empty((self.rows, self.cells), numpy.int32),
+                numpy.empty((self.rows, self.cells), numpy.int32))
+
+    def _result(self, power, outside, overlong):
+        if self._flat:
+            return StreamSpectrum(power[0], outside[0], overlong[0])
+        return StreamSpectrum(power, outside, overlong)
+
+    def push(self, samples, edges=None):
+        """samples [rows, block] (or [block] for one row).  None for the first `latency` pushes, then StreamSpectrum(power[rows, C,
+        F], outside[rows, C], overlong[rows, C]) of the block pushed `latency` pushes ago (no row axis for 1-D input)."""
+        x = numpy.ascontiguousarray(samples, dtype=numpy.float64)
+        flat = x.ndim == 1
+        x2 = x.reshape(1, -1) if flat else x
+        if x2.shape != (self.rows, self.block):
+            raise ValueError("expected blocks of shape (%d, %d)" % (self.rows, self.block))
+        if edges is not None:
+            self._edges = self._check_edges(edges)
+        e = self._edges
+        power, outside, overlong = self._outputs()
+        em = ctypes.c_int32(0)
+        self._check(self._L.itd_spectrum_stream_push_host_f64(self._h, _np_ptr(x2), _np_ptr(e), e.shape[-1] if e.ndim == 2 else 0,
+                                                              _np_ptr(power), _np_ptr(outside), _np_ptr(overlong), ctypes.byref(em)))
+        self._flat = flat
+        return self._result(power, outside, overlong) if em.value else None
+
+    def flush(self, edges=None):
+        """The next block still held (one per call); None once the stream is empty."""
+        if edges is not None:
+            self._edges = self._check_edges(edges)
+        e = self._edges
+        power, outside, overlong = self._outputs()
+        em = ctypes.c_int32(0)
+        self._check(self._L.itd_spectrum_stream_flush_host_f64(self._h, _np_ptr(e), e.shape[-1] if e.ndim == 2 else 0, _np_ptr(power),
+                                                               _np_ptr(outside), _np_ptr(overlong), ctypes.byref(em)))
+        return self._result(power, outside, overlong) if em.value else None
