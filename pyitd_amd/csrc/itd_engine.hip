@@ -1340,7 +1340,7 @@ int settle_fused_levels(itd_engine *e, int B)
     if (!nfail) { e->policy.fused_levels_delivered(e->last.kf_cap != 0, e->last.m); return ITD_OK; }
     const auto what = e->policy.fused_levels_refused(bits, fail_lev, e->last.kf_level, e->last.kf_cap, e->last.m, FormPolicy::many(nfail, B));
     if (what == FormPolicy::Refusal::Fail) {
-        snprintf(e->err, sizeof(e->err), "fused sparse levels: not the reference's result (fail bits 0x%x: 1 verification, 2 capacity, 4 non-finite, 8 ties, 16 halo wait); ITD_FUSE_ONLY forbids the level-by-level repeat", bits);
+        snprintf(e->err, sizeof(e->err), "fused sparse levels: not the reference's result (fail bits 0x%x: 1 verification, 2 capacity, 4 non-finite, 16 halo wait); ITD_FUSE_ONLY forbids the level-by-level repeat", bits);
         return ITD_ERR_HIP;
     }
     return what == FormPolicy::Refusal::RepairSignals ? repair_signals(e, B) : repeat_call(e, B, e->policy.level0_fused(), false);

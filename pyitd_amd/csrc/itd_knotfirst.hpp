@@ -104,7 +104,7 @@ struct KfEntry { double X, B, S; int32_t pos; int32_t pad; };   // a level's tab
 static_assert(sizeof(KfEntry) == 32, "table entries are two 16-byte words");
 
 // failure bits (KfSig::fail, SigState::kf_fail)
-constexpr int kKfFailVerify = 1, kKfFailCapacity = 2, kKfFailNonFinite = 4, kKfFailTies = 8;
+constexpr int kKfFailVerify = 1, kKfFailCapacity = 2, kKfFailNonFinite = 4, kKfFailTies = 8;   // (kKfFailTies: declared, raised by no kernel — too many near ties are a capacity, bit 2)
 constexpr int kKfFailWait = 16;   // a halo wait was given up (a neighbour that never became resident within ITD_KC_TIMEOUT) or met a neighbour that had given up
 
 struct KfSig {

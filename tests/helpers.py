@@ -104,6 +104,18 @@ def kf_rates_draws(seed=11, cases=12, families=11):
                 yield idx - 1, kind, m, x
 
 
+def kf_rates_tally(results):
+    """The tally of tools/kf_rates.py: results = (family, max_iteration, outcome) per draw.  Returns ({(family, max_iteration): {outcome:
+    count}}, the number of wrong results) — an outcome is wrong if it STARTS with "WRONG": the tool appends the range size to the
+    outcomes of calls that ran with halved ranges ("WRONG (32 tiles)")."""
+    tallies, wrong = {}, 0
+    for kind, m, r in results:
+        t = tallies.setdefault((kind, m), {})
+        t[r] = t.get(r, 0) + 1
+        wrong += r.startswith("WRONG")
+    return tallies, wrong
+
+
 # Draws of kf_rates_draws(seed=11) on which round 4's first knot-side launch delivered WRONG rows (a halo search re-read an end workgroup
 # it had already passed and doubled a knot) with every verification of that time green: the delivery-rate sweep found them
 # (profiles/r04); tests/test_gpu_fused.py holds them "delivered or refused, never wrong" at every range size.

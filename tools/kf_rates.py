@@ -1,6 +1,7 @@
 """How often do the fused sparse levels (itd_set_fuse_mode) deliver, per signal family?  ITD_FUSE_ONLY on random draws: a case
 either equals the C oracle bit for bit ("delivered") or the engine reports that the fused form cannot deliver it ("refused",
-with the failure bits: 1 verification, 2 capacity, 4 non-finite, 8 ties, 16 a halo wait given up / a neighbour that gave up) — a third outcome would be a bug and is counted as
+with the failure bits: 1 verification, 2 capacity, 4 non-finite, 16 a halo wait given up / a neighbour that gave up; 8 is declared
+and raised by no kernel) — a third outcome would be a bug and is counted as
 WRONG.  usage (GPU box): python tools/kf_rates.py [cases per family] [seed]"""
 import os, sys, re
 import numpy as np
@@ -11,7 +12,7 @@ import pyitd_amd
 from pyitd_amd.engine import FUSE_ONLY
 from pyitd_amd import ITDError
 from oracle import cpu_oracle
-from helpers import canon_u64, kf_rates_draws
+from helpers import canon_u64, kf_rates_draws, kf_rates_tally
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 12
 NAMES = ["white noise", "random walk", "quantised (plateaus)", "smooth + few knots", "sine + noise at a random level",
@@ -58,16 +59,14 @@ n_wrong = 0
 
 
 print("%-36s %-6s %s" % ("family", "levels", "outcomes over %d draws (n in 70 000 .. 400 000, float32 / float64)" % cases))
-wrong = 0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 11
-tallies = {}
+results = []
 for idx, kind, m, x in kf_rates_draws(seed, cases):      # (tests/helpers.py: the sweep's seed and a draw's index name a case for good)
     r = one(x, m)
     if r.startswith("WRONG"):
         print("   draw %d of kf_rates_draws(seed=%d, cases=%d)" % (idx, seed, cases), flush=True)
-    t = tallies.setdefault((kind, m), {})
-    t[r] = t.get(r, 0) + 1
-    wrong += r == "WRONG"
+    results.append((kind, m, r))
+tallies, wrong = kf_rates_tally(results)      # (tests/helpers.py: "WRONG (32 tiles)" counts too)
 for (kind, m), tally in sorted(tallies.items()):
     print("%-36s %-6d %s" % (NAMES[kind], m + 1, ", ".join("%s: %d" % kv for kv in sorted(tally.items()))), flush=True)
 print("WRONG results: %d" % wrong)
