@@ -20,6 +20,7 @@ ISENT = -123456
 PAD = 7
 OK, INVALID = 0, 1
 RULES = ("any", "valid")
+MODE_TOL = 1e-11            # of the row's scale: the project's bound on a mode against the long-double restatement
 
 
 @pytest.fixture(scope="module")
@@ -52,7 +53,7 @@ def test_records_and_modes_of_every_decided_case(rule):
                 if not (modes[b] == 0.0).all():
                     wrong.append("%s: rejected, but the mode is not all zero" % name)
             else:
-                err, tol = float(np.max(np.abs(modes[b] - mode))), 1e-11 * float(np.max(np.abs(x)))
+                err, tol = float(np.max(np.abs(modes[b] - mode))), MODE_TOL * float(np.max(np.abs(x)))
                 if not err <= tol:
                     wrong.append("%s: mode off by %.3g, allowed %.3g" % (name, err, tol))
     assert not wrong, "\n" + "\n".join(wrong)
