@@ -934,6 +934,61 @@ int itd_spectrum_stream_push_host_f64(itd_stream *s, const double *block_host, c
 int itd_spectrum_stream_flush_host_f64(itd_stream *s, const double *edges_host, int64_t edges_stride, double *power_host,
                                        int32_t *outside_host, int32_t *overlong_host, int32_t *emitted);
 
+/* ---- the instantaneous stream: amplitude, phase, frequency and half-wave length block by block, at a fixed latency (DESIGN.md
+ *      section 24) -----------------------------------------------------------------------------------------------------------------
+ * The third consumer stage behind a levels stream: blocks of `rows` rows in lock step go in; the per-sample instantaneous amplitude,
+ * phase and frequency and the length of every sample's half wave come out, a known number of blocks later — wherever a value is
+ * delivered, bit for bit the whole-row operator's.  With blocks of L samples and a horizon of H samples, row r after P pushes is
+ * x[0 .. P L).  On the concatenated row:
+ *   len[j]       the number of samples of sample j's half wave: the half waves of itd_waves_batch_* on the indices of the whole
+ *                stream; the last one ends at the flushed stream's last sample.
+ *   A[j], phase[j], f[j]   the bits itd_instantaneous_batch_f64 gives for the concatenated row (the same expressions; the stream's
+ *                last sample takes the backward difference, known at the flush).
+ *   long[j]      len[j] > H.
+ *   overlong[j]  the spectrum stream's rule above, unchanged: long[j], or long[j + 1] where j + 1 exists, or, for the stream's last
+ *                sample, long[j - 1].
+ *   emitted block b, for each of its L samples:
+ *                amplitude[j] = A[j], phase[j] = phase[j]   where !long[j]  (both need only j's own half wave and x[j + 1])
+ *                frequency[j] = f[j]                        where !overlong[j]
+ *                length[j]    = len[j] (int32)              where !long[j], else 0
+ *                every float64 value that is not delivered is the one pattern 0x7FF8000000000000.  A sample in front of a too-long
+ *                half wave keeps its amplitude and phase and loses only its frequency.
+ *   counts       per row and emitted block two int32: the long samples, the overlong samples (a superset).
+ * With a horizon that holds every half wave the three float outputs are itd_instantaneous_batch_f64 of the concatenated rows bit
+ * for bit, length is itd_waves_batch_*'s length repeated over each half wave, and both counts are 0.
+ * Latency and locality are the spectrum stream's: D = ceil((H + 1) / L) blocks (itd_inst_stream_latency; -1 if s is not an
+ * instantaneous stream); block b is decided from the samples [b L - H, (b+1) L + H] that exist and from nothing else.  Push p
+ * (counted from 0) emits block p - D when p >= D; every flush emits the next block still held, then emitted = 0 and the stream
+ * starts afresh.  A push between flushes is refused.
+ *   8 <= block <= 4096 (any value, no multiple of 64 is asked for), 1 <= rows <= 65535, 1 <= horizon <= 2^22.  Everything is
+ *   allocated at create: the rings (rows (2 D + 1) block 8 bytes), one 16-byte record per block in them, the host forms' staging
+ *   and an engine of the stream's own; ITD_ERR_NOMEM when it does not fit.  ITD_ERR_INVALID_ARG before any HIP call for a NULL
+ *   handle, a NULL required pointer or a value out of range.  A call that fails leaves the stream as it was.
+ *   block_dev: row r's block at block_dev + r in_stride (in_stride >= block when rows > 1) — the dense [channels][M+1][block] rows of
+ *     itd_levels_stream_push_f64 go in as channels (M+1) rows with in_stride = block.
+ *   amp_dev, phase_dev, freq_dev (float64), length_dev (int32): each optional, a NULL one is skipped; row r's block at
+ *     + r out_stride (one stride for the four, >= block when rows > 1).  At least one is required whenever the call emits; they
+ *     are written only then.
+ *   counts_dev: optional; row r's two counts at counts_dev + r counts_stride (>= 2 when rows > 1).
+ * Device forms: one launch per call on `stream`, no host synchronisation, no host read; *emitted follows from the block count alone.
+ * Host forms: contiguous [rows][block] in and out, counts_host [rows][2]; each output optional, at least one required on every
+ * call; pinned staging, one synchronisation per call.  A NaN in any pushed block sets bit 2 of itd_stream_status until
+ * itd_stream_reset; that row is unspecified from then on, nothing outside the row's own slots is written.  itd_stream_destroy /
+ * reset / blocks / status / last_error apply; every other stream kind's push and flush entries refuse an instantaneous stream,
+ * and these refuse theirs. */
+#define ITD_STREAM_INSTANT 5  /* an instantaneous stream (itd_inst_stream_create); not a kind itd_stream_create takes */
+int itd_inst_stream_create(itd_stream **out, int device_id, int64_t block, int32_t rows, int64_t horizon);
+int itd_inst_stream_latency(const itd_stream *s);
+int itd_inst_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_stride, double *amp_dev, double *phase_dev,
+                             double *freq_dev, int32_t *length_dev, int64_t out_stride, int32_t *counts_dev, int64_t counts_stride,
+                             int32_t *emitted, void *stream);
+int itd_inst_stream_flush_f64(itd_stream *s, double *amp_dev, double *phase_dev, double *freq_dev, int32_t *length_dev,
+                              int64_t out_stride, int32_t *counts_dev, int64_t counts_stride, int32_t *emitted, void *stream);
+int itd_inst_stream_push_host_f64(itd_stream *s, const double *block_host, double *amp_host, double *phase_host, double *freq_host,
+                                  int32_t *length_host, int32_t *counts_host, int32_t *emitted);
+int itd_inst_stream_flush_host_f64(itd_stream *s, double *amp_host, double *phase_host, double *freq_host, int32_t *length_host,
+                                   int32_t *counts_host, int32_t *emitted);
+
 /* ---- introspection for benchmarks -------------------------------------------------------------
  * hipEvent pairs on the launch stream.  Extraction launches are dispatched with their own start/stop events
  * (hipExtLaunchKernel: the events take the dispatch's own begin/end timestamps, so they agree with rocprofv3's kernel durations); the

@@ -10,7 +10,7 @@ from . import _lib
 from ._lib import ITDError, build
 from .batch import instantaneous_batch, single_waves, tfe_spectrum, wave_filter, wave_histogram, Spectrum, WaveHistogram, Waves
 from .engine import Engine
-from .streaming import SpectrumStream, StreamSpectrum
+from .streaming import InstantaneousStream, SpectrumStream, StreamInstant, StreamSpectrum, blockwise_instantaneous
 from .itd import (ITD, baseline_knot_estimation, detect_knots, detect_peaks, find_extrema, generate_sine_wave, instantaneous, isin, itd,
                   itd_baseline_extract, itd_baseline_extract_cubic, itd_baseline_extract_fast, itd_baseline_extract_iq, itd_batch, itd_levels,
                   itd_sine_wrapper, matlab_detect_peaks, release_engines)
@@ -24,5 +24,6 @@ __all__ = ["itd_baseline_extract_modified", "itd_baseline_extract_spline", "itd_
            "crossways_itd_baseline_extract", "retrieve_statistical_image_component", "totalextract2d", "ITD", "ITDError", "Engine", "build", "itd", "itd_levels", "itd_batch", "itd_baseline_extract", "detect_peaks",
            "matlab_detect_peaks", "detect_knots", "baseline_knot_estimation", "isin", "find_extrema", "generate_sine_wave",
            "itd_baseline_extract_fast", "itd_baseline_extract_cubic", "itd_baseline_extract_iq", "itd_sine_wrapper", "release_engines", "instantaneous", "instantaneous_batch", "single_waves", "wave_filter", "Waves", "tfe_spectrum", "Spectrum", "wave_histogram", "WaveHistogram", "SpectrumStream", "StreamSpectrum",
+           "InstantaneousStream", "StreamInstant", "blockwise_instantaneous",
            "fourier_mode_decomposition_any", "fourier_mode_decomposition_valid", "itd_fourier_decomposition",
            "itd_fourier_decomposition_lean", "itd_fourier_decomposition_batch"]

@@ -298,6 +298,8 @@ struct itd_stream {
     int32_t F = 0, weight = 0;      // bins; 0 count, 1 amplitude, 2 energy
     int64_t hop = 0;
     Buf<int32_t> d_cnt; Pinned<int32_t> h_cnt;       // host form: outside and overlong, [2][C][L / hop]
+    // instantaneous stream (ITD_STREAM_INSTANT, k_inst_stream in itd_inst_stream.hpp): the spectrum stream's ring, records, counters
+    // and D; host form: d_out / h_out = amplitude, phase, frequency [3][C][L], d_cnt / h_cnt = length [C][L], then the counts [C][2]
 };
 
 namespace {
@@ -538,7 +540,7 @@ int itd_stream_reset(itd_stream *s)
 int64_t itd_stream_blocks(const itd_stream *s)
 {
     if (!s) return -1;
-    if (s->kind == ITD_STREAM_WAVES || s->kind == ITD_STREAM_SPECTRUM) return (s->P < 0 ? s->t : s->P) - s->sent;
+    if (s->kind >= ITD_STREAM_WAVES) return (s->P < 0 ? s->t : s->P) - s->sent;   // (the ring streams: wave filter, spectrum, instantaneous)
     if (s->kind != ITD_STREAM_LEVELS) return s->pushed;
     return (s->P < 0 ? s->t : s->P) - std::max<int64_t>(0, s->t - s->M - 1);   // pushed, less the blocks whose rows have left
 }
@@ -547,7 +549,7 @@ const char *itd_stream_last_error(const itd_stream *s) { return s && s->eng ? s-
 int itd_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_stride, double *baseline_dev, int64_t baseline_stride,
                         double *rot_dev, int64_t rot_stride, int32_t *emitted, void *stream)
 {
-    if (!s || !block_dev || s->kind >= ITD_STREAM_LEVELS) return ITD_ERR_INVALID_ARG;   // (a levels, a wave or a spectrum stream: its own entries)
+    if (!s || !block_dev || s->kind >= ITD_STREAM_LEVELS) return ITD_ERR_INVALID_ARG;   // (a levels stream and every ring stream: their own entries)
     if (s->C > 1 && (in_stride < s->L || (baseline_dev && baseline_stride < s->L) || (rot_dev && rot_stride < s->L))) return ITD_ERR_INVALID_ARG;
     if (s->pushed >= 1 && !baseline_dev) return ITD_ERR_INVALID_ARG;      // this push emits a block
     DevGuard g(s->eng->device);
@@ -894,25 +896,26 @@ int itd_levels_stream_flush_host_f64(itd_stream *s, double *rows_host, uint8_t *
 //      k_wave_stream in itd_wave_stream.hpp) --------------------------------------------------------------------------------
 namespace {
 
-// one step, ONE launch: the arriving block (blk, or nullptr on a flush step) into the ring, block b (b < 0: none) filtered and out
-int wave_step(itd_stream *s, const double *blk, int64_t in_stride, const double *bounds, int64_t bounds_stride, double *out,
-              int64_t out_stride, int64_t b, hipStream_t st)
+// What the ring streams (wave filter, spectrum, instantaneous) share on the host: the ring fields of a step's launch arguments
+// (WaveStreamArgs, SpectrumStreamArgs, InstStreamArgs hold the same ones), the launch, and the block counting of push and flush.
+
+// One step's launch, ONE per step: the arriving block (blk, or nullptr on a flush step) goes into the ring, block b (b < 0: none)
+// is emitted from the samples [b L - H, (b+1) L + reach) that exist.  The caller has filled in what its kernel takes besides.
+template <typename Args>
+int ring_step(itd_stream *s, Args &a, const double *blk, int64_t in_stride, int64_t b, int64_t reach, hipStream_t st)
 {
     const int64_t L = s->L, D = s->D, R = 2 * D + 1;
-    WaveStreamArgs a = {};
     a.in = blk; a.in_stride = in_stride;
     a.ring = s->ring;
     a.rec = s->rec;
     a.arr = s->t * L;
-    a.bounds = bounds; a.bounds_stride = bounds_stride;
-    a.out = out; a.out_stride = out_stride;
     a.status = s->d_status;
     a.L = (int32_t)L; a.D = (int32_t)D; a.H = (int32_t)s->H;
     a.store_slot = blk ? (int32_t)(s->t % R) : 0;
     a.emit = b >= 0 ? 1 : 0;
     if (b >= 0) {
         const int64_t exists = (s->P < 0 ? s->t + 1 : s->P) * L;          // (a push: the arriving block included)
-        const int64_t lo = std::max<int64_t>(b * L - s->H, 0), hi = std::min<int64_t>((b + 1) * L + s->H, exists);
+        const int64_t lo = std::max<int64_t>(b * L - s->H, 0), hi = std::min<int64_t>((b + 1) * L + reach, exists);
         a.base = (b - D) * L;
         a.slot0 = (int32_t)((((b - D) % R) + R) % R);
         a.rd_lo = (int32_t)(lo - a.base);
@@ -926,11 +929,12 @@ int wave_step(itd_stream *s, const double *blk, int64_t in_stride, const double 
     return ITD_OK;
 }
 
-int wave_push(itd_stream *s, const double *blk, int64_t in_stride, const double *bounds, int64_t bounds_stride, double *out,
-              int64_t out_stride, int32_t *emitted, hipStream_t st)
+// push p stores block p and (p >= D) emits block p - D; step(b) runs the launch
+template <typename Step>
+int ring_push(itd_stream *s, int32_t *emitted, Step step)
 {
     const bool emits = s->t >= s->D;
-    const int rc = wave_step(s, blk, in_stride, bounds, bounds_stride, out, out_stride, emits ? s->t - s->D : -1, st);
+    const int rc = step(emits ? s->t - s->D : -1);
     if (rc) return rc;
     ++s->t;
     if (emits) ++s->sent;
@@ -939,14 +943,14 @@ int wave_push(itd_stream *s, const double *blk, int64_t in_stride, const double 
 }
 
 // one block per call: the next block still held
-int wave_flush(itd_stream *s, const double *bounds, int64_t bounds_stride, double *out, int64_t out_stride, int32_t *emitted,
-               hipStream_t st)
+template <typename Step>
+int ring_flush(itd_stream *s, int32_t *emitted, Step step)
 {
     if (emitted) *emitted = 0;
     if (s->P < 0 && s->t == 0) return ITD_OK;      // empty: nothing to run
     const bool begins = s->P < 0;                  // the first flush step: the stream's length is fixed from here on
     if (begins) s->P = s->t;
-    const int rc = wave_step(s, nullptr, 0, bounds, bounds_stride, out, out_stride, s->sent, st);
+    const int rc = step(s->sent);
     if (rc) {                                      // nothing was emitted: the stream is as it was, pushes are still taken
         if (begins) s->P = -1;
         return rc;
@@ -954,6 +958,28 @@ int wave_flush(itd_stream *s, const double *bounds, int64_t bounds_stride, doubl
     if (emitted) *emitted = 1;
     if (++s->sent == s->P) { s->t = 0; s->P = -1; s->sent = 0; }          // the last block: the stream starts afresh
     return ITD_OK;
+}
+
+// the arriving block (blk, or nullptr on a flush step) into the ring, block b (b < 0: none) filtered and out
+int wave_step(itd_stream *s, const double *blk, int64_t in_stride, const double *bounds, int64_t bounds_stride, double *out,
+              int64_t out_stride, int64_t b, hipStream_t st)
+{
+    WaveStreamArgs a = {};
+    a.bounds = bounds; a.bounds_stride = bounds_stride;
+    a.out = out; a.out_stride = out_stride;
+    return ring_step(s, a, blk, in_stride, b, s->H, st);
+}
+
+int wave_push(itd_stream *s, const double *blk, int64_t in_stride, const double *bounds, int64_t bounds_stride, double *out,
+              int64_t out_stride, int32_t *emitted, hipStream_t st)
+{
+    return ring_push(s, emitted, [&](int64_t b) { return wave_step(s, blk, in_stride, bounds, bounds_stride, out, out_stride, b, st); });
+}
+
+int wave_flush(itd_stream *s, const double *bounds, int64_t bounds_stride, double *out, int64_t out_stride, int32_t *emitted,
+               hipStream_t st)
+{
+    return ring_flush(s, emitted, [&](int64_t b) { return wave_step(s, nullptr, 0, bounds, bounds_stride, out, out_stride, b, st); });
 }
 
 bool wave_io_ok(const itd_stream *s, bool emits, const double *bounds, int64_t bounds_stride, const double *out, int64_t out_stride)
@@ -1082,65 +1108,28 @@ namespace {
 int spectrum_step(itd_stream *s, const double *blk, int64_t in_stride, const double *edges, int64_t edges_stride, double *power,
                   int64_t power_stride, int32_t *outside, int32_t *overlong, int64_t count_stride, int64_t b, hipStream_t st)
 {
-    const int64_t L = s->L, D = s->D, R = 2 * D + 1;
     SpectrumStreamArgs a = {};
-    a.in = blk; a.in_stride = in_stride;
-    a.ring = s->ring;
-    a.rec = s->rec;
-    a.arr = s->t * L;
     a.edges = edges; a.edges_stride = edges_stride;
     a.power = power; a.power_stride = power_stride;
     a.outside = outside; a.overlong = overlong; a.count_stride = count_stride;
-    a.status = s->d_status;
-    a.L = (int32_t)L; a.D = (int32_t)D; a.H = (int32_t)s->H;
     a.F = s->F; a.spc = (int32_t)(s->hop / 64); a.weight = s->weight;
-    a.store_slot = blk ? (int32_t)(s->t % R) : 0;
-    a.emit = b >= 0 ? 1 : 0;
-    if (b >= 0) {
-        const int64_t exists = (s->P < 0 ? s->t + 1 : s->P) * L;          // (a push: the arriving block included)
-        const int64_t lo = std::max<int64_t>(b * L - s->H, 0), hi = std::min<int64_t>((b + 1) * L + s->H + 1, exists);
-        a.base = (b - D) * L;
-        a.slot0 = (int32_t)((((b - D) % R) + R) % R);
-        a.rd_lo = (int32_t)(lo - a.base);
-        a.rd_hi = (int32_t)(hi - a.base);
-        a.at_start = lo == 0 ? 1 : 0;
-        a.at_end = s->P >= 0 && hi == exists ? 1 : 0;
-    }
-    void *args[] = {&a};
-    HIP_TRY(s->eng, hipLaunchKernel(s->fn, dim3((unsigned)s->C), dim3((unsigned)s->threads), args, s->lds, st));
-    HIP_TRY(s->eng, hipGetLastError());
-    return ITD_OK;
+    return ring_step(s, a, blk, in_stride, b, s->H + 1, st);              // (one sample past the wave filter's reach: A of sample (b+1) L)
 }
 
 int spectrum_push(itd_stream *s, const double *blk, int64_t in_stride, const double *edges, int64_t edges_stride, double *power,
                   int64_t power_stride, int32_t *outside, int32_t *overlong, int64_t count_stride, int32_t *emitted, hipStream_t st)
 {
-    const bool emits = s->t >= s->D;
-    const int rc = spectrum_step(s, blk, in_stride, edges, edges_stride, power, power_stride, outside, overlong, count_stride,
-                                 emits ? s->t - s->D : -1, st);
-    if (rc) return rc;
-    ++s->t;
-    if (emits) ++s->sent;
-    if (emitted) *emitted = emits ? 1 : 0;
-    return ITD_OK;
+    return ring_push(s, emitted, [&](int64_t b) {
+        return spectrum_step(s, blk, in_stride, edges, edges_stride, power, power_stride, outside, overlong, count_stride, b, st);
+    });
 }
 
-// one block per call: the next block still held
 int spectrum_flush(itd_stream *s, const double *edges, int64_t edges_stride, double *power, int64_t power_stride, int32_t *outside,
                    int32_t *overlong, int64_t count_stride, int32_t *emitted, hipStream_t st)
 {
-    if (emitted) *emitted = 0;
-    if (s->P < 0 && s->t == 0) return ITD_OK;      // empty: nothing to run
-    const bool begins = s->P < 0;                  // the first flush step: the stream's length is fixed from here on
-    if (begins) s->P = s->t;
-    const int rc = spectrum_step(s, nullptr, 0, edges, edges_stride, power, power_stride, outside, overlong, count_stride, s->sent, st);
-    if (rc) {                                      // nothing was emitted: the stream is as it was, pushes are still taken
-        if (begins) s->P = -1;
-        return rc;
-    }
-    if (emitted) *emitted = 1;
-    if (++s->sent == s->P) { s->t = 0; s->P = -1; s->sent = 0; }          // the last block: the stream starts afresh
-    return ITD_OK;
+    return ring_flush(s, emitted, [&](int64_t b) {
+        return spectrum_step(s, nullptr, 0, edges, edges_stride, power, power_stride, outside, overlong, count_stride, b, st);
+    });
 }
 
 bool spectrum_io_ok(const itd_stream *s, bool emits, const double *edges, int64_t edges_stride, const double *power, int64_t power_stride,
@@ -1288,5 +1277,172 @@ int itd_spectrum_stream_flush_host_f64(itd_stream *s, const double *edges_host, 
                                        int32_t *outside_host, int32_t *overlong_host, int32_t *emitted)
 {
     return spectrum_host(s, nullptr, edges_host, edges_stride, power_host, outside_host, overlong_host, emitted, true);
+}
+}  // extern "C"
+
+// ---- the instantaneous stream: itd_inst_stream_* (include/pyitd_hip.h; the kernel and the LDS budget: k_inst_stream in
+//      itd_inst_stream.hpp; locality and latency are the spectrum stream's) -----------------------------------------------------
+namespace {
+
+struct InstOut {
+    double *amp, *phase, *freq;
+    int32_t *length;
+    int64_t stride;
+    int32_t *counts;
+    int64_t counts_stride;
+    bool any() const { return amp || phase || freq || length; }
+};
+
+int inst_step(itd_stream *s, const double *blk, int64_t in_stride, const InstOut &o, int64_t b, hipStream_t st)
+{
+    InstStreamArgs a = {};
+    a.amp = o.amp; a.phase = o.phase; a.freq = o.freq; a.length = o.length; a.out_stride = o.stride;
+    a.counts = o.counts; a.counts_stride = o.counts_stride;
+    return ring_step(s, a, blk, in_stride, b, s->H + 1, st);
+}
+
+int inst_push(itd_stream *s, const double *blk, int64_t in_stride, const InstOut &o, int32_t *emitted, hipStream_t st)
+{
+    return ring_push(s, emitted, [&](int64_t b) { return inst_step(s, blk, in_stride, o, b, st); });
+}
+
+int inst_flush(itd_stream *s, const InstOut &o, int32_t *emitted, hipStream_t st)
+{
+    return ring_flush(s, emitted, [&](int64_t b) { return inst_step(s, nullptr, 0, o, b, st); });
+}
+
+bool inst_io_ok(const itd_stream *s, bool emits, const InstOut &o)
+{
+    if (emits && !o.any()) return false;
+    if (s->C == 1) return true;
+    if (o.any() && o.stride < s->L) return false;
+    return !o.counts || o.counts_stride >= 2;
+}
+
+}  // namespace
+
+extern "C" {
+
+int itd_inst_stream_create(itd_stream **out, int device_id, int64_t block, int32_t rows, int64_t horizon)
+{
+    if (!out) return ITD_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (block < kInstStreamMinBlock || block > kInstStreamMaxBlock || rows < 1 || rows > kMaxGridY) return ITD_ERR_INVALID_ARG;
+    if (horizon < 1 || horizon > kWaveStreamMaxHorizon) return ITD_ERR_INVALID_ARG;
+    itd_stream *s = new (std::nothrow) itd_stream();
+    if (!s) return ITD_ERR_NOMEM;
+    int rc = itd_engine_create(&s->eng, device_id, 3 * block, 1);
+    if (rc) { delete s; return rc; }
+    s->L = block; s->C = rows; s->kind = ITD_STREAM_INSTANT; s->H = horizon;
+    s->D = (int32_t)((horizon + 1 + block - 1) / block);
+    s->threads = block <= 256 * kWaveStreamSpt ? 256 : 512;
+    s->fn = s->threads == 256 ? reinterpret_cast<const void *>(&k_inst_stream<256>) : reinterpret_cast<const void *>(&k_inst_stream<512>);
+    s->lds = inst_stream_lds((int)block);
+    DevGuard g(device_id);
+    const size_t C = (size_t)rows, L = (size_t)block, R = 2 * (size_t)s->D + 1;
+    // the grant is the kernel function's, not this stream's: the most its instance ever asks for (wave stream: the same rule)
+    hipError_t hrc = allow_lds(s->eng, s->fn, inst_stream_lds(s->threads == 256 ? 256 * kWaveStreamSpt : kInstStreamMaxBlock));
+    if (hrc == hipSuccess) hrc = s->ring.alloc(C * R * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->rec.alloc(C * R * sizeof(WaveBlockRec));
+    if (hrc == hipSuccess) hrc = s->d_status.alloc(64);
+    if (hrc == hipSuccess) hrc = hipMemset(s->d_status, 0, 64);
+    // the host form's staging: [rows][L] in, [3][rows][L] float64 and [rows][L] + [rows][2] int32 out
+    if (hrc == hipSuccess) hrc = s->d_in.alloc(C * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->d_out.alloc(3 * C * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->d_cnt.alloc(C * (L + 2) * sizeof(int32_t));
+    if (hrc == hipSuccess) hrc = s->h_in.alloc(C * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->h_out.alloc(3 * C * L * sizeof(double));
+    if (hrc == hipSuccess) hrc = s->h_cnt.alloc(C * (L + 2) * sizeof(int32_t));
+    if (hrc == hipSuccess) hrc = hipDeviceSynchronize();     // (the fill ran on the null stream)
+    if (hrc != hipSuccess) {
+        const bool oom = hrc == hipErrorOutOfMemory;
+        (void)hipGetLastError();
+        itd_stream_destroy(s);
+        return oom ? ITD_ERR_NOMEM : ITD_ERR_HIP;
+    }
+    *out = s;
+    return ITD_OK;
+}
+
+int itd_inst_stream_latency(const itd_stream *s) { return s && s->kind == ITD_STREAM_INSTANT ? s->D : -1; }
+
+int itd_inst_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_stride, double *amp_dev, double *phase_dev, double *freq_dev,
+                             int32_t *length_dev, int64_t out_stride, int32_t *counts_dev, int64_t counts_stride, int32_t *emitted,
+                             void *stream)
+{
+    if (!s || !block_dev || s->kind != ITD_STREAM_INSTANT) return ITD_ERR_INVALID_ARG;
+    if (s->P >= 0) return ITD_ERR_INVALID_ARG;                               // flushing: drain or reset first
+    if (s->C > 1 && in_stride < s->L) return ITD_ERR_INVALID_ARG;
+    const InstOut o = {amp_dev, phase_dev, freq_dev, length_dev, out_stride, counts_dev, counts_stride};
+    if (!inst_io_ok(s, s->t >= s->D, o)) return ITD_ERR_INVALID_ARG;
+    DevGuard g(s->eng->device);
+    return inst_push(s, block_dev, in_stride, o, emitted, stream_of(s->eng, stream));
+}
+
+int itd_inst_stream_flush_f64(itd_stream *s, double *amp_dev, double *phase_dev, double *freq_dev, int32_t *length_dev, int64_t out_stride,
+                              int32_t *counts_dev, int64_t counts_stride, int32_t *emitted, void *stream)
+{
+    if (!s || s->kind != ITD_STREAM_INSTANT) return ITD_ERR_INVALID_ARG;
+    const InstOut o = {amp_dev, phase_dev, freq_dev, length_dev, out_stride, counts_dev, counts_stride};
+    if (!inst_io_ok(s, itd_stream_blocks(s) > 0, o)) return ITD_ERR_INVALID_ARG;
+    DevGuard g(s->eng->device);
+    return inst_flush(s, o, emitted, stream_of(s->eng, stream));
+}
+
+}  // extern "C"
+
+namespace {
+// host form: pinned staging in and out, ONE synchronisation per call; only the outputs asked for are computed and copied
+int inst_host(itd_stream *s, const double *block_host, double *amp_host, double *phase_host, double *freq_host, int32_t *length_host,
+              int32_t *counts_host, int32_t *emitted, bool flush)
+{
+    if (!s || s->kind != ITD_STREAM_INSTANT || (!flush && !block_host)) return ITD_ERR_INVALID_ARG;
+    if (!amp_host && !phase_host && !freq_host && !length_host) return ITD_ERR_INVALID_ARG;
+    if (!flush && s->P >= 0) return ITD_ERR_INVALID_ARG;
+    itd_engine *e = s->eng;
+    DevGuard g(e->device);
+    const size_t cnt = (size_t)s->C * (size_t)s->L, ccnt = (size_t)s->C * 2;
+    double *const host[3] = {amp_host, phase_host, freq_host};
+    const InstOut o = {amp_host ? s->d_out + 0 * cnt : nullptr, phase_host ? s->d_out + 1 * cnt : nullptr,
+                       freq_host ? s->d_out + 2 * cnt : nullptr, length_host ? s->d_cnt + 0 : nullptr, s->L,
+                       counts_host ? s->d_cnt + cnt : nullptr, 2};
+    hipStream_t st = e->own_stream;
+    int32_t em = 0;
+    int rc;
+    if (flush) rc = inst_flush(s, o, &em, st);
+    else {
+        memcpy(s->h_in, block_host, cnt * sizeof(double));
+        HIP_TRY(e, hipMemcpyAsync(s->d_in, s->h_in, cnt * sizeof(double), hipMemcpyHostToDevice, st));
+        rc = inst_push(s, s->d_in, s->L, o, &em, st);
+    }
+    if (rc) return rc;
+    if (em) {
+        for (int k = 0; k < 3; ++k)
+            if (host[k]) HIP_TRY(e, hipMemcpyAsync(s->h_out + k * cnt, s->d_out + k * cnt, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (length_host) HIP_TRY(e, hipMemcpyAsync(s->h_cnt + 0, s->d_cnt + 0, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (counts_host) HIP_TRY(e, hipMemcpyAsync(s->h_cnt + cnt, s->d_cnt + cnt, ccnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(e, hipStreamSynchronize(st));
+    if (em) {
+        for (int k = 0; k < 3; ++k)
+            if (host[k]) memcpy(host[k], s->h_out + k * cnt, cnt * sizeof(double));
+        if (length_host) memcpy(length_host, s->h_cnt + 0, cnt * sizeof(int32_t));
+        if (counts_host) memcpy(counts_host, s->h_cnt + cnt, ccnt * sizeof(int32_t));
+    }
+    if (emitted) *emitted = em;
+    return ITD_OK;
+}
+}  // namespace
+
+extern "C" {
+int itd_inst_stream_push_host_f64(itd_stream *s, const double *block_host, double *amp_host, double *phase_host, double *freq_host,
+                                  int32_t *length_host, int32_t *counts_host, int32_t *emitted)
+{
+    return inst_host(s, block_host, amp_host, phase_host, freq_host, length_host, counts_host, emitted, false);
+}
+int itd_inst_stream_flush_host_f64(itd_stream *s, double *amp_host, double *phase_host, double *freq_host, int32_t *length_host,
+                                   int32_t *counts_host, int32_t *emitted)
+{
+    return inst_host(s, nullptr, amp_host, phase_host, freq_host, length_host, counts_host, emitted, true);
 }
 }  // extern "C"

@@ -20,7 +20,8 @@
 // Push p stores block p and (p >= D) emits block p - D; the flush steps emit the blocks still held.
 //
 // One launch per step, one workgroup per row (k_wave_stream; steps 1 to 3 are device functions — WaveRing, wave_ring_store,
-// wave_ring_cut, wave_ring_search_left / _right — that k_spectrum_stream of itd_spectrum_stream.hpp calls too):
+// wave_ring_cut, wave_ring_search_left / _right — that k_spectrum_stream of itd_spectrum_stream.hpp and k_inst_stream of
+// itd_inst_stream.hpp call too):
 //   1. the arriving block into the row's ring (a NaN in it: status = 2, a plain store); the launch itself reads the arriving block
 //      from the caller's pointer, so no fence stands between the store and the searches;
 //   2. the emitted block's samples in registers, their crossing flags as ballots and a prefix over them in LDS: every sample's
@@ -89,7 +90,7 @@ inline size_t wave_stream_lds(int L)
            groups * sizeof(int32_t) + 8 * sizeof(int32_t) + sizeof(unsigned long long);
 }
 
-// ---- what the stream kernels share (k_wave_stream here, k_spectrum_stream in itd_spectrum_stream.hpp): one row's ring as a launch
+// ---- what the stream kernels share (k_wave_stream here, k_spectrum_stream, k_inst_stream in their own headers): one row's ring as a launch
 // sees it, the arriving block's record, and the two searches that pass whole blocks by their records ---------------------------------
 
 // One row's ring window: window position w (0 <= w < R L) is the sample base + w of the stream; window block k sits in ring slot
@@ -133,7 +134,7 @@ struct WaveRing {
     }
 };
 
-// the ring of row `row` under a launch's arguments (WaveStreamArgs, SpectrumStreamArgs: the same ring fields)
+// the ring of row `row` under a launch's arguments (WaveStreamArgs, SpectrumStreamArgs, InstStreamArgs: the same ring fields)
 template <typename Args>
 __device__ __forceinline__ WaveRing wave_ring_of(const Args &a, int64_t row, int lane)
 {

@@ -27,7 +27,9 @@ whole-signal operator, so a stream whose blocks hold a few knots each reproduces
 LevelsStream: the full multi-level decomposition block by block.  WaveFilterStream: the single-wave feature filter
 (pyitd_amd.wave_filter) block by block at a fixed latency — what takes a LevelsStream's rows and gives feature-filtered components,
 entirely on the device.  SpectrumStream: the time-frequency-energy spectrum (pyitd_amd.tfe_spectrum) block by
-block at a fixed latency — finished time slices of a live decomposition's spectrum.
+block at a fixed latency — finished time slices of a live decomposition's spectrum.  InstantaneousStream: the
+per-sample amplitude, phase, frequency and half-wave length themselves (pyitd_amd.instantaneous_batch) block by block at the same
+latency.
 """
 import ctypes
 from collections import namedtuple
@@ -589,3 +591,155 @@ class SpectrumStream:
         self._check(self._L.itd_spectrum_stream_flush_host_f64(self._h, _np_ptr(e), e.shape[-1] if e.ndim == 2 else 0, _np_ptr(power),
                                                                _np_ptr(outside), _np_ptr(overlong), ctypes.byref(em)))
         return self._result(power, outside, overlong) if em.value else None
+
+
+StreamInstant = namedtuple("StreamInstant", "amplitude phase frequency length long overlong")
+_INSTANT = ("amplitude", "phase", "frequency", "length")
+
+
+def _check_want(want):
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in _INSTANT for w in want):
+        raise ValueError("want: a non-empty subset of %s, got %r" % (_INSTANT, want))
+    return want
+
+
+class InstantaneousStream:
+    """The instantaneous amplitude, phase and frequency and every sample's half-wave length block by block at a fixed latency
+    (itd_inst_stream_* in include/pyitd_hip.h): blocks of `rows` rows go in, the same blocks' per-sample quantities come out —
+    wherever a value is delivered, bit for bit what pyitd_amd.instantaneous_batch (and single_waves, for the length) gives for the
+    concatenated rows.  A sample whose half wave is longer than `horizon` samples is LONG: its amplitude and phase are the NaN
+    pattern 0x7FF8000000000000 and its length is 0.  A sample that is long or whose successor is (the stream's last sample: or whose
+    predecessor is) is OVERLONG: its frequency is that NaN — a sample in front of a too-long half wave keeps its amplitude and
+    phase and loses only its frequency.  That is the price of the bounded latency.  ONE launch per push on the GPU.
+
+        st = InstantaneousStream(1024, rows=9, horizon=2048)
+        st.latency                                      # D = ceil((horizon + 1) / block) = 3
+        for block in blocks:                            # block: [rows, 1024]
+            out = st.push(block)                        # None for the first D pushes, then block p - D's StreamInstant:
+            ...                                         # out.amplitude, out.phase, out.frequency [rows, 1024]; out.long, out.overlong [rows]
+        while (out := st.flush()) is not None: ...
+
+    block: 8 .. 4096 samples, any value.  want: a non-empty subset of "amplitude", "phase", "frequency", "length"; a field that is
+    not wanted is None and is not computed.  long / overlong: the block's counts of such samples per row (int32).  A NaN in a pushed
+    block sets status() bit 2 until reset(); that row is unspecified from then on.
+
+    Behind a LevelsStream on device pointers, everything on one stream `s`:
+
+        lv = LevelsStream(1024, levels=3, channels=2)
+        it = InstantaneousStream(1024, rows=2 * 4, horizon=2048)
+        # rows_d [2, 4, 1024], amp_d / ph_d / fr_d [8, 1024] float64, len_d [8, 1024] and cnt_d [8, 2] int32: on the device
+        if lv.push_dev(block_ptr, 1024, rows_ptr, 1024, 4 * 1024, None, s):
+            if it.push_dev(rows_ptr, 1024, amp_ptr, ph_ptr, fr_ptr, len_ptr, 1024, cnt_ptr, 2, s):
+                ...                                     # the block pushed levels + 1 + D steps ago; any per-sample rule on amplitude,
+                                                        # frequency, phase and length is an elementwise operation on these
+    """
+
+    def __init__(self, block, rows=1, horizon=None, want=("amplitude", "phase", "frequency"), device=0):
+        horizon = block if horizon is None else horizon
+        if isinstance(block, bool) or int(block) != block or not 8 <= block <= 4096:
+            raise ValueError("block must be 8 .. 4096 samples")
+        if not 1 <= rows <= 65535:
+            raise ValueError("rows must be 1 .. 65535")
+        if not 1 <= horizon <= 2 ** 22:
+            raise ValueError("horizon must be 1 .. 2^22 samples")
+        self.want = _check_want(want)
+        self._L = _lib.load()
+        h = ctypes.c_void_p()
+        rc = self._L.itd_inst_stream_create(ctypes.byref(h), int(device), int(block), int(rows), int(horizon))
+        if rc:
+            raise ITDError(rc, "itd_inst_stream_create(block=%d, rows=%d, horizon=%d)" % (block, rows, horizon))
+        self._h = h
+        self.block, self.rows, self.horizon, self.device = int(block), int(rows), int(horizon), int(device)
+        self._flat = False          # the last push took a 1-D block: the blocks that leave have no row axis either
+
+    close = Stream.close
+    __del__ = Stream.__del__
+    _check = Stream._check
+    blocks_held = Stream.blocks_held
+    reset = Stream.reset
+    status = Stream.status
+
+    @property
+    def latency(self):
+        """D = ceil((horizon + 1) / block): push p emits block p - D."""
+        return self._L.itd_inst_stream_latency(self._h)
+
+    # ---- device buffers (raw pointers; asynchronous on `stream`) ----------------------------------------------------
+    def push_dev(self, block_ptr, in_stride, amp_ptr, phase_ptr, freq_ptr, length_ptr, out_stride, counts_ptr=None, counts_stride=0,
+                 stream=None):
+        """Store one block of every row; True if a block's outputs were written (a None output is skipped)."""
+        em = ctypes.c_int32(0)
+        self._check(self._L.itd_inst_stream_push_f64(self._h, block_ptr, in_stride, amp_ptr, phase_ptr, freq_ptr, length_ptr, out_stride,
+                                                     counts_ptr, counts_stride, ctypes.byref(em), stream))
+        return bool(em.value)
+
+    def flush_dev(self, amp_ptr, phase_ptr, freq_ptr, length_ptr, out_stride, counts_ptr=None, counts_stride=0, stream=None):
+        em = ctypes.c_int32(0)
+        self._check(self._L.itd_inst_stream_flush_f64(self._h, amp_ptr, phase_ptr, freq_ptr, length_ptr, out_stride, counts_ptr,
+                                                      counts_stride, ctypes.byref(em), stream))
+        return bool(em.value)
+
+    # ---- numpy in -> numpy out (one synchronisation per call) ----------------------------------------------------------
+    def _outputs(self):
+        shape = (self.rows, self.block)
+        return ([numpy.empty(shape, numpy.int32 if w == "length" else numpy.float64) if w in self.want else None for w in _INSTANT],
+                numpy.empty((self.rows, 2), numpy.int32))
+
+    def _result(self, outs, counts):
+        if self._flat:
+            return StreamInstant(*[None if o is None else o[0] for o in outs], counts[0, 0], counts[0, 1])
+        return StreamInstant(*outs, counts[:, 0].copy(), counts[:, 1].copy())
+
+    def push(self, samples):
+        """samples [rows, block] (or [block] for one row).  None for the first `latency` pushes, then the StreamInstant of the block
+        pushed `latency` pushes ago (no row axis for 1-D input)."""
+        x = numpy.ascontiguousarray(samples, dtype=numpy.float64)
+        flat = x.ndim == 1
+        x2 = x.reshape(1, -1) if flat else x
+        if x2.shape != (self.rows, self.block):
+            raise ValueError("expected blocks of shape (%d, %d)" % (self.rows, self.block))
+        outs, counts = self._outputs()
+        em = ctypes.c_int32(0)
+        self._check(self._L.itd_inst_stream_push_host_f64(self._h, _np_ptr(x2), *[_np_ptr(o) for o in outs], _np_ptr(counts),
+                                                          ctypes.byref(em)))
+        self._flat = flat
+        return self._result(outs, counts) if em.value else None
+
+    def flush(self):
+        """The next block still held (one per call); None once the stream is empty."""
+        outs, counts = self._outputs()
+        em = ctypes.c_int32(0)
+        self._check(self._L.itd_inst_stream_flush_host_f64(self._h, *[_np_ptr(o) for o in outs], _np_ptr(counts), ctypes.byref(em)))
+        return self._result(outs, counts) if em.value else None
+
+
+def blockwise_instantaneous(rows, block, horizon, want=("amplitude", "phase", "frequency"), device=0):
+    """Run rows[R, n_blocks * block] (or [n]) through an InstantaneousStream: what a caller with an unbounded source does block by
+    block.  Returns StreamInstant: the wanted arrays shaped like the input (the others None), long and overlong as int32
+    [R, n_blocks] ([n_blocks] for 1-D input)."""
+    x = numpy.asarray(rows, dtype=numpy.float64)
+    flat = x.ndim == 1
+    x2 = x.reshape(1, -1) if flat else x
+    if x2.ndim != 2:
+        raise ValueError("rows: [R, n] or [n]")
+    R, n = x2.shape
+    if n % block or n < block:
+        raise ValueError("the length must be a multiple of the block")
+    st = InstantaneousStream(block, R, horizon, want, device)
+    outs = []
+    try:
+        for k in range(n // block):
+            r = st.push(x2[:, k * block:(k + 1) * block])
+            if r is not None:
+                outs.append(r)
+        while True:
+            r = st.flush()
+            if r is None:
+                break
+            outs.append(r)
+    finally:
+        st.close()
+    fields = [None if outs[0][i] is None else numpy.concatenate([o[i] for o in outs], axis=1) for i in range(4)]
+    fields += [numpy.stack([o[i] for o in outs], axis=1) for i in (4, 5)]
+    return StreamInstant(*[None if f is None else (f[0] if flat else f) for f in fields])
