@@ -3048,4 +3048,5 @@ int itd_get_kernel_timing(itd_engine *e, int32_t which, double *ms_total, int32_
 }  // extern "C"
 
 #include "itd_engine_batch.inc"
+#include "itd_ring_streams.inc"
 #include "itd_fourier.inc"

@@ -13,8 +13,8 @@
 //   * block-wise operation (itd.cpp:31-38), itd_stream_*: a device-resident mirrored ring per channel (itd_stream.hpp), the
 //     window's knots, their selection and the operator all on the device — a push enqueues launches and returns; the host form
 //     synchronises once per push for its copies.  The recipe: include/pyitd_hip.h, DESIGN.md section 7.
-//   * the wave-filter stream, itd_wave_stream_*: itd_wave_filter_batch_*'s filter block by block at a fixed latency, one launch per
-//     push (itd_wave_stream.hpp, DESIGN.md section 21).
+//   * struct itd_stream, for the ring streams too (itd_wave_stream_*, itd_spectrum_stream_*, itd_inst_stream_*), whose host code is
+//     in itd_ring_streams.inc, included behind this file.
 
 namespace {
 
@@ -287,19 +287,20 @@ struct itd_stream {
     Buf<uint8_t> d_exact; Pinned<uint8_t> h_exact;   // host form: [C]
     size_t lds = 0;
     const void *fn = nullptr;
-    // wave-filter stream (ITD_STREAM_WAVES, k_wave_stream in itd_wave_stream.hpp): C rows, ring = [C][2 D + 1][L]; t = the blocks
-    // pushed, P as above
-    int64_t H = 0, sent = 0;        // the horizon; the blocks emitted since create / reset / the last flush
-    int32_t D = 0;                  // the latency in blocks, ceil(H / L)
-    Buf<double> d_bnd; Pinned<double> h_bnd;         // host form: [C][4]
-    Buf<WaveBlockRec> rec;          // [C][2 D + 1]: what every block in the ring left behind when it arrived
-    // spectrum stream (ITD_STREAM_SPECTRUM, k_spectrum_stream in itd_spectrum_stream.hpp): the wave stream's ring, records and counters
-    // with D = ceil((H + 1) / L); host form: d_out / h_out = power [C][L / hop][F], d_bnd / h_bnd = edges [C][F + 1]
-    int32_t F = 0, weight = 0;      // bins; 0 count, 1 amplitude, 2 energy
-    int64_t hop = 0;
-    Buf<int32_t> d_cnt; Pinned<int32_t> h_cnt;       // host form: outside and overlong, [2][C][L / hop]
-    // instantaneous stream (ITD_STREAM_INSTANT, k_inst_stream in itd_inst_stream.hpp): the spectrum stream's ring, records, counters
-    // and D; host form: d_out / h_out = amplitude, phase, frequency [3][C][L], d_cnt / h_cnt = length [C][L], then the counts [C][2]
+    // the ring streams (ITD_STREAM_WAVES, _SPECTRUM, _INSTANT; itd_ring_streams.inc): C rows, ring = [C][2 D + 1][L]; they use L, C,
+    // kind, ring, d_status, threads, lds, fn and the staging d_in / h_in, d_out / h_out above, and besides
+    struct Ring {
+        RingCount cnt = kRingCountFresh;                 // blocks pushed, in all, emitted (itd_ring_plan.hpp)
+        int64_t H = 0;                                   // the horizon
+        int32_t D = 0;                                   // the latency in blocks, ceil((H + the kind's reach) / L)
+        Buf<WaveBlockRec> rec;                           // [C][2 D + 1]: what every block in the ring left behind when it arrived
+        int32_t F = 0, weight = 0;                       // spectrum: bins; 0 count, 1 amplitude, 2 energy
+        int64_t hop = 0;                                 // spectrum
+        // host form, besides d_in / h_in = [C][L] and d_out / h_out: a kind's float64 parameters and int32 results; what each kind
+        // keeps where is stated next to its host form (wave_staging, spectrum_staging, inst_staging)
+        Buf<double> d_bnd; Pinned<double> h_bnd;
+        Buf<int32_t> d_cnt; Pinned<int32_t> h_cnt;
+    } rs;
 };
 
 namespace {
@@ -531,7 +532,7 @@ int itd_stream_reset(itd_stream *s)
     s->pushed = 0;
     s->t = 0;
     s->P = -1;
-    s->sent = 0;
+    s->rs.cnt = kRingCountFresh;
     HIP_TRY(s->eng, hipMemsetAsync(s->d_status, 0, sizeof(int32_t), s->eng->own_stream));
     HIP_TRY(s->eng, hipStreamSynchronize(s->eng->own_stream));
     return ITD_OK;
@@ -540,7 +541,7 @@ int itd_stream_reset(itd_stream *s)
 int64_t itd_stream_blocks(const itd_stream *s)
 {
     if (!s) return -1;
-    if (s->kind >= ITD_STREAM_WAVES) return (s->P < 0 ? s->t : s->P) - s->sent;   // (the ring streams: wave filter, spectrum, instantaneous)
+    if (s->kind >= ITD_STREAM_WAVES) return ring_held(s->rs.cnt);         // (the ring streams: wave filter, spectrum, instantaneous)
     if (s->kind != ITD_STREAM_LEVELS) return s->pushed;
     return (s->P < 0 ? s->t : s->P) - std::max<int64_t>(0, s->t - s->M - 1);   // pushed, less the blocks whose rows have left
 }
@@ -889,560 +890,5 @@ int itd_levels_stream_push_host_f64(itd_stream *s, const double *block_host, dou
 int itd_levels_stream_flush_host_f64(itd_stream *s, double *rows_host, uint8_t *exact_host, int32_t *emitted)
 {
     return levels_host(s, nullptr, rows_host, exact_host, emitted, true);
-}
-}  // extern "C"
-
-// ---- the wave-filter stream: itd_wave_stream_* (include/pyitd_hip.h; the kernel, the locality rule and the ring:
-//      k_wave_stream in itd_wave_stream.hpp) --------------------------------------------------------------------------------
-namespace {
-
-// What the ring streams (wave filter, spectrum, instantaneous) share on the host: the ring fields of a step's launch arguments
-// (WaveStreamArgs, SpectrumStreamArgs, InstStreamArgs hold the same ones), the launch, and the block counting of push and flush.
-
-// One step's launch, ONE per step: the arriving block (blk, or nullptr on a flush step) goes into the ring, block b (b < 0: none)
-// is emitted from the samples [b L - H, (b+1) L + reach) that exist.  The caller has filled in what its kernel takes besides.
-template <typename Args>
-int ring_step(itd_stream *s, Args &a, const double *blk, int64_t in_stride, int64_t b, int64_t reach, hipStream_t st)
-{
-    const int64_t L = s->L, D = s->D, R = 2 * D + 1;
-    a.in = blk; a.in_stride = in_stride;
-    a.ring = s->ring;
-    a.rec = s->rec;
-    a.arr = s->t * L;
-    a.status = s->d_status;
-    a.L = (int32_t)L; a.D = (int32_t)D; a.H = (int32_t)s->H;
-    a.store_slot = blk ? (int32_t)(s->t % R) : 0;
-    a.emit = b >= 0 ? 1 : 0;
-    if (b >= 0) {
-        const int64_t exists = (s->P < 0 ? s->t + 1 : s->P) * L;          // (a push: the arriving block included)
-        const int64_t lo = std::max<int64_t>(b * L - s->H, 0), hi = std::min<int64_t>((b + 1) * L + reach, exists);
-        a.base = (b - D) * L;
-        a.slot0 = (int32_t)((((b - D) % R) + R) % R);
-        a.rd_lo = (int32_t)(lo - a.base);
-        a.rd_hi = (int32_t)(hi - a.base);
-        a.at_start = lo == 0 ? 1 : 0;
-        a.at_end = s->P >= 0 && hi == exists ? 1 : 0;
-    }
-    void *args[] = {&a};
-    HIP_TRY(s->eng, hipLaunchKernel(s->fn, dim3((unsigned)s->C), dim3((unsigned)s->threads), args, s->lds, st));
-    HIP_TRY(s->eng, hipGetLastError());
-    return ITD_OK;
-}
-
-// push p stores block p and (p >= D) emits block p - D; step(b) runs the launch
-template <typename Step>
-int ring_push(itd_stream *s, int32_t *emitted, Step step)
-{
-    const bool emits = s->t >= s->D;
-    const int rc = step(emits ? s->t - s->D : -1);
-    if (rc) return rc;
-    ++s->t;
-    if (emits) ++s->sent;
-    if (emitted) *emitted = emits ? 1 : 0;
-    return ITD_OK;
-}
-
-// one block per call: the next block still held
-template <typename Step>
-int ring_flush(itd_stream *s, int32_t *emitted, Step step)
-{
-    if (emitted) *emitted = 0;
-    if (s->P < 0 && s->t == 0) return ITD_OK;      // empty: nothing to run
-    const bool begins = s->P < 0;                  // the first flush step: the stream's length is fixed from here on
-    if (begins) s->P = s->t;
-    const int rc = step(s->sent);
-    if (rc) {                                      // nothing was emitted: the stream is as it was, pushes are still taken
-        if (begins) s->P = -1;
-        return rc;
-    }
-    if (emitted) *emitted = 1;
-    if (++s->sent == s->P) { s->t = 0; s->P = -1; s->sent = 0; }          // the last block: the stream starts afresh
-    return ITD_OK;
-}
-
-// the arriving block (blk, or nullptr on a flush step) into the ring, block b (b < 0: none) filtered and out
-int wave_step(itd_stream *s, const double *blk, int64_t in_stride, const double *bounds, int64_t bounds_stride, double *out,
-              int64_t out_stride, int64_t b, hipStream_t st)
-{
-    WaveStreamArgs a = {};
-    a.bounds = bounds; a.bounds_stride = bounds_stride;
-    a.out = out; a.out_stride = out_stride;
-    return ring_step(s, a, blk, in_stride, b, s->H, st);
-}
-
-int wave_push(itd_stream *s, const double *blk, int64_t in_stride, const double *bounds, int64_t bounds_stride, double *out,
-              int64_t out_stride, int32_t *emitted, hipStream_t st)
-{
-    return ring_push(s, emitted, [&](int64_t b) { return wave_step(s, blk, in_stride, bounds, bounds_stride, out, out_stride, b, st); });
-}
-
-int wave_flush(itd_stream *s, const double *bounds, int64_t bounds_stride, double *out, int64_t out_stride, int32_t *emitted,
-               hipStream_t st)
-{
-    return ring_flush(s, emitted, [&](int64_t b) { return wave_step(s, nullptr, 0, bounds, bounds_stride, out, out_stride, b, st); });
-}
-
-bool wave_io_ok(const itd_stream *s, bool emits, const double *bounds, int64_t bounds_stride, const double *out, int64_t out_stride)
-{
-    if (bounds_stride != 0 && bounds_stride < 4) return false;
-    if (emits && (!bounds || !out)) return false;
-    return s->C == 1 || !out || out_stride >= s->L;
-}
-
-}  // namespace
-
-extern "C" {
-
-int itd_wave_stream_create(itd_stream **out, int device_id, int64_t block, int32_t rows, int64_t horizon)
-{
-    if (!out) return ITD_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (block < 8 || block > kWaveStreamMaxBlock || rows < 1 || rows > kMaxGridY) return ITD_ERR_INVALID_ARG;
-    if (horizon < 1 || horizon > kWaveStreamMaxHorizon) return ITD_ERR_INVALID_ARG;
-    static_assert(kWaveStreamMaxBlock == kResidentMax, "the stream's largest block is the resident limit");
-    itd_stream *s = new (std::nothrow) itd_stream();
-    if (!s) return ITD_ERR_NOMEM;
-    int rc = itd_engine_create(&s->eng, device_id, 3 * block, 1);
-    if (rc) { delete s; return rc; }
-    s->L = block; s->C = rows; s->kind = ITD_STREAM_WAVES; s->H = horizon;
-    s->D = (int32_t)((horizon + block - 1) / block);
-    s->threads = block <= 256 * kWaveStreamSpt ? 256 : 1024;
-    s->fn = s->threads == 256 ? reinterpret_cast<const void *>(&k_wave_stream<256>) : reinterpret_cast<const void *>(&k_wave_stream<1024>);
-    s->lds = wave_stream_lds((int)block);
-    DevGuard g(device_id);
-    const size_t C = (size_t)rows, L = (size_t)block, R = 2 * (size_t)s->D + 1;
-    // the grant is the kernel function's, not this stream's: the most its instance ever asks for, so that a later stream with a
-    // shorter block does not lower it under a live one
-    hipError_t hrc = allow_lds(s->eng, s->fn, wave_stream_lds(s->threads == 256 ? 256 * kWaveStreamSpt : kWaveStreamMaxBlock));
-    if (hrc == hipSuccess) hrc = s->ring.alloc(C * R * L * sizeof(double));
-    if (hrc == hipSuccess) hrc = s->rec.alloc(C * R * sizeof(WaveBlockRec));
-    if (hrc == hipSuccess) hrc = s->d_status.alloc(64);
-    if (hrc == hipSuccess) hrc = hipMemset(s->d_status, 0, 64);
-    // the host form's staging: [rows][L] in and out, [rows][4] bounds
-    if (hrc == hipSuccess) hrc = s->d_in.alloc(C * L * sizeof(double));
-    if (hrc == hipSuccess) hrc = s->d_out.alloc(C * L * sizeof(double));
-    if (hrc == hipSuccess) hrc = s->d_bnd.alloc(C * 4 * sizeof(double));
-    if (hrc == hipSuccess) hrc = s->h_in.alloc(C * L * sizeof(double));
-    if (hrc == hipSuccess) hrc = s->h_out.alloc(C * L * sizeof(double));
-    if (hrc == hipSuccess) hrc = s->h_bnd.alloc(C * 4 * sizeof(double));
-    if (hrc == hipSuccess) hrc = hipDeviceSynchronize();     // (the fill ran on the null stream)
-    if (hrc != hipSuccess) {
-        const bool oom = hrc == hipErrorOutOfMemory;
-        (void)hipGetLastError();
-        itd_stream_destroy(s);
-        return oom ? ITD_ERR_NOMEM : ITD_ERR_HIP;
-    }
-    *out = s;
-    return ITD_OK;
-}
-
-int itd_wave_stream_latency(const itd_stream *s) { return s && s->kind == ITD_STREAM_WAVES ? s->D : -1; }
-
-int itd_wave_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_stride, const double *bounds_dev, int64_t bounds_stride,
-                             double *out_dev, int64_t out_stride, int32_t *emitted, void *stream)
-{
-    if (!s || !block_dev || s->kind != ITD_STREAM_WAVES) return ITD_ERR_INVALID_ARG;
-    if (s->P >= 0) return ITD_ERR_INVALID_ARG;                               // flushing: drain or reset first
-    if (s->C > 1 && in_stride < s->L) return ITD_ERR_INVALID_ARG;
-    if (!wave_io_ok(s, s->t >= s->D, bounds_dev, bounds_stride, out_dev, out_stride)) return ITD_ERR_INVALID_ARG;
-    DevGuard g(s->eng->device);
-    return wave_push(s, block_dev, in_stride, bounds_dev, bounds_stride, out_dev, out_stride, emitted, stream_of(s->eng, stream));
-}
-
-int itd_wave_stream_flush_f64(itd_stream *s, const double *bounds_dev, int64_t bounds_stride, double *out_dev, int64_t out_stride,
-                              int32_t *emitted, void *stream)
-{
-    if (!s || s->kind != ITD_STREAM_WAVES) return ITD_ERR_INVALID_ARG;
-    if (!wave_io_ok(s, itd_stream_blocks(s) > 0, bounds_dev, bounds_stride, out_dev, out_stride)) return ITD_ERR_INVALID_ARG;
-    DevGuard g(s->eng->device);
-    return wave_flush(s, bounds_dev, bounds_stride, out_dev, out_stride, emitted, stream_of(s->eng, stream));
-}
-
-}  // extern "C"
-
-namespace {
-// host form: pinned staging in and out, ONE synchronisation per call
-int wave_host(itd_stream *s, const double *block_host, const double *bounds_host, double *out_host, int32_t *emitted, bool flush)
-{
-    if (!s || s->kind != ITD_STREAM_WAVES || (!flush && !block_host) || !bounds_host || !out_host) return ITD_ERR_INVALID_ARG;
-    if (!flush && s->P >= 0) return ITD_ERR_INVALID_ARG;
-    itd_engine *e = s->eng;
-    DevGuard g(e->device);
-    const size_t cnt = (size_t)s->C * (size_t)s->L, bcnt = (size_t)s->C * 4;
-    hipStream_t st = e->own_stream;
-    int32_t em = 0;
-    int rc;
-    memcpy(s->h_bnd, bounds_host, bcnt * sizeof(double));
-    HIP_TRY(e, hipMemcpyAsync(s->d_bnd, s->h_bnd, bcnt * sizeof(double), hipMemcpyHostToDevice, st));
-    if (flush) rc = wave_flush(s, s->d_bnd, 4, s->d_out, s->L, &em, st);
-    else {
-        memcpy(s->h_in, block_host, cnt * sizeof(double));
-        HIP_TRY(e, hipMemcpyAsync(s->d_in, s->h_in, cnt * sizeof(double), hipMemcpyHostToDevice, st));
-        rc = wave_push(s, s->d_in, s->L, s->d_bnd, 4, s->d_out, s->L, &em, st);
-    }
-    if (rc) return rc;
-    if (em) HIP_TRY(e, hipMemcpyAsync(s->h_out, s->d_out, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(e, hipStreamSynchronize(st));
-    if (em) memcpy(out_host, s->h_out, cnt * sizeof(double));
-    if (emitted) *emitted = em;
-    return ITD_OK;
-}
-}  // namespace
-
-extern "C" {
-int itd_wave_stream_push_host_f64(itd_stream *s, const double *block_host, const double *bounds_host, double *out_host, int32_t *emitted)
-{
-    return wave_host(s, block_host, bounds_host, out_host, emitted, false);
-}
-int itd_wave_stream_flush_host_f64(itd_stream *s, const double *bounds_host, double *out_host, int32_t *emitted)
-{
-    return wave_host(s, nullptr, bounds_host, out_host, emitted, true);
-}
-}  // extern "C"
-
-// ---- the spectrum stream: itd_spectrum_stream_* (include/pyitd_hip.h; the kernel, the locality rule and the LDS budget:
-//      k_spectrum_stream in itd_spectrum_stream.hpp) ---------------------------------------------------------------------------
-namespace {
-
-// one step, ONE launch: the arriving block (blk, or nullptr on a flush step) into the ring, block b's cells (b < 0: none) out
-int spectrum_step(itd_stream *s, const double *blk, int64_t in_stride, const double *edges, int64_t edges_stride, double *power,
-                  int64_t power_stride, int32_t *outside, int32_t *overlong, int64_t count_stride, int64_t b, hipStream_t st)
-{
-    SpectrumStreamArgs a = {};
-    a.edges = edges; a.edges_stride = edges_stride;
-    a.power = power; a.power_stride = power_stride;
-    a.outside = outside; a.overlong = overlong; a.count_stride = count_stride;
-    a.F = s->F; a.spc = (int32_t)(s->hop / 64); a.weight = s->weight;
-    return ring_step(s, a, blk, in_stride, b, s->H + 1, st);              // (one sample past the wave filter's reach: A of sample (b+1) L)
-}
-
-int spectrum_push(itd_stream *s, const double *blk, int64_t in_stride, const double *edges, int64_t edges_stride, double *power,
-                  int64_t power_stride, int32_t *outside, int32_t *overlong, int64_t count_stride, int32_t *emitted, hipStream_t st)
-{
-    return ring_push(s, emitted, [&](int64_t b) {
-        return spectrum_step(s, blk, in_stride, edges, edges_stride, power, power_stride, outside, overlong, count_stride, b, st);
-    });
-}
-
-int spectrum_flush(itd_stream *s, const double *edges, int64_t edges_stride, double *power, int64_t power_stride, int32_t *outside,
-                   int32_t *overlong, int64_t count_stride, int32_t *emitted, hipStream_t st)
-{
-    return ring_flush(s, emitted, [&](int64_t b) {
-        return spectrum_step(s, nullptr, 0, edges, edges_stride, power, power_stride, outside, overlong, count_stride, b, st);
-    });
-}
-
-bool spectrum_io_ok(const itd_stream *s, bool emits, const double *edges, int64_t edges_stride, const double *power, int64_t power_stride,
-                    const int32_t *outside, const int32_t *overlong, int64_t count_stride)
-{
-    const int64_t cells = s->L / s->hop;
-    if (edges_stride != 0 && edges_stride < s->F + 1) return false;
-    if (emits && (!edges || !power)) return false;
-    if (s->C == 1) return true;
-    if (power && power_stride < cells * s->F) return false;
-    return !(outside || overlong) || count_stride >= cells;
-}
-
-bool spectrum_hop_ok(int64_t hop) { return hop >= 64 && hop % 64 == 0 && (hop >= kTfeTile || hop == 64 || hop == 128 || hop == 256); }
-
-}  // namespace
-
-extern "C" {
-
-int itd_spectrum_stream_create(itd_stream **out, int device_id, int64_t block, int32_t rows, int64_t horizon, int64_t hop, int32_t bins,
-                               int32_t weight)
-{
-    if (!out) return ITD_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (block < kSpectrumStreamMinBlock || block > kSpectrumStreamMaxBlock || rows < 1 || rows > kMaxGridY) return ITD_ERR_INVALID_ARG;
-    if (horizon < 1 || horizon > kWaveStreamMaxHorizon) return ITD_ERR_INVALID_ARG;
-    if (!spectrum_hop_ok(hop) || block % hop != 0) return ITD_ERR_INVALID_ARG;
-    if (bins < 1 || bins > kTfeMaxBins || weight < 0 || weight > 2) return ITD_ERR_INVALID_ARG;
-    itd_stream *s = new (std::nothrow) itd_stream();
-    if (!s) return ITD_ERR_NOMEM;
-    int rc = itd_engine_create(&s->eng, device_id, 3 * block, 1);
-    if (rc) { delete s; return rc; }
-    s->L = block; s->C = rows; s->kind = ITD_STREAM_SPECTRUM; s->H = horizon;
-    s->hop = hop; s->F = bins; s->weight = weight;
-    s->D = (int32_t)((horizon + 1 + block - 1) / block);
-    s->threads = block <= 256 * kWaveStreamSpt ? 256 : 512;
-    s->fn = s->threads == 256 ? reinterpret_cast<const void *>(&k_spectrum_stream<256>) : reinterpret_cast<const void *>(&k_spectrum_stream<512>);
-    s->lds = spectrum_stream_lds((int)block, bins, s->threads);
-    DevGuard g(device_id);
-    const size_t C = (size_t)rows, L = (size_t)block, R = 2 * (size_t)s->D + 1, cells = (size_t)(block / hop), F = (size_t)bins;
-    // the grant is the kernel function's, not this stream's: the most its instance ever asks for (wave stream: the same rule)
-    hipError_t hrc = allow_lds(s->eng, s->fn, spectrum_stream_lds(s->threads == 256 ? 256 * kWaveStreamSpt : kSpectrumStreamMaxBlock,
-                                                                  kTfeMaxBins, s->threads));
-    if (hrc == hipSuccess) hrc = s->ring.alloc(C * R * L * sizeof(double));
-    if (hrc == hipSuccess) hrc = s->rec.alloc(C * R * sizeof(WaveBlockRec));
-    if (hrc == hipSuccess) hrc = s->d_status.alloc(64);
-    if (hrc == hipSuccess) hrc = hipMemset(s->d_status, 0, 64);
-    // the host form's staging: [rows][L] in, [rows][cells][F] power and [2][rows][cells] counts out, [rows][F + 1] edges
-    if (hrc == hipSuccess) hrc = s->d_in.alloc(C * L * sizeof(double));
-    if (hrc == hipSuccess) hrc = s->d_out.alloc(C * cells * F * sizeof(double));
-    if (hrc == hipSuccess) hrc = s->d_bnd.alloc(C * (F + 1) * sizeof(double));
-    if (hrc == hipSuccess) hrc = s->d_cnt.alloc(2 * C * cells * sizeof(int32_t));
-    if (hrc == hipSuccess) hrc = s->h_in.alloc(C * L * sizeof(double));
-    if (hrc == hipSuccess) hrc = s->h_out.alloc(C * cells * F * sizeof(double));
-    if (hrc == hipSuccess) hrc = s->h_bnd.alloc(C * (F + 1) * sizeof(double));
-    if (hrc == hipSuccess) hrc = s->h_cnt.alloc(2 * C * cells * sizeof(int32_t));
-    if (hrc == hipSuccess) hrc = hipDeviceSynchronize();     // (the fill ran on the null stream)
-    if (hrc != hipSuccess) {
-        const bool oom = hrc == hipErrorOutOfMemory;
-        (void)hipGetLastError();
-        itd_stream_destroy(s);
-        return oom ? ITD_ERR_NOMEM : ITD_ERR_HIP;
-    }
-    *out = s;
-    return ITD_OK;
-}
-
-int itd_spectrum_stream_latency(const itd_stream *s) { return s && s->kind == ITD_STREAM_SPECTRUM ? s->D : -1; }
-
-int itd_spectrum_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_stride, const double *edges_dev, int64_t edges_stride,
-                                 double *power_dev, int64_t power_stride, int32_t *outside_dev, int32_t *overlong_dev, int64_t count_stride,
-                                 int32_t *emitted, void *stream)
-{
-    if (!s || !block_dev || s->kind != ITD_STREAM_SPECTRUM) return ITD_ERR_INVALID_ARG;
-    if (s->P >= 0) return ITD_ERR_INVALID_ARG;                               // flushing: drain or reset first
-    if (s->C > 1 && in_stride < s->L) return ITD_ERR_INVALID_ARG;
-    if (!spectrum_io_ok(s, s->t >= s->D, edges_dev, edges_stride, power_dev, power_stride, outside_dev, overlong_dev, count_stride))
-        return ITD_ERR_INVALID_ARG;
-    DevGuard g(s->eng->device);
-    return spectrum_push(s, block_dev, in_stride, edges_dev, edges_stride, power_dev, power_stride, outside_dev, overlong_dev, count_stride,
-                         emitted, stream_of(s->eng, stream));
-}
-
-int itd_spectrum_stream_flush_f64(itd_stream *s, const double *edges_dev, int64_t edges_stride, double *power_dev, int64_t power_stride,
-                                  int32_t *outside_dev, int32_t *overlong_dev, int64_t count_stride, int32_t *emitted, void *stream)
-{
-    if (!s || s->kind != ITD_STREAM_SPECTRUM) return ITD_ERR_INVALID_ARG;
-    if (!spectrum_io_ok(s, itd_stream_blocks(s) > 0, edges_dev, edges_stride, power_dev, power_stride, outside_dev, overlong_dev, count_stride))
-        return ITD_ERR_INVALID_ARG;
-    DevGuard g(s->eng->device);
-    return spectrum_flush(s, edges_dev, edges_stride, power_dev, power_stride, outside_dev, overlong_dev, count_stride, emitted,
-                          stream_of(s->eng, stream));
-}
-
-}  // extern "C"
-
-namespace {
-// host form: pinned staging in and out, ONE synchronisation per call
-int spectrum_host(itd_stream *s, const double *block_host, const double *edges_host, int64_t edges_stride, double *power_host,
-                  int32_t *outside_host, int32_t *overlong_host, int32_t *emitted, bool flush)
-{
-    if (!s || s->kind != ITD_STREAM_SPECTRUM || (!flush && !block_host) || !edges_host || !power_host) return ITD_ERR_INVALID_ARG;
-    if (edges_stride != 0 && edges_stride < s->F + 1) return ITD_ERR_INVALID_ARG;
-    if (!flush && s->P >= 0) return ITD_ERR_INVALID_ARG;
-    itd_engine *e = s->eng;
-    DevGuard g(e->device);
-    const size_t C = (size_t)s->C, cnt = C * (size_t)s->L, cells = (size_t)(s->L / s->hop), F1 = (size_t)s->F + 1;
-    const size_t pcnt = C * cells * (size_t)s->F, ccnt = C * cells;
-    hipStream_t st = e->own_stream;
-    int32_t em = 0;
-    int rc;
-    for (size_t r = 0; r < (edges_stride ? C : 1); ++r) memcpy(s->h_bnd + r * F1, edges_host + r * (size_t)edges_stride, F1 * sizeof(double));
-    HIP_TRY(e, hipMemcpyAsync(s->d_bnd, s->h_bnd, (edges_stride ? C : 1) * F1 * sizeof(double), hipMemcpyHostToDevice, st));
-    const int64_t es = edges_stride ? (int64_t)F1 : 0, ps = (int64_t)(cells * (size_t)s->F);
-    int32_t *d_outside = s->d_cnt, *d_overlong = s->d_cnt + ccnt;
-    if (flush) rc = spectrum_flush(s, s->d_bnd, es, s->d_out, ps, d_outside, d_overlong, (int64_t)cells, &em, st);
-    else {
-        memcpy(s->h_in, block_host, cnt * sizeof(double));
-        HIP_TRY(e, hipMemcpyAsync(s->d_in, s->h_in, cnt * sizeof(double), hipMemcpyHostToDevice, st));
-        rc = spectrum_push(s, s->d_in, s->L, s->d_bnd, es, s->d_out, ps, d_outside, d_overlong, (int64_t)cells, &em, st);
-    }
-    if (rc) return rc;
-    if (em) {
-        HIP_TRY(e, hipMemcpyAsync(s->h_out, s->d_out, pcnt * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_TRY(e, hipMemcpyAsync(s->h_cnt, s->d_cnt, 2 * ccnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(e, hipStreamSynchronize(st));
-    if (em) {
-        memcpy(power_host, s->h_out, pcnt * sizeof(double));
-        if (outside_host) memcpy(outside_host, s->h_cnt, ccnt * sizeof(int32_t));
-        if (overlong_host) memcpy(overlong_host, s->h_cnt + ccnt, ccnt * sizeof(int32_t));
-    }
-    if (emitted) *emitted = em;
-    return ITD_OK;
-}
-}  // namespace
-
-extern "C" {
-int itd_spectrum_stream_push_host_f64(itd_stream *s, const double *block_host, const double *edges_host, int64_t edges_stride,
-                                      double *power_host, int32_t *outside_host, int32_t *overlong_host, int32_t *emitted)
-{
-    return spectrum_host(s, block_host, edges_host, edges_stride, power_host, outside_host, overlong_host, emitted, false);
-}
-int itd_spectrum_stream_flush_host_f64(itd_stream *s, const double *edges_host, int64_t edges_stride, double *power_host,
-                                       int32_t *outside_host, int32_t *overlong_host, int32_t *emitted)
-{
-    return spectrum_host(s, nullptr, edges_host, edges_stride, power_host, outside_host, overlong_host, emitted, true);
-}
-}  // extern "C"
-
-// ---- the instantaneous stream: itd_inst_stream_* (include/pyitd_hip.h; the kernel and the LDS budget: k_inst_stream in
-//      itd_inst_stream.hpp; locality and latency are the spectrum stream's) -----------------------------------------------------
-namespace {
-
-struct InstOut {
-    double *amp, *phase, *freq;
-    int32_t *length;
-    int64_t stride;
-    int32_t *counts;
-    int64_t counts_stride;
-    bool any() const { return amp || phase || freq || length; }
-};
-
-int inst_step(itd_stream *s, const double *blk, int64_t in_stride, const InstOut &o, int64_t b, hipStream_t st)
-{
-    InstStreamArgs a = {};
-    a.amp = o.amp; a.phase = o.phase; a.freq = o.freq; a.length = o.length; a.out_stride = o.stride;
-    a.counts = o.counts; a.counts_stride = o.counts_stride;
-    return ring_step(s, a, blk, in_stride, b, s->H + 1, st);
-}
-
-int inst_push(itd_stream *s, const double *blk, int64_t in_stride, const InstOut &o, int32_t *emitted, hipStream_t st)
-{
-    return ring_push(s, emitted, [&](int64_t b) { return inst_step(s, blk, in_stride, o, b, st); });
-}
-
-int inst_flush(itd_stream *s, const InstOut &o, int32_t *emitted, hipStream_t st)
-{
-    return ring_flush(s, emitted, [&](int64_t b) { return inst_step(s, nullptr, 0, o, b, st); });
-}
-
-bool inst_io_ok(const itd_stream *s, bool emits, const InstOut &o)
-{
-    if (emits && !o.any()) return false;
-    if (s->C == 1) return true;
-    if (o.any() && o.stride < s->L) return false;
-    return !o.counts || o.counts_stride >= 2;
-}
-
-}  // namespace
-
-extern "C" {
-
-int itd_inst_stream_create(itd_stream **out, int device_id, int64_t block, int32_t rows, int64_t horizon)
-{
-    if (!out) return ITD_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (block < kInstStreamMinBlock || block > kInstStreamMaxBlock || rows < 1 || rows > kMaxGridY) return ITD_ERR_INVALID_ARG;
-    if (horizon < 1 || horizon > kWaveStreamMaxHorizon) return ITD_ERR_INVALID_ARG;
-    itd_stream *s = new (std::nothrow) itd_stream();
-    if (!s) return ITD_ERR_NOMEM;
-    int rc = itd_engine_create(&s->eng, device_id, 3 * block, 1);
-    if (rc) { delete s; return rc; }
-    s->L = block; s->C = rows; s->kind = ITD_STREAM_INSTANT; s->H = horizon;
-    s->D = (int32_t)((horizon + 1 + block - 1) / block);
-    s->threads = block <= 256 * kWaveStreamSpt ? 256 : 512;
-    s->fn = s->threads == 256 ? reinterpret_cast<const void *>(&k_inst_stream<256>) : reinterpret_cast<const void *>(&k_inst_stream<512>);
-    s->lds = inst_stream_lds((int)block);
-    DevGuard g(device_id);
-    const size_t C = (size_t)rows, L = (size_t)block, R = 2 * (size_t)s->D + 1;
-    // the grant is the kernel function's, not this stream's: the most its instance ever asks for (wave stream: the same rule)
-    hipError_t hrc = allow_lds(s->eng, s->fn, inst_stream_lds(s->threads == 256 ? 256 * kWaveStreamSpt : kInstStreamMaxBlock));
-    if (hrc == hipSuccess) hrc = s->ring.alloc(C * R * L * sizeof(double));
-    if (hrc == hipSuccess) hrc = s->rec.alloc(C * R * sizeof(WaveBlockRec));
-    if (hrc == hipSuccess) hrc = s->d_status.alloc(64);
-    if (hrc == hipSuccess) hrc = hipMemset(s->d_status, 0, 64);
-    // the host form's staging: [rows][L] in, [3][rows][L] float64 and [rows][L] + [rows][2] int32 out
-    if (hrc == hipSuccess) hrc = s->d_in.alloc(C * L * sizeof(double));
-    if (hrc == hipSuccess) hrc = s->d_out.alloc(3 * C * L * sizeof(double));
-    if (hrc == hipSuccess) hrc = s->d_cnt.alloc(C * (L + 2) * sizeof(int32_t));
-    if (hrc == hipSuccess) hrc = s->h_in.alloc(C * L * sizeof(double));
-    if (hrc == hipSuccess) hrc = s->h_out.alloc(3 * C * L * sizeof(double));
-    if (hrc == hipSuccess) hrc = s->h_cnt.alloc(C * (L + 2) * sizeof(int32_t));
-    if (hrc == hipSuccess) hrc = hipDeviceSynchronize();     // (the fill ran on the null stream)
-    if (hrc != hipSuccess) {
-        const bool oom = hrc == hipErrorOutOfMemory;
-        (void)hipGetLastError();
-        itd_stream_destroy(s);
-        return oom ? ITD_ERR_NOMEM : ITD_ERR_HIP;
-    }
-    *out = s;
-    return ITD_OK;
-}
-
-int itd_inst_stream_latency(const itd_stream *s) { return s && s->kind == ITD_STREAM_INSTANT ? s->D : -1; }
-
-int itd_inst_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_stride, double *amp_dev, double *phase_dev, double *freq_dev,
-                             int32_t *length_dev, int64_t out_stride, int32_t *counts_dev, int64_t counts_stride, int32_t *emitted,
-                             void *stream)
-{
-    if (!s || !block_dev || s->kind != ITD_STREAM_INSTANT) return ITD_ERR_INVALID_ARG;
-    if (s->P >= 0) return ITD_ERR_INVALID_ARG;                               // flushing: drain or reset first
-    if (s->C > 1 && in_stride < s->L) return ITD_ERR_INVALID_ARG;
-    const InstOut o = {amp_dev, phase_dev, freq_dev, length_dev, out_stride, counts_dev, counts_stride};
-    if (!inst_io_ok(s, s->t >= s->D, o)) return ITD_ERR_INVALID_ARG;
-    DevGuard g(s->eng->device);
-    return inst_push(s, block_dev, in_stride, o, emitted, stream_of(s->eng, stream));
-}
-
-int itd_inst_stream_flush_f64(itd_stream *s, double *amp_dev, double *phase_dev, double *freq_dev, int32_t *length_dev, int64_t out_stride,
-                              int32_t *counts_dev, int64_t counts_stride, int32_t *emitted, void *stream)
-{
-    if (!s || s->kind != ITD_STREAM_INSTANT) return ITD_ERR_INVALID_ARG;
-    const InstOut o = {amp_dev, phase_dev, freq_dev, length_dev, out_stride, counts_dev, counts_stride};
-    if (!inst_io_ok(s, itd_stream_blocks(s) > 0, o)) return ITD_ERR_INVALID_ARG;
-    DevGuard g(s->eng->device);
-    return inst_flush(s, o, emitted, stream_of(s->eng, stream));
-}
-
-}  // extern "C"
-
-namespace {
-// host form: pinned staging in and out, ONE synchronisation per call; only the outputs asked for are computed and copied
-int inst_host(itd_stream *s, const double *block_host, double *amp_host, double *phase_host, double *freq_host, int32_t *length_host,
-              int32_t *counts_host, int32_t *emitted, bool flush)
-{
-    if (!s || s->kind != ITD_STREAM_INSTANT || (!flush && !block_host)) return ITD_ERR_INVALID_ARG;
-    if (!amp_host && !phase_host && !freq_host && !length_host) return ITD_ERR_INVALID_ARG;
-    if (!flush && s->P >= 0) return ITD_ERR_INVALID_ARG;
-    itd_engine *e = s->eng;
-    DevGuard g(e->device);
-    const size_t cnt = (size_t)s->C * (size_t)s->L, ccnt = (size_t)s->C * 2;
-    double *const host[3] = {amp_host, phase_host, freq_host};
-    const InstOut o = {amp_host ? s->d_out + 0 * cnt : nullptr, phase_host ? s->d_out + 1 * cnt : nullptr,
-                       freq_host ? s->d_out + 2 * cnt : nullptr, length_host ? s->d_cnt + 0 : nullptr, s->L,
-                       counts_host ? s->d_cnt + cnt : nullptr, 2};
-    hipStream_t st = e->own_stream;
-    int32_t em = 0;
-    int rc;
-    if (flush) rc = inst_flush(s, o, &em, st);
-    else {
-        memcpy(s->h_in, block_host, cnt * sizeof(double));
-        HIP_TRY(e, hipMemcpyAsync(s->d_in, s->h_in, cnt * sizeof(double), hipMemcpyHostToDevice, st));
-        rc = inst_push(s, s->d_in, s->L, o, &em, st);
-    }
-    if (rc) return rc;
-    if (em) {
-        for (int k = 0; k < 3; ++k)
-            if (host[k]) HIP_TRY(e, hipMemcpyAsync(s->h_out + k * cnt, s->d_out + k * cnt, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (length_host) HIP_TRY(e, hipMemcpyAsync(s->h_cnt + 0, s->d_cnt + 0, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        if (counts_host) HIP_TRY(e, hipMemcpyAsync(s->h_cnt + cnt, s->d_cnt + cnt, ccnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(e, hipStreamSynchronize(st));
-    if (em) {
-        for (int k = 0; k < 3; ++k)
-            if (host[k]) memcpy(host[k], s->h_out + k * cnt, cnt * sizeof(double));
-        if (length_host) memcpy(length_host, s->h_cnt + 0, cnt * sizeof(int32_t));
-        if (counts_host) memcpy(counts_host, s->h_cnt + cnt, ccnt * sizeof(int32_t));
-    }
-    if (emitted) *emitted = em;
-    return ITD_OK;
-}
-}  // namespace
-
-extern "C" {
-int itd_inst_stream_push_host_f64(itd_stream *s, const double *block_host, double *amp_host, double *phase_host, double *freq_host,
-                                  int32_t *length_host, int32_t *counts_host, int32_t *emitted)
-{
-    return inst_host(s, block_host, amp_host, phase_host, freq_host, length_host, counts_host, emitted, false);
-}
-int itd_inst_stream_flush_host_f64(itd_stream *s, double *amp_host, double *phase_host, double *freq_host, int32_t *length_host,
-                                   int32_t *counts_host, int32_t *emitted)
-{
-    return inst_host(s, nullptr, amp_host, phase_host, freq_host, length_host, counts_host, emitted, true);
 }
 }  // extern "C"

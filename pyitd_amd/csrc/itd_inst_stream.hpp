@@ -43,22 +43,12 @@ constexpr int kInstStreamMaxBlock = 4096;
 constexpr unsigned long long kInstStreamNaN = 0x7FF8000000000000ull;    // every float64 value that is not delivered
 
 struct InstStreamArgs {
-    const double *in;              // this push's block of every row (in_stride apart); nullptr on a flush step
-    int64_t in_stride;
-    double *ring;                  // [rows][R][L]
-    WaveBlockRec *rec;             // [rows][R]
-    int64_t arr;                   // the absolute index of the arriving block's first sample
+    RingStepArgs r;                // the ring's fields (itd_ring_plan.hpp); the readable range is the spectrum stream's
     double *amp, *phase, *freq;    // the emitted block of row r at r out_stride (each or nullptr)
     int32_t *length;
     int64_t out_stride;
     int32_t *counts;               // (long, overlong) of row r at r counts_stride (or nullptr)
     int64_t counts_stride;
-    int32_t *status;               // = 2: a pushed block held a NaN
-    int64_t base;                  // the absolute index of window position 0: (b - D) L
-    int32_t L, D, H;
-    int32_t slot0, store_slot, emit;
-    int32_t rd_lo, rd_hi;          // the readable range in window positions: max(D L - H, -base) .. min((D+1) L + H + 1, what exists)
-    int32_t at_start, at_end;      // it begins at the stream's start; it ends at the flushed stream's end
 };
 
 // dynamic LDS of a launch for blocks of L samples
@@ -67,55 +57,36 @@ inline size_t inst_stream_lds(int L) { return (size_t)(L + 1) * 8 + wave_stream_
 template <int TH>
 __global__ __launch_bounds__(TH) void k_inst_stream(InstStreamArgs a)
 {
-    constexpr int SPT = kWaveStreamSpt, U = kWaveStreamUnroll, W = TH / 64;
+    constexpr int SPT = kWaveStreamSpt, W = TH / 64;
     static_assert(TH % 64 == 0, "geometry");
     extern __shared__ __attribute__((aligned(16))) unsigned char is_lds[];
     const double pi = 3.14159265358979323846;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int L = a.L, D = a.D, H = a.H;
+    const int L = a.r.L, D = a.r.D, H = a.r.H;
     const int G = (L + 63) >> 6;                                          // 64-sample steps of the block, the last one ragged
     double *ph = reinterpret_cast<double *>(is_lds);                                   // [L + 1] phase
-    unsigned long long *mag = reinterpret_cast<unsigned long long *>(ph + (L + 1));    // [L + 1], the cut's arrays (wave_stream_lds)
-    unsigned long long *bal = mag + (L + 1);                                          // [G]
-    unsigned long long *amx = bal + G;                                                // [1]
-    int32_t *edge = reinterpret_cast<int32_t *>(amx + 1);                              // [L + 2]
-    int32_t *pre = edge + (L + 2);                                                    // [G]
-    int32_t *ctl = pre + G;           // [0] c, [1] left, [2] right, [3] the arriving block's flag, [4] long, [5] overlong samples
+    const WaveCutLds q = wave_cut_lds(reinterpret_cast<unsigned char *>(ph + (L + 1)), L);   // the cut's arrays (wave_stream_lds)
+    unsigned long long *const mag = q.mag, *const bal = q.bal;
+    int32_t *const edge = q.edge, *const ctl = q.ctl;                     // ctl[4] long, ctl[5] overlong samples
     const int64_t row = blockIdx.x;
-    const WaveRing rg = wave_ring_of(a, row, lane);
+    const WaveRing rg = wave_ring_of(a.r, row, lane);
 
     // 1. the arriving block into its slot, its record behind it
-    if (rg.in) wave_ring_store<TH>(rg, a.arr, a.store_slot, a.status, amx, &ctl[3], tid);
-    if (!a.emit) return;
+    if (rg.in) wave_ring_store<TH>(rg, a.r.arr, a.r.store_slot, a.r.status, q.amx, &ctl[3], tid);
+    if (!a.r.emit) return;
     const int b0 = D * L;
 
     // 2. the block cut at its crossings, the far ends of its outer half waves
-    for (int i = tid; i <= L; i += TH) mag[i] = 0ull;
-    if (tid == 0) { ctl[1] = INT32_MIN; ctl[2] = INT32_MAX; ctl[4] = 0; ctl[5] = 0; }
-    const double *const blk = rg.ring + (int64_t)((a.slot0 + D) % rg.R) * L;
+    if (tid == 0) { ctl[4] = 0; ctl[5] = 0; }
+    const double *const blk = rg.ring + (int64_t)((a.r.slot0 + D) % rg.R) * L;
     double xr[SPT], slope[SPT];
     bool cr[SPT];
     int seg[SPT];
-    const int c = wave_ring_cut<TH, true>(rg, blk, mag, bal, edge, pre, &ctl[0], tid, wave, xr, slope, cr, seg);
-    {
-        unsigned long long m;
-        int found;
-        wave_ring_search_left<TH, U>(rg, &ctl[1], tid, m, found);
-        if (m) atomicMax(&mag[0], m);
-        if (tid == 0) edge[0] = found != INT32_MIN ? found - b0 : (a.at_start ? a.rd_lo - 1 - b0 : -H - 2);
-    }
-    {
-        unsigned long long m;
-        int found;
-        wave_ring_search_right<TH, U>(rg, &ctl[2], tid, m, found);
-        if (m) atomicMax(&mag[c], m);
-        if (tid == 0) edge[c + 1] = found != INT32_MAX ? found - b0 : (a.at_end ? a.rd_hi - 1 - b0 : L + H + 2);
-    }
-    __syncthreads();
+    const int c = wave_ring_block<TH, true>(rg, a.r, q, blk, tid, wave, xr, slope, cr, seg);
 
     // 3. amplitude, length and phase of every sample; long and overlong
-    const bool has_ext = b0 + L < a.rd_hi;                                // sample (b+1) L exists (and then (b+1) L + 1 too, readable: H >= 1)
+    const bool has_ext = b0 + L < a.r.rd_hi;                                // sample (b+1) L exists (and then (b+1) L + 1 too, readable: H >= 1)
     // (the block's length once more, through readfirstlane: s < Lq is then compared anew below — against L the compiler keeps the
     // cut's eight lane masks of s < L alive across the searches and spills SGPRs for them)
     const int Lq = __builtin_amdgcn_readfirstlane(L);

@@ -45,23 +45,13 @@ constexpr int kSpectrumStreamMinBlock = 64;
 constexpr int kSpectrumStreamMaxBlock = 4096;
 
 struct SpectrumStreamArgs {
-    const double *in;              // this push's block of every row (in_stride apart); nullptr on a flush step
-    int64_t in_stride;
-    double *ring;                  // [rows][R][L]
-    WaveBlockRec *rec;             // [rows][R]
-    int64_t arr;                   // the absolute index of the arriving block's first sample
+    RingStepArgs r;                // the ring's fields (itd_ring_plan.hpp); the readable range reaches one sample past the wave filter's
     const double *edges;           // edges[0 .. F] of row r at r edges_stride (0: one set for all rows)
     int64_t edges_stride;
     double *power;                 // the emitted block's cells [C][F] of row r at r power_stride
     int64_t power_stride;
     int32_t *outside, *overlong;   // [C] of row r at r count_stride (or nullptr)
     int64_t count_stride;
-    int32_t *status;               // = 2: a pushed block held a NaN
-    int64_t base;                  // the absolute index of window position 0: (b - D) L
-    int32_t L, D, H;
-    int32_t slot0, store_slot, emit;
-    int32_t rd_lo, rd_hi;          // the readable range in window positions: max(D L - H, -base) .. min((D+1) L + H + 1, what exists)
-    int32_t at_start, at_end;      // it begins at the stream's start; it ends at the flushed stream's end
     int32_t F, spc, weight;        // bins; 64-sample steps per cell (hop / 64); 0 count, 1 amplitude, 2 energy
 };
 
@@ -84,60 +74,40 @@ __device__ __forceinline__ void spectrum_wave_sync()
 template <int TH>
 __global__ __launch_bounds__(TH) void k_spectrum_stream(SpectrumStreamArgs a)
 {
-    constexpr int SPT = kWaveStreamSpt, U = kWaveStreamUnroll, W = TH / 64;
+    constexpr int SPT = kWaveStreamSpt, W = TH / 64;
     static_assert(TH % 64 == 0, "geometry");
     extern __shared__ __attribute__((aligned(16))) unsigned char ss_lds[];
     const double pi = 3.14159265358979323846;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int L = a.L, D = a.D, H = a.H, F = a.F;
+    const int L = a.r.L, D = a.r.D, H = a.r.H, F = a.F;
     const int G = L >> 6;                                                 // 64-sample steps of the block (L is a multiple of 64)
     double *wq = reinterpret_cast<double *>(ss_lds);                                   // [L + 1] phase, then weight
     double *edg = wq + (L + 1);                                                       // [F + 1]
     int32_t *bin = reinterpret_cast<int32_t *>(edg + (F + 1));                         // [L]
     unsigned char *un = reinterpret_cast<unsigned char *>(bin + L);                   // the cut's arrays, then acc / msk
-    unsigned long long *mag = reinterpret_cast<unsigned long long *>(un);              // [L + 1]
-    unsigned long long *bal = mag + (L + 1);                                          // [G]
-    unsigned long long *amx = bal + G;                                                // [1]
-    int32_t *edge = reinterpret_cast<int32_t *>(amx + 1);                              // [L + 2]
-    int32_t *pre = edge + (L + 2);                                                    // [G]
-    int32_t *ctl = pre + G;                                                           // [0] c, [1] left, [2] right, [3] the arriving block's flag
+    const WaveCutLds q = wave_cut_lds(un, L);
+    unsigned long long *const mag = q.mag;
+    int32_t *const edge = q.edge;
     const int64_t row = blockIdx.x;
-    const WaveRing rg = wave_ring_of(a, row, lane);
+    const WaveRing rg = wave_ring_of(a.r, row, lane);
 
     // 1. the arriving block into its slot, its record behind it
-    if (rg.in) wave_ring_store<TH>(rg, a.arr, a.store_slot, a.status, amx, &ctl[3], tid);
-    if (!a.emit) return;
+    if (rg.in) wave_ring_store<TH>(rg, a.r.arr, a.r.store_slot, a.r.status, q.amx, &q.ctl[3], tid);
+    if (!a.r.emit) return;
     const int b0 = D * L;
     const double *erow = a.edges + row * a.edges_stride;
     for (int i = tid; i <= F; i += TH) edg[i] = erow[i];
 
     // 2. the block cut at its crossings, the far ends of its outer half waves
-    for (int i = tid; i <= L; i += TH) mag[i] = 0ull;
-    if (tid == 0) { ctl[1] = INT32_MIN; ctl[2] = INT32_MAX; }
-    const double *const blk = rg.ring + (int64_t)((a.slot0 + D) % rg.R) * L;
+    const double *const blk = rg.ring + (int64_t)((a.r.slot0 + D) % rg.R) * L;
     double xr[SPT], slope[SPT];
     bool cr[SPT];
     int seg[SPT];
-    const int c = wave_ring_cut<TH, true>(rg, blk, mag, bal, edge, pre, &ctl[0], tid, wave, xr, slope, cr, seg);
-    {
-        unsigned long long m;
-        int found;
-        wave_ring_search_left<TH, U>(rg, &ctl[1], tid, m, found);
-        if (m) atomicMax(&mag[0], m);
-        if (tid == 0) edge[0] = found != INT32_MIN ? found - b0 : (a.at_start ? a.rd_lo - 1 - b0 : -H - 2);
-    }
-    {
-        unsigned long long m;
-        int found;
-        wave_ring_search_right<TH, U>(rg, &ctl[2], tid, m, found);
-        if (m) atomicMax(&mag[c], m);
-        if (tid == 0) edge[c + 1] = found != INT32_MAX ? found - b0 : (a.at_end ? a.rd_hi - 1 - b0 : L + H + 2);
-    }
-    __syncthreads();
+    const int c = wave_ring_block<TH, true>(rg, a.r, q, blk, tid, wave, xr, slope, cr, seg);
 
     // 3. amplitude, phase, frequency, bin and weight of every sample
-    const bool has_ext = b0 + L < a.rd_hi;                                // sample (b+1) L exists (and then (b+1) L + 1 too, readable: H >= 1)
+    const bool has_ext = b0 + L < a.r.rd_hi;                                // sample (b+1) L exists (and then (b+1) L + 1 too, readable: H >= 1)
     double A[SPT];
     bool ovl[SPT];
 #pragma unroll

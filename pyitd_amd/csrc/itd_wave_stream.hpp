@@ -19,9 +19,10 @@
 // H <= D L, so the readable range lies in the blocks b - D .. b + D: a ring of R = 2 D + 1 blocks per row, block q in slot q % R.
 // Push p stores block p and (p >= D) emits block p - D; the flush steps emit the blocks still held.
 //
-// One launch per step, one workgroup per row (k_wave_stream; steps 1 to 3 are device functions — WaveRing, wave_ring_store,
-// wave_ring_cut, wave_ring_search_left / _right — that k_spectrum_stream of itd_spectrum_stream.hpp and k_inst_stream of
-// itd_inst_stream.hpp call too):
+// One launch per step, one workgroup per row (k_wave_stream; steps 1 to 3 are device functions — WaveRing, wave_ring_store, and
+// wave_ring_block over wave_ring_cut and wave_ring_search_left / _right — that k_spectrum_stream of itd_spectrum_stream.hpp and
+// k_inst_stream of itd_inst_stream.hpp call too; the launch's ring fields, RingStepArgs, and the host's arithmetic for them are in
+// itd_ring_plan.hpp):
 //   1. the arriving block into the row's ring (a NaN in it: status = 2, a plain store); the launch itself reads the arriving block
 //      from the caller's pointer, so no fence stands between the store and the searches;
 //   2. the emitted block's samples in registers, their crossing flags as ballots and a prefix over them in LDS: every sample's
@@ -44,6 +45,7 @@
 #include <stdint.h>
 
 #include "itd_halfwave.hpp"
+#include "itd_ring_plan.hpp"
 
 #pragma clang fp contract(off)
 
@@ -54,32 +56,12 @@ constexpr int kWaveStreamUnroll = 4;         // samples per thread and chunk of 
 constexpr int kWaveStreamMaxBlock = 8192;    // = kResidentMax
 constexpr int64_t kWaveStreamMaxHorizon = (int64_t)1 << 22;
 
-// what a block leaves behind when it arrives: cross = a crossing index among its samples 0 .. L-2 (their successors are the
-// block's own; whether its last sample is one is known from the next block's first), mx = max |x| of the block as a bit pattern
-struct WaveBlockRec {
-    unsigned long long mx;
-    int32_t cross, pad;
-};
-static_assert(sizeof(WaveBlockRec) == 16, "WaveBlockRec layout");
-
 struct WaveStreamArgs {
-    const double *in;              // this push's block of every row (in_stride apart); nullptr on a flush step
-    int64_t in_stride;
-    double *ring;                  // [rows][R][L]
-    WaveBlockRec *rec;             // [rows][R]: the record of the block in every ring slot
-    int64_t arr;                   // the absolute index of the arriving block's first sample
+    RingStepArgs r;                // the ring's fields (itd_ring_plan.hpp)
     const double *bounds;          // (amp_lo, amp_hi, len_lo, len_hi) of row r at r bounds_stride
     int64_t bounds_stride;
     double *out;                   // the emitted block of row r at r out_stride (emit = 1)
     int64_t out_stride;
-    int32_t *status;               // = 2: a pushed block held a NaN
-    int64_t base;                  // the absolute index of window position 0: (b - D) L (negative in a stream's first D blocks)
-    int32_t L, D, H;
-    int32_t slot0;                 // the ring slot of window block 0: (b - D) mod R; window block k sits in slot (slot0 + k) % R
-    int32_t store_slot;            // the ring slot the arriving block goes to (in != nullptr)
-    int32_t emit;                  // 0: a push that only stores
-    int32_t rd_lo, rd_hi;          // the readable range in window positions: max(D L - H, -base) .. min((D+1) L + H, what exists)
-    int32_t at_start, at_end;      // it begins at the stream's start; it ends at the flushed stream's end
 };
 
 // dynamic LDS of a launch for blocks of L samples
@@ -134,9 +116,8 @@ struct WaveRing {
     }
 };
 
-// the ring of row `row` under a launch's arguments (WaveStreamArgs, SpectrumStreamArgs, InstStreamArgs: the same ring fields)
-template <typename Args>
-__device__ __forceinline__ WaveRing wave_ring_of(const Args &a, int64_t row, int lane)
+// the ring of row `row` under a launch's ring fields
+__device__ __forceinline__ WaveRing wave_ring_of(const RingStepArgs &a, int64_t row, int lane)
 {
     const int R = 2 * a.D + 1;
     return {a.in ? a.in + row * a.in_stride : nullptr, a.ring + row * (int64_t)R * a.L, a.rec + row * (int64_t)R, a.base, a.base + a.rd_hi,
@@ -313,57 +294,84 @@ __device__ __forceinline__ int wave_ring_cut(const WaveRing &rg, const double *b
     return c;
 }
 
+// The cut's arrays in LDS, wave_stream_lds(L) bytes from `base` on (8-byte aligned).  ctl: [0] c, [1] the left search's crossing,
+// [2] the right search's, [3] the arriving block's flag, [4 .. 7] the caller's.
+struct WaveCutLds {
+    unsigned long long *mag, *bal, *amx;         // [L + 1]; [G]; [1] the arriving block's max |x|
+    int32_t *edge, *pre, *ctl;                   // [L + 2], positions relative to the block; [G]; [8]
+};
+__device__ __forceinline__ WaveCutLds wave_cut_lds(unsigned char *base, int L)
+{
+    const int G = (L + 63) >> 6;                                          // 64-sample groups of the block
+    WaveCutLds q;
+    q.mag = reinterpret_cast<unsigned long long *>(base);
+    q.bal = q.mag + (L + 1);
+    q.amx = q.bal + G;
+    q.edge = reinterpret_cast<int32_t *>(q.amx + 1);
+    q.pre = q.edge + (L + 2);
+    q.ctl = q.pre + G;
+    return q;
+}
+
+// Steps 2 and 3 of an emitting launch, called by every thread of the row's workgroup behind step 1: the emitted block (window block
+// D, blk) cut at its crossings (wave_ring_cut: xr, slope, cr, seg and the LDS arrays), then the outer searches, chunk by chunk, each
+// ending at the first chunk that holds a crossing, which complete mag[0], edge[0], mag[c] and edge[c + 1].  Returns c behind a barrier.
+template <int TH, bool kSlope>
+__device__ __forceinline__ int wave_ring_block(const WaveRing &rg, const RingStepArgs &a, const WaveCutLds &q, const double *blk, int tid,
+                                               int wave, double (&xr)[kWaveStreamSpt], double (&slope)[kWaveStreamSpt],
+                                               bool (&cr)[kWaveStreamSpt], int (&seg)[kWaveStreamSpt])
+{
+    constexpr int U = kWaveStreamUnroll;
+    const int L = a.L, H = a.H, b0 = a.D * L;                             // b0: the emitted block's first window position
+    for (int i = tid; i <= L; i += TH) q.mag[i] = 0ull;
+    if (tid == 0) { q.ctl[1] = INT32_MIN; q.ctl[2] = INT32_MAX; }
+    const int c = wave_ring_cut<TH, kSlope>(rg, blk, q.mag, q.bal, q.edge, q.pre, &q.ctl[0], tid, wave, xr, slope, cr, seg);
+    {
+        unsigned long long m;
+        int found;
+        wave_ring_search_left<TH, U>(rg, &q.ctl[1], tid, m, found);
+        if (m) atomicMax(&q.mag[0], m);
+        // half wave 0 begins behind the crossing; without one at the stream's start (if the range reaches it), else out of reach
+        if (tid == 0) q.edge[0] = found != INT32_MIN ? found - b0 : (a.at_start ? a.rd_lo - 1 - b0 : -H - 2);
+    }
+    {
+        unsigned long long m;
+        int found;
+        wave_ring_search_right<TH, U>(rg, &q.ctl[2], tid, m, found);
+        if (m) atomicMax(&q.mag[c], m);
+        // half wave c ends at the crossing; without one at the flushed stream's last sample (if the range reaches it), else out of reach
+        if (tid == 0) q.edge[c + 1] = found != INT32_MAX ? found - b0 : (a.at_end ? a.rd_hi - 1 - b0 : L + H + 2);
+    }
+    __syncthreads();
+    return c;
+}
+
 template <int TH>
 __global__ __launch_bounds__(TH) void k_wave_stream(WaveStreamArgs a)
 {
-    constexpr int SPT = kWaveStreamSpt, U = kWaveStreamUnroll, W = TH / 64;
+    constexpr int SPT = kWaveStreamSpt, W = TH / 64;
     static_assert(TH % 64 == 0 && TH * SPT >= 64, "geometry");
     extern __shared__ __attribute__((aligned(16))) unsigned char ws_lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int L = a.L, D = a.D, H = a.H;
+    const int L = a.r.L, D = a.r.D, H = a.r.H;
     const int G = (L + 63) >> 6;                                          // 64-sample groups of the block
-    unsigned long long *mag = reinterpret_cast<unsigned long long *>(ws_lds);          // [L + 1]
-    unsigned long long *bal = mag + (L + 1);                                          // [G]
-    unsigned long long *amx = bal + G;                                                // [1] the arriving block's max |x|
-    int32_t *edge = reinterpret_cast<int32_t *>(amx + 1);                              // [L + 2], positions relative to the block
-    int32_t *pre = edge + (L + 2);                                                    // [G]
-    int32_t *ctl = pre + G;           // [0] c, [1] the left search's crossing, [2] the right search's, [3] the arriving block's flag
+    const WaveCutLds q = wave_cut_lds(ws_lds, L);
+    unsigned long long *const mag = q.mag;
+    int32_t *const edge = q.edge;
     const int64_t row = blockIdx.x;
-    const WaveRing rg = wave_ring_of(a, row, lane);
+    const WaveRing rg = wave_ring_of(a.r, row, lane);
 
     // 1. the arriving block into its slot, its record behind it
-    if (rg.in) wave_ring_store<TH>(rg, a.arr, a.store_slot, a.status, amx, &ctl[3], tid);
-    if (!a.emit) return;
-    const int b0 = D * L;                                                 // the emitted block's first window position
+    if (rg.in) wave_ring_store<TH>(rg, a.r.arr, a.r.store_slot, a.r.status, q.amx, &q.ctl[3], tid);
+    if (!a.r.emit) return;
 
-    // 2. the block: samples, flags, half-wave numbers, inner maxima
-    for (int i = tid; i <= L; i += TH) mag[i] = 0ull;
-    if (tid == 0) { ctl[1] = INT32_MIN; ctl[2] = INT32_MAX; }
-    const double *const blk = rg.ring + (int64_t)((a.slot0 + D) % rg.R) * L;    // (window block D: never the arriving one, D >= 1)
+    // 2., 3. the block: samples, flags, half-wave numbers, inner maxima; the outer searches
+    const double *const blk = rg.ring + (int64_t)((a.r.slot0 + D) % rg.R) * L;    // (window block D: never the arriving one, D >= 1)
     double xr[SPT], unused[SPT];
     bool cr[SPT];
     int seg[SPT];
-    const int c = wave_ring_cut<TH, false>(rg, blk, mag, bal, edge, pre, &ctl[0], tid, wave, xr, unused, cr, seg);
-
-    // 3. the outer searches, chunk by chunk, each ending at the first chunk that holds a crossing
-    {
-        unsigned long long m;
-        int found;
-        wave_ring_search_left<TH, U>(rg, &ctl[1], tid, m, found);
-        if (m) atomicMax(&mag[0], m);
-        // half wave 0 begins behind the crossing; without one at the stream's start (if the range reaches it), else out of reach
-        if (tid == 0) edge[0] = found != INT32_MIN ? found - b0 : (a.at_start ? a.rd_lo - 1 - b0 : -H - 2);
-    }
-    {
-        unsigned long long m;
-        int found;
-        wave_ring_search_right<TH, U>(rg, &ctl[2], tid, m, found);
-        if (m) atomicMax(&mag[c], m);
-        // half wave c ends at the crossing; without one at the flushed stream's last sample (if the range reaches it), else out of reach
-        if (tid == 0) edge[c + 1] = found != INT32_MAX ? found - b0 : (a.at_end ? a.rd_hi - 1 - b0 : L + H + 2);
-    }
-    __syncthreads();
+    wave_ring_block<TH, false>(rg, a.r, q, blk, tid, wave, xr, unused, cr, seg);
 
     // 4. every half wave of the block decided
     const double *bnd = a.bounds + row * a.bounds_stride;

@@ -6,7 +6,7 @@ first extrema in the last buffer / set the first and last baseline knots manuall
 compute only the baseline[i] array for the inner third of the buffer overall / rotate buffers, rinse and repeat", and the
 reuse of retained extrema along channels (itd.cpp:40-44).  Everything numeric runs on the GPU inside the library: the ring
 of the last three blocks, the window's extrema, the knot selection and the operator (pyitd_amd/csrc/itd_stream.hpp,
-itd_engine_batch.inc); this module only hands blocks in and out.  The recipe's exact statement (window geometry, knot selection) is in include/pyitd_hip.h
+itd_engine_batch.inc; the three fixed-latency streams: itd_ring_streams.inc); this module only hands blocks in and out.  The recipe's exact statement (window geometry, knot selection) is in include/pyitd_hip.h
 and DESIGN.md section 7; the GPU tests hold these classes to an independent CPU statement of it.
 
     st = Stream(4096, kind="linear")             # tier-1 operator, ITD.py:79-121
@@ -46,24 +46,22 @@ def _np_ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
-class Stream:
-    """One stream = `channels` channels in lock step, blocks of `block` samples."""
+_NO_STREAM = object()
 
-    def __init__(self, block, channels=1, kind="cubic", margin=8, shared_knots=False, device=0):
-        if kind not in KINDS:
-            raise ValueError("kind must be 'cubic' or 'linear'")
-        if block < 8 or channels < 1 or (kind == "cubic" and margin < 1):
-            raise ValueError("block >= 8 samples, channels >= 1, margin >= 1 extremum")
-        if kind == "linear" and shared_knots:
-            raise ValueError("the tier-1 operator's knots are the signal's own (ITD.py:87-98): shared_knots needs kind='cubic'")
+
+class _Handle:
+    """Owns one itd_stream* of the library: what every kind of stream does with its handle."""
+
+    _L = _h = None
+
+    def _open(self, create, detail, *args):
+        """self._h = the stream `create`(*args) makes; ITDError(status, detail) if it does not"""
         self._L = _lib.load()
         h = ctypes.c_void_p()
-        rc = self._L.itd_stream_create(ctypes.byref(h), int(device), int(block), int(channels), KINDS[kind], int(margin),
-                                       1 if shared_knots else 0)
+        rc = getattr(self._L, create)(ctypes.byref(h), *args)
         if rc:
-            raise ITDError(rc, "itd_stream_create(block=%d, channels=%d, kind=%s)" % (block, channels, kind))
+            raise ITDError(rc, detail)
         self._h = h
-        self.block, self.channels, self.kind, self.margin, self.device = int(block), int(channels), kind, int(margin), int(device)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -80,6 +78,13 @@ class Stream:
         if rc:
             raise ITDError(rc, self._L.itd_stream_last_error(self._h).decode())
 
+    def _call(self, name, *args, stream=_NO_STREAM):
+        """One push or flush entry `name`(handle, *args, &emitted[, stream]): True if it emitted a block."""
+        em = ctypes.c_int32(0)
+        tail = (ctypes.byref(em),) if stream is _NO_STREAM else (ctypes.byref(em), stream)
+        self._check(getattr(self._L, name)(self._h, *args, *tail))
+        return bool(em.value)
+
     @property
     def blocks_held(self):
         return self._L.itd_stream_blocks(self._h)
@@ -93,18 +98,37 @@ class Stream:
         self._check(self._L.itd_stream_status(self._h, ctypes.byref(v)))
         return v.value
 
+    def _block(self, samples, rows):
+        """samples as float64 [rows, block], and whether they came without the row axis"""
+        x = numpy.ascontiguousarray(samples, dtype=numpy.float64)
+        flat = x.ndim == 1
+        x2 = x.reshape(1, -1) if flat else x
+        if x2.shape != (rows, self.block):
+            raise ValueError("expected blocks of shape (%d, %d)" % (rows, self.block))
+        return x2, flat
+
+
+class Stream(_Handle):
+    """One stream = `channels` channels in lock step, blocks of `block` samples."""
+
+    def __init__(self, block, channels=1, kind="cubic", margin=8, shared_knots=False, device=0):
+        if kind not in KINDS:
+            raise ValueError("kind must be 'cubic' or 'linear'")
+        if block < 8 or channels < 1 or (kind == "cubic" and margin < 1):
+            raise ValueError("block >= 8 samples, channels >= 1, margin >= 1 extremum")
+        if kind == "linear" and shared_knots:
+            raise ValueError("the tier-1 operator's knots are the signal's own (ITD.py:87-98): shared_knots needs kind='cubic'")
+        self._open("itd_stream_create", "itd_stream_create(block=%d, channels=%d, kind=%s)" % (block, channels, kind), int(device), int(block),
+                   int(channels), KINDS[kind], int(margin), 1 if shared_knots else 0)
+        self.block, self.channels, self.kind, self.margin, self.device = int(block), int(channels), kind, int(margin), int(device)
+
     # ---- device buffers (raw pointers; asynchronous on `stream`) ----------------------------------------------------
     def push_dev(self, block_ptr, in_stride, base_ptr, base_stride, rot_ptr=None, rot_stride=0, stream=None):
         """Store one block of every channel; True if the previous block's baseline (rotation) was written."""
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_stream_push_f64(self._h, block_ptr, in_stride, base_ptr, base_stride, rot_ptr, rot_stride,
-                                                ctypes.byref(em), stream))
-        return bool(em.value)
+        return self._call("itd_stream_push_f64", block_ptr, in_stride, base_ptr, base_stride, rot_ptr, rot_stride, stream=stream)
 
     def flush_dev(self, base_ptr, base_stride, rot_ptr=None, rot_stride=0, stream=None):
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_stream_flush_f64(self._h, base_ptr, base_stride, rot_ptr, rot_stride, ctypes.byref(em), stream))
-        return bool(em.value)
+        return self._call("itd_stream_flush_f64", base_ptr, base_stride, rot_ptr, rot_stride, stream=stream)
 
     # ---- numpy in -> numpy out (one synchronisation per call) ----------------------------------------------------------
     def _shape_out(self, a, flat):
@@ -113,16 +137,10 @@ class Stream:
     def push(self, samples):
         """samples [channels, block] (or [block] for one channel).  Returns None for the first block; afterwards the PREVIOUS
         block's baseline (cubic) or (rotation, baseline) (linear), shaped like the input."""
-        x = numpy.ascontiguousarray(samples, dtype=numpy.float64)
-        flat = x.ndim == 1
-        x2 = x.reshape(1, -1) if flat else x
-        if x2.shape != (self.channels, self.block):
-            raise ValueError("expected blocks of shape (%d, %d)" % (self.channels, self.block))
+        x2, flat = self._block(samples, self.channels)
         base = numpy.empty_like(x2)
         rot = numpy.empty_like(x2) if self.kind == "linear" else None
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_stream_push_host_f64(self._h, _np_ptr(x2), _np_ptr(base), _np_ptr(rot), ctypes.byref(em)))
-        if not em.value:
+        if not self._call("itd_stream_push_host_f64", _np_ptr(x2), _np_ptr(base), _np_ptr(rot)):
             return None
         if self.kind == "linear":
             return self._shape_out(rot, flat), self._shape_out(base, flat)
@@ -132,9 +150,7 @@ class Stream:
         """The last block's result (it has no successor); None if the stream holds nothing."""
         base = numpy.empty((self.channels, self.block))
         rot = numpy.empty_like(base) if self.kind == "linear" else None
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_stream_flush_host_f64(self._h, _np_ptr(base), _np_ptr(rot), ctypes.byref(em)))
-        if not em.value:
+        if not self._call("itd_stream_flush_host_f64", _np_ptr(base), _np_ptr(rot)):
             return None
         flat = (self.channels == 1) if flat is None else flat
         if self.kind == "linear":
@@ -156,25 +172,41 @@ class BlockwiseLinear(Stream):
         super().__init__(block, 1, "linear", 1, False, device)
 
 
-def blockwise(x, block, kind="cubic", margin=8, shared_knots=False, device=0):
-    """Run a whole array x[channels, n_blocks * block] (or [n]) through a stream: what a caller with an unbounded source
-    does block by block.  Returns baseline (cubic) or (rotation, baseline) (linear)."""
+def _as_rows(x, block, two_d=False):
+    """x as float64 [rows, n_blocks * block], and whether it came without the row axis"""
     x = numpy.asarray(x, dtype=numpy.float64)
     flat = x.ndim == 1
     x2 = x.reshape(1, -1) if flat else x
-    C, n = x2.shape
+    if two_d and x2.ndim != 2:
+        raise ValueError("rows: [R, n] or [n]")
+    rows, n = x2.shape
     if n % block or n < block:
         raise ValueError("the length must be a multiple of the block")
-    st = Stream(block, C, kind, margin, shared_knots, device)
+    return x2, flat
+
+
+def _push_then_drain(st, x2, args=None, **flush_kw):
+    """Every block of x2 through st.push, then st.flush until it gives None; st is closed.  args(st): what push takes behind the
+    block and flush in front of flush_kw.  Returns what the calls gave, in order."""
     outs = []
     try:
-        for k in range(n // block):
-            r = st.push(x2[:, k * block:(k + 1) * block])
+        a = args(st) if args else ()
+        for k in range(x2.shape[1] // st.block):
+            r = st.push(x2[:, k * st.block:(k + 1) * st.block], *a)
             if r is not None:
                 outs.append(r)
-        outs.append(st.flush(flat=False))
+        while (r := st.flush(*a, **flush_kw)) is not None:
+            outs.append(r)
     finally:
         st.close()
+    return outs
+
+
+def blockwise(x, block, kind="cubic", margin=8, shared_knots=False, device=0):
+    """Run a whole array x[channels, n_blocks * block] (or [n]) through a stream: what a caller with an unbounded source
+    does block by block.  Returns baseline (cubic) or (rotation, baseline) (linear)."""
+    x2, flat = _as_rows(x, block)
+    outs = _push_then_drain(Stream(block, x2.shape[0], kind, margin, shared_knots, device), x2, flat=False)
     if kind == "linear":
         rot = numpy.concatenate([o[0] for o in outs], axis=1)
         base = numpy.concatenate([o[1] for o in outs], axis=1)
@@ -183,7 +215,7 @@ def blockwise(x, block, kind="cubic", margin=8, shared_knots=False, device=0):
     return base[0] if flat else base
 
 
-class LevelsStream:
+class LevelsStream(_Handle):
     """The full multi-level ITD block by block (itd_levels_stream_* in include/pyitd_hip.h): a chain of levels + 1 tier-1
     stages, stage k >= 1 on the baselines of stage k-1; every step is ONE launch on the GPU for blocks up to 2730 samples, a launch
     sequence (bit-identical) for longer ones.
@@ -205,12 +237,8 @@ class LevelsStream:
             raise ValueError("levels must be 1 .. 21")
         if not 1 <= channels <= 65535:
             raise ValueError("channels must be 1 .. 65535")
-        self._L = _lib.load()
-        h = ctypes.c_void_p()
-        rc = self._L.itd_levels_stream_create(ctypes.byref(h), int(device), int(block), int(channels), int(levels))
-        if rc:
-            raise ITDError(rc, "itd_levels_stream_create(block=%d, channels=%d, levels=%d)" % (block, channels, levels))
-        self._h = h
+        self._open("itd_levels_stream_create", "itd_levels_stream_create(block=%d, channels=%d, levels=%d)" % (block, channels, levels),
+                   int(device), int(block), int(channels), int(levels))
         self.block, self.levels, self.channels, self.device = int(block), int(levels), int(channels), int(device)
 
     @property
@@ -222,26 +250,13 @@ class LevelsStream:
         """Run every step as the launch sequence even where one launch would do (bit-identical; for comparing the forms)."""
         self._check(self._L.itd_levels_stream_set_sequence(self._h, 1 if on else 0))
 
-    close = Stream.close
-    __del__ = Stream.__del__
-    _check = Stream._check
-    blocks_held = Stream.blocks_held
-    reset = Stream.reset
-    status = Stream.status
-
     # ---- device buffers (raw pointers; asynchronous on `stream`) ----------------------------------------------------
     def push_dev(self, block_ptr, in_stride, rows_ptr, row_stride, chan_stride, exact_ptr=None, stream=None):
         """Store one block of every channel; True if a block's rows (and flags) were written."""
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_levels_stream_push_f64(self._h, block_ptr, in_stride, rows_ptr, row_stride, chan_stride,
-                                                       exact_ptr, ctypes.byref(em), stream))
-        return bool(em.value)
+        return self._call("itd_levels_stream_push_f64", block_ptr, in_stride, rows_ptr, row_stride, chan_stride, exact_ptr, stream=stream)
 
     def flush_dev(self, rows_ptr, row_stride, chan_stride, exact_ptr=None, stream=None):
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_levels_stream_flush_f64(self._h, rows_ptr, row_stride, chan_stride, exact_ptr,
-                                                        ctypes.byref(em), stream))
-        return bool(em.value)
+        return self._call("itd_levels_stream_flush_f64", rows_ptr, row_stride, chan_stride, exact_ptr, stream=stream)
 
     # ---- numpy in -> numpy out (one synchronisation per call) ----------------------------------------------------------
     def _out(self, rows, exact, flat):
@@ -251,25 +266,17 @@ class LevelsStream:
     def push(self, samples):
         """samples [channels, block] (or [block] for one channel).  None, or (rows[channels, levels+1, block], exact[channels])
         with the channel axis dropped for 1-D input."""
-        x = numpy.ascontiguousarray(samples, dtype=numpy.float64)
-        flat = x.ndim == 1
-        x2 = x.reshape(1, -1) if flat else x
-        if x2.shape != (self.channels, self.block):
-            raise ValueError("expected blocks of shape (%d, %d)" % (self.channels, self.block))
+        x2, flat = self._block(samples, self.channels)
         rows = numpy.empty((self.channels, self.levels + 1, self.block))
         exact = numpy.zeros(self.channels, dtype=numpy.uint8)
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_levels_stream_push_host_f64(self._h, _np_ptr(x2), _np_ptr(rows), _np_ptr(exact),
-                                                            ctypes.byref(em)))
-        return self._out(rows, exact, flat) if em.value else None
+        em = self._call("itd_levels_stream_push_host_f64", _np_ptr(x2), _np_ptr(rows), _np_ptr(exact))
+        return self._out(rows, exact, flat) if em else None
 
     def flush(self, flat=None):
         """The next block still held (one per call); None once the stream is empty."""
         rows = numpy.empty((self.channels, self.levels + 1, self.block))
         exact = numpy.zeros(self.channels, dtype=numpy.uint8)
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_levels_stream_flush_host_f64(self._h, _np_ptr(rows), _np_ptr(exact), ctypes.byref(em)))
-        if not em.value:
+        if not self._call("itd_levels_stream_flush_host_f64", _np_ptr(rows), _np_ptr(exact)):
             return None
         return self._out(rows, exact, self.channels == 1 if flat is None else flat)
 
@@ -277,32 +284,61 @@ class LevelsStream:
 def blockwise_itd(x, block, levels, device=0):
     """Run x[channels, n_blocks * block] (or [n]) through a LevelsStream.  Returns (rows[channels, levels+1, n],
     exact[channels, n_blocks]) (no channel axis for 1-D input)."""
-    x = numpy.asarray(x, dtype=numpy.float64)
-    flat = x.ndim == 1
-    x2 = x.reshape(1, -1) if flat else x
-    C, n = x2.shape
-    if n % block or n < block:
-        raise ValueError("the length must be a multiple of the block")
-    st = LevelsStream(block, levels, C, device)
-    outs = []
-    try:
-        for k in range(n // block):
-            r = st.push(x2[:, k * block:(k + 1) * block])
-            if r is not None:
-                outs.append(r)
-        while True:
-            r = st.flush(flat=False)
-            if r is None:
-                break
-            outs.append(r)
-    finally:
-        st.close()
+    x2, flat = _as_rows(x, block)
+    outs = _push_then_drain(LevelsStream(block, levels, x2.shape[0], device), x2, flat=False)
     rows = numpy.concatenate([o[0] for o in outs], axis=2)
     exact = numpy.stack([o[1] for o in outs], axis=1)
     return (rows[0], exact[0]) if flat else (rows, exact)
 
 
-class WaveFilterStream:
+class _RingStream(_Handle):
+    """What the three fixed-latency streams share (itd_<_NAME>_stream_* in include/pyitd_hip.h): `rows` rows in lock step, blocks of
+    `block` samples, a horizon, D = latency blocks between a push and its block's results.  A kind gives its name, its validation of
+    the block, the arguments of its device entries, and for the numpy form _outputs() (the arrays a call fills, None where one is not
+    wanted) and _result(outs)."""
+
+    _NAME = None
+
+    @staticmethod
+    def _check_rows_horizon(rows, horizon):
+        if not 1 <= rows <= 65535:
+            raise ValueError("rows must be 1 .. 65535")
+        if not 1 <= horizon <= 2 ** 22:
+            raise ValueError("horizon must be 1 .. 2^22 samples")
+
+    def _create(self, block, rows, horizon, device, extra=(), detail=""):
+        name = "itd_%s_stream_create" % self._NAME
+        self._open(name, "%s(block=%d, rows=%d, horizon=%d%s)" % (name, block, rows, horizon, detail), int(device), int(block), int(rows),
+                   int(horizon), *extra)
+        self.block, self.rows, self.horizon, self.device = int(block), int(rows), int(horizon), int(device)
+        self._flat = False          # the last push took a 1-D block: the blocks that leave have no row axis either
+
+    @property
+    def latency(self):
+        """D: push p emits block p - D.  D = ceil(horizon / block) for the wave filter, ceil((horizon + 1) / block) for the spectrum
+        and the instantaneous stream."""
+        return getattr(self._L, "itd_%s_stream_latency" % self._NAME)(self._h)
+
+    # ---- device buffers (raw pointers; asynchronous on `stream`): the kinds' push_dev / flush_dev name their arguments ----------
+    def _dev(self, step, args, stream):
+        return self._call("itd_%s_stream_%s_f64" % (self._NAME, step), *args, stream=stream)
+
+    # ---- numpy in -> numpy out (one synchronisation per call) ----------------------------------------------------------
+    def _host(self, block, params=()):
+        """One call of the host form: a push of `block` (what _block made of the caller's samples), or a flush step (None).
+        params: what the entry takes between the block and the outputs.  The kind's result, or None if nothing was emitted."""
+        step, head = "flush", ()
+        if block is not None:
+            x2, flat = block
+            step, head = "push", (_np_ptr(x2),)
+        outs = self._outputs()
+        em = self._call("itd_%s_stream_%s_host_f64" % (self._NAME, step), *head, *params, *[_np_ptr(o) for o in outs])
+        if block is not None:
+            self._flat = flat
+        return self._result(outs) if em else None
+
+
+class WaveFilterStream(_RingStream):
     """The single-wave feature filter block by block at a fixed latency (itd_wave_stream_* in include/pyitd_hip.h): blocks of
     `rows` rows go in, the same blocks come out with the samples of the half waves outside the bounds set to +0.0 — bit for bit
     pyitd_amd.wave_filter of the concatenated rows with the upper length bound capped at `horizon`.  A half wave longer than
@@ -328,47 +364,22 @@ class WaveFilterStream:
                 ...                                     # out_d holds the filtered rows of the block pushed levels + 1 + D steps ago
     """
 
+    _NAME = "wave"
+
     def __init__(self, block, rows=1, horizon=None, device=0):
         horizon = block if horizon is None else horizon
         if not 8 <= block <= 8192:
             raise ValueError("block must be 8 .. 8192 samples")
-        if not 1 <= rows <= 65535:
-            raise ValueError("rows must be 1 .. 65535")
-        if not 1 <= horizon <= 2 ** 22:
-            raise ValueError("horizon must be 1 .. 2^22 samples")
-        self._L = _lib.load()
-        h = ctypes.c_void_p()
-        rc = self._L.itd_wave_stream_create(ctypes.byref(h), int(device), int(block), int(rows), int(horizon))
-        if rc:
-            raise ITDError(rc, "itd_wave_stream_create(block=%d, rows=%d, horizon=%d)" % (block, rows, horizon))
-        self._h = h
-        self.block, self.rows, self.horizon, self.device = int(block), int(rows), int(horizon), int(device)
-        self._flat = False          # the last push took a 1-D block: the blocks that leave are 1-D too
-
-    close = Stream.close
-    __del__ = Stream.__del__
-    _check = Stream._check
-    blocks_held = Stream.blocks_held
-    reset = Stream.reset
-    status = Stream.status
-
-    @property
-    def latency(self):
-        """D = ceil(horizon / block): push p emits block p - D."""
-        return self._L.itd_wave_stream_latency(self._h)
+        self._check_rows_horizon(rows, horizon)
+        self._create(block, rows, horizon, device)
 
     # ---- device buffers (raw pointers; asynchronous on `stream`) ----------------------------------------------------
     def push_dev(self, block_ptr, in_stride, bounds_ptr, bounds_stride, out_ptr, out_stride, stream=None):
         """Store one block of every row; True if a filtered block was written."""
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_wave_stream_push_f64(self._h, block_ptr, in_stride, bounds_ptr, bounds_stride, out_ptr, out_stride,
-                                                     ctypes.byref(em), stream))
-        return bool(em.value)
+        return self._dev("push", (block_ptr, in_stride, bounds_ptr, bounds_stride, out_ptr, out_stride), stream)
 
     def flush_dev(self, bounds_ptr, bounds_stride, out_ptr, out_stride, stream=None):
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_wave_stream_flush_f64(self._h, bounds_ptr, bounds_stride, out_ptr, out_stride, ctypes.byref(em), stream))
-        return bool(em.value)
+        return self._dev("flush", (bounds_ptr, bounds_stride, out_ptr, out_stride), stream)
 
     # ---- numpy in -> numpy out (one synchronisation per call) ----------------------------------------------------------
     def _bounds(self, bounds, amplitude, length):
@@ -388,57 +399,27 @@ class WaveFilterStream:
     def push(self, samples, bounds=None, amplitude=None, length=None):
         """samples [rows, block] (or [block] for one row).  None for the first `latency` pushes, then the filtered block pushed
         `latency` pushes ago, shaped like the input."""
-        x = numpy.ascontiguousarray(samples, dtype=numpy.float64)
-        flat = x.ndim == 1
-        x2 = x.reshape(1, -1) if flat else x
-        if x2.shape != (self.rows, self.block):
-            raise ValueError("expected blocks of shape (%d, %d)" % (self.rows, self.block))
+        block = self._block(samples, self.rows)
         b = self._bounds(bounds, amplitude, length)
-        out = numpy.empty_like(x2)
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_wave_stream_push_host_f64(self._h, _np_ptr(x2), _np_ptr(b), _np_ptr(out), ctypes.byref(em)))
-        self._flat = flat
-        if not em.value:
-            return None
-        return out[0] if flat else out
+        return self._host(block, (_np_ptr(b),))
 
     def flush(self, bounds=None, amplitude=None, length=None):
         """The next block still held (one per call), shaped like the blocks of the last push; None once the stream is empty."""
         b = self._bounds(bounds, amplitude, length)
-        out = numpy.empty((self.rows, self.block))
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_wave_stream_flush_host_f64(self._h, _np_ptr(b), _np_ptr(out), ctypes.byref(em)))
-        if not em.value:
-            return None
-        return out[0] if self._flat else out
+        return self._host(None, (_np_ptr(b),))
+
+    def _outputs(self):
+        return (numpy.empty((self.rows, self.block)),)
+
+    def _result(self, outs):
+        return outs[0][0] if self._flat else outs[0]
 
 
 def blockwise_wave_filter(rows, block, horizon, amplitude=(0.0, numpy.inf), length=(0.0, numpy.inf), device=0):
     """Run rows[R, n_blocks * block] (or [n]) through a WaveFilterStream: what a caller with an unbounded source does block by
     block.  Returns the filtered rows, shaped like the input: wave_filter(rows, amplitude, (length[0], min(length[1], horizon)))."""
-    x = numpy.asarray(rows, dtype=numpy.float64)
-    flat = x.ndim == 1
-    x2 = x.reshape(1, -1) if flat else x
-    if x2.ndim != 2:
-        raise ValueError("rows: [R, n] or [n]")
-    R, n = x2.shape
-    if n % block or n < block:
-        raise ValueError("the length must be a multiple of the block")
-    st = WaveFilterStream(block, R, horizon, device)
-    outs = []
-    try:
-        b = st._bounds(None, amplitude, length)
-        for k in range(n // block):
-            r = st.push(x2[:, k * block:(k + 1) * block], b)
-            if r is not None:
-                outs.append(r)
-        while True:
-            r = st.flush(b)
-            if r is None:
-                break
-            outs.append(r)
-    finally:
-        st.close()
+    x2, flat = _as_rows(rows, block, two_d=True)
+    outs = _push_then_drain(WaveFilterStream(block, x2.shape[0], horizon, device), x2, lambda st: (st._bounds(None, amplitude, length),))
     y = numpy.concatenate(outs, axis=1)
     return y[0] if flat else y
 
@@ -451,7 +432,7 @@ def _legal_hop(hop):
     return not isinstance(hop, bool) and int(hop) == hop and hop >= 64 and hop % 64 == 0 and (hop >= 512 or hop in (64, 128, 256))
 
 
-class SpectrumStream:
+class SpectrumStream(_RingStream):
     """The time-frequency-energy spectrum block by block at a fixed latency (itd_spectrum_stream_* in include/pyitd_hip.h): blocks
     of `rows` rows go in, finished time slices of their spectra come out — the cells pyitd_amd.tfe_spectrum gives for the
     concatenated rows, bit for bit, wherever no half wave is longer than `horizon` samples.  A sample whose half wave, or whose
@@ -482,6 +463,8 @@ class SpectrumStream:
                 ...                                     # power_d holds the cells of the block pushed levels + 1 + D steps ago
     """
 
+    _NAME = "spectrum"
+
     def __init__(self, block, rows=1, horizon=None, edges=None, hop=None, weight="energy", device=0):
         horizon = block if horizon is None else horizon
         if isinstance(block, bool) or int(block) != block or not 64 <= block <= 4096:
@@ -492,40 +475,17 @@ class SpectrumStream:
             hop = block
         if not _legal_hop(hop) or block % hop:
             raise ValueError("hop: a positive multiple of 64 (below 512: 64, 128 or 256) that divides the block, got %r" % (hop,))
-        if not 1 <= rows <= 65535:
-            raise ValueError("rows must be 1 .. 65535")
-        if not 1 <= horizon <= 2 ** 22:
-            raise ValueError("horizon must be 1 .. 2^22 samples")
+        self._check_rows_horizon(rows, horizon)
         if weight not in _WEIGHTS:
             raise ValueError("weight: one of %s, got %r" % (_WEIGHTS, weight))
         if edges is None:
             raise ValueError("edges: float64 [F + 1] or [rows, F + 1]")
-        self.block, self.rows, self.horizon, self.hop, self.weight, self.device = int(block), int(rows), int(horizon), int(hop), weight, int(device)
-        self.cells = self.block // self.hop
+        self.rows, self.hop, self.weight = int(rows), int(hop), weight
+        self.cells = int(block) // self.hop
         self.bins = None
         self._edges = self._check_edges(edges)
         self.bins = self._edges.shape[-1] - 1
-        self._L = _lib.load()
-        h = ctypes.c_void_p()
-        rc = self._L.itd_spectrum_stream_create(ctypes.byref(h), self.device, self.block, self.rows, self.horizon, self.hop, self.bins,
-                                                _WEIGHTS.index(weight))
-        if rc:
-            raise ITDError(rc, "itd_spectrum_stream_create(block=%d, rows=%d, horizon=%d, hop=%d, bins=%d)"
-                           % (block, rows, horizon, hop, self.bins))
-        self._h = h
-        self._flat = False          # the last push took a 1-D block: the slices that leave have no row axis either
-
-    close = Stream.close
-    __del__ = Stream.__del__
-    _check = Stream._check
-    blocks_held = Stream.blocks_held
-    reset = Stream.reset
-    status = Stream.status
-
-    @property
-    def latency(self):
-        """D = ceil((horizon + 1) / block): push p emits block p - D."""
-        return self._L.itd_spectrum_stream_latency(self._h)
+        self._create(block, rows, horizon, device, (self.hop, self.bins, _WEIGHTS.index(weight)), ", hop=%d, bins=%d" % (hop, self.bins))
 
     def _check_edges(self, edges):
         e = numpy.ascontiguousarray(edges, dtype=numpy.float64)
@@ -541,56 +501,36 @@ class SpectrumStream:
     def push_dev(self, block_ptr, in_stride, edges_ptr, edges_stride, power_ptr, power_stride, outside_ptr=None, overlong_ptr=None,
                  count_stride=0, stream=None):
         """Store one block of every row; True if a block's cells were written."""
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_spectrum_stream_push_f64(self._h, block_ptr, in_stride, edges_ptr, edges_stride, power_ptr, power_stride,
-                                                         outside_ptr, overlong_ptr, count_stride, ctypes.byref(em), stream))
-        return bool(em.value)
+        return self._dev("push", (block_ptr, in_stride, edges_ptr, edges_stride, power_ptr, power_stride, outside_ptr, overlong_ptr,
+                                  count_stride), stream)
 
     def flush_dev(self, edges_ptr, edges_stride, power_ptr, power_stride, outside_ptr=None, overlong_ptr=None, count_stride=0,
                   stream=None):
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_spectrum_stream_flush_f64(self._h, edges_ptr, edges_stride, power_ptr, power_stride, outside_ptr,
-                                                          overlong_ptr, count_stride, ctypes.byref(em), stream))
-        return bool(em.value)
+        return self._dev("flush", (edges_ptr, edges_stride, power_ptr, power_stride, outside_ptr, overlong_ptr, count_stride), stream)
 
     # ---- numpy in -> numpy out (one synchronisation per call) ----------------------------------------------------------
     def _outputs(self):
         return (numpy.empty((self.rows, self.cells, self.bins)), numpy.empty((self.rows, self.cells), numpy.int32),
                 numpy.empty((self.rows, self.cells), numpy.int32))
 
-    def _result(self, power, outside, overlong):
-        if self._flat:
-            return StreamSpectrum(power[0], outside[0], overlong[0])
-        return StreamSpectrum(power, outside, overlong)
+    def _result(self, outs):
+        return StreamSpectrum(*[o[0] for o in outs]) if self._flat else StreamSpectrum(*outs)
+
+    def _edge_params(self, edges):
+        if edges is not None:
+            self._edges = self._check_edges(edges)
+        e = self._edges
+        return _np_ptr(e), e.shape[-1] if e.ndim == 2 else 0
 
     def push(self, samples, edges=None):
         """samples [rows, block] (or [block] for one row).  None for the first `latency` pushes, then StreamSpectrum(power[rows, C,
         F], outside[rows, C], overlong[rows, C]) of the block pushed `latency` pushes ago (no row axis for 1-D input)."""
-        x = numpy.ascontiguousarray(samples, dtype=numpy.float64)
-        flat = x.ndim == 1
-        x2 = x.reshape(1, -1) if flat else x
-        if x2.shape != (self.rows, self.block):
-            raise ValueError("expected blocks of shape (%d, %d)" % (self.rows, self.block))
-        if edges is not None:
-            self._edges = self._check_edges(edges)
-        e = self._edges
-        power, outside, overlong = self._outputs()
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_spectrum_stream_push_host_f64(self._h, _np_ptr(x2), _np_ptr(e), e.shape[-1] if e.ndim == 2 else 0,
-                                                              _np_ptr(power), _np_ptr(outside), _np_ptr(overlong), ctypes.byref(em)))
-        self._flat = flat
-        return self._result(power, outside, overlong) if em.value else None
+        block = self._block(samples, self.rows)
+        return self._host(block, self._edge_params(edges))
 
     def flush(self, edges=None):
         """The next block still held (one per call); None once the stream is empty."""
-        if edges is not None:
-            self._edges = self._check_edges(edges)
-        e = self._edges
-        power, outside, overlong = self._outputs()
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_spectrum_stream_flush_host_f64(self._h, _np_ptr(e), e.shape[-1] if e.ndim == 2 else 0, _np_ptr(power),
-                                                               _np_ptr(outside), _np_ptr(overlong), ctypes.byref(em)))
-        return self._result(power, outside, overlong) if em.value else None
+        return self._host(None, self._edge_params(edges))
 
 
 StreamInstant = namedtuple("StreamInstant", "amplitude phase frequency length long overlong")
@@ -604,7 +544,7 @@ def _check_want(want):
     return want
 
 
-class InstantaneousStream:
+class InstantaneousStream(_RingStream):
     """The instantaneous amplitude, phase and frequency and every sample's half-wave length block by block at a fixed latency
     (itd_inst_stream_* in include/pyitd_hip.h): blocks of `rows` rows go in, the same blocks' per-sample quantities come out —
     wherever a value is delivered, bit for bit what pyitd_amd.instantaneous_batch (and single_waves, for the length) gives for the
@@ -635,58 +575,34 @@ class InstantaneousStream:
                                                         # frequency, phase and length is an elementwise operation on these
     """
 
+    _NAME = "inst"
+
     def __init__(self, block, rows=1, horizon=None, want=("amplitude", "phase", "frequency"), device=0):
         horizon = block if horizon is None else horizon
         if isinstance(block, bool) or int(block) != block or not 8 <= block <= 4096:
             raise ValueError("block must be 8 .. 4096 samples")
-        if not 1 <= rows <= 65535:
-            raise ValueError("rows must be 1 .. 65535")
-        if not 1 <= horizon <= 2 ** 22:
-            raise ValueError("horizon must be 1 .. 2^22 samples")
+        self._check_rows_horizon(rows, horizon)
         self.want = _check_want(want)
-        self._L = _lib.load()
-        h = ctypes.c_void_p()
-        rc = self._L.itd_inst_stream_create(ctypes.byref(h), int(device), int(block), int(rows), int(horizon))
-        if rc:
-            raise ITDError(rc, "itd_inst_stream_create(block=%d, rows=%d, horizon=%d)" % (block, rows, horizon))
-        self._h = h
-        self.block, self.rows, self.horizon, self.device = int(block), int(rows), int(horizon), int(device)
-        self._flat = False          # the last push took a 1-D block: the blocks that leave have no row axis either
-
-    close = Stream.close
-    __del__ = Stream.__del__
-    _check = Stream._check
-    blocks_held = Stream.blocks_held
-    reset = Stream.reset
-    status = Stream.status
-
-    @property
-    def latency(self):
-        """D = ceil((horizon + 1) / block): push p emits block p - D."""
-        return self._L.itd_inst_stream_latency(self._h)
+        self._create(block, rows, horizon, device)
 
     # ---- device buffers (raw pointers; asynchronous on `stream`) ----------------------------------------------------
     def push_dev(self, block_ptr, in_stride, amp_ptr, phase_ptr, freq_ptr, length_ptr, out_stride, counts_ptr=None, counts_stride=0,
                  stream=None):
         """Store one block of every row; True if a block's outputs were written (a None output is skipped)."""
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_inst_stream_push_f64(self._h, block_ptr, in_stride, amp_ptr, phase_ptr, freq_ptr, length_ptr, out_stride,
-                                                     counts_ptr, counts_stride, ctypes.byref(em), stream))
-        return bool(em.value)
+        return self._dev("push", (block_ptr, in_stride, amp_ptr, phase_ptr, freq_ptr, length_ptr, out_stride, counts_ptr, counts_stride),
+                         stream)
 
     def flush_dev(self, amp_ptr, phase_ptr, freq_ptr, length_ptr, out_stride, counts_ptr=None, counts_stride=0, stream=None):
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_inst_stream_flush_f64(self._h, amp_ptr, phase_ptr, freq_ptr, length_ptr, out_stride, counts_ptr,
-                                                      counts_stride, ctypes.byref(em), stream))
-        return bool(em.value)
+        return self._dev("flush", (amp_ptr, phase_ptr, freq_ptr, length_ptr, out_stride, counts_ptr, counts_stride), stream)
 
     # ---- numpy in -> numpy out (one synchronisation per call) ----------------------------------------------------------
     def _outputs(self):
         shape = (self.rows, self.block)
-        return ([numpy.empty(shape, numpy.int32 if w == "length" else numpy.float64) if w in self.want else None for w in _INSTANT],
-                numpy.empty((self.rows, 2), numpy.int32))
+        return [numpy.empty(shape, numpy.int32 if w == "length" else numpy.float64) if w in self.want else None for w in _INSTANT] + \
+            [numpy.empty((self.rows, 2), numpy.int32)]
 
-    def _result(self, outs, counts):
+    def _result(self, outs):
+        outs, counts = outs[:4], outs[4]
         if self._flat:
             return StreamInstant(*[None if o is None else o[0] for o in outs], counts[0, 0], counts[0, 1])
         return StreamInstant(*outs, counts[:, 0].copy(), counts[:, 1].copy())
@@ -694,52 +610,19 @@ class InstantaneousStream:
     def push(self, samples):
         """samples [rows, block] (or [block] for one row).  None for the first `latency` pushes, then the StreamInstant of the block
         pushed `latency` pushes ago (no row axis for 1-D input)."""
-        x = numpy.ascontiguousarray(samples, dtype=numpy.float64)
-        flat = x.ndim == 1
-        x2 = x.reshape(1, -1) if flat else x
-        if x2.shape != (self.rows, self.block):
-            raise ValueError("expected blocks of shape (%d, %d)" % (self.rows, self.block))
-        outs, counts = self._outputs()
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_inst_stream_push_host_f64(self._h, _np_ptr(x2), *[_np_ptr(o) for o in outs], _np_ptr(counts),
-                                                          ctypes.byref(em)))
-        self._flat = flat
-        return self._result(outs, counts) if em.value else None
+        return self._host(self._block(samples, self.rows))
 
     def flush(self):
         """The next block still held (one per call); None once the stream is empty."""
-        outs, counts = self._outputs()
-        em = ctypes.c_int32(0)
-        self._check(self._L.itd_inst_stream_flush_host_f64(self._h, *[_np_ptr(o) for o in outs], _np_ptr(counts), ctypes.byref(em)))
-        return self._result(outs, counts) if em.value else None
+        return self._host(None)
 
 
 def blockwise_instantaneous(rows, block, horizon, want=("amplitude", "phase", "frequency"), device=0):
     """Run rows[R, n_blocks * block] (or [n]) through an InstantaneousStream: what a caller with an unbounded source does block by
     block.  Returns StreamInstant: the wanted arrays shaped like the input (the others None), long and overlong as int32
     [R, n_blocks] ([n_blocks] for 1-D input)."""
-    x = numpy.asarray(rows, dtype=numpy.float64)
-    flat = x.ndim == 1
-    x2 = x.reshape(1, -1) if flat else x
-    if x2.ndim != 2:
-        raise ValueError("rows: [R, n] or [n]")
-    R, n = x2.shape
-    if n % block or n < block:
-        raise ValueError("the length must be a multiple of the block")
-    st = InstantaneousStream(block, R, horizon, want, device)
-    outs = []
-    try:
-        for k in range(n // block):
-            r = st.push(x2[:, k * block:(k + 1) * block])
-            if r is not None:
-                outs.append(r)
-        while True:
-            r = st.flush()
-            if r is None:
-                break
-            outs.append(r)
-    finally:
-        st.close()
+    x2, flat = _as_rows(rows, block, two_d=True)
+    outs = _push_then_drain(InstantaneousStream(block, x2.shape[0], horizon, want, device), x2)
     fields = [None if outs[0][i] is None else numpy.concatenate([o[i] for o in outs], axis=1) for i in range(4)]
     fields += [numpy.stack([o[i] for o in outs], axis=1) for i in (4, 5)]
     return StreamInstant(*[None if f is None else (f[0] if flat else f) for f in fields])

@@ -21,7 +21,7 @@ import pytest
 import inst_stream_ref as isr
 import spectrum_stream_ref as ssr
 from helpers import fuzz_signal
-from wave_stream_ref import run_length_signal
+from ring_stream_runs import enveloped_signals as signals, latency, push_and_flush
 
 pytestmark = pytest.mark.gpu
 SENT = -7.25e300
@@ -42,10 +42,6 @@ def S():
     return streaming
 
 
-def latency(L, H):
-    return -(-(H + 1) // L)
-
-
 def same(got, want, what, names=NAMES):
     assert len(got) == len(want) == len(names)
     for g, w, name in zip(got, want, names):
@@ -58,17 +54,6 @@ def same(got, want, what, names=NAMES):
         bad = np.flatnonzero(gb.ravel() != wb.ravel())
         assert bad.size == 0, "%s: %d of %d %s values differ, first at %d: %r vs %r" % (what, bad.size, g.size, name, bad[0], g.ravel()[bad[0]],
                                                                                      w.ravel()[bad[0]])
-
-
-def signals(rng, L, H, rows, blocks):
-    """x[rows, blocks L]: run-length signals under a smooth envelope (every other one with exact zeros), every third row noise"""
-    x = []
-    for r in range(rows):
-        if r % 3 == 2:
-            x.append(fuzz_signal(rng, 0, blocks * L))
-        else:
-            x.append(run_length_signal(rng, L, H, blocks, zeros=(r % 3 == 1)) * ssr.envelope(blocks * L, rng))
-    return np.stack(x)
 
 
 def expected(P, x, L, H):
@@ -85,17 +70,7 @@ def expected(P, x, L, H):
 def run_stream(st, x):
     """push every block, flush until empty: the six fields (per-sample ones [R, n], counts [R, blocks]; None where not wanted), the
     pushes' emission pattern, the flushes that emitted"""
-    L = st.block
-    outs, pattern, flushed = [], [], 0
-    for p in range(x.shape[1] // L):
-        r = st.push(x[:, p * L:(p + 1) * L])
-        pattern.append(r is not None)
-        if r is not None:
-            outs.append(r)
-    while (r := st.flush()) is not None:
-        flushed += 1
-        outs.append(r)
-    assert st.blocks_held == 0
+    outs, pattern, flushed = push_and_flush(st, x)
     got = [None if outs[0][i] is None else np.concatenate([o[i] for o in outs], axis=1) for i in range(4)]
     got += [np.stack([o[i] for o in outs], axis=1) for i in (4, 5)]
     return tuple(got), pattern, flushed

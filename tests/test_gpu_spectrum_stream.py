@@ -17,8 +17,8 @@ import pytest
 import spectrum_ref as sr
 import spectrum_stream_ref as ssr
 from helpers import fuzz_signal
+from ring_stream_runs import enveloped_signals as signals, latency, push_and_flush
 from waves_ref import ref_table
-from wave_stream_ref import run_length_signal
 
 pytestmark = pytest.mark.gpu
 SENT = -7.25e300
@@ -39,10 +39,6 @@ def S():
     return streaming
 
 
-def latency(L, H):
-    return -(-(H + 1) // L)
-
-
 def edges_of(kind, F):
     """uniform on [0.02, 0.6) or logarithmic on [1e-4, 0.5): the frequency 0.5 that a run of one-sample half waves gives — all that
     is left inside a horizon of 1 — lies inside the first and outside the second"""
@@ -59,17 +55,6 @@ def same(got, want, what):
                                                                                     w.ravel()[bad[0]])
 
 
-def signals(rng, L, H, rows, blocks):
-    """x[rows, blocks L]: run-length signals under a smooth envelope (every other one with exact zeros), every third row noise"""
-    x = []
-    for r in range(rows):
-        if r % 3 == 2:
-            x.append(fuzz_signal(rng, 0, blocks * L))
-        else:
-            x.append(run_length_signal(rng, L, H, blocks, zeros=(r % 3 == 1)) * ssr.envelope(blocks * L, rng))
-    return np.stack(x)
-
-
 def overlong_rows(x, H):
     return np.stack([ssr.overlong_of(np.repeat(ref_table(r)[1].astype(np.int64), ref_table(r)[1]), H) for r in x])
 
@@ -84,17 +69,7 @@ def expected(A, f, overlong, edges, hop, weight):
 def run_stream(st, x, edges=None):
     """push every block, flush until empty: (power[R, T, F], outside[R, T], overlong[R, T]), the pushes' emission pattern, the
     flushes that emitted"""
-    L = st.block
-    outs, pattern, flushed = [], [], 0
-    for p in range(x.shape[1] // L):
-        r = st.push(x[:, p * L:(p + 1) * L], edges)
-        pattern.append(r is not None)
-        if r is not None:
-            outs.append(r)
-    while (r := st.flush()) is not None:
-        flushed += 1
-        outs.append(r)
-    assert st.blocks_held == 0
+    outs, pattern, flushed = push_and_flush(st, x, (edges,))
     return tuple(np.concatenate([o[i] for o in outs], axis=1) for i in range(3)), pattern, flushed
 
 

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from helpers import assert_bits_equal, fuzz_signal
+from ring_stream_runs import latency as ring_latency, push_and_flush
 from waves_ref import ref_filter, ref_table
 from wave_stream_ref import run_length_signal
 
@@ -25,7 +26,7 @@ def S():
 
 
 def latency(L, H):
-    return -(-H // L)
+    return ring_latency(L, H, reach=0)
 
 
 def capped(bounds, H):
@@ -42,17 +43,7 @@ def reference(x, bounds, H):
 
 def run_stream(st, x, bounds):
     """push every block, flush until empty: (output, the pushes' emission pattern, the flushes that emitted)"""
-    L = st.block
-    outs, pattern, flushed = [], [], 0
-    for p in range(x.shape[1] // L):
-        r = st.push(x[:, p * L:(p + 1) * L], bounds)
-        pattern.append(r is not None)
-        if r is not None:
-            outs.append(r)
-    while (r := st.flush(bounds)) is not None:
-        flushed += 1
-        outs.append(r)
-    assert st.blocks_held == 0
+    outs, pattern, flushed = push_and_flush(st, x, (bounds,), (bounds,))
     return np.concatenate(outs, axis=1), pattern, flushed
 
 
