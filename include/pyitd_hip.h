@@ -989,6 +989,63 @@ int itd_inst_stream_push_host_f64(itd_stream *s, const double *block_host, doubl
 int itd_inst_stream_flush_host_f64(itd_stream *s, double *amp_host, double *phase_host, double *freq_host, int32_t *length_host,
                                    int32_t *counts_host, int32_t *emitted);
 
+/* ---- the histogram stream: the half waves' joint amplitude-length histogram block by block, at a fixed latency (DESIGN.md
+ *      section 25) -----------------------------------------------------------------------------------------------------------------
+ * itd_wave_hist_batch_* needs the whole row.  A histogram stream takes blocks of `rows` rows in lock step and gives finished time
+ * slices of their histograms a known number of blocks later: the distribution a live wave-filter stream's bounds follow.  With
+ * blocks of L samples, a horizon of H samples and hop | L (C = L / hop cells per block), row r after P pushes is x[0 .. P L).
+ * Crossing indices, half waves, length_k, A_k and peak_k (the smallest index with |x| == A_k) are itd_waves_batch_*'s on the indices
+ * of the whole stream; the last half wave ends at the flushed stream's last sample.  ae[0 .. na], le[0 .. nl]: the edges of
+ * itd_wave_hist_batch_*, with its comparisons.
+ *   length_k <= H   half wave k is counted exactly once, in absolute time bin peak_k / hop: where both its bins exist
+ *                   count[t][i][j] += 1 and samples[t][i][j] += length_k, otherwise outside[t] += 1.
+ *   length_k >  H   it is in none of the three; each of its samples j adds 1 to overlong[j / hop] — the price of the bounded latency.
+ *   emitted block b   the cells b C .. (b+1) C - 1: count[C][na][nl], samples[C][na][nl], outside[C], overlong[C], all int32.  Every
+ *                   cell is written, an empty one as 0; gaps beyond the dense extent of a row's slot are not written.  No overflow:
+ *                   samples <= hop + 2 (H - 1).  Where no half wave is longer than H the concatenated slices are
+ *                   itd_wave_hist_batch_f64(concatenated rows, ae, le, hop) integer for integer (that call wants hop to be a
+ *                   multiple of 512; the definition holds for every hop) and overlong is all 0.
+ * Latency D = ceil(H / L) blocks (itd_hist_stream_latency; -1 if s is not a histogram stream), the wave-filter stream's.  Block b is
+ * decided from the samples [b L - H, (b+1) L + H) that exist and from nothing else: a half wave that touches the block, with the
+ * maxima ML left of it, MB inside it and MR right of it, has its peak in the block iff its part of the block is non-empty, it begins
+ * in the block or ML < MB (the earlier index wins a tie), and MR <= MB.  Push p (counted from 0) emits block p - D when p >= D; every
+ * flush emits the next block still held, then emitted = 0 and the stream starts afresh.  A push between flushes is refused.
+ *   64 <= block <= 4096, hop a positive multiple of 64 that divides block, 1 <= rows <= 65535, 1 <= horizon <= 2^22,
+ *   1 <= na, nl <= 64, na nl <= 1024 and C na nl <= 8192 (the block's histogram is held in LDS).  Everything is allocated at create:
+ *   the rings (rows (2 D + 1) block 8 bytes), one 16-byte record per block in them, the host forms' staging and an engine of the
+ *   stream's own; ITD_ERR_NOMEM when it does not fit.  ITD_ERR_INVALID_ARG before any HIP call for a NULL handle, a NULL required
+ *   pointer or a value out of range.  A call that fails leaves the stream as it was.
+ *   block_dev: row r's block at block_dev + r in_stride (in_stride >= block when rows > 1).
+ *   aedges_dev, ledges_dev: row r's edges at + r aedges_stride / ledges_stride; a stride is 0 (one set for every row) or >= na + 1 /
+ *     >= nl + 1; device memory, read when the launch runs (strictly increasing, no NaN, +-inf allowed at the ends: the caller's duty);
+ *     a caller may move them between pushes; required whenever the call emits.
+ *   count_dev, samples_dev: row r's cells at + r hist_stride (one stride for the two, >= C na nl when rows > 1); required whenever
+ *     the call emits, written only then.
+ *   outside_dev, overlong_dev: optional; row r's counts at + r count_stride (>= C when rows > 1).
+ * Device forms: one launch per call on `stream`, no host synchronisation, no host read; *emitted follows from the block count alone.
+ * Host forms: contiguous [rows][block] in, [rows][C][na][nl] and [rows][C] out (outside_host and overlong_host optional), the edges
+ * with their strides as above; pinned staging, one synchronisation per call.  A NaN in any pushed block sets bit 2 of
+ * itd_stream_status until itd_stream_reset; that row is unspecified from then on, nothing outside the row's own slots is written.
+ * itd_stream_destroy / reset / blocks / status / last_error apply; every other stream kind's push and flush entries refuse a
+ * histogram stream, and these refuse theirs. */
+#define ITD_STREAM_HIST 6     /* a histogram stream (itd_hist_stream_create); not a kind itd_stream_create takes */
+int itd_hist_stream_create(itd_stream **out, int device_id, int64_t block, int32_t rows, int64_t horizon, int64_t hop, int32_t na,
+                           int32_t nl);
+int itd_hist_stream_latency(const itd_stream *s);
+int itd_hist_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_stride, const double *aedges_dev, int64_t aedges_stride,
+                             const double *ledges_dev, int64_t ledges_stride, int32_t *count_dev, int32_t *samples_dev,
+                             int64_t hist_stride, int32_t *outside_dev, int32_t *overlong_dev, int64_t count_stride, int32_t *emitted,
+                             void *stream);
+int itd_hist_stream_flush_f64(itd_stream *s, const double *aedges_dev, int64_t aedges_stride, const double *ledges_dev,
+                              int64_t ledges_stride, int32_t *count_dev, int32_t *samples_dev, int64_t hist_stride,
+                              int32_t *outside_dev, int32_t *overlong_dev, int64_t count_stride, int32_t *emitted, void *stream);
+int itd_hist_stream_push_host_f64(itd_stream *s, const double *block_host, const double *aedges_host, int64_t aedges_stride,
+                                  const double *ledges_host, int64_t ledges_stride, int32_t *count_host, int32_t *samples_host,
+                                  int32_t *outside_host, int32_t *overlong_host, int32_t *emitted);
+int itd_hist_stream_flush_host_f64(itd_stream *s, const double *aedges_host, int64_t aedges_stride, const double *ledges_host,
+                                   int64_t ledges_stride, int32_t *count_host, int32_t *samples_host, int32_t *outside_host,
+                                   int32_t *overlong_host, int32_t *emitted);
+
 /* ---- introspection for benchmarks -------------------------------------------------------------
  * hipEvent pairs on the launch stream.  Extraction launches are dispatched with their own start/stop events
  * (hipExtLaunchKernel: the events take the dispatch's own begin/end timestamps, so they agree with rocprofv3's kernel durations); the

@@ -11,6 +11,7 @@ from ._lib import ITDError, build
 from .batch import instantaneous_batch, single_waves, tfe_spectrum, wave_filter, wave_histogram, Spectrum, WaveHistogram, Waves
 from .engine import Engine
 from .streaming import InstantaneousStream, SpectrumStream, StreamInstant, StreamSpectrum, blockwise_instantaneous
+from .streaming import StreamHistogram, WaveHistogramStream, blockwise_wave_histogram
 from .itd import (ITD, baseline_knot_estimation, detect_knots, detect_peaks, find_extrema, generate_sine_wave, instantaneous, isin, itd,
                   itd_baseline_extract, itd_baseline_extract_cubic, itd_baseline_extract_fast, itd_baseline_extract_iq, itd_batch, itd_levels,
                   itd_sine_wrapper, matlab_detect_peaks, release_engines)
@@ -25,5 +26,6 @@ __all__ = ["itd_baseline_extract_modified", "itd_baseline_extract_spline", "itd_
            "matlab_detect_peaks", "detect_knots", "baseline_knot_estimation", "isin", "find_extrema", "generate_sine_wave",
            "itd_baseline_extract_fast", "itd_baseline_extract_cubic", "itd_baseline_extract_iq", "itd_sine_wrapper", "release_engines", "instantaneous", "instantaneous_batch", "single_waves", "wave_filter", "Waves", "tfe_spectrum", "Spectrum", "wave_histogram", "WaveHistogram", "SpectrumStream", "StreamSpectrum",
            "InstantaneousStream", "StreamInstant", "blockwise_instantaneous",
+           "WaveHistogramStream", "StreamHistogram", "blockwise_wave_histogram",
            "fourier_mode_decomposition_any", "fourier_mode_decomposition_valid", "itd_fourier_decomposition",
            "itd_fourier_decomposition_lean", "itd_fourier_decomposition_batch"]

@@ -130,6 +130,12 @@ ABI = {
     "itd_inst_stream_flush_f64": (_INT, [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P]),
     "itd_inst_stream_push_host_f64": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "itd_inst_stream_flush_host_f64": (_INT, [_P, _P, _P, _P, _P, _P, _P]),
+    "itd_hist_stream_create": (_INT, [ctypes.POINTER(_P), _INT, _I64, _I32, _I64, _I64, _I32, _I32]),
+    "itd_hist_stream_latency": (_INT, [_P]),
+    "itd_hist_stream_push_f64": (_INT, [_P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P, _P]),
+    "itd_hist_stream_flush_f64": (_INT, [_P, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P, _P]),
+    "itd_hist_stream_push_host_f64": (_INT, [_P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P]),
+    "itd_hist_stream_flush_host_f64": (_INT, [_P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P]),
     "itd_set_nan_input_mode": (_INT, [_P, _I32]),
     "itd_set_batch_chunk": (_INT, [_P, _I32]),
     "itd_set_batch_streams": (_INT, [_P, _I32]),

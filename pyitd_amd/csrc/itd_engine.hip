@@ -36,6 +36,7 @@
 #include "itd_wave_stream.hpp"
 #include "itd_spectrum_stream.hpp"
 #include "itd_inst_stream.hpp"
+#include "itd_hist_stream.hpp"
 #include "itd_spline.hpp"
 #include "itd_nak.hpp"
 #include "itd_wpe.hpp"

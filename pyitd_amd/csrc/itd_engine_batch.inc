@@ -287,7 +287,7 @@ struct itd_stream {
     Buf<uint8_t> d_exact; Pinned<uint8_t> h_exact;   // host form: [C]
     size_t lds = 0;
     const void *fn = nullptr;
-    // the ring streams (ITD_STREAM_WAVES, _SPECTRUM, _INSTANT; itd_ring_streams.inc): C rows, ring = [C][2 D + 1][L]; they use L, C,
+    // the ring streams (ITD_STREAM_WAVES, _SPECTRUM, _INSTANT, _HIST; itd_ring_streams.inc): C rows, ring = [C][2 D + 1][L]; they use L, C,
     // kind, ring, d_status, threads, lds, fn and the staging d_in / h_in, d_out / h_out above, and besides
     struct Ring {
         RingCount cnt = kRingCountFresh;                 // blocks pushed, in all, emitted (itd_ring_plan.hpp)
@@ -295,7 +295,8 @@ struct itd_stream {
         int32_t D = 0;                                   // the latency in blocks, ceil((H + the kind's reach) / L)
         Buf<WaveBlockRec> rec;                           // [C][2 D + 1]: what every block in the ring left behind when it arrived
         int32_t F = 0, weight = 0;                       // spectrum: bins; 0 count, 1 amplitude, 2 energy
-        int64_t hop = 0;                                 // spectrum
+        int64_t hop = 0;                                 // spectrum, histogram
+        int32_t Na = 0, Nl = 0;                          // histogram: bins per axis (F = the cells of a block, L / hop Na Nl)
         // host form, besides d_in / h_in = [C][L] and d_out / h_out: a kind's float64 parameters and int32 results; what each kind
         // keeps where is stated next to its host form (wave_staging, spectrum_staging, inst_staging)
         Buf<double> d_bnd; Pinned<double> h_bnd;
@@ -541,7 +542,7 @@ int itd_stream_reset(itd_stream *s)
 int64_t itd_stream_blocks(const itd_stream *s)
 {
     if (!s) return -1;
-    if (s->kind >= ITD_STREAM_WAVES) return ring_held(s->rs.cnt);         // (the ring streams: wave filter, spectrum, instantaneous)
+    if (s->kind >= ITD_STREAM_WAVES) return ring_held(s->rs.cnt);         // (the ring streams: wave filter, spectrum, instantaneous, histogram)
     if (s->kind != ITD_STREAM_LEVELS) return s->pushed;
     return (s->P < 0 ? s->t : s->P) - std::max<int64_t>(0, s->t - s->M - 1);   // pushed, less the blocks whose rows have left
 }

@@ -4,6 +4,7 @@
 //     the wave-filter stream    itd_wave_stream_*      k_wave_stream      itd_wave_stream.hpp      DESIGN.md section 21
 //     the spectrum stream       itd_spectrum_stream_*  k_spectrum_stream  itd_spectrum_stream.hpp  DESIGN.md section 22
 //     the instantaneous stream  itd_inst_stream_*      k_inst_stream      itd_inst_stream.hpp      DESIGN.md section 24
+//     the histogram stream      itd_hist_stream_*      k_hist_stream      itd_hist_stream.hpp      DESIGN.md section 25
 // Written once for all of them: the launch of a step (ring_step; its window arithmetic and the block counting: itd_ring_plan.hpp),
 // create, the device entries' guards and the host form (ring_create, ring_entry, ring_host).  A kind supplies
 //   * its kernel, whose argument struct begins with a RingStepArgs, and a function that fills the struct's own fields;
@@ -56,7 +57,7 @@ int ring_run(itd_stream *s, const RingKind &k, RingStepArgs *a, bool flush, cons
 
 // create: the checks, the engine, D, the geometry, the LDS grant, the ring, the records, the status and the host form's staging
 int ring_create(itd_stream **out, int device_id, int64_t block, int32_t rows, int64_t horizon, const RingKind &k, int64_t hop = 0,
-                int32_t bins = 0, int32_t weight = 0)
+                int32_t bins = 0, int32_t weight = 0, int32_t na = 0, int32_t nl = 0)
 {
     if (!out) return ITD_ERR_INVALID_ARG;
     *out = nullptr;
@@ -68,6 +69,7 @@ int ring_create(itd_stream **out, int device_id, int64_t block, int32_t rows, in
     if (rc) { delete s; return rc; }
     s->L = block; s->C = rows; s->kind = k.id; s->rs.H = horizon;
     s->rs.hop = hop; s->rs.F = bins; s->rs.weight = weight;
+    s->rs.Na = na; s->rs.Nl = nl;
     s->rs.D = (int32_t)((horizon + k.reach + block - 1) / block);
     const bool small = block <= 256 * kWaveStreamSpt;
     s->threads = small ? 256 : k.big_threads;
@@ -433,6 +435,123 @@ int itd_inst_stream_flush_host_f64(itd_stream *s, double *amp_host, double *phas
                                    int32_t *counts_host, int32_t *emitted)
 {
     return inst_host(s, nullptr, amp_host, phase_host, freq_host, length_host, counts_host, emitted, true);
+}
+
+}  // extern "C"
+
+// ---- the histogram stream (latency and locality are the wave filter's: reach 0) ------------------------------------------------------
+namespace {
+
+// (s: a histogram stream, or what the entries refuse)
+HistStreamArgs hist_args(const itd_stream *s, const double *aedges, int64_t aedges_stride, const double *ledges, int64_t ledges_stride,
+                         int32_t *count, int32_t *samples, int64_t hist_stride, int32_t *outside, int32_t *overlong, int64_t count_stride)
+{
+    HistStreamArgs a = {};
+    a.aedges = aedges; a.aedges_stride = aedges_stride;
+    a.ledges = ledges; a.ledges_stride = ledges_stride;
+    a.count = count; a.samples = samples; a.hist_stride = hist_stride;
+    a.outside = outside; a.overlong = overlong; a.count_stride = count_stride;
+    if (s) { a.Na = s->rs.Na; a.Nl = s->rs.Nl; a.spc = (int32_t)(s->rs.hop / 64); }
+    return a;
+}
+
+bool hist_io_ok(const itd_stream *s, bool emits, const RingStepArgs *r)
+{
+    const HistStreamArgs &a = *reinterpret_cast<const HistStreamArgs *>(r);
+    const int64_t cells = s->L / s->rs.hop;
+    if (a.aedges_stride != 0 && a.aedges_stride < s->rs.Na + 1) return false;
+    if (a.ledges_stride != 0 && a.ledges_stride < s->rs.Nl + 1) return false;
+    if (emits && (!a.aedges || !a.ledges || !a.count || !a.samples)) return false;
+    if (s->C == 1) return true;
+    if ((a.count || a.samples) && a.hist_stride < s->rs.F) return false;
+    return !(a.outside || a.overlong) || a.count_stride >= cells;
+}
+
+// host form: d_out / h_out = count, then samples: [2][C][F] int32 (F = the cells of a block: L / hop Na Nl); d_bnd / h_bnd = the
+// amplitude edges [C][Na + 1], then the length edges [C][Nl + 1] (one row each where all rows share a set); d_cnt / h_cnt = outside,
+// then overlong: [2][C][L / hop]
+RingStaging hist_staging(const itd_stream *s)
+{
+    const size_t C = (size_t)s->C, cells = (size_t)(s->L / s->rs.hop), F = (size_t)s->rs.F;
+    return {2 * C * F * sizeof(int32_t), C * (size_t)(s->rs.Na + s->rs.Nl + 2) * sizeof(double), 2 * C * cells * sizeof(int32_t)};
+}
+
+const RingKind kHistKind = {ITD_STREAM_HIST, 0, kHistStreamMinBlock, kHistStreamMaxBlock, 512,
+                            reinterpret_cast<const void *>(&k_hist_stream<256>), reinterpret_cast<const void *>(&k_hist_stream<512>),
+                            hist_stream_lds, kHistStreamMaxCells, hist_io_ok, hist_staging};
+
+int hist_host(itd_stream *s, const double *block_host, const double *aedges_host, int64_t aedges_stride, const double *ledges_host,
+              int64_t ledges_stride, int32_t *count_host, int32_t *samples_host, int32_t *outside_host, int32_t *overlong_host,
+              int32_t *emitted, bool flush)
+{
+    if (!s || s->kind != ITD_STREAM_HIST || !aedges_host || !ledges_host || !count_host || !samples_host) return ITD_ERR_INVALID_ARG;
+    if (aedges_stride != 0 && aedges_stride < s->rs.Na + 1) return ITD_ERR_INVALID_ARG;
+    if (ledges_stride != 0 && ledges_stride < s->rs.Nl + 1) return ITD_ERR_INVALID_ARG;
+    const size_t C = (size_t)s->C, cells = (size_t)(s->L / s->rs.hop), F = (size_t)s->rs.F, ccnt = C * cells;
+    const size_t A1 = (size_t)s->rs.Na + 1, L1 = (size_t)s->rs.Nl + 1;
+    int32_t *const d_hist = reinterpret_cast<int32_t *>(s->d_out.get()), *const h_hist = reinterpret_cast<int32_t *>(s->h_out.get());
+    int32_t *const d_cnt = s->rs.d_cnt, *const h_cnt = s->rs.h_cnt;
+    double *const d_ae = s->rs.d_bnd, *const h_ae = s->rs.h_bnd;
+    double *const d_le = d_ae + C * A1, *const h_le = h_ae + C * A1;
+    HistStreamArgs a = hist_args(s, d_ae, aedges_stride ? (int64_t)A1 : 0, d_le, ledges_stride ? (int64_t)L1 : 0, d_hist, d_hist + C * F,
+                                 (int64_t)F, d_cnt, d_cnt + ccnt, (int64_t)cells);
+    return ring_host(s, kHistKind, &a.r, flush, block_host,
+                     {{aedges_host, h_ae, d_ae, aedges_stride ? C : 1, A1 * sizeof(double), (size_t)aedges_stride * sizeof(double)},
+                      {ledges_host, h_le, d_le, ledges_stride ? C : 1, L1 * sizeof(double), (size_t)ledges_stride * sizeof(double)}},
+                     {{count_host, h_hist, d_hist, C * F * sizeof(int32_t)},
+                      {samples_host, h_hist + C * F, d_hist + C * F, C * F * sizeof(int32_t)},
+                      {outside_host, h_cnt, d_cnt, ccnt * sizeof(int32_t)},
+                      {overlong_host, h_cnt + ccnt, d_cnt + ccnt, ccnt * sizeof(int32_t)}},
+                     emitted);
+}
+
+}  // namespace
+
+extern "C" {
+
+int itd_hist_stream_create(itd_stream **out, int device_id, int64_t block, int32_t rows, int64_t horizon, int64_t hop, int32_t na, int32_t nl)
+{
+    if (!out) return ITD_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (hop < 64 || hop % 64 != 0 || block < hop || block % hop != 0) return ITD_ERR_INVALID_ARG;
+    if (na < 1 || na > kWaveHistMaxBins || nl < 1 || nl > kWaveHistMaxBins || na * nl > kWaveHistMaxCells) return ITD_ERR_INVALID_ARG;
+    if (block > kHistStreamMaxBlock || (block / hop) * na * nl > kHistStreamMaxCells) return ITD_ERR_INVALID_ARG;
+    return ring_create(out, device_id, block, rows, horizon, kHistKind, hop, (int32_t)(block / hop) * na * nl, 0, na, nl);
+}
+
+int itd_hist_stream_latency(const itd_stream *s) { return ring_latency(s, kHistKind); }
+
+int itd_hist_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_stride, const double *aedges_dev, int64_t aedges_stride,
+                             const double *ledges_dev, int64_t ledges_stride, int32_t *count_dev, int32_t *samples_dev, int64_t hist_stride,
+                             int32_t *outside_dev, int32_t *overlong_dev, int64_t count_stride, int32_t *emitted, void *stream)
+{
+    HistStreamArgs a = hist_args(s, aedges_dev, aedges_stride, ledges_dev, ledges_stride, count_dev, samples_dev, hist_stride, outside_dev,
+                                 overlong_dev, count_stride);
+    return ring_entry(s, kHistKind, &a.r, false, block_dev, in_stride, emitted, stream);
+}
+
+int itd_hist_stream_flush_f64(itd_stream *s, const double *aedges_dev, int64_t aedges_stride, const double *ledges_dev, int64_t ledges_stride,
+                              int32_t *count_dev, int32_t *samples_dev, int64_t hist_stride, int32_t *outside_dev, int32_t *overlong_dev,
+                              int64_t count_stride, int32_t *emitted, void *stream)
+{
+    HistStreamArgs a = hist_args(s, aedges_dev, aedges_stride, ledges_dev, ledges_stride, count_dev, samples_dev, hist_stride, outside_dev,
+                                 overlong_dev, count_stride);
+    return ring_entry(s, kHistKind, &a.r, true, nullptr, 0, emitted, stream);
+}
+
+int itd_hist_stream_push_host_f64(itd_stream *s, const double *block_host, const double *aedges_host, int64_t aedges_stride,
+                                  const double *ledges_host, int64_t ledges_stride, int32_t *count_host, int32_t *samples_host,
+                                  int32_t *outside_host, int32_t *overlong_host, int32_t *emitted)
+{
+    return hist_host(s, block_host, aedges_host, aedges_stride, ledges_host, ledges_stride, count_host, samples_host, outside_host,
+                     overlong_host, emitted, false);
+}
+int itd_hist_stream_flush_host_f64(itd_stream *s, const double *aedges_host, int64_t aedges_stride, const double *ledges_host,
+                                   int64_t ledges_stride, int32_t *count_host, int32_t *samples_host, int32_t *outside_host,
+                                   int32_t *overlong_host, int32_t *emitted)
+{
+    return hist_host(s, nullptr, aedges_host, aedges_stride, ledges_host, ledges_stride, count_host, samples_host, outside_host, overlong_host,
+                     emitted, true);
 }
 
 }  // extern "C"

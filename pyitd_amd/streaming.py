@@ -29,7 +29,8 @@ LevelsStream: the full multi-level decomposition block by block.  WaveFilterStre
 entirely on the device.  SpectrumStream: the time-frequency-energy spectrum (pyitd_amd.tfe_spectrum) block by
 block at a fixed latency — finished time slices of a live decomposition's spectrum.  InstantaneousStream: the
 per-sample amplitude, phase, frequency and half-wave length themselves (pyitd_amd.instantaneous_batch) block by block at the same
-latency.
+latency.  WaveHistogramStream: the half waves' joint amplitude-length histogram (pyitd_amd.wave_histogram)
+block by block at the wave filter's latency — the distribution a live filter's bounds follow.
 """
 import ctypes
 from collections import namedtuple
@@ -292,7 +293,7 @@ def blockwise_itd(x, block, levels, device=0):
 
 
 class _RingStream(_Handle):
-    """What the three fixed-latency streams share (itd_<_NAME>_stream_* in include/pyitd_hip.h): `rows` rows in lock step, blocks of
+    """What the four fixed-latency streams share (itd_<_NAME>_stream_* in include/pyitd_hip.h): `rows` rows in lock step, blocks of
     `block` samples, a horizon, D = latency blocks between a push and its block's results.  A kind gives its name, its validation of
     the block, the arguments of its device entries, and for the numpy form _outputs() (the arrays a call fills, None where one is not
     wanted) and _result(outs)."""
@@ -315,8 +316,8 @@ class _RingStream(_Handle):
 
     @property
     def latency(self):
-        """D: push p emits block p - D.  D = ceil(horizon / block) for the wave filter, ceil((horizon + 1) / block) for the spectrum
-        and the instantaneous stream."""
+        """D: push p emits block p - D.  D = ceil(horizon / block) for the wave filter and the histogram, ceil((horizon + 1) / block)
+        for the spectrum and the instantaneous stream."""
         return getattr(self._L, "itd_%s_stream_latency" % self._NAME)(self._h)
 
     # ---- device buffers (raw pointers; asynchronous on `stream`): the kinds' push_dev / flush_dev name their arguments ----------
@@ -626,3 +627,122 @@ def blockwise_instantaneous(rows, block, horizon, want=("amplitude", "phase", "f
     fields = [None if outs[0][i] is None else numpy.concatenate([o[i] for o in outs], axis=1) for i in range(4)]
     fields += [numpy.stack([o[i] for o in outs], axis=1) for i in (4, 5)]
     return StreamInstant(*[None if f is None else (f[0] if flat else f) for f in fields])
+
+
+StreamHistogram = namedtuple("StreamHistogram", "count samples outside overlong")
+MAX_STREAM_HIST_CELLS = 8192          # cells per block: (block / hop) * amplitude bins * length bins
+
+
+class WaveHistogramStream(_RingStream):
+    """The half waves' joint amplitude-length histogram block by block at a fixed latency (itd_hist_stream_* in include/pyitd_hip.h):
+    blocks of `rows` rows go in, finished time slices of their histograms come out — the distribution a live WaveFilterStream's bounds
+    follow.  A half wave of at most `horizon` samples is counted exactly once, in the time bin of its peak: wherever no half wave is
+    longer than that, the slices are pyitd_amd.wave_histogram of the concatenated rows integer for integer.  A longer one is in no
+    cell and not in `outside`; each of its samples adds 1 to `overlong` of its time bin — the price of the bounded latency.  ONE
+    launch per push on the GPU.
+
+        st = WaveHistogramStream(1024, rows=9, horizon=2048, amplitude_edges=ae, length_edges=le, hop=512)
+        st.latency                                      # D = ceil(horizon / block) = 2
+        for block in blocks:                            # block: [rows, 1024]
+            out = st.push(block)                        # None for the first D pushes, then block p - D's StreamHistogram:
+            ...                                         # out.count, out.samples [rows, 2, Na, Nl]; out.outside, out.overlong [rows, 2]
+        while (out := st.flush()) is not None: ...
+
+    block: a multiple of hop, 64 .. 4096; hop: a positive multiple of 64 that divides the block, by default the block.  Each edge
+    argument as wave_histogram checks it: float64 [N + 1] (one set for every row) or [rows, N + 1], strictly increasing, no NaN,
+    -inf / +inf allowed at the ends, 1 <= N <= 64, at most 1024 cells, and at most 8192 cells per block ((block / hop) Na Nl);
+    push(samples, amplitude_edges=, length_edges=) replaces them from that push on.  All four outputs are int32.  A NaN in a pushed
+    block sets status() bit 2 until reset(); that row is unspecified from then on.
+
+    Behind a LevelsStream on device pointers, everything on one stream `s`:
+
+        lv = LevelsStream(1024, levels=3, channels=2)
+        hs = WaveHistogramStream(1024, rows=2 * 4, horizon=2048, amplitude_edges=ae, length_edges=le, hop=512)
+        # rows_d [2, 4, 1024] float64, ae_d [Na + 1], le_d [Nl + 1] float64, count_d / samples_d [8, 2, Na, Nl], out_d / ovl_d [8, 2] int32
+        if lv.push_dev(block_ptr, 1024, rows_ptr, 1024, 4 * 1024, None, s):
+            if hs.push_dev(rows_ptr, 1024, ae_ptr, 0, le_ptr, 0, count_ptr, samples_ptr, 2 * Na * Nl, out_ptr, ovl_ptr, 2, s):
+                ...                                     # the cells of the block pushed levels + 1 + D steps ago
+    """
+
+    _NAME = "hist"
+
+    def __init__(self, block, rows=1, horizon=None, amplitude_edges=None, length_edges=None, hop=None, device=0):
+        horizon = block if horizon is None else horizon
+        if isinstance(block, bool) or int(block) != block or not 64 <= block <= 4096:
+            raise ValueError("block must be 64 .. 4096 samples")
+        hop = block if hop is None else hop
+        if isinstance(hop, bool) or int(hop) != hop or hop < 64 or hop % 64 or block % hop:
+            raise ValueError("hop: a positive multiple of 64 that divides the block, got %r" % (hop,))
+        self._check_rows_horizon(rows, horizon)
+        if amplitude_edges is None or length_edges is None:
+            raise ValueError("amplitude_edges and length_edges: float64 [N + 1] or [rows, N + 1]")
+        self.rows, self.hop = int(rows), int(hop)
+        self.cells = int(block) // self.hop
+        self.abins = self.lbins = None
+        self._ae, self._le = self._check_edges(amplitude_edges, "amplitude_edges"), self._check_edges(length_edges, "length_edges")
+        self.abins, self.lbins = self._ae.shape[-1] - 1, self._le.shape[-1] - 1
+        from .batch import MAX_WAVE_CELLS
+        if self.abins * self.lbins > MAX_WAVE_CELLS:
+            raise ValueError("%d x %d bins are more than %d cells" % (self.abins, self.lbins, MAX_WAVE_CELLS))
+        if self.cells * self.abins * self.lbins > MAX_STREAM_HIST_CELLS:
+            raise ValueError("%d time bins of %d x %d bins are more than %d cells per block" %
+                             (self.cells, self.abins, self.lbins, MAX_STREAM_HIST_CELLS))
+        self._create(block, rows, horizon, device, (self.hop, self.abins, self.lbins),
+                     ", hop=%d, bins=%d x %d" % (hop, self.abins, self.lbins))
+
+    def _check_edges(self, edges, name):
+        from .batch import _hist_edges
+        e = _hist_edges(edges, name, (self.rows,))
+        bins = self.abins if name == "amplitude_edges" else self.lbins
+        if bins is not None and e.shape[-1] != bins + 1:
+            raise ValueError("%s: the stream has %d bins, got %d edges" % (name, bins, e.shape[-1]))
+        return e
+
+    # ---- device buffers (raw pointers; asynchronous on `stream`) ----------------------------------------------------
+    def push_dev(self, block_ptr, in_stride, aedges_ptr, aedges_stride, ledges_ptr, ledges_stride, count_ptr, samples_ptr, hist_stride,
+                 outside_ptr=None, overlong_ptr=None, count_stride=0, stream=None):
+        """Store one block of every row; True if a block's cells were written."""
+        return self._dev("push", (block_ptr, in_stride, aedges_ptr, aedges_stride, ledges_ptr, ledges_stride, count_ptr, samples_ptr,
+                                  hist_stride, outside_ptr, overlong_ptr, count_stride), stream)
+
+    def flush_dev(self, aedges_ptr, aedges_stride, ledges_ptr, ledges_stride, count_ptr, samples_ptr, hist_stride, outside_ptr=None,
+                  overlong_ptr=None, count_stride=0, stream=None):
+        return self._dev("flush", (aedges_ptr, aedges_stride, ledges_ptr, ledges_stride, count_ptr, samples_ptr, hist_stride, outside_ptr,
+                                   overlong_ptr, count_stride), stream)
+
+    # ---- numpy in -> numpy out (one synchronisation per call) ----------------------------------------------------------
+    def _outputs(self):
+        hist, cnt = (self.rows, self.cells, self.abins, self.lbins), (self.rows, self.cells)
+        return tuple(numpy.empty(shape, numpy.int32) for shape in (hist, hist, cnt, cnt))
+
+    def _result(self, outs):
+        return StreamHistogram(*[o[0] for o in outs]) if self._flat else StreamHistogram(*outs)
+
+    def _edge_params(self, amplitude_edges, length_edges):
+        if amplitude_edges is not None:
+            self._ae = self._check_edges(amplitude_edges, "amplitude_edges")
+        if length_edges is not None:
+            self._le = self._check_edges(length_edges, "length_edges")
+        ae, le = self._ae, self._le
+        return _np_ptr(ae), ae.shape[-1] if ae.ndim == 2 else 0, _np_ptr(le), le.shape[-1] if le.ndim == 2 else 0
+
+    def push(self, samples, amplitude_edges=None, length_edges=None):
+        """samples [rows, block] (or [block] for one row).  None for the first `latency` pushes, then StreamHistogram(count[rows, C, Na,
+        Nl], samples[rows, C, Na, Nl], outside[rows, C], overlong[rows, C]) of the block pushed `latency` pushes ago (no row axis for
+        1-D input)."""
+        block = self._block(samples, self.rows)
+        return self._host(block, self._edge_params(amplitude_edges, length_edges))
+
+    def flush(self, amplitude_edges=None, length_edges=None):
+        """The next block still held (one per call); None once the stream is empty."""
+        return self._host(None, self._edge_params(amplitude_edges, length_edges))
+
+
+def blockwise_wave_histogram(rows, block, horizon, amplitude_edges, length_edges, hop=None, device=0):
+    """Run rows[R, n_blocks * block] (or [n]) through a WaveHistogramStream: what a caller with an unbounded source does block by
+    block.  Returns StreamHistogram with the blocks' slices concatenated along the time axis: count, samples [R, T, Na, Nl], outside,
+    overlong [R, T] with T = n / hop (no row axis for 1-D input)."""
+    x2, flat = _as_rows(rows, block, two_d=True)
+    outs = _push_then_drain(WaveHistogramStream(block, x2.shape[0], horizon, amplitude_edges, length_edges, hop, device), x2)
+    fields = [numpy.concatenate([o[i] for o in outs], axis=1) for i in range(4)]
+    return StreamHistogram(*[f[0] if flat else f for f in fields])
