@@ -821,7 +821,9 @@ int itd_stream_status(itd_stream *s, int32_t *status);
  * step (one workgroup per channel holds the window in LDS); longer blocks take a launch sequence (per stage: the batched tier-1
  * extraction of every channel's window, then one routing / certificate kernel), bit-identical to the one-launch form.
  * itd_levels_stream_set_sequence(s, 1) forces the sequence form on a short block (0: back to one launch; refused for a long
- * block); itd_levels_stream_form returns the form in use (0 one launch, 1 sequence, -1 not a levels stream).  Everything is
+ * block); itd_levels_stream_form returns the form in use (0 one launch, 1 sequence, -1 not a levels stream).  The form may be
+ * switched between any two steps of a stream that holds blocks (both forms keep the same rings, delay line and flag bytes; the
+ * results are those of either form alone).  Everything is
  * allocated at create (or, for a forced sequence form, by the setter; ITD_ERR_NOMEM when it does not fit): M+1 rings of 5
  * blocks and M (M+1) / 2 delayed blocks per channel, plus, for the sequence form, the windows' results (6 blocks per channel).  itd_stream_destroy / reset / status / blocks / last_error apply; the
  * single-level push / flush entries refuse a levels stream.

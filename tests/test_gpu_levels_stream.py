@@ -2,11 +2,13 @@
   * the composition of oracle_blockwise_linear, M+1 times, each on the previous baseline — bit for bit, every emitted block;
   * the numpy statement of the exactness rule in tests/test_levels_stream_cpu.py — the flags exactly;
   * the whole-signal oracle (oracle/cpu_oracle.itd(x, M-1)) on every certified block — bit for bit;
-  * hand-chained single-level linear streams where a window holds a NaN."""
+  * hand-chained single-level linear streams where a window holds a NaN, and beside them the plain-rules reference
+    tests/levels_plain_ref.plain_composition (rows, flags and status, both forms)."""
 import numpy as np
 import pytest
 
 from helpers import assert_bits_equal, fuzz_signal
+from levels_plain_ref import plain_composition
 from test_levels_stream_cpu import levels_composition, rich_signal, whole_rows
 
 pytestmark = pytest.mark.gpu
@@ -124,6 +126,19 @@ def test_deep_levels_in_short_blocks_are_not_certified_where_they_differ(S):
     assert differs and not exact[differs].any()
 
 
+def hold_to_plain_composition(S, x, L, M, rows, exact, what):
+    """rows / exact (one channel, as blockwise_itd gave them) and both forms' rows, flags and status against the plain-rules reference"""
+    ref_rows, ref_exact, ref_status = plain_composition(x, L, M)
+    assert_bits_equal(rows, ref_rows[0], what + " rows, plain rules")
+    np.testing.assert_array_equal(exact, ref_exact[0], what + " flags, plain rules")
+    for sequence in (False, True):
+        got = run_stream(S, x[None], L, M, sequence)
+        assert_bits_equal(got[0], ref_rows, what + " rows, plain rules, sequence=%s" % sequence)
+        np.testing.assert_array_equal(got[1], ref_exact, what + " flags, plain rules, sequence=%s" % sequence)
+        assert got[4] == ref_status, what + " status, sequence=%s" % sequence
+    return ref_status
+
+
 def test_plateaus_across_block_edges(S):
     """A plateau under a window's start makes that window's first segment 0/0 (ITD.py:115-116): the stream's baseline holds a
     NaN the whole signal does not, and the later stages follow the single-level stream's plain rules there."""
@@ -141,6 +156,7 @@ def test_plateaus_across_block_edges(S):
     for j in np.nonzero(exact)[0]:
         assert_bits_equal(rows[:, j * L:(j + 1) * L], whole[:, j * L:(j + 1) * L], "plateau block %d" % j)
     assert not exact[1:4].any()                                # windows whose first segment lies on the long plateau
+    assert hold_to_plain_composition(S, x, L, M, rows, exact, "plateau") == 2      # (0/0: a NaN in stage 1's input)
 
 
 def hand_chain(L, M, x):
@@ -185,6 +201,7 @@ def test_nan_block_sets_status_and_follows_the_hand_chain(S):
     exact = np.array([bool(o[1]) for o in outs])
     assert not exact[2:5].any()                # every window that holds the NaN at stage 0
     assert_bits_equal(rows, hand_chain(L, M, x), "NaN rows")
+    assert hold_to_plain_composition(S, x, L, M, rows, exact, "NaN") == 2
 
 
 def test_leading_silence(S):
@@ -194,6 +211,7 @@ def test_leading_silence(S):
     rows, exact = S.blockwise_itd(x, L, M)
     assert not exact[:2].any()
     assert_bits_equal(rows, hand_chain(L, M, x), "leading silence")
+    assert hold_to_plain_composition(S, x, L, M, rows, exact, "leading silence") == 2
 
 
 def test_device_form_equals_host_form_and_reuse(S):

@@ -1,5 +1,5 @@
-"""The contract the three ring streams share (pyitd_amd.streaming.WaveFilterStream, SpectrumStream, InstantaneousStream over one
-host-side body, pyitd_amd/csrc/itd_ring_streams.inc), on the smallest shapes that exercise it: the latency D = ceil((H + reach) / L),
+"""The contract the four ring streams share (pyitd_amd.streaming.WaveFilterStream, SpectrumStream, InstantaneousStream,
+WaveHistogramStream over one host-side body, pyitd_amd/csrc/itd_ring_streams.inc), on the smallest shapes that exercise it: the latency D = ceil((H + reach) / L),
 the emission pattern of push, blocks_held after every call, min(pushed, D) emitting flushes, the refusal of a push between two flush
 steps, and the restart after a drain.  What each kind computes is held to its reference in its own file."""
 import numpy as np
@@ -12,8 +12,9 @@ pytestmark = pytest.mark.gpu
 ROWS = 2
 INVALID_ARG = 1                                                           # ITD_ERR_INVALID_ARG (include/pyitd_hip.h)
 # kind: (the block L, the reach)
-KINDS = {"wave": (8, 0), "spectrum": (64, 1), "inst": (8, 1)}
+KINDS = {"wave": (8, 0), "spectrum": (64, 1), "inst": (8, 1), "hist": (64, 0)}
 EDGES = np.linspace(0.0, 0.6, 6)
+LENGTH_EDGES = np.array([1.0, 3.0, 9.0, 27.0, np.inf])                    # (the histogram stream's second axis)
 
 
 def make(S, kind, H):
@@ -22,6 +23,8 @@ def make(S, kind, H):
         return S.WaveFilterStream(L, ROWS, H)
     if kind == "spectrum":
         return S.SpectrumStream(L, ROWS, H, edges=EDGES)
+    if kind == "hist":
+        return S.WaveHistogramStream(L, ROWS, H, amplitude_edges=EDGES, length_edges=LENGTH_EDGES)
     return S.InstantaneousStream(L, ROWS, H, want=("amplitude", "phase", "frequency", "length"))
 
 
@@ -92,6 +95,9 @@ def test_latency_emission_flush_refusal_and_restart(kind, hk):
     buf = torch.zeros(ROWS, L, dtype=torch.float64, device="cuda")
     out = torch.zeros(ROWS, L * 8, dtype=torch.float64, device="cuda")
     edges = torch.from_numpy(EDGES).cuda()
+    ledges = torch.from_numpy(LENGTH_EDGES).cuda()
+    cells = (len(EDGES) - 1) * (len(LENGTH_EDGES) - 1)
+    hist = torch.zeros(2, ROWS, cells, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     refused = []
 
@@ -102,6 +108,8 @@ def test_latency_emission_flush_refusal_and_restart(kind, hk):
                 st.push_dev(buf.data_ptr(), L, out.data_ptr(), 0, out.data_ptr(), L)
             elif kind == "spectrum":
                 st.push_dev(buf.data_ptr(), L, edges.data_ptr(), 0, out.data_ptr(), L * 8)
+            elif kind == "hist":
+                st.push_dev(buf.data_ptr(), L, edges.data_ptr(), 0, ledges.data_ptr(), 0, hist[0].data_ptr(), hist[1].data_ptr(), cells)
             else:
                 st.push_dev(buf.data_ptr(), L, out.data_ptr(), None, None, None, L)
         assert err.value.status == INVALID_ARG
