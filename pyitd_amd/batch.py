@@ -5,17 +5,18 @@ single-wave analysis: the table of half waves, the feature filter and the half w
 (itd_waves_batch_*, itd_wave_filter_batch_*, itd_wave_hist_batch_*).
 
 The reference applies its operators row by row under numba.prange (siftED2D.ipynb cell 1) and re-uses retained extrema along
-channels (itd.cpp:40-44); here a whole batch is one launch sequence and no knot count crosses PCIe in between.  Device
-memory comes from the C ABI's own allocator (engine.DeviceBuffer): no torch needed.
+channels (itd.cpp:40-44); here a whole batch is one launch sequence and no knot count crosses PCIe in between.  Every call is
+written once against a placement (_place.py): numpy rows are staged through the C ABI's own allocator (no torch needed), a torch
+CUDA tensor is used where it lies.
 """
-import contextlib
 from collections import namedtuple
 
 import numpy
 
 from ._lib import ITDError
-from .engine import DETECT_KNOTS, ITD_ERR_NONFINITE, DeviceBuffer
-from .itd import _engine_for, _is_torch, _np_dtype
+from ._place import Numpy, _is_torch, _np_dtype, rows_of
+from .engine import DETECT_KNOTS, ITD_ERR_NONFINITE
+from .itd import _engine_for
 
 
 def _rows(x):
@@ -31,16 +32,10 @@ def itd_baseline_extract_batch(x, device=0, want_counts=False):
     x = _rows(x)
     B, n = x.shape
     eng = _engine_for(n, device)
-    d_x, d_rot, d_base, d_info = (DeviceBuffer(x.nbytes, device), DeviceBuffer(x.nbytes, device), DeviceBuffer(x.nbytes, device),
-                                  DeviceBuffer(4 * B, device))
-    try:
-        d_x.upload(x)
-        eng.extract_batch_dev(d_x.ptr, n, B, n, d_rot.ptr, n, d_base.ptr, n, d_info.ptr)
-        info = d_info.download(numpy.empty(B, numpy.int32))      # itd_dev_copy synchronises
-        rot, base = d_rot.download(numpy.empty_like(x)), d_base.download(numpy.empty_like(x))
-    finally:
-        for b in (d_x, d_rot, d_base, d_info):
-            b.free()
+    with Numpy(device, x) as S:
+        d_rot, d_base, d_info = S.empty(x.shape, x.dtype), S.empty(x.shape, x.dtype), S.empty(B, numpy.int32)
+        S.run(eng.extract_batch_dev, S.x, n, B, n, S.ptr(d_rot), n, S.ptr(d_base), n, S.ptr(d_info))
+        info, rot, base = S.host(d_info), S.host(d_rot), S.host(d_base)
     counts = numpy.where(info < 0, -1 - info, info).astype(numpy.int64)
     for b in numpy.flatnonzero(info < 0):
         r, bs, kn, _ = eng.baseline_extract_host(x[b], want_knots=True)
@@ -54,14 +49,10 @@ def count_knots_batch(x, mode=DETECT_KNOTS, device=0):
     x = _rows(x)
     B, n = x.shape
     eng = _engine_for(n, device)
-    d_x, d_info = DeviceBuffer(x.nbytes, device), DeviceBuffer(4 * B, device)
-    try:
-        d_x.upload(x)
-        eng.detect_batch_dev(d_x.ptr, n, B, n, mode, None, 0, d_info.ptr)
-        info = d_info.download(numpy.empty(B, numpy.int32))
-    finally:
-        d_x.free()
-        d_info.free()
+    with Numpy(device, x) as S:
+        d_info = S.empty(B, numpy.int32)
+        S.run(eng.detect_batch_dev, S.x, n, B, n, mode, None, 0, S.ptr(d_info))
+        info = S.host(d_info)
     out = info.astype(numpy.int64)
     for b in numpy.flatnonzero(info < 0):
         out[b] = len(eng.detect_host(x[b], mode)) if mode <= 2 else -1 - info[b]
@@ -74,15 +65,10 @@ def detect_knots_batch(x, mode=DETECT_KNOTS, device=0):
     B, n = x.shape
     eng = _engine_for(n, device)
     stride = max(n - 2, 1)
-    d_x, d_idx, d_info = DeviceBuffer(x.nbytes, device), DeviceBuffer(4 * B * stride, device), DeviceBuffer(4 * B, device)
-    try:
-        d_x.upload(x)
-        eng.detect_batch_dev(d_x.ptr, n, B, n, mode, d_idx.ptr, stride, d_info.ptr)
-        info = d_info.download(numpy.empty(B, numpy.int32))
-        idx = d_idx.download(numpy.empty((B, stride), numpy.int32))
-    finally:
-        for b in (d_x, d_idx, d_info):
-            b.free()
+    with Numpy(device, x) as S:
+        d_idx, d_info = S.empty((B, stride), numpy.int32), S.empty(B, numpy.int32)
+        S.run(eng.detect_batch_dev, S.x, n, B, n, mode, S.ptr(d_idx), stride, S.ptr(d_info))
+        info, idx = S.host(d_info), S.host(d_idx)
     out = []
     for b in range(B):
         if info[b] < 0 and mode <= 2:
@@ -102,77 +88,25 @@ def itd_baseline_extract_fast_channels(x, extrema_input, idx, device=0):
     x = _rows(x)
     C, n = x.shape
     eng = _engine_for(n, device)
-    d_x, d_base, d_info = DeviceBuffer(x.nbytes, device), DeviceBuffer(x.nbytes, device), DeviceBuffer(4 * C, device)
-    d_e = None
-    try:
-        d_x.upload(x)
-        d_base.upload(numpy.zeros_like(x))
+    with Numpy(device, x) as S:
+        d_base, d_info, d_e = S.full(x.shape, x.dtype, 0.0), S.empty(C, numpy.int32), None
         if extrema_input is not None:
             e = numpy.ascontiguousarray(extrema_input, dtype=numpy.int64)
             if e.shape[0] < idx + 1:
                 raise ValueError("extrema_input needs idx+1 entries")
             if e[: idx + 1].min() < 0 or e[: idx + 1].max() >= n:
                 raise IndexError("extrema outside the signal")      # what the reference's indexing would raise
-            e32 = e[: idx + 1].astype(numpy.int32)
-            d_e = DeviceBuffer(e32.nbytes, device)
-            d_e.upload(e32)
-            eng.cubic_batch_dev(d_x.ptr, n, C, n, d_e.ptr, 0, int(idx), d_base.ptr, n, d_info.ptr)
-        else:
-            eng.cubic_batch_dev(d_x.ptr, n, C, n, None, 0, 0, d_base.ptr, n, d_info.ptr)
-        info = d_info.download(numpy.empty(C, numpy.int32))
+            d_e = S.put(e[: idx + 1].astype(numpy.int32))
+        S.run(eng.cubic_batch_dev, S.x, n, C, n, S.ptr(d_e), 0, 0 if d_e is None else int(idx), S.ptr(d_base), n, S.ptr(d_info))
+        info = S.host(d_info)
         if (info == -1).any():
             raise ValueError("extrema_input must be strictly increasing")
         if (info == -2).any():
             raise ValueError("NaN in the signal (the cubic operator has no NaN branch)")
-        return d_base.download(numpy.empty_like(x))
-    finally:
-        for b in (d_x, d_base, d_info, d_e):
-            if b is not None:
-                b.free()
+        return S.host(d_base)
 
 
 _INSTANTANEOUS = ("amplitude", "phase", "frequency")
-
-
-def _row_stride(shape, strides):
-    """The one stride (in elements) between consecutive rows of an array [..., n] whose last axis is dense, or None if its
-    leading axes do not collapse to one."""
-    if strides[-1] != 1:
-        return None
-    lead = [(d, st) for d, st in zip(shape[:-1], strides[:-1]) if d > 1]
-    if not lead:
-        return shape[-1]
-    for (_, outer), (d, inner) in zip(lead[:-1], lead[1:]):
-        if outer != d * inner:
-            return None
-    return lead[-1][1] if lead[-1][1] >= shape[-1] else None
-
-
-def _accept_rows(rows, what):
-    """The acceptance of rows[..., n]: (torch?, the array or tensor, input dtype, shape, n, row count)."""
-    torch_in = _is_torch(rows)
-    a = rows if torch_in else numpy.asarray(rows)
-    idt = numpy.dtype(_np_dtype(a.dtype))
-    if idt not in (numpy.dtype(numpy.float32), numpy.dtype(numpy.float64)):
-        raise ValueError("rows must be float32 or float64, got %s" % (a.dtype,))
-    shape = tuple(a.shape)
-    if len(shape) < 2:
-        raise ValueError("expected rows[..., n] with at least one leading axis, got shape %s" % (shape,))
-    if shape[-1] < 3:
-        raise ValueError("%s needs at least 3 samples" % what)
-    R = int(numpy.prod(shape[:-1], dtype=numpy.int64))
-    if R < 1:
-        raise ValueError("no rows in an array of shape %s" % (shape,))
-    return torch_in, a, idt, shape, shape[-1], R
-
-
-def _tensor_stride(a, shape):
-    if not a.is_cuda:
-        raise ValueError("expected a CUDA tensor")
-    stride = _row_stride(shape, tuple(a.stride()))
-    if stride is None:
-        raise ValueError("the leading axes of a tensor with strides %s do not collapse to one row stride" % (tuple(a.stride()),))
-    return stride
 
 
 def _refuse_nan(info):
@@ -188,24 +122,6 @@ def _out_dtype(out_dtype):
     return odt
 
 
-class _Staged(contextlib.ExitStack):
-    """The device buffers of one numpy-staged call (hipMalloc through the C ABI), freed when the block is left."""
-
-    def __init__(self, device):
-        super().__init__()
-        self.dev = int(device)
-
-    def empty(self, nbytes):
-        b = DeviceBuffer(nbytes, self.dev)
-        self.callback(b.free)
-        return b
-
-    def upload(self, array):
-        b = self.empty(array.nbytes)
-        b.upload(array)
-        return b
-
-
 def instantaneous_batch(rows, device=0, out_dtype=None, want=_INSTANTANEOUS):
     """Instantaneous amplitude, phase and frequency (pyitd_amd.instantaneous) of every row of rows[..., n] in one asynchronous
     call: the rows of a batched decomposition as itd_batch delivers them, float64 or float32 (widened exactly on the GPU).
@@ -219,36 +135,26 @@ def instantaneous_batch(rows, device=0, out_dtype=None, want=_INSTANTANEOUS):
     if not want or any(w not in _INSTANTANEOUS for w in want) or len(set(want)) != len(want):
         raise ValueError("want: a non-empty selection of %s without repeats, got %r" % (_INSTANTANEOUS, want))
     odt = _out_dtype(out_dtype)
-    torch_in, a, idt, shape, n, R = _accept_rows(rows, "the instantaneous step")
-    if torch_in:
-        import torch
-        stride = _tensor_stride(a, shape)
-        dev = a.device.index
-        tdt = torch.float32 if odt == numpy.float32 else torch.float64
-        outs = {w: torch.empty(shape, dtype=tdt, device=a.device) for w in want}
-        info = torch.empty(R, dtype=torch.int32, device=a.device)
-        eng = _engine_for(3, dev)
-        torch.cuda.synchronize(a.device)    # the engine runs on its own stream
-        eng.instantaneous_batch_dev(a.data_ptr(), idt, n, R, stride, *[outs[w].data_ptr() if w in outs else None for w in _INSTANTANEOUS],
-                                    n, odt == numpy.float32, info.data_ptr())
-        torch.cuda.synchronize(a.device)
-        _refuse_nan(info.cpu().numpy())
-        return tuple(outs[w] for w in want)
-    a = numpy.ascontiguousarray(a).reshape(R, n)
-    with _Staged(device) as S:
-        bufs = {w: S.empty(R * n * odt.itemsize) for w in want}
-        d_x, d_info = S.upload(a), S.empty(4 * R)
+    place, idt, shape, n, R, stride = rows_of(rows, "the instantaneous step", device)
+    with place as S:
+        outs = {w: S.empty(shape, odt) for w in want}
+        info = S.empty(R, numpy.int32)
         eng = _engine_for(3, S.dev)
-        eng.instantaneous_batch_dev(d_x.ptr, idt, n, R, n, *[bufs[w].ptr if w in bufs else None for w in _INSTANTANEOUS],
-                                    n, odt == numpy.float32, d_info.ptr)
-        _refuse_nan(d_info.download(numpy.empty(R, numpy.int32)))      # itd_dev_copy synchronises
-        return tuple(bufs[w].download(numpy.empty((R, n), odt)).reshape(shape) for w in want)
+        S.run(eng.instantaneous_batch_dev, S.x, idt, n, R, stride, *[S.ptr(outs.get(w)) for w in _INSTANTANEOUS], n, odt == numpy.float32,
+              S.ptr(info))
+        _refuse_nan(S.host(info))
+        return tuple(S.result(outs[w]) for w in want)
 
 
 # ---- the time-frequency-energy spectrum (itd_tfe_spectrum_*) ---------------------------------------------------------------
 Spectrum = namedtuple("Spectrum", "power outside")
 _WEIGHTS = ("count", "amplitude", "energy")
 MAX_BINS = 512
+
+
+def _legal_hop(hop):
+    """The spectrum's hop rule, the many-row call's and the stream's: a positive multiple of 64, below 512 only 64, 128 or 256."""
+    return not isinstance(hop, bool) and int(hop) == hop and hop >= 64 and hop % 64 == 0 and (hop >= 512 or hop in (64, 128, 256))
 
 
 def _spectrum_args(edges, hop, weight):
@@ -260,7 +166,7 @@ def _spectrum_args(edges, hop, weight):
         raise ValueError("edges: a 1-D array of 2 to %d entries, got shape %s" % (MAX_BINS + 1, e.shape))
     if not numpy.isfinite(e).all() or not (e[1:] > e[:-1]).all():
         raise ValueError("edges must be finite and strictly increasing")
-    if isinstance(hop, bool) or int(hop) != hop or hop < 64 or hop % 64 != 0 or (hop < 512 and hop not in (64, 128, 256)):
+    if not _legal_hop(hop):
         raise ValueError("hop: a positive multiple of 64 (below 512: 64, 128 or 256), got %r" % (hop,))
     if weight not in _WEIGHTS:
         raise ValueError("weight: one of %s, got %r" % (_WEIGHTS, weight))
@@ -281,32 +187,15 @@ def tfe_spectrum(rows, edges, hop, weight="energy", device=0):
     marginal spectrum sums a spectrum of many time bins rather than asking for hop >= n.  Raises ValueError for bad edges, hop or
     weight, ITDError (non-finite) naming the rows that hold a NaN."""
     e, hop, wcode = _spectrum_args(edges, hop, weight)
-    torch_in, a, idt, shape, n, R = _accept_rows(rows, "the spectrum")
+    place, idt, shape, n, R, stride = rows_of(rows, "the spectrum", device)
     F, T = e.size - 1, -(-n // hop)
     lead = shape[:-1]
-    if torch_in:
-        import torch
-        stride = _tensor_stride(a, shape)
-        dev = a.device.index
-        power = torch.empty((R, T, F), dtype=torch.float64, device=a.device)
-        outside = torch.empty((R, T), dtype=torch.int32, device=a.device)
-        info = torch.empty(R, dtype=torch.int32, device=a.device)
-        d_e = torch.from_numpy(e).to(a.device)
-        eng = _engine_for(3, dev)
-        torch.cuda.synchronize(a.device)    # the engine runs on its own stream
-        eng.tfe_spectrum_dev(a.data_ptr(), idt, n, R, stride, d_e.data_ptr(), F, hop, wcode, power.data_ptr(), T * F, outside.data_ptr(),
-                             info.data_ptr())
-        torch.cuda.synchronize(a.device)
-        _refuse_nan(info.cpu().numpy())
-        return Spectrum(power.reshape(lead + (T, F)), outside.reshape(lead + (T,)))
-    a = numpy.ascontiguousarray(a).reshape(R, n)
-    with _Staged(device) as S:
-        d_x, d_e, d_p, d_o, d_info = S.upload(a), S.upload(e), S.empty(8 * R * T * F), S.empty(4 * R * T), S.empty(4 * R)
+    with place as S:
+        power, outside, info, d_e = S.empty(lead + (T, F), numpy.float64), S.empty(lead + (T,), numpy.int32), S.empty(R, numpy.int32), S.put(e)
         eng = _engine_for(3, S.dev)
-        eng.tfe_spectrum_dev(d_x.ptr, idt, n, R, n, d_e.ptr, F, hop, wcode, d_p.ptr, T * F, d_o.ptr, d_info.ptr)
-        _refuse_nan(d_info.download(numpy.empty(R, numpy.int32)))          # itd_dev_copy synchronises
-        return Spectrum(d_p.download(numpy.empty((R, T, F))).reshape(lead + (T, F)),
-                        d_o.download(numpy.empty((R, T), numpy.int32)).reshape(lead + (T,)))
+        S.run(eng.tfe_spectrum_dev, S.x, idt, n, R, stride, S.ptr(d_e), F, hop, wcode, S.ptr(power), T * F, S.ptr(outside), S.ptr(info))
+        _refuse_nan(S.host(info))
+        return Spectrum(S.result(power), S.result(outside))
 
 
 # ---- single-wave analysis: the table of half waves and the feature filter (itd_waves_batch_*, itd_wave_filter_batch_*) -------
@@ -335,47 +224,21 @@ def single_waves(rows, cap=None, device=0):
         if int(cap) != cap or int(cap) < 1:
             raise ValueError("cap must be a positive integer or None, got %r" % (cap,))
         cap = int(cap)
-    torch_in, a, idt, shape, n, R = _accept_rows(rows, "single-wave analysis")
+    place, idt, shape, n, R, stride = rows_of(rows, "single-wave analysis", device)
     lead = shape[:-1]
-    if torch_in:
-        import torch
-        stride = _tensor_stride(a, shape)
-        dev = a.device.index
-        count = torch.empty(R, dtype=torch.int32, device=a.device)
-        info = torch.empty(R, dtype=torch.int32, device=a.device)
-        eng = _engine_for(3, dev)
-        torch.cuda.synchronize(a.device)    # the engine runs on its own stream
-        if cap is None:
-            eng.waves_batch_dev(a.data_ptr(), idt, n, R, stride, None, None, None, None, 0, 0, count.data_ptr(), info.data_ptr())
-            torch.cuda.synchronize(a.device)
-            _refuse_nan(info.cpu().numpy())
-            cap = int(count.max())
-        ints = [torch.full((R, cap), -1, dtype=torch.int32, device=a.device) for _ in range(3)]
-        value = torch.full((R, cap), float("nan"), dtype=torch.float64, device=a.device)
-        torch.cuda.synchronize(a.device)
-        eng.waves_batch_dev(a.data_ptr(), idt, n, R, stride, *[t.data_ptr() for t in ints], value.data_ptr(), cap, cap,
-                            count.data_ptr(), info.data_ptr())
-        torch.cuda.synchronize(a.device)
-        _refuse_nan(info.cpu().numpy())
-        _refuse_overflow(count.cpu().numpy(), cap)
-        return Waves(count.reshape(lead), *[t.reshape(lead + (cap,)) for t in ints], value.reshape(lead + (cap,)))
-    a = numpy.ascontiguousarray(a).reshape(R, n)
-    with _Staged(device) as S:
-        d_x, d_count, d_info = S.upload(a), S.empty(4 * R), S.empty(4 * R)
+    with place as S:
+        count, info = S.empty(lead, numpy.int32), S.empty(R, numpy.int32)
         eng = _engine_for(3, S.dev)
         if cap is None:
-            eng.waves_batch_dev(d_x.ptr, idt, n, R, n, None, None, None, None, 0, 0, d_count.ptr, d_info.ptr)
-            _refuse_nan(d_info.download(numpy.empty(R, numpy.int32)))       # itd_dev_copy synchronises
-            cap = int(d_count.download(numpy.empty(R, numpy.int32)).max())
-        fill_i, fill_v = numpy.full((R, cap), -1, numpy.int32), numpy.full((R, cap), numpy.nan)
-        fills = (fill_i, fill_i, fill_i, fill_v)
-        tabs = [S.upload(f) for f in fills]
-        eng.waves_batch_dev(d_x.ptr, idt, n, R, n, *[b.ptr for b in tabs], cap, cap, d_count.ptr, d_info.ptr)
-        _refuse_nan(d_info.download(numpy.empty(R, numpy.int32)))
-        count = d_count.download(numpy.empty(R, numpy.int32))
-        _refuse_overflow(count, cap)
-        outs = [b.download(numpy.empty_like(f)).reshape(lead + (cap,)) for b, f in zip(tabs, fills)]
-        return Waves(count.reshape(lead), *outs)
+            S.run(eng.waves_batch_dev, S.x, idt, n, R, stride, None, None, None, None, 0, 0, S.ptr(count), S.ptr(info))
+            _refuse_nan(S.host(info))
+            cap = int(S.host(count).max())
+        tabs = [S.full(lead + (cap,), numpy.int32, -1) for _ in range(3)] + [S.full(lead + (cap,), numpy.float64, numpy.nan)]
+        S.run(eng.waves_batch_dev, S.x, idt, n, R, stride, *[S.ptr(t) for t in tabs], cap, cap, S.ptr(count), S.ptr(info))
+        _refuse_nan(S.host(info))
+        counts = S.host(count)
+        _refuse_overflow(counts, cap)
+        return Waves(S.result(count, counts), *[S.result(t) for t in tabs])
 
 
 def _wave_bounds(amplitude, length, lead):
@@ -414,30 +277,15 @@ def wave_filter(rows, amplitude=(0.0, numpy.inf), length=(0.0, numpy.inf), out_d
     rows as for single_waves; out_dtype: None / float64, or float32 (numpy or torch): each kept sample rounded once on the GPU.
     Returns an array (tensor for a tensor) shaped like rows.  Raises ITDError (non-finite) naming the rows that hold a NaN."""
     odt = _out_dtype(out_dtype)
-    torch_in, a, idt, shape, n, R = _accept_rows(rows, "the wave filter")
+    place, idt, shape, n, R, stride = rows_of(rows, "the wave filter", device)
     bounds = _wave_bounds(amplitude, length, shape[:-1])
     bstride = 0 if bounds.ndim == 1 else 4
-    if torch_in:
-        import torch
-        stride = _tensor_stride(a, shape)
-        dev = a.device.index
-        out = torch.empty(shape, dtype=torch.float32 if odt == numpy.float32 else torch.float64, device=a.device)
-        info = torch.empty(R, dtype=torch.int32, device=a.device)
-        d_b = torch.from_numpy(bounds).to(a.device)
-        eng = _engine_for(3, dev)
-        torch.cuda.synchronize(a.device)    # the engine runs on its own stream
-        eng.wave_filter_batch_dev(a.data_ptr(), idt, n, R, stride, d_b.data_ptr(), bstride, out.data_ptr(), n, odt == numpy.float32,
-                                  info.data_ptr())
-        torch.cuda.synchronize(a.device)
-        _refuse_nan(info.cpu().numpy())
-        return out
-    a = numpy.ascontiguousarray(a).reshape(R, n)
-    with _Staged(device) as S:
-        d_x, d_b, d_out, d_info = S.upload(a), S.upload(bounds), S.empty(R * n * odt.itemsize), S.empty(4 * R)
+    with place as S:
+        out, info, d_b = S.empty(shape, odt), S.empty(R, numpy.int32), S.put(bounds)
         eng = _engine_for(3, S.dev)
-        eng.wave_filter_batch_dev(d_x.ptr, idt, n, R, n, d_b.ptr, bstride, d_out.ptr, n, odt == numpy.float32, d_info.ptr)
-        _refuse_nan(d_info.download(numpy.empty(R, numpy.int32)))           # itd_dev_copy synchronises
-        return d_out.download(numpy.empty((R, n), odt)).reshape(shape)
+        S.run(eng.wave_filter_batch_dev, S.x, idt, n, R, stride, S.ptr(d_b), bstride, S.ptr(out), n, odt == numpy.float32, S.ptr(info))
+        _refuse_nan(S.host(info))
+        return S.result(out)
 
 
 # ---- the joint amplitude-length histogram of the half waves (itd_wave_hist_batch_*) ------------------------------------------
@@ -488,7 +336,7 @@ def wave_histogram(rows, amplitude_edges, length_edges, hop=None, device=0):
     the leading axes of rows — every level of a decomposition, with its own time-scale, may have its own; 1 to 64 bins per axis, at
     most 1024 cells, strictly increasing, -inf / +inf allowed at the ends.  hop: None (one time bin) or a positive multiple of 512.
     Raises ValueError for bad edges or hop, ITDError (non-finite) naming the rows that hold a NaN."""
-    torch_in, a, idt, shape, n, R = _accept_rows(rows, "the wave histogram")
+    place, idt, shape, n, R, stride = rows_of(rows, "the wave histogram", device)
     lead = shape[:-1]
     ae, le = _hist_edges(amplitude_edges, "amplitude_edges", lead), _hist_edges(length_edges, "length_edges", lead)
     Na, Nl = ae.shape[-1] - 1, le.shape[-1] - 1
@@ -497,29 +345,12 @@ def wave_histogram(rows, amplitude_edges, length_edges, hop=None, device=0):
     hop = _hist_hop(hop, n)
     T = -(-n // hop)
     astride, lstride = (0 if ae.ndim == 1 else Na + 1), (0 if le.ndim == 1 else Nl + 1)
-    slot = T * Na * Nl
-    if torch_in:
-        import torch
-        stride = _tensor_stride(a, shape)
-        dev = a.device.index
-        count, samples = (torch.empty((R, T, Na, Nl), dtype=torch.int32, device=a.device) for _ in range(2))
-        outside = torch.empty((R, T), dtype=torch.int32, device=a.device)
-        info = torch.empty(R, dtype=torch.int32, device=a.device)
-        d_a, d_l = torch.from_numpy(ae).to(a.device), torch.from_numpy(le).to(a.device)
-        eng = _engine_for(3, dev)
-        torch.cuda.synchronize(a.device)    # the engine runs on its own stream
-        eng.wave_hist_batch_dev(a.data_ptr(), idt, n, R, stride, d_a.data_ptr(), astride, Na, d_l.data_ptr(), lstride, Nl, hop,
-                                count.data_ptr(), samples.data_ptr(), slot, outside.data_ptr(), info.data_ptr())
-        torch.cuda.synchronize(a.device)
-        _refuse_nan(info.cpu().numpy())
-        return WaveHistogram(count.reshape(lead + (T, Na, Nl)), samples.reshape(lead + (T, Na, Nl)), outside.reshape(lead + (T,)))
-    a = numpy.ascontiguousarray(a).reshape(R, n)
-    with _Staged(device) as S:
-        d_x, d_a, d_l = S.upload(a), S.upload(ae), S.upload(le)
-        d_c, d_s, d_o, d_info = S.empty(4 * R * slot), S.empty(4 * R * slot), S.empty(4 * R * T), S.empty(4 * R)
+    with place as S:
+        count, samples = S.empty(lead + (T, Na, Nl), numpy.int32), S.empty(lead + (T, Na, Nl), numpy.int32)
+        outside, info = S.empty(lead + (T,), numpy.int32), S.empty(R, numpy.int32)
+        d_a, d_l = S.put(ae), S.put(le)
         eng = _engine_for(3, S.dev)
-        eng.wave_hist_batch_dev(d_x.ptr, idt, n, R, n, d_a.ptr, astride, Na, d_l.ptr, lstride, Nl, hop, d_c.ptr, d_s.ptr, slot, d_o.ptr,
-                                d_info.ptr)
-        _refuse_nan(d_info.download(numpy.empty(R, numpy.int32)))          # itd_dev_copy synchronises
-        return WaveHistogram(*[b.download(numpy.empty((R, T, Na, Nl), numpy.int32)).reshape(lead + (T, Na, Nl)) for b in (d_c, d_s)],
-                             d_o.download(numpy.empty((R, T), numpy.int32)).reshape(lead + (T,)))
+        S.run(eng.wave_hist_batch_dev, S.x, idt, n, R, stride, S.ptr(d_a), astride, Na, S.ptr(d_l), lstride, Nl, hop, S.ptr(count),
+              S.ptr(samples), T * Na * Nl, S.ptr(outside), S.ptr(info))
+        _refuse_nan(S.host(info))
+        return WaveHistogram(S.result(count), S.result(samples), S.result(outside))

@@ -17,7 +17,8 @@ import ctypes
 
 import numpy
 
-from .engine import DeviceBuffer, _np_ptr
+from ._place import Numpy
+from .engine import _np_ptr
 from .itd import _engine_for, find_extrema, generate_sine_wave
 
 _NO_CAP = 2 ** 31 - 1
@@ -148,14 +149,12 @@ def fourier_mode_batch(rows, rule="any", device=0):
     B, n = x.shape
     eng = _engine_for(n, device)
     fn = {"any": eng._L.itd_fourier_mode_any_f64, "valid": eng._L.itd_fourier_mode_valid_f64}[rule]
-    buf = DeviceBuffer(2 * x.nbytes + B * 32, device)
-    try:
+    with Numpy(device) as S:        # one buffer: the rows, the modes, the records
+        buf = S.empty(2 * x.nbytes + B * 32, numpy.uint8)
         buf.upload(x)
         eng._check(fn(eng._h, buf.ptr, n, B, n, buf.ptr + x.nbytes, n, buf.ptr + 2 * x.nbytes, None))
         modes = buf.download(numpy.empty((B, n)), x.nbytes)
         recs = buf.download(numpy.empty((B, 8), numpy.int32), 2 * x.nbytes)
-    finally:
-        buf.free()
     return modes, recs[:, :6].copy()
 
 
@@ -176,10 +175,8 @@ def debug_fft(x, inverse=False, device=0):
     z = numpy.ascontiguousarray(numpy.atleast_2d(numpy.asarray(x, dtype=numpy.complex128)))
     B, n = z.shape
     eng = _engine_for(max(n, 3), device)
-    buf = DeviceBuffer(2 * z.nbytes, device)
-    try:
+    with Numpy(device) as S:
+        buf = S.empty(2 * z.nbytes, numpy.uint8)
         buf.upload(z)
         eng._check(eng._L.itd_debug_fft_f64(eng._h, ctypes.c_void_p(buf.ptr), ctypes.c_void_p(buf.ptr + z.nbytes), n, B, 1 if inverse else 0))
         return buf.download(numpy.empty((B, n), numpy.complex128), z.nbytes)
-    finally:
-        buf.free()

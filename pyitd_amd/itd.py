@@ -12,6 +12,7 @@ fallback — without the library or a GPU these functions raise.
 import numpy
 
 from . import _lib
+from ._place import Numpy, Tensor, _is_torch, _np_dtype
 from .engine import DETECT_KNOTS, DETECT_PEAKS, DETECT_VALLEYS, STOP_TIMEOUT, Engine, rows_dtype_of, selection_of, zero_absent_slots
 
 _engines = {}
@@ -237,17 +238,6 @@ class ITD:
         return self.rotations
 
 
-def _is_torch(x):
-    return type(x).__module__.split(".")[0] == "torch"
-
-
-def _np_dtype(dtype):
-    """torch.float32 / torch.float64 as numpy's; everything else as given."""
-    if _is_torch(dtype):
-        return {"torch.float32": numpy.float32, "torch.float64": numpy.float64}.get(str(dtype), str(dtype))
-    return dtype
-
-
 def itd_batch(x, max_iteration: int = 11, keep_baselines: bool = False, device=None, out_dtype=None, select=None):
     """Decompose a batch of independent signals x[B, N] in one call (device resident, one engine launch sequence
     for the whole batch — the batched form of ITD.itd the reference only has as `numba.prange` over rows,
@@ -275,71 +265,45 @@ def itd_batch(x, max_iteration: int = 11, keep_baselines: bool = False, device=N
         raise ValueError("max_iteration must be in 0..20 (the reference's buffers hold 22 rows, ITD.py:384-385)")
     R = selection_of(select, max_iteration)[2] if select is not None else max_iteration + 2
 
-    def result(eng, B, fetch):
-        """The call's summary read (NaN input: ValueError) and the result dict around fetch(), the rows — and the baselines — as the
-        caller gets them, once the call has run."""
-        s = eng.summary(B)
-        if (s["nan_levels"] == -2).any():
-            raise ValueError("an input signal contains NaN")
-        rows, bases = fetch()
-        if select is not None:
-            zero_absent_slots(rows, select, s["n_rows"])
-        out = {"n_rows": s["n_rows"], "stop": s["stop"], "knot_counts": s["knot_counts"], "rows": rows}
-        if keep_baselines:
-            out["baselines"] = bases
-            out["n_baselines"] = s["n_baselines"]
-        return out
-
     if _is_torch(x):
         import torch
         if not x.is_cuda or x.dim() != 2:
             raise ValueError("expected a 2-D CUDA tensor")
-        xt = x if x.dtype in (torch.float32, torch.float64) else x.double()
-        if xt.stride(1) != 1:
-            xt = xt.contiguous()
-        dev = xt.device.index
-        B, n = xt.shape
-        if n < 3:
-            raise ValueError("ITD needs at least 3 samples")
-        rows = torch.empty((B, R, n), dtype=torch.float32 if rdt == numpy.float32 else torch.float64, device=xt.device)
-        bases = torch.zeros((B, R, n), dtype=torch.float64, device=xt.device) if keep_baselines else None
-        eng = _batch_engine_for(n, B, dev)
-        torch.cuda.synchronize(xt.device)   # the engine runs on its own stream
-        eng.decompose_dev(xt.data_ptr(), numpy.float32 if xt.dtype == torch.float32 else numpy.float64, n, B,
-                          xt.stride(0), max_iteration, rows.data_ptr(), bases.data_ptr() if keep_baselines else None, None,
-                          rows_dtype=rdt, select=select)
-
-        def fetch():
-            if select is not None:
-                torch.cuda.synchronize(xt.device)
-            return rows, bases
-        return result(eng, B, fetch)
-    from .engine import DeviceBuffer
-    a = numpy.asarray(x)
-    if a.ndim != 2:
-        raise ValueError("expected x[B, N]")
-    if a.dtype != numpy.float32:
-        a = numpy.asarray(a, dtype=numpy.float64)
-    a = numpy.ascontiguousarray(a)
-    dev = 0 if device is None else int(device)
+        a = x if x.dtype in (torch.float32, torch.float64) else x.double()
+        if a.stride(1) != 1:
+            a = a.contiguous()
+        place, stride = Tensor(a), a.stride(0)
+    else:
+        a = numpy.asarray(x)
+        if a.ndim != 2:
+            raise ValueError("expected x[B, N]")
+        if a.dtype != numpy.float32:
+            a = numpy.asarray(a, dtype=numpy.float64)
+        a = numpy.ascontiguousarray(a)
+        place, stride = Numpy(0 if device is None else device, a), a.shape[1]
     B, n = a.shape
     if n < 3:
         raise ValueError("ITD needs at least 3 samples")
-    d_x = DeviceBuffer(a.nbytes, dev)
-    d_rows = DeviceBuffer(B * R * n * rdt.itemsize, dev)
-    d_bases = DeviceBuffer(B * R * n * 8, dev) if keep_baselines else None
-    try:
-        d_x.upload(a)
-        eng = _batch_engine_for(n, B, dev)
-        eng.decompose_dev(d_x.ptr, a.dtype, n, B, n, max_iteration, d_rows.ptr, d_bases.ptr if keep_baselines else None, None,
-                          rows_dtype=rdt, select=select)
-        return result(eng, B, lambda: (d_rows.download(numpy.empty((B, R, n), rdt)),
-                                       d_bases.download(numpy.empty((B, R, n), numpy.float64)) if keep_baselines else None))
-    finally:
-        d_x.free()
-        d_rows.free()
-        if d_bases is not None:
-            d_bases.free()
+    with place as S:
+        rows = S.empty((B, R, n), rdt)
+        bases = S.empty((B, R, n), numpy.float64) if keep_baselines else None
+        eng = _batch_engine_for(n, B, S.dev)
+        if keep_baselines:      # the baselines beyond n_baselines stay zero
+            S.run(eng.copy, S.ptr(bases), None, 8 * B * R * n, 3)
+        S.run(eng.decompose_dev, S.x, _np_dtype(a.dtype), n, B, stride, max_iteration, S.ptr(rows), S.ptr(bases), None, rows_dtype=rdt,
+              select=select)
+        s = eng.summary(B)      # waits for the engine's stream
+        if (s["nan_levels"] == -2).any():
+            raise ValueError("an input signal contains NaN")
+        if select is None:
+            S.settled()
+        out = {"n_rows": s["n_rows"], "stop": s["stop"], "knot_counts": s["knot_counts"], "rows": S.result(rows)}
+        if select is not None:
+            zero_absent_slots(out["rows"], select, s["n_rows"])
+        if keep_baselines:
+            out["baselines"] = S.result(bases)
+            out["n_baselines"] = s["n_baselines"]
+        return out
 
 
 # ---- cubic-spline baseline variant with externally supplied knots: itd_fourier_decomposition.py / itd.cpp ------------------

@@ -426,11 +426,6 @@ def blockwise_wave_filter(rows, block, horizon, amplitude=(0.0, numpy.inf), leng
 
 
 StreamSpectrum = namedtuple("StreamSpectrum", "power outside overlong")
-_WEIGHTS = ("count", "amplitude", "energy")
-
-
-def _legal_hop(hop):
-    return not isinstance(hop, bool) and int(hop) == hop and hop >= 64 and hop % 64 == 0 and (hop >= 512 or hop in (64, 128, 256))
 
 
 class SpectrumStream(_RingStream):
@@ -467,6 +462,7 @@ class SpectrumStream(_RingStream):
     _NAME = "spectrum"
 
     def __init__(self, block, rows=1, horizon=None, edges=None, hop=None, weight="energy", device=0):
+        from .batch import _WEIGHTS, _legal_hop
         horizon = block if horizon is None else horizon
         if isinstance(block, bool) or int(block) != block or not 64 <= block <= 4096:
             raise ValueError("block must be 64 .. 4096 samples")

@@ -22,12 +22,12 @@ def test_entries_refuse_a_null_engine():
 
 def test_wrapper_refuses_bad_arguments_before_any_engine(monkeypatch):
     import pyitd_amd
-    from pyitd_amd import batch
+    from pyitd_amd import _place, batch
 
     def no_engine(*a, **k):
         raise AssertionError("an engine was asked for")
     monkeypatch.setattr(batch, "_engine_for", no_engine)
-    monkeypatch.setattr(batch, "DeviceBuffer", no_engine)
+    monkeypatch.setattr(_place, "DeviceBuffer", no_engine)
     good = np.zeros((2, 5))
     for bad, kw in ((np.zeros(5), {}), (np.zeros((2, 2)), {}), (np.zeros((2, 5), np.int32), {}), (good, {"want": ("amplitude", "energy")}),
                     (good, {"want": ()}), (good, {"out_dtype": np.int16})):
@@ -36,7 +36,7 @@ def test_wrapper_refuses_bad_arguments_before_any_engine(monkeypatch):
 
 
 def test_leading_axes_collapse_to_one_row_stride_or_not():
-    from pyitd_amd.batch import _row_stride
+    from pyitd_amd._place import _row_stride
     assert _row_stride((3, 4, 10), (40, 10, 1)) == 10
     assert _row_stride((3, 4, 10), (52, 13, 1)) == 13            # padded rows, still one stride
     assert _row_stride((3, 4, 10), (100, 13, 1)) is None         # padded planes

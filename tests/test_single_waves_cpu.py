@@ -42,12 +42,12 @@ def test_entries_refuse_a_null_engine():
 
 def test_wrappers_refuse_bad_arguments_before_any_engine(monkeypatch):
     import pyitd_amd
-    from pyitd_amd import batch
+    from pyitd_amd import _place, batch
 
     def no_engine(*a, **k):
         raise AssertionError("an engine was asked for")
     monkeypatch.setattr(batch, "_engine_for", no_engine)
-    monkeypatch.setattr(batch, "DeviceBuffer", no_engine)
+    monkeypatch.setattr(_place, "DeviceBuffer", no_engine)
     good = np.zeros((2, 5))
     for bad, kw in ((np.zeros(5), {}), (np.zeros((2, 2)), {}), (np.zeros((2, 5), np.int32), {}), (good, {"cap": 0}), (good, {"cap": -3}),
                     (good, {"cap": 2.5})):

@@ -20,12 +20,12 @@ def test_entries_refuse_a_null_engine():
 
 def test_wrapper_refuses_bad_arguments_before_any_engine(monkeypatch):
     import pyitd_amd
-    from pyitd_amd import batch
+    from pyitd_amd import _place, batch
 
     def no_engine(*a, **k):
         raise AssertionError("an engine was asked for")
     monkeypatch.setattr(batch, "_engine_for", no_engine)
-    monkeypatch.setattr(batch, "DeviceBuffer", no_engine)
+    monkeypatch.setattr(_place, "DeviceBuffer", no_engine)
     good, edges = np.zeros((2, 700)), np.linspace(0.0, 0.5, 5)
     bad_edges = (0.25, [0.1], np.zeros((2, 3)), [0.0, 0.2, 0.2], [0.0, 0.3, 0.2], [0.0, np.nan, 0.5], [0.0, 0.1, np.inf],
                  np.linspace(0.0, 0.5, 515))

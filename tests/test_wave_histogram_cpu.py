@@ -66,12 +66,12 @@ def test_the_reference_keeps_the_two_invariants(fam):
 
 def test_wrapper_refuses_bad_arguments_before_any_engine(monkeypatch):
     import pyitd_amd
-    from pyitd_amd import batch
+    from pyitd_amd import _place, batch
 
     def no_engine(*a, **k):
         raise AssertionError("an engine was asked for")
     monkeypatch.setattr(batch, "_engine_for", no_engine)
-    monkeypatch.setattr(batch, "DeviceBuffer", no_engine)
+    monkeypatch.setattr(_place, "DeviceBuffer", no_engine)
     good, ae, le = np.zeros((2, 700)), [0.0, 0.5, 1.0], [1.0, 10.0, np.inf]
     nan = float("nan")
     bad_edges = (0.25, [0.1], [0.0, nan, 1.0], [nan, 1.0], [0.0, 0.2, 0.2], [0.0, 0.3, 0.2], [0.0, np.inf, np.inf], [-np.inf, -np.inf, 0.0],
