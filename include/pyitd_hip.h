@@ -1048,6 +1048,59 @@ int itd_hist_stream_flush_host_f64(itd_stream *s, const double *aedges_host, int
                                    int64_t ledges_stride, int32_t *count_host, int32_t *samples_host, int32_t *outside_host,
                                    int32_t *overlong_host, int32_t *emitted);
 
+/* ---- the table stream: the half-wave table block by block, no horizon and no latency ----------------------
+ * itd_waves_batch_* needs the whole row; the ring streams above stop at a horizon.  A table stream takes blocks of `rows` rows in lock
+ * step and gives every half wave — start, length, peak, signed extremum — in the push in which its end becomes known, whatever its
+ * length: the events a real-time detector works on.  With blocks of L samples, row r after P pushes is x[0 .. P L); indices count
+ * from the stream's first sample.
+ *   crossing index i   i >= 1, x[i + 1] exists, and the sign changes strictly between x[i] and x[i + 1] (x[i] > 0 > x[i + 1] or
+ *                   x[i] < 0 < x[i + 1]; a zero in between is no crossing): itd_waves_batch_*'s on the concatenated row.
+ *   half wave k     start_k, length_k, A_k, peak_k (the smallest index with |x| == A_k), value_k = x[peak_k] with its sign bit:
+ *                   itd_waves_batch_*'s.  It is complete when its last sample c_k is a known crossing index: when sample c_k + 1
+ *                   has been pushed.
+ *   push p          (counted from 0) brings the samples [p L, (p+1) L), decides exactly the crossing indices max(1, p L - 1) ..
+ *                   (p+1) L - 2 and emits the half waves that end there, in order: at most L - 2 events per row in a stream's
+ *                   first push, at most L in every later one.  Whether a block's last sample is a crossing index is decided by the
+ *                   next push.
+ *   flush           emits the one half wave still open, which ends at sample P L - 1; the stream then starts afresh.  A flush of an
+ *                   empty stream emits nothing (emitted = 0) and writes nothing.
+ * The events of every push and of the flush, concatenated row by row, are itd_waves_batch_f64 of the concatenated row: positions
+ * integer for integer, value bit for bit.  No horizon, no `overlong`: exact for half waves of any length.
+ *   origin          every reported start and peak is origin + index (a recording's sample clock); the rule i >= 1 stays relative to
+ *                   the stream's first sample.
+ *   output          row r owns a slot of event_stride entries in each of four arrays: start, length, peak (int64), value
+ *                   (float64); count[r] (int32) = the events of this step.  Entries [0, count) are the completed half waves.  After
+ *                   a push entry `count` is the half wave still open: its start, its length so far, its peak and value so far.
+ *                   After a flush count = 1, entry 0 is the final half wave and no open entry is written.  Nothing at or beyond
+ *                   entry count + 1 of a slot (a flush: beyond entry 0) and nothing outside the slots is written.
+ *   8 <= block <= 4096 (any value), 1 <= rows <= 65535, any origin.  Everything is allocated at create: 48 bytes per row for the
+ *   open half wave, the status word, the host forms' staging and an engine of the stream's own; ITD_ERR_NOMEM when it does not
+ *   fit.  ITD_ERR_INVALID_ARG before any HIP call for a NULL handle, a NULL required pointer, a value out of range or a stride that
+ *   is too short.  A call that fails leaves the stream as it was.
+ *   block_dev: row r's block at block_dev + r in_stride (in_stride >= block when rows > 1) — the dense [channels][M+1][block] rows of
+ *     itd_levels_stream_push_f64 go in as channels (M+1) rows with in_stride = block.
+ *   start_dev, length_dev, peak_dev (int64), value_dev (float64): each optional, a NULL one is skipped; row r's slot at
+ *     + r event_stride (one stride for the four, >= block + 1 when rows > 1).
+ *   count_dev: required, [rows] int32.
+ * Device forms: one launch per call on `stream`, no host synchronisation, no host read; *emitted is 1 for every push and for a flush
+ * of a stream that holds blocks, else 0: it follows from the block count alone.  Host forms: contiguous [rows][block] in,
+ * [rows][block + 1] tables (each optional) and count_host [rows] (required) out; pinned staging, one synchronisation per call.  A NaN
+ * in any pushed block sets bit 2 of itd_stream_status until itd_stream_reset; that row's entries are unspecified from then on (its
+ * count stays within 0 .. block), nothing outside the row's own slots is written, other rows are unaffected.  itd_stream_destroy /
+ * reset (back to block 0; the open half wave is dropped) / blocks (the blocks pushed since the stream began) / status / last_error
+ * apply; every other stream kind's push and flush entries refuse a table stream, and these refuse theirs. */
+#define ITD_STREAM_TABLE 7    /* a table stream (itd_table_stream_create); not a kind itd_stream_create takes */
+int itd_table_stream_create(itd_stream **out, int device_id, int64_t block, int32_t rows, int64_t origin);
+int itd_table_stream_push_f64(itd_stream *s, const double *block_dev, int64_t in_stride, int64_t *start_dev, int64_t *length_dev,
+                              int64_t *peak_dev, double *value_dev, int64_t event_stride, int32_t *count_dev, int32_t *emitted,
+                              void *stream);
+int itd_table_stream_flush_f64(itd_stream *s, int64_t *start_dev, int64_t *length_dev, int64_t *peak_dev, double *value_dev,
+                               int64_t event_stride, int32_t *count_dev, int32_t *emitted, void *stream);
+int itd_table_stream_push_host_f64(itd_stream *s, const double *block_host, int64_t *start_host, int64_t *length_host,
+                                   int64_t *peak_host, double *value_host, int32_t *count_host, int32_t *emitted);
+int itd_table_stream_flush_host_f64(itd_stream *s, int64_t *start_host, int64_t *length_host, int64_t *peak_host, double *value_host,
+                                    int32_t *count_host, int32_t *emitted);
+
 /* ---- introspection for benchmarks -------------------------------------------------------------
  * hipEvent pairs on the launch stream.  Extraction launches are dispatched with their own start/stop events
  * (hipExtLaunchKernel: the events take the dispatch's own begin/end timestamps, so they agree with rocprofv3's kernel durations); the

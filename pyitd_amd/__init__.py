@@ -12,6 +12,7 @@ from .batch import instantaneous_batch, single_waves, tfe_spectrum, wave_filter,
 from .engine import Engine
 from .streaming import InstantaneousStream, SpectrumStream, StreamInstant, StreamSpectrum, blockwise_instantaneous
 from .streaming import StreamHistogram, WaveHistogramStream, blockwise_wave_histogram
+from .streaming import StreamWaves, WaveTableStream, blockwise_single_waves
 from .itd import (ITD, baseline_knot_estimation, detect_knots, detect_peaks, find_extrema, generate_sine_wave, instantaneous, isin, itd,
                   itd_baseline_extract, itd_baseline_extract_cubic, itd_baseline_extract_fast, itd_baseline_extract_iq, itd_batch, itd_levels,
                   itd_sine_wrapper, matlab_detect_peaks, release_engines)
@@ -27,5 +28,6 @@ __all__ = ["itd_baseline_extract_modified", "itd_baseline_extract_spline", "itd_
            "itd_baseline_extract_fast", "itd_baseline_extract_cubic", "itd_baseline_extract_iq", "itd_sine_wrapper", "release_engines", "instantaneous", "instantaneous_batch", "single_waves", "wave_filter", "Waves", "tfe_spectrum", "Spectrum", "wave_histogram", "WaveHistogram", "SpectrumStream", "StreamSpectrum",
            "InstantaneousStream", "StreamInstant", "blockwise_instantaneous",
            "WaveHistogramStream", "StreamHistogram", "blockwise_wave_histogram",
+           "WaveTableStream", "StreamWaves", "blockwise_single_waves",
            "fourier_mode_decomposition_any", "fourier_mode_decomposition_valid", "itd_fourier_decomposition",
            "itd_fourier_decomposition_lean", "itd_fourier_decomposition_batch"]

@@ -136,6 +136,11 @@ ABI = {
     "itd_hist_stream_flush_f64": (_INT, [_P, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P, _P]),
     "itd_hist_stream_push_host_f64": (_INT, [_P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P]),
     "itd_hist_stream_flush_host_f64": (_INT, [_P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P]),
+    "itd_table_stream_create": (_INT, [ctypes.POINTER(_P), _INT, _I64, _I32, _I64]),
+    "itd_table_stream_push_f64": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _I64, _P, _P, _P]),
+    "itd_table_stream_flush_f64": (_INT, [_P, _P, _P, _P, _P, _I64, _P, _P, _P]),
+    "itd_table_stream_push_host_f64": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "itd_table_stream_flush_host_f64": (_INT, [_P, _P, _P, _P, _P, _P, _P]),
     "itd_set_nan_input_mode": (_INT, [_P, _I32]),
     "itd_set_batch_chunk": (_INT, [_P, _I32]),
     "itd_set_batch_streams": (_INT, [_P, _I32]),

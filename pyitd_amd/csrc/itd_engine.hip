@@ -37,6 +37,7 @@
 #include "itd_spectrum_stream.hpp"
 #include "itd_inst_stream.hpp"
 #include "itd_hist_stream.hpp"
+#include "itd_table_stream.hpp"
 #include "itd_spline.hpp"
 #include "itd_nak.hpp"
 #include "itd_wpe.hpp"
@@ -3050,4 +3051,5 @@ int itd_get_kernel_timing(itd_engine *e, int32_t which, double *ms_total, int32_
 
 #include "itd_engine_batch.inc"
 #include "itd_ring_streams.inc"
+#include "itd_table_stream.inc"
 #include "itd_fourier.inc"

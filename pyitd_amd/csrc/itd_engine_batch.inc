@@ -302,6 +302,12 @@ struct itd_stream {
         Buf<double> d_bnd; Pinned<double> h_bnd;
         Buf<int32_t> d_cnt; Pinned<int32_t> h_cnt;
     } rs;
+    // the table stream (ITD_STREAM_TABLE; itd_table_stream.inc): C rows, no ring; it uses L, C, kind, d_status, threads, lds, fn, the
+    // staging d_in / h_in, d_out / h_out, rs.d_cnt / h_cnt, rs.cnt.t (the blocks pushed) and besides
+    struct Table {
+        int64_t origin = 0;                              // added to every position that is reported
+        Buf<TableCarry> carry;                           // [C]: the half wave that is open between two pushes
+    } tb;
 };
 
 namespace {
@@ -542,7 +548,8 @@ int itd_stream_reset(itd_stream *s)
 int64_t itd_stream_blocks(const itd_stream *s)
 {
     if (!s) return -1;
-    if (s->kind >= ITD_STREAM_WAVES) return ring_held(s->rs.cnt);         // (the ring streams: wave filter, spectrum, instantaneous, histogram)
+    // (the ring streams: wave filter, spectrum, instantaneous, histogram; the table stream emits nothing late: what it pushed)
+    if (s->kind >= ITD_STREAM_WAVES) return ring_held(s->rs.cnt);
     if (s->kind != ITD_STREAM_LEVELS) return s->pushed;
     return (s->P < 0 ? s->t : s->P) - std::max<int64_t>(0, s->t - s->M - 1);   // pushed, less the blocks whose rows have left
 }

@@ -31,6 +31,8 @@ block at a fixed latency — finished time slices of a live decomposition's spec
 per-sample amplitude, phase, frequency and half-wave length themselves (pyitd_amd.instantaneous_batch) block by block at the same
 latency.  WaveHistogramStream: the half waves' joint amplitude-length histogram (pyitd_amd.wave_histogram)
 block by block at the wave filter's latency — the distribution a live filter's bounds follow.
+WaveTableStream: the half-wave table itself (pyitd_amd.single_waves) block by block with no horizon and no latency — every half wave
+leaves in the push in which its end becomes known; the open half wave is carried from push to push.
 """
 import ctypes
 from collections import namedtuple
@@ -742,3 +744,112 @@ def blockwise_wave_histogram(rows, block, horizon, amplitude_edges, length_edges
     outs = _push_then_drain(WaveHistogramStream(block, x2.shape[0], horizon, amplitude_edges, length_edges, hop, device), x2)
     fields = [numpy.concatenate([o[i] for o in outs], axis=1) for i in range(4)]
     return StreamHistogram(*[f[0] if flat else f for f in fields])
+
+
+StreamWaves = namedtuple("StreamWaves", "count start length peak value")
+
+
+class WaveTableStream(_Handle):
+    """The half-wave table block by block, with no horizon and no latency (itd_table_stream_* in include/pyitd_hip.h): blocks of
+    `rows` rows go in, every half wave — start, length, peak, signed extremum — comes out in the push in which its end becomes known,
+    whatever its length.  The events of every push and of the flush, concatenated row by row, are pyitd_amd.single_waves of the
+    concatenated rows: positions integer for integer, value bit for bit.  What a real-time detector works on ("this half wave was 40
+    samples long and 5 uV high"), at 32 bytes per half wave.  ONE launch per push on the GPU; the state between two pushes is the open
+    half wave, 48 bytes per row.
+
+        st = WaveTableStream(1024, rows=9)
+        for block in blocks:                            # block: [rows, 1024]
+            w = st.push(block)                          # StreamWaves: w.count [rows] int32, the tables [rows, 1025]
+            ...                                         # row r: entries [0, w.count[r]) ended in this push (a stream's first push:
+                                                        # at most block - 2, later ones: at most block); entry w.count[r] is the
+                                                        # half wave still open — its start, its length, peak and value so far
+        last = st.flush()                               # count == 1, tables [rows, 1]: the final half wave; None if the stream is empty
+
+    block: 8 .. 4096 samples, any value.  origin: added to every reported start and peak (a recording's sample clock).  start, length
+    and peak are int64, value float64.  Whether a block's last sample ends a half wave is known from the next block's first sample:
+    that event leaves with the next push.  A NaN in a pushed block sets status() bit 2 until reset(); that row's entries are
+    unspecified from then on.  reset() drops the open half wave; blocks_held counts the blocks pushed since the stream began.
+
+    Behind a LevelsStream on device pointers, everything on one stream `s`:
+
+        lv = LevelsStream(1024, levels=3, channels=2)
+        tb = WaveTableStream(1024, rows=2 * 4)
+        # rows_d [2, 4, 1024] float64; start_d, length_d, peak_d [8, 1025] int64, value_d [8, 1025] float64, count_d [8] int32
+        if lv.push_dev(block_ptr, 1024, rows_ptr, 1024, 4 * 1024, None, s):
+            tb.push_dev(rows_ptr, 1024, start_ptr, length_ptr, peak_ptr, value_ptr, 1025, count_ptr, s)
+    """
+
+    def __init__(self, block, rows=1, origin=0, device=0):
+        if isinstance(block, bool) or int(block) != block or not 8 <= block <= 4096:
+            raise ValueError("block must be 8 .. 4096 samples")
+        if not 1 <= rows <= 65535:
+            raise ValueError("rows must be 1 .. 65535")
+        if int(origin) != origin or not -2 ** 62 <= origin <= 2 ** 62:
+            raise ValueError("origin must be an integer of at most 2^62 in magnitude")
+        self._open("itd_table_stream_create", "itd_table_stream_create(block=%d, rows=%d, origin=%d)" % (block, rows, origin), int(device),
+                   int(block), int(rows), int(origin))
+        self.block, self.rows, self.origin, self.device = int(block), int(rows), int(origin), int(device)
+        self._flat = False          # the last push took a 1-D block: what leaves has no row axis either
+
+    # ---- device buffers (raw pointers; asynchronous on `stream`) ----------------------------------------------------
+    def push_dev(self, block_ptr, in_stride, start_ptr, length_ptr, peak_ptr, value_ptr, event_stride, count_ptr, stream=None):
+        """One block of every row; always True.  Row r's slot: event_stride entries in each table (a None table is skipped)."""
+        return self._call("itd_table_stream_push_f64", block_ptr, in_stride, start_ptr, length_ptr, peak_ptr, value_ptr, event_stride,
+                          count_ptr, stream=stream)
+
+    def flush_dev(self, start_ptr, length_ptr, peak_ptr, value_ptr, event_stride, count_ptr, stream=None):
+        """The open half wave into entry 0 of every row's slot, count = 1; False (nothing written) if the stream is empty."""
+        return self._call("itd_table_stream_flush_f64", start_ptr, length_ptr, peak_ptr, value_ptr, event_stride, count_ptr, stream=stream)
+
+    # ---- numpy in -> numpy out (one synchronisation per call) ----------------------------------------------------------
+    def _host(self, name, head):
+        slot = self.block + 1
+        tabs = [numpy.empty((self.rows, slot), numpy.float64 if k == 3 else numpy.int64) for k in range(4)]
+        count = numpy.zeros(self.rows, numpy.int32)
+        if not self._call(name, *head, *[_np_ptr(t) for t in tabs], _np_ptr(count)):
+            return None
+        return count, tabs
+
+    def push(self, samples):
+        """samples [rows, block] (or [block] for one row).  StreamWaves(count[rows] int32, start, length, peak [rows, block + 1] int64,
+        value [rows, block + 1] float64) (no row axis for 1-D input); entries behind `count` of a row are not meaningful."""
+        x2, flat = self._block(samples, self.rows)
+        count, tabs = self._host("itd_table_stream_push_host_f64", (_np_ptr(x2),))
+        self._flat = flat
+        return StreamWaves(count[0], *[t[0] for t in tabs]) if flat else StreamWaves(count, *tabs)
+
+    def flush(self):
+        """The final half wave: StreamWaves with count == 1 and tables [rows, 1], shaped like the last push's; None if the stream
+        is empty."""
+        r = self._host("itd_table_stream_flush_host_f64", ())
+        if r is None:
+            return None
+        count, tabs = r
+        tabs = [numpy.ascontiguousarray(t[:, :1]) for t in tabs]
+        return StreamWaves(count[0], *[t[0] for t in tabs]) if self._flat else StreamWaves(count, *tabs)
+
+
+def blockwise_single_waves(rows, block, origin=0, device=0):
+    """Run rows[R, n_blocks * block] (or [n]) through a WaveTableStream: what a caller with an unbounded source does block by block.
+    Returns batch.Waves(count, start, length, peak, value) with every row's events concatenated, the tables padded to the largest
+    count as single_waves pads them (-1; nan): for origin = 0 it equals single_waves(rows) entry for entry, with int64 positions."""
+    from .batch import Waves
+    x2, flat = _as_rows(rows, block, two_d=True)
+    R = x2.shape[0]
+    st = WaveTableStream(block, R, origin, device)
+    try:
+        steps = [st.push(x2[:, k * block:(k + 1) * block]) for k in range(x2.shape[1] // block)]
+        steps.append(st.flush())
+    finally:
+        st.close()
+    count = numpy.sum([w.count for w in steps], axis=0).astype(numpy.int32)
+    cap = int(count.max())
+    tabs = [numpy.full((R, cap), numpy.nan if k == 3 else -1, numpy.float64 if k == 3 else numpy.int64) for k in range(4)]
+    for r in range(R):
+        at = 0
+        for w in steps:
+            c = int(w.count[r])
+            for k in range(4):
+                tabs[k][r, at:at + c] = w[1 + k][r, :c]
+            at += c
+    return Waves(count[0], *[t[0] for t in tabs]) if flat else Waves(count, *tabs)
