@@ -716,6 +716,49 @@ int itd_wave_hist_batch_f32(itd_engine *e, const float *rows_dev, int64_t n, int
                             int64_t hop, int32_t *count_dev, int32_t *samples_dev, int64_t hist_stride, int32_t *outside_dev,
                             int32_t *info_dev, void *stream);
 
+/* ---- the wave filter's bounds from histogram quantiles: the step between itd_wave_hist_batch_* and
+ * itd_wave_filter_batch_*, on the device.  Asynchronous on `stream`, no host synchronisation, no host read, graph-capturable.
+ * A row has a histogram h[T][na][nl] of int32 cells, non-negative (the caller's duty) — `count` or `samples` of itd_wave_hist_batch_*
+ * or of the histogram stream's slices: the caller chooses by the pointer it passes —, a range of time bins [t0, t1), its edges
+ * ae[0..na], le[0..nl] and eight float64 parameters q = (aq_lo, aq_hi, lq_lo, lq_hi, as_lo, as_hi, ls_lo, ls_hi).  In int64:
+ *   ma[i] = sum over t0 <= t < t1 and j of h[t][i][j],  ml[j] = the same over t and i,  N = sum ma = sum ml, below 2^53.
+ * One axis with marginal m[0..B), edges e[0..B], inclusive prefix sums cum[i], quantiles q_lo, q_hi and scales s_lo, s_hi:
+ *   N == 0      iL = 0, iU = B - 1: the whole edge range.
+ *   otherwise   tau_lo = q_lo * (double)N and tau_hi = q_hi * (double)N, one IEEE multiply each;
+ *               iL = the smallest i with (double)cum[i] > tau_lo; if there is none (q_lo = 1; a NaN), the smallest i with
+ *                    cum[i] == N, the last non-empty bin;
+ *               iU = max(iL, the smallest i with (double)cum[i] >= tau_hi; if there is none (q_hi above 1; a NaN), B - 1).
+ *   lo = e[iL] * s_lo, hi = e[iU + 1] * s_hi, one IEEE multiply each: a scale of 1.0 gives the edge's own bits; inf * 0 gives a
+ *   NaN bound, with which the filter keeps nothing.
+ * So 0 <= iL <= iU < B whatever q holds; for 0 <= q_lo <= q_hi <= 1 bin iL is not empty and the bins iL .. iU hold at least
+ * (q_hi - q_lo) N of the total.  The filter's intervals are closed while the bins are half-open: a half wave whose amplitude equals
+ * the upper edge e[iU + 1] exactly is kept.  Output: bounds (amp_lo, amp_hi, len_lo, len_hi) in itd_wave_filter_batch_*'s layout,
+ * and N.  Every decision is an integer sum and a comparison, every sum an integer add (no floating-point atomics): the same bits
+ * from run to run and in any batch position.
+ *   hist_dev: row r's cells at r * hist_stride elements; hist_stride >= T * na * nl when rows > 1.  0 <= t0 < t1 <= T < 2^31.
+ *   1 <= na <= 64, 1 <= nl <= 64, na * nl <= 1024.
+ *   aedges_dev, ledges_dev, quant_dev: row r's at r * the stride; a stride of 0 is one set for every row, otherwise
+ *     aedges_stride >= na + 1, ledges_stride >= nl + 1, quant_stride >= 8.  Device memory, read when the call runs: a captured call
+ *     follows them, and the histogram, from replay to replay.
+ *   bounds_dev: row r's four float64 at r * bounds_stride, bounds_stride >= 4.  total_dev (optional): [rows] int64.  Nothing else
+ *     is written, whatever the parameters hold.
+ * Any rows >= 1; more than 65535 go in chunks.  ITD_ERR_INVALID_ARG before any launch for a NULL handle or required pointer or a
+ * value or stride out of range.
+ * The call runs on a handle of its own, itd_bounds (itd_bounds_create(out, device) / itd_bounds_destroy; itd_bounds_last_error for
+ * the text behind ITD_ERR_HIP), not on an itd_engine: the handle owns the call's stream (used when `stream` is NULL) and its
+ * workspace (1 KB per row of min(rows, 65535) rows, grown on demand and zeroed by a kernel of the call), so nothing of this call
+ * lies in an engine that other operators work in, and no order of other calls can reach its result.  The batched operators' capture
+ * rule holds: capture a call only after one of its row count has run; a captured call stays valid until a call on the same handle
+ * with more rows grows the workspace.  Not thread-safe: one handle per host thread. */
+typedef struct itd_bounds itd_bounds;   /* opaque */
+int itd_bounds_create(itd_bounds **out, int device_id);
+void itd_bounds_destroy(itd_bounds *b);
+const char *itd_bounds_last_error(const itd_bounds *b);
+int itd_wave_bounds_batch(itd_bounds *b, const int32_t *hist_dev, int32_t rows, int64_t hist_stride, int64_t T, int64_t t0, int64_t t1,
+                          int32_t na, int32_t nl, const double *aedges_dev, int64_t aedges_stride, const double *ledges_dev,
+                          int64_t ledges_stride, const double *quant_dev, int64_t quant_stride, double *bounds_dev, int64_t bounds_stride,
+                          int64_t *total_dev, void *stream);
+
 /* ---- the ITD-Fourier cascade (itd_fourier_decomposition.py:131-303) and its FFT ---------------------------------------------
  * itd_debug_fft_f64 (tests): `batch` transforms of n complex float64 points (interleaved re, im; transform b at 2 b n doubles) from
  *   in_dev into out_dev (may be in_dev): inverse 0 = numpy.fft.fft, 1 = numpy.fft.ifft (scaled by 1 / n).  n <= 8192: one
@@ -1100,6 +1143,36 @@ int itd_table_stream_push_host_f64(itd_stream *s, const double *block_host, int6
                                    int64_t *peak_host, double *value_host, int32_t *count_host, int32_t *emitted);
 int itd_table_stream_flush_host_f64(itd_stream *s, int64_t *start_host, int64_t *length_host, int64_t *peak_host, double *value_host,
                                     int32_t *count_host, int32_t *emitted);
+
+/* ---- the bounds stream: the wave filter's bounds of a sliding window over a histogram stream's slices ------
+ * itd_wave_bounds_batch needs the whole histogram.  A bounds stream takes, push by push, the `slices` = C time slices [C][na][nl]
+ * that a histogram stream emits per block for each of `rows` rows, and after push p (counted from 0) writes the bounds of the last
+ * min(W, p + 1) pushes: by definition itd_wave_bounds_batch over the concatenated slices with
+ * [t0, t1) = [max(0, p + 1 - W) C, (p + 1) C), with the edges and the parameters of this push, bit for bit.  No latency, no flush.
+ * One launch per push: it replaces the window's oldest push by the new one in a device ring of per-push marginals and int64 running
+ * sums per row — exact integers — and finishes as the many-row call does.  The ring slot is a launch argument.
+ * Built for this order per block, all on one HIP stream through device pointers: the histogram stream's push, this push, the
+ * wave-filter stream's push with the same horizon and so the same latency — block p - D is then filtered with bounds that already
+ * include its own half waves.
+ *   1 <= rows <= 65535, 1 <= na, nl <= 64, na nl <= 1024, slices >= 1 with slices na nl <= 8192 (the histogram stream's limit),
+ *   1 <= window <= 65536 pushes.  Everything is allocated at create: rows (window + 1) (na + nl) 8 bytes of sums, the host form's
+ *   staging and an engine of the stream's own; ITD_ERR_NOMEM when it does not fit.
+ *   hist_dev: row r's cells at + r hist_stride (>= slices na nl when rows > 1), `count` or `samples` as the caller chooses.
+ *   edges, parameters, bounds, total: as for itd_wave_bounds_batch, read and written when the launch runs.
+ * The host form takes contiguous hist_host [rows][slices][na][nl], edges and parameters with a stride of 0 (one set) or exactly
+ * na + 1 / nl + 1 / 8, and gives bounds_host [rows][4] and total_host [rows] (optional); pinned staging, one synchronisation per call.
+ * ITD_ERR_INVALID_ARG before any HIP call for a NULL handle, a NULL required pointer or a value out of range; a call that fails
+ * leaves the stream as it was.  itd_stream_reset empties the window; itd_stream_destroy / blocks (the pushes since the stream
+ * began) / status (always 0) / last_error apply; every other stream kind's push and flush entries refuse a bounds stream, and these
+ * refuse theirs. */
+#define ITD_STREAM_BOUNDS 8   /* a bounds stream (itd_bounds_stream_create); not a kind itd_stream_create takes */
+int itd_bounds_stream_create(itd_stream **out, int device_id, int32_t rows, int32_t na, int32_t nl, int32_t slices, int32_t window);
+int itd_bounds_stream_push(itd_stream *s, const int32_t *hist_dev, int64_t hist_stride, const double *aedges_dev, int64_t aedges_stride,
+                           const double *ledges_dev, int64_t ledges_stride, const double *quant_dev, int64_t quant_stride,
+                           double *bounds_dev, int64_t bounds_stride, int64_t *total_dev, void *stream);
+int itd_bounds_stream_push_host(itd_stream *s, const int32_t *hist_host, const double *aedges_host, int64_t aedges_stride,
+                                const double *ledges_host, int64_t ledges_stride, const double *quant_host, int64_t quant_stride,
+                                double *bounds_host, int64_t *total_host);
 
 /* ---- introspection for benchmarks -------------------------------------------------------------
  * hipEvent pairs on the launch stream.  Extraction launches are dispatched with their own start/stop events

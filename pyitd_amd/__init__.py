@@ -13,6 +13,8 @@ from .engine import Engine
 from .streaming import InstantaneousStream, SpectrumStream, StreamInstant, StreamSpectrum, blockwise_instantaneous
 from .streaming import StreamHistogram, WaveHistogramStream, blockwise_wave_histogram
 from .streaming import StreamWaves, WaveTableStream, blockwise_single_waves
+from .batch import wave_filter_bounds
+from .streaming import WaveBoundsStream
 from .itd import (ITD, baseline_knot_estimation, detect_knots, detect_peaks, find_extrema, generate_sine_wave, instantaneous, isin, itd,
                   itd_baseline_extract, itd_baseline_extract_cubic, itd_baseline_extract_fast, itd_baseline_extract_iq, itd_batch, itd_levels,
                   itd_sine_wrapper, matlab_detect_peaks, release_engines)
@@ -29,5 +31,6 @@ __all__ = ["itd_baseline_extract_modified", "itd_baseline_extract_spline", "itd_
            "InstantaneousStream", "StreamInstant", "blockwise_instantaneous",
            "WaveHistogramStream", "StreamHistogram", "blockwise_wave_histogram",
            "WaveTableStream", "StreamWaves", "blockwise_single_waves",
+           "wave_filter_bounds", "WaveBoundsStream",
            "fourier_mode_decomposition_any", "fourier_mode_decomposition_valid", "itd_fourier_decomposition",
            "itd_fourier_decomposition_lean", "itd_fourier_decomposition_batch"]

@@ -89,6 +89,10 @@ ABI = {
     "itd_wave_filter_batch_f32": (_INT, [_P, _P, _I64, _I32, _I64, _P, _I64, _P, _I64, _I32, _P, _P]),
     "itd_wave_hist_batch_f64": (_INT, [_P, _P, _I64, _I32, _I64, _P, _I64, _I32, _P, _I64, _I32, _I64, _P, _P, _I64, _P, _P, _P]),
     "itd_wave_hist_batch_f32": (_INT, [_P, _P, _I64, _I32, _I64, _P, _I64, _I32, _P, _I64, _I32, _I64, _P, _P, _I64, _P, _P, _P]),
+    "itd_bounds_create": (_INT, [ctypes.POINTER(_P), _INT]),
+    "itd_bounds_destroy": (None, [_P]),
+    "itd_bounds_last_error": (ctypes.c_char_p, [_P]),
+    "itd_wave_bounds_batch": (_INT, [_P, _P, _I32, _I64, _I64, _I64, _I64, _I32, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P]),
     "itd_debug_fft_f64": (_INT, [_P, _P, _P, _I64, _I32, _I32]),
     "itd_fourier_mode_any_f64": (_INT, [_P, _P, _I64, _I64, _I64, _P, _I64, _P, _P]),
     "itd_fourier_mode_valid_f64": (_INT, [_P, _P, _I64, _I64, _I64, _P, _I64, _P, _P]),
@@ -141,6 +145,9 @@ ABI = {
     "itd_table_stream_flush_f64": (_INT, [_P, _P, _P, _P, _P, _I64, _P, _P, _P]),
     "itd_table_stream_push_host_f64": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "itd_table_stream_flush_host_f64": (_INT, [_P, _P, _P, _P, _P, _P, _P]),
+    "itd_bounds_stream_create": (_INT, [ctypes.POINTER(_P), _INT, _I32, _I32, _I32, _I32, _I32]),
+    "itd_bounds_stream_push": (_INT, [_P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P]),
+    "itd_bounds_stream_push_host": (_INT, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P]),
     "itd_set_nan_input_mode": (_INT, [_P, _I32]),
     "itd_set_batch_chunk": (_INT, [_P, _I32]),
     "itd_set_batch_streams": (_INT, [_P, _I32]),

@@ -91,7 +91,7 @@ class Tensor:
         self._torch, self._t, self.dev, self.x = torch, t, t.device.index, None
         self._torch_busy, self._running = True, False
         if not _TORCH_DTYPES:
-            _TORCH_DTYPES.update({numpy.dtype(name): getattr(torch, name) for name in ("float32", "float64", "int32")})
+            _TORCH_DTYPES.update({numpy.dtype(name): getattr(torch, name) for name in ("float32", "float64", "int32", "int64")})
 
     def __enter__(self):
         self.x = self._t.data_ptr()

@@ -14,9 +14,9 @@ from collections import namedtuple
 import numpy
 
 from ._lib import ITDError
-from ._place import Numpy, _is_torch, _np_dtype, rows_of
+from ._place import Numpy, Tensor, _is_torch, _np_dtype, _row_stride, rows_of
 from .engine import DETECT_KNOTS, ITD_ERR_NONFINITE
-from .itd import _engine_for
+from .itd import _engine_for, _wave_bounds_for
 
 
 def _rows(x):
@@ -354,3 +354,107 @@ def wave_histogram(rows, amplitude_edges, length_edges, hop=None, device=0):
               S.ptr(samples), T * Na * Nl, S.ptr(outside), S.ptr(info))
         _refuse_nan(S.host(info))
         return WaveHistogram(S.result(count), S.result(samples), S.result(outside))
+
+
+# ---- the wave filter's bounds from the histogram's quantiles (itd_wave_bounds_batch) -----------------------------------------
+def _bounds_params(amplitude_q, length_q, amplitude_scale, length_scale, lead):
+    """The eight parameters (aq_lo, aq_hi, lq_lo, lq_hi, as_lo, as_hi, ls_lo, ls_hi) as float64 [8] (one set for every row) or
+    [R, 8]; refuses NaN, quantiles outside [0, 1] and lo > hi."""
+    cols = []
+    for name, pair, quantile in (("amplitude_q", amplitude_q, True), ("length_q", length_q, True),
+                                 ("amplitude_scale", amplitude_scale, False), ("length_scale", length_scale, False)):
+        try:
+            lo, hi = pair
+        except (TypeError, ValueError):
+            raise ValueError("%s: a pair (lo, hi), got %r" % (name, pair))
+        lo, hi = numpy.asarray(lo, dtype=numpy.float64), numpy.asarray(hi, dtype=numpy.float64)
+        if numpy.isnan(lo).any() or numpy.isnan(hi).any():
+            raise ValueError("%s: a NaN" % name)
+        if quantile:
+            if (lo < 0).any() or (lo > 1).any() or (hi < 0).any() or (hi > 1).any():
+                raise ValueError("%s: quantiles lie in [0, 1]" % name)
+            try:
+                both = numpy.broadcast_arrays(lo, hi)
+            except ValueError:
+                raise ValueError("%s: lo %s and hi %s do not broadcast" % (name, lo.shape, hi.shape))
+            if (both[0] > both[1]).any():
+                raise ValueError("%s: lo > hi" % name)
+        cols += [lo, hi]
+    if all(c.ndim == 0 for c in cols):
+        return numpy.array([float(c) for c in cols])
+    try:
+        cols = [numpy.broadcast_to(c, lead) for c in cols]
+    except ValueError:
+        raise ValueError("the parameters (shapes %s) do not broadcast to the leading axes %s of hist" % ([c.shape for c in cols], lead))
+    return numpy.ascontiguousarray(numpy.stack([c.reshape(-1) for c in cols], axis=1))
+
+
+def _bounds_hist(hist, device):
+    """The acceptance of hist[..., T, Na, Nl], int32 — a numpy array (made contiguous) or a torch CUDA tensor (used in place; its last
+    three axes dense, its leading axes collapsing to one stride) — before anything is allocated: (the placement to open, shape, row
+    count, row stride)."""
+    torch_in = _is_torch(hist)
+    a = hist if torch_in else numpy.asarray(hist)
+    if str(a.dtype).split(".")[-1] != "int32":
+        raise ValueError("hist must be int32, got %s" % (a.dtype,))
+    shape = tuple(a.shape)
+    if len(shape) < 3 or min(shape[-3:]) < 1:
+        raise ValueError("expected hist[..., T, Na, Nl], got shape %s" % (shape,))
+    T, Na, Nl = shape[-3:]
+    if Na > MAX_WAVE_BINS or Nl > MAX_WAVE_BINS or Na * Nl > MAX_WAVE_CELLS:
+        raise ValueError("%d x %d bins: at most %d per axis and %d cells" % (Na, Nl, MAX_WAVE_BINS, MAX_WAVE_CELLS))
+    if T >= 2 ** 31:
+        raise ValueError("at most 2^31 - 1 time bins")
+    R = int(numpy.prod(shape[:-3], dtype=numpy.int64))
+    if R < 1:
+        raise ValueError("no rows in a histogram of shape %s" % (shape,))
+    slot = T * Na * Nl
+    if not torch_in:
+        return Numpy(device, numpy.ascontiguousarray(a).reshape(R, slot)), shape, R, slot
+    if not a.is_cuda:
+        raise ValueError("expected a CUDA tensor")
+    strides = tuple(a.stride())
+    dense = all(d == 1 or st == want for d, st, want in zip(shape[-3:], strides[-3:], (Na * Nl, Nl, 1)))
+    stride = _row_stride(shape[:-3] + (slot,), strides[:-3] + (1,)) if dense else None
+    if stride is None:
+        raise ValueError("a tensor with strides %s: its last three axes must be dense and its leading axes collapse to one stride" % (strides,))
+    return Tensor(a), shape, R, stride
+
+
+def wave_filter_bounds(hist, amplitude_edges, length_edges, amplitude_q=(0.0, 1.0), length_q=(0.0, 1.0), amplitude_scale=(1.0, 1.0),
+                       length_scale=(1.0, 1.0), time_bins=None, want_total=False, device=0):
+    """wave_filter's bounds chosen on the device from the quantiles of a histogram hist[..., T, Na, Nl] (int32; `count` or `samples`
+    of wave_histogram or of a WaveHistogramStream's slices), in one asynchronous call.  Per row and axis, with the marginal m over
+    the time bins time_bins = (t0, t1) (None: all) and the other axis, its inclusive prefix sums cum and its total N: iL is the
+    first bin with cum > q_lo N (q_lo = 1: the last non-empty bin), iU the first bin at or behind iL with cum >= q_hi N; the bounds
+    are edges[iL] * scale_lo and edges[iU + 1] * scale_hi.  The bins iL .. iU hold at least (q_hi - q_lo) N; an empty histogram
+    gives the whole edge range.  The filter's intervals are closed, so a half wave exactly on the upper edge is kept as well.  All
+    sums are integers: the same bits from run to run and in any batch position.
+
+    hist: a numpy array or a torch CUDA tensor.  Each edge argument as wave_histogram takes it; every parameter pair (lo, hi) holds
+    scalars or arrays that broadcast to the leading axes of hist.  Returns float64 [..., 4] = (amp_lo, amp_hi, len_lo, len_hi) per
+    row (a tensor for a tensor) — what WaveFilterStream.push takes as bounds=, Engine.wave_filter_batch_dev and the streams' push_dev
+    by pointer where it lies, and wave_filter column by column: amplitude=(b[..., 0], b[..., 1]), length=(b[..., 2], b[..., 3]) —;
+    with want_total also N, int64 [...].
+    Raises ValueError for a quantile outside [0, 1], lo > hi, a NaN, bad edges or a bad range of time bins."""
+    place, shape, R, stride = _bounds_hist(hist, device)
+    lead, (T, Na, Nl) = shape[:-3], shape[-3:]
+    ae, le = _hist_edges(amplitude_edges, "amplitude_edges", lead), _hist_edges(length_edges, "length_edges", lead)
+    if ae.shape[-1] != Na + 1 or le.shape[-1] != Nl + 1:
+        raise ValueError("hist has %d x %d bins, the edges are %d and %d" % (Na, Nl, ae.shape[-1], le.shape[-1]))
+    q = _bounds_params(amplitude_q, length_q, amplitude_scale, length_scale, lead)
+    try:
+        t0, t1 = (0, T) if time_bins is None else time_bins
+        ok = int(t0) == t0 and int(t1) == t1 and 0 <= t0 < t1 <= T
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("time_bins: None or (t0, t1) with 0 <= t0 < t1 <= %d, got %r" % (T, time_bins))
+    astride, lstride, qstride = (0 if ae.ndim == 1 else Na + 1), (0 if le.ndim == 1 else Nl + 1), (0 if q.ndim == 1 else 8)
+    with place as S:
+        bounds, total = S.empty((R, 4), numpy.float64), S.empty((R,), numpy.int64) if want_total else None
+        d_a, d_l, d_q = S.put(ae), S.put(le), S.put(q)
+        S.run(_wave_bounds_for(S.dev).batch_dev, S.x, R, stride, T, int(t0), int(t1), Na, Nl, S.ptr(d_a), astride, S.ptr(d_l), lstride, S.ptr(d_q),
+              qstride, S.ptr(bounds), 4, S.ptr(total))
+        b = S.result(bounds).reshape(lead + (4,))
+        return (b, S.result(total).reshape(lead)) if want_total else b

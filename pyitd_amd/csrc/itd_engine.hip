@@ -38,6 +38,7 @@
 #include "itd_inst_stream.hpp"
 #include "itd_hist_stream.hpp"
 #include "itd_table_stream.hpp"
+#include "itd_wave_bounds.hpp"
 #include "itd_spline.hpp"
 #include "itd_nak.hpp"
 #include "itd_wpe.hpp"
@@ -3052,4 +3053,5 @@ int itd_get_kernel_timing(itd_engine *e, int32_t which, double *ms_total, int32_
 #include "itd_engine_batch.inc"
 #include "itd_ring_streams.inc"
 #include "itd_table_stream.inc"
+#include "itd_wave_bounds.inc"
 #include "itd_fourier.inc"

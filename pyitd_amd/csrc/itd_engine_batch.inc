@@ -308,6 +308,14 @@ struct itd_stream {
         int64_t origin = 0;                              // added to every position that is reported
         Buf<TableCarry> carry;                           // [C]: the half wave that is open between two pushes
     } tb;
+    // the bounds stream (ITD_STREAM_BOUNDS; itd_wave_bounds.inc): C rows, rs.Na x rs.Nl bins, rs.F cells per push; it uses kind,
+    // d_status, rs.cnt.t (the pushes) and besides
+    struct Bounds {
+        int32_t slices = 0, W = 0;                       // time slices per push; the window in pushes
+        Buf<unsigned long long> ring, run;               // [C][W][Na + Nl] the window's pushes' marginals; [C][Na + Nl] their sums
+        Buf<int32_t> d_hist; Pinned<int32_t> h_hist;     // host form: [C][F]
+        Buf<double> d_par; Pinned<double> h_par;         // host form: ae [C][Na + 1], le [C][Nl + 1], q [C][8], bounds [C][4], total [C] (int64)
+    } bd;
 };
 
 namespace {

@@ -659,3 +659,38 @@ class DeviceBuffer:
             self.free()
         except Exception:
             pass
+
+
+class WaveBounds:
+    """The handle of the many-row bounds call (itd_bounds_* in include/pyitd_hip.h): a stream and a workspace of its own, apart from
+    every Engine, so that nothing another operator does can reach the call's result."""
+
+    def __init__(self, device=0):
+        self._L = _lib.load()
+        h = ctypes.c_void_p()
+        rc = self._L.itd_bounds_create(ctypes.byref(h), int(device))
+        if rc:
+            raise ITDError(rc, "itd_bounds_create(device=%d)" % device)
+        self._h, self.device = h, int(device)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.itd_bounds_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def batch_dev(self, hist_ptr, rows, hist_stride, T, t0, t1, abins, lbins, aedges_ptr, aedges_stride, ledges_ptr, ledges_stride,
+                  quant_ptr, quant_stride, bounds_ptr, bounds_stride=4, total_ptr=None, stream=None):
+        """The wave filter's bounds (amp_lo, amp_hi, len_lo, len_hi), float64 at bounds_stride per row, from the quantiles of the time
+        bins [t0, t1) of every row's int32 histogram [T, abins, lbins] (hist_stride elements apart); edges and the eight float64
+        parameters in device memory, a stride of 0: one set for every row; total int64 [rows] (optional).  Pointers in, nothing
+        copied, nothing awaited; stream None: the handle's own."""
+        rc = self._L.itd_wave_bounds_batch(self._h, hist_ptr, rows, hist_stride, T, t0, t1, abins, lbins, aedges_ptr, aedges_stride,
+                                           ledges_ptr, ledges_stride, quant_ptr, quant_stride, bounds_ptr, bounds_stride, total_ptr, stream)
+        if rc:
+            raise ITDError(rc, self._L.itd_bounds_last_error(self._h).decode())

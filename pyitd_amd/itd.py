@@ -63,10 +63,22 @@ def _batch_engine_for(n, batch, device=0):
     return eng
 
 
+_wave_bounds = {}
+
+
+def _wave_bounds_for(device=0):
+    """The handle of the many-row bounds call, one per device."""
+    key = int(device)
+    if key not in _wave_bounds:
+        from .engine import WaveBounds
+        _wave_bounds[key] = WaveBounds(key)
+    return _wave_bounds[key]
+
+
 def release_engines():
     """Free every cached engine (their HBM workspaces)."""
     _flush_pending()
-    for cache in (_engines, _batch_engines):
+    for cache in (_engines, _batch_engines, _wave_bounds):
         for eng in cache.values():
             eng.close()
         cache.clear()

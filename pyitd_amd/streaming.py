@@ -33,6 +33,8 @@ latency.  WaveHistogramStream: the half waves' joint ampl
 block by block at the wave filter's latency — the distribution a live filter's bounds follow.
 WaveTableStream: the half-wave table itself (pyitd_amd.single_waves) block by block with no horizon and no latency — every half wave
 leaves in the push in which its end becomes known; the open half wave is carried from push to push.
+WaveBoundsStream: the wave filter's bounds from the quantiles of a sliding window over a WaveHistogramStream's slices, one launch per
+push — what joins the histogram stream to a live WaveFilterStream on the device.
 """
 import ctypes
 from collections import namedtuple
@@ -629,6 +631,7 @@ def blockwise_instantaneous(rows, block, horizon, want=("amplitude", "phase", "f
 
 StreamHistogram = namedtuple("StreamHistogram", "count samples outside overlong")
 MAX_STREAM_HIST_CELLS = 8192          # cells per block: (block / hop) * amplitude bins * length bins
+MAX_BOUNDS_WINDOW = 65536             # pushes in a WaveBoundsStream's window
 
 
 class WaveHistogramStream(_RingStream):
@@ -853,3 +856,67 @@ def blockwise_single_waves(rows, block, origin=0, device=0):
                 tabs[k][r, at:at + c] = w[1 + k][r, :c]
             at += c
     return Waves(count[0], *[t[0] for t in tabs]) if flat else Waves(count, *tabs)
+
+
+class WaveBoundsStream(_Handle):
+    """The wave filter's bounds from the quantiles of a sliding window over a histogram stream's slices (itd_bounds_stream_* in
+    include/pyitd_hip.h): push by push the `slices` time slices [rows, slices, Na, Nl] (int32) a WaveHistogramStream emits per block go
+    in, and the bounds of the last min(window, pushes) pushes come out — by definition pyitd_amd.wave_filter_bounds of the concatenated
+    slices with time_bins = (max(0, p + 1 - window) * slices, (p + 1) * slices) after push p, bit for bit.  No latency, no flush.  ONE
+    launch per push on the GPU; the state is a ring of per-push marginals and their running sums, exact integers.
+
+        bs = WaveBoundsStream(rows=9, Na=32, Nl=32, slices=2, window=16)
+        b = bs.push(hist.count, ae, le, amplitude_q=(0.1, 0.9))     # float64 [rows, 4]: WaveFilterStream.push(block, bounds=b)
+
+    On device pointers, per block and everything on one stream `s`: the histogram stream's push, this push, the wave-filter stream's
+    push with the same horizon — block p - D is then filtered with bounds that already include its own half waves:
+
+        if hs.push_dev(rows_ptr, L, ae_ptr, 0, le_ptr, 0, count_ptr, samples_ptr, C * Na * Nl, None, None, 0, s):
+            bs.push_dev(count_ptr, C * Na * Nl, ae_ptr, 0, le_ptr, 0, q_ptr, 0, bounds_ptr, 4, None, s)
+        wf.push_dev(rows_ptr, L, bounds_ptr, 4, out_ptr, L, s)
+
+    reset() empties the window; blocks_held counts the pushes since the stream began."""
+
+    def __init__(self, rows, Na, Nl, slices, window, device=0):
+        from .batch import MAX_WAVE_BINS, MAX_WAVE_CELLS
+        for name, v in (("rows", rows), ("Na", Na), ("Nl", Nl), ("slices", slices), ("window", window)):
+            if isinstance(v, bool) or int(v) != v or v < 1:
+                raise ValueError("%s must be a positive integer, got %r" % (name, v))
+        if rows > 65535:
+            raise ValueError("rows must be 1 .. 65535")
+        if Na > MAX_WAVE_BINS or Nl > MAX_WAVE_BINS or Na * Nl > MAX_WAVE_CELLS:
+            raise ValueError("%d x %d bins: at most %d per axis and %d cells" % (Na, Nl, MAX_WAVE_BINS, MAX_WAVE_CELLS))
+        if slices * Na * Nl > MAX_STREAM_HIST_CELLS:
+            raise ValueError("%d time slices of %d x %d bins are more than %d cells per push" % (slices, Na, Nl, MAX_STREAM_HIST_CELLS))
+        if window > MAX_BOUNDS_WINDOW:
+            raise ValueError("window must be 1 .. %d pushes" % MAX_BOUNDS_WINDOW)
+        self._open("itd_bounds_stream_create", "itd_bounds_stream_create(rows=%d, bins=%d x %d, slices=%d, window=%d)" %
+                   (rows, Na, Nl, slices, window), int(device), int(rows), int(Na), int(Nl), int(slices), int(window))
+        self.rows, self.abins, self.lbins, self.slices, self.window, self.device = int(rows), int(Na), int(Nl), int(slices), int(window), int(device)
+
+    # ---- device buffers (raw pointers; asynchronous on `stream`) ----------------------------------------------------
+    def push_dev(self, hist_ptr, hist_stride, aedges_ptr, aedges_stride, ledges_ptr, ledges_stride, quant_ptr, quant_stride, bounds_ptr,
+                 bounds_stride=4, total_ptr=None, stream=None):
+        """One push's slices of every row in, the window's bounds (and totals, int64 [rows]) out; strides of 0: one set for every row."""
+        self._check(self._L.itd_bounds_stream_push(self._h, hist_ptr, hist_stride, aedges_ptr, aedges_stride, ledges_ptr, ledges_stride,
+                                                   quant_ptr, quant_stride, bounds_ptr, bounds_stride, total_ptr, stream))
+
+    # ---- numpy in -> numpy out (one synchronisation per call) ----------------------------------------------------------
+    def push(self, hist, amplitude_edges, length_edges, amplitude_q=(0.0, 1.0), length_q=(0.0, 1.0), amplitude_scale=(1.0, 1.0),
+             length_scale=(1.0, 1.0), want_total=False):
+        """hist [rows, slices, Na, Nl] int32; edges and parameters as wave_filter_bounds takes them for the leading axis (rows,).
+        Returns the bounds float64 [rows, 4]; with want_total also the window's totals, int64 [rows]."""
+        from .batch import _bounds_params, _hist_edges
+        h = numpy.ascontiguousarray(hist)
+        if h.dtype != numpy.int32 or h.shape != (self.rows, self.slices, self.abins, self.lbins):
+            raise ValueError("expected int32 slices of shape (%d, %d, %d, %d)" % (self.rows, self.slices, self.abins, self.lbins))
+        ae, le = _hist_edges(amplitude_edges, "amplitude_edges", (self.rows,)), _hist_edges(length_edges, "length_edges", (self.rows,))
+        if ae.shape[-1] != self.abins + 1 or le.shape[-1] != self.lbins + 1:
+            raise ValueError("the stream has %d x %d bins, the edges are %d and %d" % (self.abins, self.lbins, ae.shape[-1], le.shape[-1]))
+        q = _bounds_params(amplitude_q, length_q, amplitude_scale, length_scale, (self.rows,))
+        bounds = numpy.empty((self.rows, 4), numpy.float64)
+        total = numpy.empty(self.rows, numpy.int64) if want_total else None
+        self._check(self._L.itd_bounds_stream_push_host(self._h, _np_ptr(h), _np_ptr(ae), ae.shape[-1] if ae.ndim == 2 else 0, _np_ptr(le),
+                                                        le.shape[-1] if le.ndim == 2 else 0, _np_ptr(q), 8 if q.ndim == 2 else 0,
+                                                        _np_ptr(bounds), _np_ptr(total)))
+        return (bounds, total) if want_total else bounds
